@@ -2,6 +2,8 @@
 """Benchmark of the RecNet train step (train.py:248-273) on MI355X.
 
   python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run)
+  python bench.py ... --full                             (+ roofline, phase table, exact-fp32 path, CPU baselines)
+  python bench.py ... --dump-outputs DIR                 (what the last timed step computed, DIR/<name>.npy)
 
 Workload (BASELINE.json configs[1]): decoder + GLOBAL reconstructor, B=100 captions per GPU, 28x1536
 features, V=4188, E=468, H=512, A=128, R=1536, LSTM/LSTM, 30-token cap with caption 0 at full length
@@ -208,6 +210,40 @@ def fp32_exact(R, cfg_over, V, enc, targets, targets_g, B, F, steps=10, warmup=3
             "note": "same workload, precision=f32 (fp32 MFMA operands); the parity path of TOL['f32'] in tests/gpu_util.py"}
 
 
+DUMP_SAMPLE = 1 << 19      # elements kept of a larger tensor (halved until the whole dump fits DUMP_LIMIT)
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(out_dir, st):
+    """What a caller of the timed path holds after its last step, as DIR/<name>.npy in float32: the losses (one file per
+    _lib.SCALAR_NAMES entry) and, per model (dec / rec), every parameter after the update (<model>.<param>.npy) and its
+    gradient (<model>.<param>.grad.npy).  A tensor of more than `cap` elements is reduced to a fixed seeded sample of `cap`
+    of them (the same indices in every run and for parameter and gradient); `cap` starts at DUMP_SAMPLE and is halved until
+    the whole dump fits DUMP_LIMIT bytes."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.float32(v) for k, v in st.engine.scalar_dict().items()}
+    tensors = {}
+    for tag, md in (("dec", st.decoder), ("rec", st.reconstructor)):
+        if md is None:
+            continue
+        ms = md["_state"]
+        grads = ms.flat()["grad"].views
+        for k, p in ms.params().items():
+            tensors["%s.%s" % (tag, k)] = p
+            tensors["%s.%s.grad" % (tag, k)] = grads[k]
+    cap = DUMP_SAMPLE
+    while sum(128 + 4 * min(t.numel(), cap) for t in tensors.values()) + 132 * len(arrays) > DUMP_LIMIT:     # (128: .npy header)
+        cap //= 2
+    for name, t in tensors.items():
+        a = t.detach().float().reshape(-1).cpu().numpy()
+        if a.size > cap:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))]
+        arrays[name] = a
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -218,8 +254,12 @@ def main():
     ap.add_argument("--precision", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--frames", type=int, default=28, help="encoder_output_len F (C4: 40)")
     ap.add_argument("--feat", type=int, default=1536, help="encoder_output_size D = reconstructor size (C4: 2048, C5: 3584)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-fp32-exact", action="store_true", help="skip the fp32_exact sub-record (the same workload on the exact-fp32 path)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure what the headline does not need: "
+                    "the dominant kernel's roofline, the phase table, the exact-fp32 path and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed (losses, updated parameters, "
+                    "gradients; float32, large tensors as a fixed seeded sample) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline sub-records")
+    ap.add_argument("--no-fp32-exact", action="store_true", help="with --full: skip the fp32_exact sub-record (the same workload on the exact-fp32 path)")
     ap.add_argument("--cpu-steps", type=int, default=3)
     ap.add_argument("--graph", type=int, default=1, help="replay the step from a captured hipGraph")
     ap.add_argument("--defer", type=int, default=2, choices=[0, 1, 2], help="one rank, graph mode — 2 (default): SPLIT reconstructor update: d W_hh and its "
@@ -334,48 +374,48 @@ def main():
         el = float(t)
     ms = el / args.steps * 1e3
     sc = step.step_impl.engine.scalar_dict()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step.step_impl)
 
     out = None
     if rank == 0:
-        # roofline of the dominant kernel, measured live with HIP events around its launches
         eng = step.step_impl.engine
-
-        def prof_pass(site):
-            # hipEvent brackets around every launch of `site` in EAGER launches of the step (engine.profile_site); site < 0: around
-            # -site empty kernels, the calibration of what the two event records add to a bracket
-            def one():
-                if site < 0:
-                    for _ in range(16):
-                        eng.profile_null_launch(-site)
-                    return
-                eng.train_step_dev(enc, targets, T, w, step.step_impl.seed_base, 3)
-            # (never the data-parallel step itself: this runs on rank 0 only, a collective here would wait for ever)
-            n_, ms_ = eng.profile_site(site if site > 0 else 5, one, 5)
-            return (n_ // 5 if site > 0 else n_), ms_
-        phases = None
-        if not step.reduce:
-            phases = phase_table(eng, runner)
-            if phases:
-                # The phase table is taken from ISOLATED replays (a synchronisation after each, to read the stamps).  Back to back — the
-                # timed loop — a replay's span is 20-35 us LONGER than isolated (the successor's packets are already in the hardware
-                # queues) and the idle time between the last kernel of one replay and the first kernel of the next is only ~5-8 us:
-                # both read DIRECTLY from the rings of start / end stamps the step's first and last kernels keep (Engine.step_ring,
-                # round 5; rounds 3-4 reported ms_per_step - isolated span as "between steps", 35-54 us, and could not explain it).
-                for _ in range(8):
-                    runner()
-                ring = eng.step_ring()
-                if len(ring) >= 3:
-                    import statistics as _st
-                    phases["span_back_to_back_us"] = round(_st.median([b - a for a, b in ring[:-1]]), 1)
-                    phases["between_steps_us"] = round(_st.median([ring[i + 1][0] - ring[i][1] for i in range(len(ring) - 1)]), 1)
-                phases["ms_per_step_minus_isolated_span_us"] = round(ms * 1e3 - phases["span_us"], 1)
-        for _ in range(int(os.environ.get("RN_BENCH_ROOFLINE_REPEATS", "1")) - 1):       # (stress of the measurement path: tools/crash_hunt.sh)
-            roofline(eng, prof_pass, kind, args.precision, T=T, cell=args.cell)
-        prof = roofline(eng, prof_pass, kind, args.precision, T=T, cell=args.cell)
-        if prof and phases:
-            # cross-check of the hipEvent brackets (taken around EAGER launches of the step) against the device's own stamps inside
-            # the REPLAYED graph (first workgroup started -> last statement of workgroup 0): what the timed region really ran
-            prof["chain_kernel_stamps_us"] = {k[len("chain_"):-len("_us")]: v for k, v in phases.items() if k.startswith("chain_") and isinstance(v, float)}
+        prof = phases = None
+        if args.full:
+            # roofline of the dominant kernel, measured live with HIP events around its launches
+            def prof_pass(site):
+                # hipEvent brackets around every launch of `site` in EAGER launches of the step (engine.profile_site); site < 0: around
+                # -site empty kernels, the calibration of what the two event records add to a bracket
+                def one():
+                    if site < 0:
+                        for _ in range(16):
+                            eng.profile_null_launch(-site)
+                        return
+                    eng.train_step_dev(enc, targets, T, w, step.step_impl.seed_base, 3)
+                # (never the data-parallel step itself: this runs on rank 0 only, a collective here would wait for ever)
+                n_, ms_ = eng.profile_site(site if site > 0 else 5, one, 5)
+                return (n_ // 5 if site > 0 else n_), ms_
+            if not step.reduce:
+                phases = phase_table(eng, runner)
+                if phases:
+                    # The phase table is taken from ISOLATED replays (a synchronisation after each, to read the stamps).  Back to back — the
+                    # timed loop — a replay's span is 20-35 us LONGER than isolated (the successor's packets are already in the hardware
+                    # queues) and the idle time between the last kernel of one replay and the first kernel of the next is only ~5-8 us:
+                    # both read DIRECTLY from the rings of start / end stamps the step's first and last kernels keep (Engine.step_ring,
+                    # round 5; rounds 3-4 reported ms_per_step - isolated span as "between steps", 35-54 us, and could not explain it).
+                    for _ in range(8):
+                        runner()
+                    ring = eng.step_ring()
+                    if len(ring) >= 3:
+                        import statistics as _st
+                        phases["span_back_to_back_us"] = round(_st.median([b - a for a, b in ring[:-1]]), 1)
+                        phases["between_steps_us"] = round(_st.median([ring[i + 1][0] - ring[i][1] for i in range(len(ring) - 1)]), 1)
+                    phases["ms_per_step_minus_isolated_span_us"] = round(ms * 1e3 - phases["span_us"], 1)
+            prof = roofline(eng, prof_pass, kind, args.precision, T=T, cell=args.cell)
+            if prof and phases:
+                # cross-check of the hipEvent brackets (taken around EAGER launches of the step) against the device's own stamps inside
+                # the REPLAYED graph (first workgroup started -> last statement of workgroup 0): what the timed region really ran
+                prof["chain_kernel_stamps_us"] = {k[len("chain_"):-len("_us")]: v for k, v in phases.items() if k.startswith("chain_") and isinstance(v, float)}
         # whole-step roofline fractions: algorithmic FLOPs against the dense bf16 MFMA peak and
         # algorithmic HBM bytes (optimiser + inputs) against 8 TB/s; per GPU (every rank does the same work)
         Bl = hi - lo
@@ -394,21 +434,23 @@ def main():
                                    "D=R=%d, V=4188, E=468, H=512, A=128, T=%d, dropout 0.5, %s cells" % (args.rec, hi - lo, F, D, T, args.cell),
                        "global_batch": Bg, "parallelism": "dp%d" % world, "hipgraph": bool(args.graph), "deferred_reconstructor_update": bool(graphed is not None and graphed.deferred and (graphed.defer_mode is True or eng.lib.recnet_dim(eng.handle, 10) == 1)), "host_feed": bool(args.feed), "grad_allreduce": bool(step.reduce),
                        "loss": round(sc["total_loss"], 5)},
-            "roofline": prof, "whole_step": whole, "phases": phases,
+            "whole_step": whole,
         }
-        if not args.no_fp32_exact and world == 1 and args.precision == "bf16" and not args.feed:
-            out["fp32_exact"] = fp32_exact(R, cfg_over, V, enc, targets, targets_g, B, F)
-        if not args.no_cpu_baseline and world == 1:
-            v, cores, med = cpu_baseline(kind, B, F, D, V, args.cpu_steps, 1, args.cell)
-            out["cpu_baseline"] = {"value": round(v, 2), "unit": "captions/s", "cores": cores, "kind": "port",
-                                   "sample": "1 warm-up + %d timed train steps of the same workload (B=%d, T=31) by "
-                                             "oracle/recnet_oracle.py on torch-CPU; median %.2f s/step" % (args.cpu_steps, B, med)}
-            # BASELINE.json configs[0] (mandatory): decoder only, B=8, the reference's CPU-runnable case
-            v1, c1, m1 = cpu_baseline(None, 8, 28, 1536, V, 5, 2, args.cell)
-            out["cpu_baseline_c1"] = {"value": round(v1, 2), "unit": "captions/s", "cores": c1, "kind": "port",
-                                      "sample": "configs[0]: decoder only, B=8, 28x1536, T=31; 2 warm-up + 5 timed train steps by "
-                                                "oracle/recnet_oracle.py on torch-CPU; median %.3f s/step (tools/c1_reference_vs_oracle.py: "
-                                                "the oracle times within noise of the imported reference)" % m1}
+        if args.full:
+            out.update(roofline=prof, phases=phases)
+            if not args.no_fp32_exact and world == 1 and args.precision == "bf16" and not args.feed:
+                out["fp32_exact"] = fp32_exact(R, cfg_over, V, enc, targets, targets_g, B, F)
+            if not args.no_cpu_baseline and world == 1:
+                v, cores, med = cpu_baseline(kind, B, F, D, V, args.cpu_steps, 1, args.cell)
+                out["cpu_baseline"] = {"value": round(v, 2), "unit": "captions/s", "cores": cores, "kind": "port",
+                                       "sample": "1 warm-up + %d timed train steps of the same workload (B=%d, T=31) by "
+                                                 "oracle/recnet_oracle.py on torch-CPU; median %.2f s/step" % (args.cpu_steps, B, med)}
+                # BASELINE.json configs[0] (mandatory): decoder only, B=8, the reference's CPU-runnable case
+                v1, c1, m1 = cpu_baseline(None, 8, 28, 1536, V, 5, 2, args.cell)
+                out["cpu_baseline_c1"] = {"value": round(v1, 2), "unit": "captions/s", "cores": c1, "kind": "port",
+                                          "sample": "configs[0]: decoder only, B=8, 28x1536, T=31; 2 warm-up + 5 timed train steps by "
+                                                    "oracle/recnet_oracle.py on torch-CPU; median %.3f s/step (tools/c1_reference_vs_oracle.py: "
+                                                    "the oracle times within noise of the imported reference)" % m1}
         print(json.dumps(out), flush=True)
     if world > 1 or under_launcher:
         dist.barrier()
