@@ -30,7 +30,7 @@ int recnet_abort_step(recnet_handle* h) {
   if (!h) return fail(RECNET_EINVAL, "null handle");
   h->dp_overlap = 0; h->side_open = 0; h->in_fused = 0; h->defer_now = 0; h->defer_err = 0;
   h->total_late = 0; h->side_tail_open = 0; h->rec_wait_pending = 0; h->rec_norm_late = 0; h->rec_loss_late = 0; h->rec_loss_defer = 0; h->prezeroed = 0; h->norms_hoisted = 0; h->hoist_pending = 0;
-  h->hoist_fork_recorded = 0; h->side_fork_recorded = 0; h->encmean_hoisted = 0; h->ctx_done = 0; h->side_pending = 0; h->late_join = 0;
+  h->hoist_fork_recorded = 0; h->side_fork_recorded = 0; h->encmean_hoisted = 0; h->ctx_done = 0; h->side_pending = 0;
   h->join_pending = 0; h->join_recorded = 0; h->deferred_done = 0; h->deferred_early = 0; h->early_opt_done = 0;
   h->xcat_done = 0; h->mp_done = 0; h->dhr_done = 0; h->dout_ready = 0; h->gg_slots = 0; h->gemm_single_group = 0;
   h->img_defer_now = 0; h->s3_late = 0;
@@ -234,7 +234,7 @@ static void side_after_decoder_fwd(recnet_handle* h, hipStream_t st) {
   const bool par = sd != st;
   h->side_pending = 0;
   // (side_fork_recorded: the caller recorded the fork event ev[0] itself, IN FRONT of a chain launch it then enqueued — the side
-  // work is enqueued behind that launch on the host but depends only on what preceded it: RN_SIDE_AFTER_CHAIN)
+  // work is enqueued behind that launch on the host but depends only on what preceded it)
   if (par) {
     if (h->side_fork_recorded) {
       hipStreamWaitEvent(sd, h->ev[0], 0);
@@ -253,8 +253,7 @@ static void side_after_decoder_fwd(recnet_handle* h, hipStream_t st) {
   // and the tail grows by 67 us: C2 1.773 against 1.724 ms)
   if (!r) r = dec_bwd_out(h, 1.0f, sd);
   h->gg_slots = 0;
-  static const int f_tail = 1;
-  if (!r && par && f_tail && h->side_phase != 2) { dec_ctx_rows(h, h->side_enc, 0, h->side_T, sd); h->ctx_done = 1; }   // off the tail
+  if (!r && par && h->side_phase != 2) { dec_ctx_rows(h, h->side_enc, 0, h->side_T, sd); h->ctx_done = 1; }   // off the tail
   if (h->side_tail_open) hipEventRecord(h->ev[18], sd);      // (dec_bwd_out recorded the join the BPTT waits for in front of this branch's rest)
   h->gws_cur = h->gws;
   h->side_err = r;
@@ -280,11 +279,6 @@ static int fwd_bwd_impl(recnet_handle* h, const float* enc, const int64_t* targe
   h->early_opt_done = 0;
   if (phase != 2) h->free_fwd = 0;                 // the fused step is teacher-forced
   if (phase != 2) h->ctx_done = 0;
-  static const int f_hoist = 1;
-  static const int f_early = 1;
-  // RN_LATE_REC_OPT=1: the reconstructor's optimiser step runs on the side stream AFTER the decoder BPTT (beside the
-  // decoder's own optimiser step) instead of under it
-  static const int f_lateopt = 0;
   // Deferred reconstructor update (opt-in, global reconstructor): the step before left its weight-gradient products and Adam
   // step pending; they run on a third stream under this step's decoder forward chain, followed by the reconstructor's share
   // of the hoisted work (its norms are those of the UPDATED parameters).  ev[12] = all of that done.
@@ -316,27 +310,24 @@ static int fwd_bwd_impl(recnet_handle* h, const float* enc, const int64_t* targe
     // Work that does not depend on the batch's forward pass (hoist_side_work below) goes to the side stream.  It is forked
     // from inside dec_fwd_chain, after the decoder's prologue has been enqueued: forked at the very start of the step it
     // ran before the prologue instead of beside it (80 us on the critical path in the kernel trace).
-    h->hoist_pending = 1; h->hoist_enc = enc; h->hoist_par = (par && f_hoist) ? 1 : 0;
+    h->hoist_pending = 1; h->hoist_enc = enc; h->hoist_par = par ? 1 : 0;
     h->norms_hoisted = 1;
     r = dec_fwd_chain(h, enc, targets, T, 1, st);
     if (h->hoist_pending) hoist_side_work(h, st);
     if (!r && h->defer_err) { r = h->defer_err; h->defer_err = 0; }
     if (r) { h->norms_hoisted = 0; return r; }
-    static const int f_join = 0;
-    static const int f_late = 1;
-    h->join_early = f_join;
     h->side_targets = targets; h->side_stepw = stepw; h->side_enc = enc; h->side_T = T; h->side_phase = phase; h->side_err = 0;
     h->side_pending = 1;
     // global reconstructor: the side work is forked from inside fwd_rec_global, behind the batched input GEMM (so that
     // GEMM does not share the chip with the vocabulary projection; the persistent chain that follows leaves CUs free)
-    if (!(par && f_late && h->kind == RECNET_REC_GLOBAL)) side_after_decoder_fwd(h, st);
+    if (!(par && h->kind == RECNET_REC_GLOBAL)) side_after_decoder_fwd(h, st);
     if (h->side_err) { h->norms_hoisted = 0; return h->side_err; }
     if (rec) {
       // bsum_r and the reconstructor's norm.  (Joining the hoisted branch through the pending-update branch instead — one
       // cross-stream edge in front of the reconstructor's chain instead of two, with the reconstructor's gate bias formed by
       // prologue_pack_kernel — was measured in round 4 and removed: the replayed graph then ran the pending update BEHIND the
       // decoder's chain instead of beside it at C3, 2.27 against 2.15 ms, and the prologue grew by 7 us.)
-      if (par && f_hoist) hipStreamWaitEvent(st, h->ev[5], 0);
+      if (par) hipStreamWaitEvent(st, h->ev[5], 0);
       if (defer && h->defer_rec != 2) hipStreamWaitEvent(st, h->ev[12], 0);          // ... and the updated parameters (deferred update)
       else if (defer) h->rec_wait_pending = 1;                  // (mode 2: only the recurrent chain waits, see fwd_rec_global)
       if (h->img_defer_now) h->rec_wait_pending = 1;            // (deferred image refresh: the chains wait for the third stream's ev[12])
@@ -347,16 +338,13 @@ static int fwd_bwd_impl(recnet_handle* h, const float* enc, const int64_t* targe
       if (h->side_pending) side_after_decoder_fwd(h, st);
       if (!r) r = h->side_err;
       if (r) return r;
-      // RN_DEFERRED_EARLY=1 forks the reconstructor's deferred gradients + optimiser step right behind its backward chain
-      // instead of in front of the decoder's BPTT.  Measured and rejected: the batched products then share the chip with the
-      // d hiddens products the BPTT waits for (C2 2.06 -> 2.10 ms, C5 5.04 -> 5.44 ms).
-      static const int f_defearly = 0;
+      // (measured and rejected in the fused step: the deferred gradients forked right behind the chain share the chip with the
+      // d hiddens products the BPTT waits for, C2 2.06 -> 2.10 ms, C5 5.04 -> 5.44 ms)
       h->deferred_done = 0;
       // phase 1 (data parallel, graph A): there is no decoder BPTT in this graph to hide the deferred products behind; forked
       // here they at least run beside the d hiddens products that follow the chain instead of after them
-      static const int f_defp1 = 1;
-      h->deferred_early = (par && !defer && ((phase == 0 && f_defearly) || (phase == 1 && f_defp1))) ? 1 : 0;
-      h->deferred_early_flags = (early_opt >= 0 && f_early && !f_lateopt) ? early_opt : -1;
+      h->deferred_early = (par && !defer && phase == 1) ? 1 : 0;
+      h->deferred_early_flags = early_opt >= 0 ? early_opt : -1;
       r = bwd_rec_chain(h, h->c.lambda_recon, h->dHsrec, st);
       h->deferred_early = 0;
       if (r) return r;
@@ -383,14 +371,8 @@ static int fwd_bwd_impl(recnet_handle* h, const float* enc, const int64_t* targe
     h->norms_hoisted = 0;
     if (phase == 1) return RECNET_OK;
   }
-  // RN_BPTT_FIRST=1: the BPTT chain is enqueued BEFORE the side stream's work of this stage (the reconstructor's deferred
-  // products and optimiser step), which is forked from the same point: the chain's workgroups need whole CUs and are to be
-  // dispatched before the products' workgroups start filling every CU partly (same reason as RN_SIDE_AFTER_CHAIN).  Measured
-  // without effect at C2 and C3 (1.906 / 1.906, 2.32 / 2.32 ms): off.
-  static const int f_bf = 0;
-  const bool chain_first = f_bf && par && h->persist_dec_bwd;
-  if (par) { if (chain_first) hipEventRecord(h->ev[2], st); else fork_to(h, 2, st, sd); }
-  if (chain_first) { r = dec_bwd_chain(h, dh, st); if (r) return r; hipStreamWaitEvent(sd, h->ev[2], 0); }
+  // (measured without effect: the BPTT chain enqueued in front of this fork, C2 1.906 / 1.906 ms, C3 2.32 / 2.32 ms)
+  if (par) fork_to(h, 2, st, sd);
   if (h->total_late) {      // (see above; sd is ordered behind the reconstructor's chains by the fork, and joined at the step's end)
     if (h->rec_loss_late) rec_loss_scalars(h, sd);
     hipLaunchKernelGGL(axpb_kernel, dim3(1), dim3(1), 0, sd, h->scal + 2, h->scal + 5, h->c.lambda_recon, h->scal + 6);
@@ -423,9 +405,8 @@ static int fwd_bwd_impl(recnet_handle* h, const float* enc, const int64_t* targe
     if (par && h->persist_dec_bwd) wait_chain(h, 1, sd);      // (the BPTT chain is launched on `st` below; this branch waits for its residency)
     r = bwd_rec_deferred(h, sd, 0); if (r) return r;
     h->gws_cur = h->gws;
-    if (early_opt >= 0 && par && f_early && !f_lateopt) {
-      // RN_REC_OPT_S3=1: the reconstructor's Adam step + re-transpose on a third stream behind its deferred products, so that
-      // the side stream is free for its half of the decoder's deferred gradients the moment the BPTT chain ends (the update
+    if (early_opt >= 0 && par) {
+      // The reconstructor's Adam step + re-transpose on a third stream behind its deferred products, so that the side stream is free for its half of the decoder's deferred gradients the moment the BPTT chain ends (the update
       // streams 0.5 GB and holds the side stream for ~130 us past the end of the chain).  Measured and rejected (round 3):
       // C2 1.993 against 1.931 ms, C3 2.322 against 2.295 ms — a third branch in the replayed graph costs more than it returns.
       // At R = 3584 (C5) the update streams 2 GB (367 us) and the decoder's second tail branch queues behind it on the side
@@ -443,24 +424,14 @@ static int fwd_bwd_impl(recnet_handle* h, const float* enc, const int64_t* targe
   // is a loss (+0.22 ms): the batched GEMMs occupy the CUs the latency-bound chain kernels need at every step.
   // (So is splitting the deferred gradients over two streams after the chain, +0.11 ms: in a replayed graph every extra
   // fork / join costs more than the concurrency returns.)
-  if (!chain_first) { r = dec_bwd_chain(h, dh, st); if (r) return r; }
-  {
-    // the decoder's deferred weight gradients: two independent halves on the two streams (the side stream's earlier
-    // work — the reconstructor's deferred gradients and optimiser step — ends about when the chain does)
-    static const int f_tail2 = 1;
-    const bool two = par && f_tail2;   // (phase 1 returned above)
-    if (two) fork_to(h, 6, st, sd);
-    r = dec_bwd_deferred(h, enc, targets, st, two ? sd : nullptr, (two && h->s3 && !s3_join) ? h->s3 : nullptr);
-    h->ctx_done = 0;
-    if (r) return r;
-    if (two && phase == 0 && rec && early_opt >= 0 && f_early && f_lateopt) {
-      hipEventRecord(h->ev[7], sd); hipStreamWaitEvent(st, h->ev[7], 0);    // the decoder's gradients are complete
-      r = optimizer_step(h, early_opt, sd, 1); if (r) return r;
-      h->early_opt_done = 1;
-      h->late_join = 1;                                                      // the caller joins after its own optimiser step
-    }
-  }
-  if (par && !h->late_join) join_from(h, 3, st, sd);
+  r = dec_bwd_chain(h, dh, st); if (r) return r;
+  // the decoder's deferred weight gradients: two independent halves on the two streams (the side stream's earlier
+  // work — the reconstructor's deferred gradients and optimiser step — ends about when the chain does)
+  if (par) fork_to(h, 6, st, sd);
+  r = dec_bwd_deferred(h, enc, targets, st, par ? sd : nullptr, (par && h->s3 && !s3_join) ? h->s3 : nullptr);
+  h->ctx_done = 0;
+  if (r) return r;
+  if (par) join_from(h, 3, st, sd);
   // (fused step: the decoder's optimiser step does not depend on the third stream's reconstructor update — the caller joins it behind
   // its own optimiser step: at 28 x 3584 the two overlap instead of 140 us of decoder update behind 600 us of reconstructor update)
   if (s3_join) { if (h->in_fused) h->s3_late = 1; else join_from(h, 11, st, h->s3); }
@@ -476,7 +447,7 @@ static int fwd_bwd(recnet_handle* h, const float* enc, const int64_t* targets, i
   if (!r && phase != 1 && early_opt < 0 && h->og[0].bound && h->og[0].tab[0].g)
     hipLaunchKernelGGL(poison_mark_kernel, dim3(1), dim3(1), 0, st, h->og[0].tab[0].g, (const float*)(h->scal + 15));
   h->defer_now = 0;
-  if (r) { h->img_defer_now = 0; h->s3_late = 0; h->total_late = 0; h->side_tail_open = 0; h->rec_wait_pending = 0; h->rec_norm_late = 0; h->rec_loss_late = 0; h->rec_loss_defer = 0; h->prezeroed = 0; h->norms_hoisted = 0; h->hoist_pending = 0; h->encmean_hoisted = 0; h->ctx_done = 0; h->side_pending = 0; h->late_join = 0; h->gws_cur = h->gws; }
+  if (r) { h->img_defer_now = 0; h->s3_late = 0; h->total_late = 0; h->side_tail_open = 0; h->rec_wait_pending = 0; h->rec_norm_late = 0; h->rec_loss_late = 0; h->rec_loss_defer = 0; h->prezeroed = 0; h->norms_hoisted = 0; h->hoist_pending = 0; h->encmean_hoisted = 0; h->ctx_done = 0; h->side_pending = 0; h->gws_cur = h->gws; }
   return r;
 }
 
@@ -501,7 +472,6 @@ int recnet_train_step_fwd_bwd(recnet_handle* h, const float* enc, const int64_t*
 // and the enqueue-time bookkeeping goes back to "between two steps" (recnet_abort_step's reset) — otherwise the third stream stayed
 // unjoined and a later non-fused optimizer_step saw img_defer_now set and skipped the refresh of the derived weight images.
 static void step_fail_cleanup(recnet_handle* h, hipStream_t st) {
-  if (h->late_join && h->s2) join_from(h, 3, st, h->s2);
   if (h->s3_late && h->s3) join_from(h, 11, st, h->s3);
   recnet_abort_step(h);
   if (h->defer_rec) { h->maybe_pending = 1; h->images_maybe_stale = 1; }      // (what the step left pending is flushed / refreshed by the next call)
@@ -529,7 +499,6 @@ int recnet_train_step(recnet_handle* h, const float* enc, const int64_t* targets
   r = fwd_bwd(h, enc, targets, T, step_weight, st, 0, flags); if (r) { h->in_fused = 0; return r; }
   r = optimizer_step(h, flags, st, h->early_opt_done ? 0 : -1); h->in_fused = 0;
   if (r) { step_fail_cleanup(h, st); return r; }
-  if (h->late_join) { join_from(h, 3, st, h->s2); h->late_join = 0; }
   if (h->s3_late) { join_from(h, 11, st, h->s3); h->s3_late = 0; }
   h->img_defer_now = 0;
   if (scalars) hipLaunchKernelGGL(export_scalars_kernel, dim3(1), dim3(1), 0, st, h->scal, scalars);
@@ -549,7 +518,6 @@ int recnet_train_step_dev(recnet_handle* h, const float* enc, const int64_t* tar
   r = fwd_bwd(h, enc, targets, T, step_weight, st, 0, flags); if (r) { h->in_fused = 0; return r; }
   r = optimizer_step(h, flags, st, h->early_opt_done ? 0 : -1); h->in_fused = 0;
   if (r) { step_fail_cleanup(h, st); return r; }
-  if (h->late_join) { join_from(h, 3, st, h->s2); h->late_join = 0; }
   if (h->s3_late) { join_from(h, 11, st, h->s3); h->s3_late = 0; }
   h->img_defer_now = 0;
   if (scalars) hipLaunchKernelGGL(export_scalars_kernel, dim3(1), dim3(1), 0, st, h->scal, scalars);

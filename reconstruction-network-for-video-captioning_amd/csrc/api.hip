@@ -20,7 +20,9 @@
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <ctype.h>
 #include <string.h>
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -69,7 +71,6 @@ struct recnet_handle {
   float* scal;           // [0] dec_ce [1] dec_reg [2] dec_loss [3] rec_mse [4] rec_reg [5] rec_loss [6] total [7] gnorm [8] clip
   // ---- decoder: fp32 state
   float *slab2 = nullptr;   // second slab buffer (local reconstructor backward: dWhr . W_r)
-  float *slab3 = nullptr;   // third: the dx part of the per-step backward product when it runs as its own branch (bwd_rec_local)
   float *bsum4 = nullptr, *bsum4r = nullptr;   // [4H], [4R] column sums of the gate gradients (source of both bias gradients)
   int prezeroed = 0;        // the step's atomic-sum targets were zeroed by one hoisted kernel (fwd_bwd)
   float *bsum_d, *Uv, *Xe, *Hs, *Cs, *acts, *Wh, *att, *logits, *rowloss, *slab, *gws, *dHs, *dHsrec, *dc_carry, *dUv,
@@ -107,7 +108,6 @@ struct recnet_handle {
   int persist_dec_bwd = 0;  // ... and its BPTT chain
   int side_pending = 0, side_T = 0, side_phase = 0, side_err = 0;   // side_after_decoder_fwd (abi_step.inc)
   const int64_t* side_targets = nullptr; const float* side_stepw = nullptr; const float* side_enc = nullptr;
-  int late_join = 0;
   int bgrp_loc = 0;              // ... of the local reconstructor's chains (<= 64 rows where more do not fit: recnet_create)
   int bgrp = 0;                  // rows per launch of the persistent chain kernels: B for B <= RC_PAN_ROWS, else B split evenly into ceil(B / 112) row groups
   // deferred reconstructor update (recnet_set_deferred_reconstructor_update): ctrl[2] on the device says whether an update is
@@ -149,7 +149,7 @@ struct recnet_handle {
   // environment switches, read ONCE per handle in recnet_create (round 6: no getenv on any enqueue path; a test that flips one creates
   // a new handle).  Each selects between two tested forms of one piece of the schedule, never the arithmetic (tests/test_gpu_knobs.py,
   // tests/test_gpu_parity.py: _chain_variants).
-  struct RnSw { int wait_chain = 1, mse_epi = 1, adam_epi = 1, dec_lw = 1, dec_rp = 1, dec_partial = 1, dec_xcat = 1, rec_epi = 2, rec_wide = 1, persist_ms = 0, gemm_group = 1; } sw;
+  struct RnSw { int wait_chain = 1, mse_epi = 1, adam_epi = 1, dec_lw = 1, dec_xcat = 1, rec_epi = 2, rec_wide = 1, persist_ms = 0, gemm_group = 1; } sw;
   int gg_slots = 0;              // workgroup slots the next grouped launches can expect (0 = whole chip): see host_common.inc
   int gemm_single_group = 0;     // set around a single product whose K slices are to be summed inside its launch (host_decoder.inc: the embedding branch)
   hipStream_t s2 = nullptr; hipEvent_t ev[24] = {}; int overlap = 1;
@@ -159,7 +159,7 @@ struct recnet_handle {
   bool dec_bound = false, rec_bound = false;
   OptGroup og[2];
   // state between forward and backward
-  int T_last = 0, train_last = 0, fwd_dec_done = 0, fwd_rec_done = 0, rec_bwd_done = 0, early_opt_done = 0, norms_hoisted = 0, join_pending = 0, join_early = 0;
+  int T_last = 0, train_last = 0, fwd_dec_done = 0, fwd_rec_done = 0, rec_bwd_done = 0, early_opt_done = 0, norms_hoisted = 0, join_pending = 0;
   // optional per-launch timing of the recurrent-step GEMM (recnet_profile_*)
   int prof_on = 0; std::vector<hipEvent_t> prof_ev; size_t prof_used = 0;
 };
@@ -272,7 +272,7 @@ static size_t carve(recnet_handle* h, char* base) {
     h->dGr = takev(F * B * ld4R); h->dUd_lp = takev(Tm * B * ldRA); h->dWhr = takev(F * B * (size_t)h->ldRA4);
     h->dWhrs = takev(F * B * ldRA); h->Wr4_w = takev(RN_TCH * RA * ldR);
     h->Ur_w = takev(RA * ldH); h->Wr_w = takev(RA * ldR); h->Wihh_w = takev(4 * R * ldHR);
-    h->slab2 = take(16 * B * R); h->slab3 = take(16 * B * H);
+    h->slab2 = take(16 * B * R);
     h->lc_panh = takev(F * rc_pan_elems((int)R) / 2 + 64);
     h->lc_panx = takev(F * rc_pan_elems((int)H) / 2 + 64);
     h->lc_pw = (_Float16*)take(F * B * ((R + 15) / 16) * RA / 2 + 64);
@@ -323,6 +323,23 @@ extern "C" {
 int recnet_abi_version(void) { return RECNET_ABI_VERSION; }
 const char* recnet_last_error(void) { return g_err.c_str(); }
 
+// A list-valued switch: the comma-separated names of variable var, blanks around a name trimmed, empty names skipped.
+static std::vector<std::string> env_list(const char* var) {
+  std::vector<std::string> out;
+  const char* e = getenv(var);
+  for (const char* p = e; p && *p;) {
+    const char* q = strchr(p, ',');
+    const char* a = p;
+    const char* b = q ? q : p + strlen(p);
+    p = q ? q + 1 : b;
+    while (a < b && isspace((unsigned char)*a)) a++;
+    while (b > a && isspace((unsigned char)b[-1])) b--;
+    if (b > a) out.emplace_back(a, b);
+  }
+  return out;
+}
+static bool has(const std::vector<std::string>& v, const std::string& name) { return std::find(v.begin(), v.end(), name) != v.end(); }
+
 int recnet_create(const recnet_config* cfg, recnet_handle** out) {
   if (!cfg || !out) return fail(RECNET_EINVAL, "null argument");
   const recnet_config& c = *cfg;
@@ -343,6 +360,17 @@ int recnet_create(const recnet_config* cfg, recnet_handle** out) {
     return fail(RECNET_EINVAL, "global reconstructor requires reconstructor_hidden_size == encoder_output_size (train.py:101)");
   if (c.reconstructor_type == RECNET_REC_LOCAL && c.reconstructor_attn_size <= 0)
     return fail(RECNET_EINVAL, "reconstructor_attn_size");
+  // Two list-valued switches, read here once; an unknown name is an error (a retired or misspelt one would run the default form):
+  //   RN_PER_STEP  chains that run on the per-step kernels instead of their persistent launch — or all;
+  //   RN_ALT       alternative forms the tests hold the default against.
+  const std::vector<std::string> per_step = env_list("RN_PER_STEP"), alts = env_list("RN_ALT");
+  const std::vector<std::string> per_step_names = {"dec", "dec_bwd", "rec", "rec_bwd", "loc", "loc_bwd", "loc_big", "all"};
+  const std::vector<std::string> alt_names = {"dec_wh_in_phase_a", "dec_no_xcat", "rec_epilogue_0", "rec_epilogue_1", "rec_bwd_narrow",
+                                              "rec_row_parts_1", "rec_row_parts_2", "loc_no_hybrid", "loc_xsplit_never", "loc_xsplit_always"};
+  for (const std::string& t : per_step) if (!has(per_step_names, t)) return fail(RECNET_EINVAL, "RN_PER_STEP: unknown name '" + t + "'");
+  for (const std::string& t : alts) if (!has(alt_names, t)) return fail(RECNET_EINVAL, "RN_ALT: unknown name '" + t + "'");
+  auto alt = [&](const char* name) { return has(alts, name); };
+  auto chain_on = [&](const char* name) { return !has(per_step, name) && !has(per_step, "all"); };
   recnet_handle* h = new recnet_handle();
   h->c = c;
   if (h->c.global_batch_size <= 0) h->c.global_batch_size = c.batch_size;
@@ -353,32 +381,12 @@ int recnet_create(const recnet_config* cfg, recnet_handle** out) {
   h->cml = c.caption_max_len; h->Tm = c.caption_max_len + 1;
   h->kind = c.reconstructor_type; h->prec = c.precision; h->lp = c.precision == RECNET_PREC_BF16;
   h->gemm_single_group = 0;
-  // Two list-valued switches (round 6: 23 variables -> 9), comma separated, read here once:
-  //   RN_PER_STEP  chains that run on the per-step kernels instead of their persistent launch: dec, dec_bwd, rec, rec_bwd, loc, loc_bwd,
-  //                loc_big — or all;
-  //   RN_ALT       alternative forms the tests hold the default against: dec_wh_in_phase_a, dec_all_rows, dec_relayed_barrier,
-  //                dec_no_xcat, rec_epilogue_0 / rec_epilogue_1, rec_bwd_narrow, rec_row_parts_1 / rec_row_parts_2, loc_no_hybrid,
-  //                loc_xsplit_never / loc_xsplit_always.
-  auto in_list = [](const char* var, const char* name, bool all_ok) {
-    const char* e = getenv(var);
-    if (!e) return false;
-    const size_t n = strlen(name);
-    for (const char* p = e; *p;) {
-      const char* q = strchr(p, ',');
-      const size_t len = q ? (size_t)(q - p) : strlen(p);
-      if ((len == n && !strncmp(p, name, n)) || (all_ok && len == 3 && !strncmp(p, "all", 3))) return true;
-      p = q ? q + 1 : p + len;
-    }
-    return false;
-  };
-  auto alt = [&](const char* name) { return in_list("RN_ALT", name, false); };
-  auto chain_on = [&](const char* name) { return !in_list("RN_PER_STEP", name, true); };
   {
     auto env = [](const char* n, int dflt) { const char* e = getenv(n); return e ? atoi(e) : dflt; };
     h->sw.wait_chain = env("RN_WAIT_CHAIN", 1); h->sw.mse_epi = env("RN_MSE_EPILOGUE", 1); h->sw.adam_epi = env("RN_ADAM_EPILOGUE", 1);
     h->sw.gemm_group = env("RN_GEMM_GROUP", 1);
-    // RN_ALT: the tested alternative forms of the chain kernels, by name (see in_list below)
-    h->sw.dec_lw = !alt("dec_wh_in_phase_a"); h->sw.dec_rp = !alt("dec_all_rows"); h->sw.dec_partial = !alt("dec_relayed_barrier");
+    // RN_ALT: the tested alternative forms of the chain kernels, by name
+    h->sw.dec_lw = !alt("dec_wh_in_phase_a");
     h->sw.dec_xcat = !alt("dec_no_xcat"); h->sw.rec_epi = alt("rec_epilogue_0") ? 0 : (alt("rec_epilogue_1") ? 1 : 2); h->sw.rec_wide = !alt("rec_bwd_narrow");
     h->sw.persist_ms = alt("rec_row_parts_1") ? 1 : (alt("rec_row_parts_2") ? 2 : 0);
   }

@@ -4,21 +4,18 @@
 // workgroup per caption: attention scores, context = (1/F) sum_f a_f P[b,f,:], gates, pointwise), each re-reading its
 // loop invariants — the packed weights (2.2 MB) and the caption's block of P = enc . W_ih[:,E:]^T (115 KB bf16 per
 // caption, 11.5 MB per step) — from L2 / memory every step.  Here both stay on chip for all T steps and the step becomes
-// two phases of one persistent kernel, separated by grid barriers (rec_chain.hpp):
-//   phase A, workgroup a < NA = (4H + A) / 16: owns 16 columns of [W_hh ; attn_W] (in MFMA B-operand registers), reads
-//            the bf16 copy of h_{t-1} of all captions (k-group-major exchange panel), writes the finished fp32
-//            pre-activations of its columns for every caption (no split-K slabs);
+// two phases of one persistent kernel:
+//   phase A, workgroup a < NA: owns 64 columns of [W_hh ; attn_W] (in MFMA B-operand registers) for one of 4 row parts (28
+//            captions), reads the bf16 copy of h_{t-1} of its part's captions (k-group-major exchange panel), writes the finished
+//            fp32 pre-activations of its columns for those captions (no split-K slabs);
 //   phase B, workgroup b < B: owns caption b — its block of P in registers (wave = gate, lane = 8 units, 32 frames x 16
 //            bytes), its rows of Uv, c_{t-1}; reads its 4H + A pre-activations, computes scores, context, gates and the
 //            cell, publishes h_t (bf16) for phase A of the next step and writes everything the backward needs.
-// A workgroup takes part in both phases (grid = max(NA, B) <= CU count, one workgroup per CU).
-// Round 5 (template parameter RP, the default): phase A is tiled as 64 columns x one of 4 row parts (28 captions) instead of 16 columns x
-// all rows, the roles are laid out XCD-aware, and the B -> A hand-over stays inside a row part (see DCF_PARTS / DCF_NA below).
-// Limits: bf16 path, H % 8 == 0, H <= 512, F <= 32, A <= 128, (4H + A) % 16 == 0, B <= 112.
+// A workgroup takes part in both phases (grid = max(NA, B) <= CU count, one workgroup per CU).  The roles are laid out XCD-aware
+// (DCF_NA below).  Hand-overs: A -> B through stamped words (G1), B -> A through the arrival line of the caption's row part
+// (arrive_part / wait_part), and one full grid barrier at the end of the launch that guards the epoch (rec_chain.hpp).
+// Limits: bf16 path, H % 8 == 0, H <= 512, F <= 32, A <= 128, (4H + A) % 16 == 0, B <= 112, T <= 63.
 #pragma once
-#ifndef DC_STAMP_PAIR
-#define DC_STAMP_PAIR 1
-#endif
 #include "common.hpp"
 #include "rec_chain.hpp"
 
@@ -29,10 +26,9 @@ struct DecChainArgs {
   const bf16_t* P; int ldp;        // [B][F][ldp]
   const float* Uv; const float* ab; const float* w;
   const float* Xe;                 // [T][B][4H] emb . W_e^T + biases
-  float* G1;                       // [T][B][4H + A] exchange: recurrent pre-activations (ll: 8-byte words {value, stamp})
-  unsigned* epoch; int ll;         // ll = 1: phase A -> B hand-over through stamped words instead of a grid barrier
-  int master;                      // 1: the last workgroup of the grid is the barrier master (rc_master_loop)
-  int partial; unsigned* rep;      // RP kernels: phase A waits for the captions of its row part only, through per-XCD replicas of the part's arrival line (see dec_chain_bwd_kernel)
+  float* G1;                       // [T][B][4H + A] exchange: recurrent pre-activations as 8-byte words {value, stamp}
+  unsigned* epoch;
+  unsigned* rep;                   // phase A waits for the captions of its row part only, through per-XCD replicas of the part's arrival line (see dec_chain_bwd_kernel)
   float* poison;                   // see rc_give_up (rec_chain.hpp)
   float* mp; float mp_scale;       // optional: mp_scale * sum_t h_t [B][H] (the global reconstructor's mean-pooled input)
   bf16_t* Xcat; int ld_xcat; DropDesc xdd;   // optional (global reconstructor, ld_xcat == 2H): its LSTM input operand [T][Bs][2H] = [h_t ; drop_t(mp)]
@@ -46,7 +42,6 @@ struct DecChainArgs {
   unsigned long long* ts;          // probe only (DC_PROBE_TS): [T][12] timestamps of one workgroup
 };
 
-#define DC_RED_LD 17
 #if defined(LC_PROBE) && !defined(DC_PROBE_TS)      // the library's probe build (make probe): stamps of workgroup 0
 #define DC_PROBE_TS
 #define DC_PROBE_WG 0
@@ -62,12 +57,12 @@ struct DecChainArgs {
 #define DC_XF 16              // extra frames
 // LW (round 4, F <= 32): the attention projection W h_{t-1} of a caption is computed BY ITS OWN workgroup — attn_W (128 x 512
 // bf16 = 128 KB) stays in LDS for the whole launch and h_{t-1}[b] never left the workgroup — so scores and context no longer
-// wait for phase A: the scores of step t + 1 are formed while the grid barrier of step t completes, the context MFMAs while
+// wait for phase A: the scores of step t + 1 are formed while the hand-over of step t completes, the context MFMAs while
 // phase A's gate pre-activations travel, and only the cell waits for them.  Phase A shrinks to the 4H gate columns.
-// RP (round 5): phase A tiled as 64 columns x one of 4 row parts (28 rows) instead of 16 columns x all 112 rows — the same number of
-// workgroups and (almost) of MFMAs, but a workgroup pulls 32 rows x H of the h_{t-1} panel through its CU's 64 B/clk L1 path instead
-// of 112 (32 KB instead of 115 KB per step: 0.2 us instead of 0.75), and its consumers and producers all lie in ITS row part, so the
-// B -> A hand-over can be partial (DecChainArgs::partial, as in dec_chain_bwd_kernel).
+// Row parts (round 5): phase A tiled as 64 columns x one of 4 row parts (28 rows) rather than 16 columns x all 112 rows — the same
+// number of workgroups and (almost) of MFMAs, but a workgroup pulls 32 rows x H of the h_{t-1} panel through its CU's 64 B/clk L1 path
+// instead of 112 (32 KB instead of 115 KB per step: 0.2 us instead of 0.75), and its consumers and producers all lie in ITS row part, so
+// the B -> A hand-over is partial (as in dec_chain_bwd_kernel).
 #define DCF_PARTS 4
 #define DCF_RLD 68      // (multiple of 4: an accumulator fragment of the TRANSPOSED product is four consecutive columns of one row = one ds_write_b128, round 6)
 // XCD-aware roles: workgroup i runs on XCD i % 8 (rec_chain.hpp), and every XCD fetches what its workgroups read into its own L2.
@@ -75,11 +70,10 @@ struct DecChainArgs {
 // as the fast index every XCD pulled the whole panel every step, eight copies of it over the fabric.  The column blocks are dealt
 // to (i % 2, i / 8); a part's arrival line is polled from its two XCDs only.
 #define DCF_NA(NN) (8 * (((((NN) + 63) >> 6) + 1) >> 1))
-template <bool XF, bool LW = false, bool RP = false>
+template <bool XF, bool LW>
 __global__ __launch_bounds__(256) void dec_chain_kernel(const DecChainArgs p) {
   static_assert(!(XF && LW), "the LDS-resident attn_W and the LDS frames 32..47 do not fit together");
-  // phase A: K-partials of the [112 x 16] tile (LW: two buffers, summed in two stages — the room attn_W needs); RP: of the [32 x 64] tile
-  __shared__ __attribute__((aligned(16))) float red[RP ? 2 * 32 * DCF_RLD : (LW ? 2 : 4) * RC_PAN_ROWS * DC_RED_LD];
+  __shared__ __attribute__((aligned(16))) float red[2 * 32 * DCF_RLD];   // phase A: the K quarters of the [32 x 64] tile, summed in two stages
   __shared__ __attribute__((aligned(16))) float spre[4 * 512];       // phase B: gate pre-activations
   __shared__ float swh[128];
   __shared__ __attribute__((aligned(16))) float sa[32 + DC_XF];
@@ -89,8 +83,8 @@ __global__ __launch_bounds__(256) void dec_chain_kernel(const DecChainArgs p) {
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int H = p.H, A = p.A, F = p.F, B = p.B, Bs = p.Bs, W4 = 4 * H, N = 4 * H + A;
   const int NN = LW ? W4 : N;                            // columns phase A produces
-  const int NCB = (NN + 63) >> 6, NCBH = (NCB + 1) >> 1;  // RP: 64-column blocks, and half of them (below)
-  const int NA = RP ? DCF_NA(NN) : (NN >> 4);
+  const int NCB = (NN + 63) >> 6, NCBH = (NCB + 1) >> 1;  // 64-column blocks, and half of them (below)
+  const int NA = DCF_NA(NN);
   const int wg = blockIdx.x;
   bf16_t* wlds = reinterpret_cast<bf16_t*>(dc_dyn);      // LW: attn_W as [k / 8][128 a][8] (an MFMA B fragment = 16 bytes per lane, 256 contiguous bytes per 16 lanes)
   if (LW) {
@@ -102,18 +96,18 @@ __global__ __launch_bounds__(256) void dec_chain_kernel(const DecChainArgs p) {
     }
     for (int j = tid; j < 512; j += 256) hl[j] = (bf16_t)0.f;
   }
-  const int cb = RP ? (wg & 1) * NCBH + (wg >> 3) : 0, part = RP ? (wg & 7) >> 1 : 0;
-  const bool isA = wg < NA && (!RP || cb < NCB), isB = wg < B;
+  const int cb = (wg & 1) * NCBH + (wg >> 3), part = (wg & 7) >> 1;
+  const bool isA = wg < NA && cb < NCB, isB = wg < B;
   const int kq = (lane >> 4) * 8;
   const size_t pan_t = rc_pan_elems(H);
 
-  // ---- phase A residents: 16 weight rows x K = H (4 waves x 4 k-steps of 32); RP: 4 column groups of 16 rows
+  // ---- phase A residents: 4 column groups of 16 weight rows x K = H (4 waves x 4 k-steps of 32)
   const int own = RC_PAN_ROWS / DCF_PARTS, own_lo = part * own;
   const int r0 = own_lo < RC_PAN_ROWS - 32 ? own_lo : RC_PAN_ROWS - 32;
-  bf16x8 wb[4][RP ? 4 : 1];
+  bf16x8 wb[4][4];
 #pragma unroll
-  for (int gq = 0; gq < (RP ? 4 : 1); ++gq) {
-    const int n = RP ? (isA ? cb : 0) * 64 + gq * 16 + (lane & 15) : (isA ? wg : 0) * 16 + (lane & 15);
+  for (int gq = 0; gq < 4; ++gq) {
+    const int n = (isA ? cb : 0) * 64 + gq * 16 + (lane & 15);
     const bf16_t* wrow = p.W + (size_t)(n < NN ? n : 0) * p.ldw + kq;
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
@@ -179,16 +173,11 @@ __global__ __launch_bounds__(256) void dec_chain_kernel(const DecChainArgs p) {
   }
   const int lane_off = ((lane >> 4) * RC_PAN_ROWS + (lane & 15)) * 8;
   unsigned ph = 0;
-  // Stamped hand-over (ll): a word is {fp32 value, stamp = launch epoch << 6 | t}, written by one 8-byte store, so the
-  // consumer can poll the data itself: no acknowledgement wait, no flag, no barrier between phase A and phase B.  The
-  // epoch (one more per launch, kept in device memory) makes the words of earlier launches stale.
+  // Stamped hand-over A -> B: a word is {fp32 value, stamp = launch epoch << 6 | t}, so the consumer can poll the data itself: no
+  // acknowledgement wait, no flag, no barrier between phase A and phase B.  The epoch (one more per launch, kept in device memory)
+  // makes the words of earlier launches stale.
   const unsigned ep0 = rc_epoch_read(p.epoch), ep = ep0 << 6, fb = ep0 << 7;
-  if (p.master && wg == (int)gridDim.x - 1) {
-    rc_master_loop(p.bar, p.bar + 256, (int)gridDim.x - 1, fb, (p.ll ? 1 : 2) * (p.T - 1));
-    return;
-  }
-  // RP + partial: the B -> A hand-over inside a row part (the comment at dec_chain_bwd_kernel's wait_part has the measurements)
-  const bool partial = RP && p.partial;
+  // the B -> A hand-over inside a row part (the comment at dec_chain_bwd_kernel's wait_part has the measurements)
   auto wait_part = [&](unsigned target) {
     if (isA && tid < 64) {
       const int n = B - own_lo < own ? B - own_lo : own;
@@ -264,10 +253,9 @@ __global__ __launch_bounds__(256) void dec_chain_kernel(const DecChainArgs p) {
       x0 = *reinterpret_cast<const f32x4*>(xe); x1 = *reinterpret_cast<const f32x4*>(xe + 4);
     }
     if (t > 0) {
-      // ================= phase A: G1[t][:, 16 columns] = h_{t-1} . W^T
+      // ================= phase A: G1[t][part's rows, 64 columns] = h_{t-1} . W^T
       DC_TS(0);
       if (isA) {
-       if constexpr (RP) {
         const bf16_t* Ap = p.Pan + (size_t)(t - 1) * pan_t + lane_off + r0 * 8;
         bf16x8 fa[4][2];
 #pragma unroll
@@ -315,97 +303,13 @@ __global__ __launch_bounds__(256) void dec_chain_kernel(const DecChainArgs p) {
           if (idx < own * 32 && row < B && cb * 64 + pc < NN) {
             const float v0 = red[rl * DCF_RLD + pc] + red[32 * DCF_RLD + rl * DCF_RLD + pc];
             const float v1 = red[rl * DCF_RLD + pc + 1] + red[32 * DCF_RLD + rl * DCF_RLD + pc + 1];
-            if (p.ll) {
-              uint64_t* L = reinterpret_cast<uint64_t*>(p.G1) + ((size_t)t * B + row) * N + cb * 64 + pc;
-              const unsigned st = ep | (unsigned)t;
-              rc_store16f(reinterpret_cast<float*>(L), f32x4{v0, __builtin_bit_cast(float, st), v1, __builtin_bit_cast(float, st)});
-            } else {
-              union { float f[2]; uint64_t q; } pk; pk.f[0] = v0; pk.f[1] = v1;
-              __hip_atomic_store(reinterpret_cast<uint64_t*>(p.G1 + ((size_t)t * B + row) * N + cb * 64 + pc), pk.q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+            // two stamped words = 16 contiguous, 16-byte-aligned bytes: one store (each 8-byte word lies inside one 32-byte
+            // sector, which is what its reader's 8-byte load observes as a unit)
+            uint64_t* L = reinterpret_cast<uint64_t*>(p.G1) + ((size_t)t * B + row) * N + cb * 64 + pc;
+            const unsigned st = ep | (unsigned)t;
+            rc_store16f(reinterpret_cast<float*>(L), f32x4{v0, __builtin_bit_cast(float, st), v1, __builtin_bit_cast(float, st)});
           }
         }
-       } else {
-        const bf16_t* Ap = p.Pan + (size_t)(t - 1) * pan_t + lane_off;
-        bf16x8 fa[4][RC_MB];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-          const int k = wave * 128 + s * 32;
-#pragma unroll
-          for (int i = 0; i < RC_MB; ++i)
-            fa[s][i] = *reinterpret_cast<const bf16x8*>(Ap + ((k < H ? (k >> 3) : 0) * RC_PAN_ROWS + i * 16) * 8);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        f32x4 acc[RC_MB];
-#pragma unroll
-        for (int i = 0; i < RC_MB; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-          for (int i = 0; i < RC_MB; ++i) acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[s][i], wb[s][0], acc[i], 0, 0, 0);
-        const int rr = (lane >> 4) * 4, cl = lane & 15;
-        if (LW) {
-          // waves 2, 3 hand their partials to waves 0, 1 through the two buffers, which then hold the two half sums
-          float* part = red + (wave & 1) * (RC_PAN_ROWS * DC_RED_LD);
-          if (wave >= 2) {
-#pragma unroll
-            for (int i = 0; i < RC_MB; ++i)
-#pragma unroll
-              for (int r = 0; r < 4; ++r) part[(i * 16 + rr + r) * DC_RED_LD + cl] = acc[i][r];
-          }
-          __syncthreads();
-          if (wave < 2) {
-#pragma unroll
-            for (int i = 0; i < RC_MB; ++i)
-#pragma unroll
-              for (int r = 0; r < 4; ++r) part[(i * 16 + rr + r) * DC_RED_LD + cl] += acc[i][r];
-          }
-        } else {
-          float* part = red + wave * (RC_PAN_ROWS * DC_RED_LD);
-#pragma unroll
-          for (int i = 0; i < RC_MB; ++i)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) part[(i * 16 + rr + r) * DC_RED_LD + cl] = acc[i][r];
-        }
-        __syncthreads();
-        DC_TS(1);
-        float* Gt = p.G1 + (size_t)t * B * N + wg * 16;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int idx = tid + j * 256, row = idx >> 3, pc = (idx & 7) * 2;
-          if (idx < RC_PAN_ROWS * 8 && row < B) {
-            float v0 = 0.f, v1 = 0.f;
-#pragma unroll
-            for (int w = 0; w < (LW ? 2 : 4); ++w) {
-              v0 += red[w * (RC_PAN_ROWS * DC_RED_LD) + row * DC_RED_LD + pc];
-              v1 += red[w * (RC_PAN_ROWS * DC_RED_LD) + row * DC_RED_LD + pc + 1];
-            }
-            if (p.ll) {
-              uint64_t* L = reinterpret_cast<uint64_t*>(p.G1) + ((size_t)t * B + row) * N + wg * 16 + pc;
-              const uint64_t st = (uint64_t)(ep | (unsigned)t) << 32;
-              // two stamped words = 16 contiguous, 16-byte-aligned bytes: one store (each 8-byte word lies inside one 32-byte
-              // sector, which is what its reader's 8-byte load observes as a unit — DC_STAMP_PAIR=0 restores two 8-byte atomics)
-              if (DC_STAMP_PAIR) {
-                rc_store16f(reinterpret_cast<float*>(L), f32x4{v0, __builtin_bit_cast(float, (unsigned)(st >> 32)), v1, __builtin_bit_cast(float, (unsigned)(st >> 32))});
-              } else {
-                __hip_atomic_store(L, st | __builtin_bit_cast(unsigned, v0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(L + 1, st | __builtin_bit_cast(unsigned, v1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-              }
-            } else {
-              union { float f[2]; uint64_t q; } pk; pk.f[0] = v0; pk.f[1] = v1;
-              __hip_atomic_store(reinterpret_cast<uint64_t*>(Gt + (size_t)row * N + pc), pk.q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-          }
-        }
-       }
-        if (!p.ll) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
-      if (!p.ll) {
-        __syncthreads();
-        DC_TS(2);
-        ++ph;
-        rc_arrive(p.bar, fb + ph);
-        { if (p.master) rc_wait_release(p.bar + 256, fb + ph); else rc_wait(p.bar, fb + ph); }
       }
       DC_TS(3);
     }
@@ -417,7 +321,7 @@ __global__ __launch_bounds__(256) void dec_chain_kernel(const DecChainArgs p) {
       // (LW: the scores of this step are already in `sa` — lw_scores ran before the barrier wait of the step before; the context
       // MFMAs below come first and the gate pre-activations of phase A are polled after them)
       auto poll_pre = [&]() {
-      if (t > 0 && p.ll) {
+      if (t > 0) {
         // poll this caption's words until every stamp is this step's
         const uint64_t* L = reinterpret_cast<const uint64_t*>(p.G1) + ((size_t)t * B + b) * N;
         const uint64_t* lc = L + (live ? col : 0);
@@ -440,13 +344,6 @@ __global__ __launch_bounds__(256) void dec_chain_kernel(const DecChainArgs p) {
           for (int j = 0; j < 8; ++j) pre[j] += __builtin_bit_cast(float, (unsigned)wv[j]);
         }
         if (tid < A) whv = __builtin_bit_cast(float, (unsigned)ww);
-      } else if (t > 0) {
-        const float* gr = p.G1 + ((size_t)t * B + b) * N;
-        f32x4 g0 = {0.f, 0.f, 0.f, 0.f}, g1 = g0;
-        if (live) { g0 = *reinterpret_cast<const f32x4*>(gr + col); g1 = *reinterpret_cast<const f32x4*>(gr + col + 4); }
-        if (tid < A) whv = gr[W4 + tid];
-        pre[0] += g0[0]; pre[1] += g0[1]; pre[2] += g0[2]; pre[3] += g0[3];
-        pre[4] += g1[0]; pre[5] += g1[1]; pre[6] += g1[2]; pre[7] += g1[3];
       }
       };
       if (!LW) {
@@ -576,7 +473,7 @@ __global__ __launch_bounds__(256) void dec_chain_kernel(const DecChainArgs p) {
       }
       if (t + 1 < p.T) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       // (the stores below are issued after the arrive, see the end of the loop body)
-      if (t + 1 < p.T) { __syncthreads(); DC_TS(6); ++ph; if (partial) arrive_part(fb + ph); else rc_arrive(p.bar, fb + ph); }
+      if (t + 1 < p.T) { __syncthreads(); DC_TS(6); ++ph; arrive_part(fb + ph); }
       bf16_t* Lt = p.Hlp + ((size_t)t * Bs + b) * p.ld_hlp;
       if (tid < (H >> 3)) *reinterpret_cast<bf16x8*>(Lt + tid * 8) = *reinterpret_cast<const bf16x8*>(hl + tid * 8);
       if (p.Xcat && tid < (H >> 3)) *reinterpret_cast<bf16x8*>(p.Xcat + ((size_t)t * Bs + b) * p.ld_xcat + tid * 8) = *reinterpret_cast<const bf16x8*>(hl + tid * 8);
@@ -593,20 +490,18 @@ __global__ __launch_bounds__(256) void dec_chain_kernel(const DecChainArgs p) {
         }
       }
       if (LW && t + 1 < p.T) lw_scores(t + 1);      // from hl = h_t, while the barrier completes
-      if (t + 1 < p.T) { if (partial) wait_part(fb + ph); else if (p.master) rc_wait_release(p.bar + 256, fb + ph); else rc_wait(p.bar, fb + ph); }
+      if (t + 1 < p.T) wait_part(fb + ph);
       DC_TS(7);
     } else if (t + 1 < p.T) {
       __syncthreads();
       ++ph;
-      if (!partial) rc_arrive(p.bar, fb + ph);
-      { if (partial) wait_part(fb + ph); else if (p.master) rc_wait_release(p.bar + 256, fb + ph); else rc_wait(p.bar, fb + ph); }
+      wait_part(fb + ph);
     }
   }
-  if (partial) {      // the launch epoch may only move once every workgroup has read it: one full barrier at the end
-    __syncthreads();
-    rc_arrive(p.bar, fb + (unsigned)p.T);
-    if (wg == 0) rc_wait(p.bar, fb + (unsigned)p.T);
-  }
+  // the launch epoch may only move once every workgroup has read it: one full barrier at the end
+  __syncthreads();
+  rc_arrive(p.bar, fb + (unsigned)p.T);
+  if (wg == 0) rc_wait(p.bar, fb + (unsigned)p.T);
   if (p.mp && isB) {
 #pragma unroll
     for (int jj = 0; jj < 2; ++jj) { const int uu = tid + 256 * jj; if (uu < H) p.mp[(size_t)b * H + uu] = hs_sum[jj] * p.mp_scale; }
@@ -648,10 +543,9 @@ struct DecChainBwdArgs {
   const float* acts; const float* Cs; const float* Hs;      // [T][B][4H], [T][B][H], [T][B][H]
   const float* Wh;                 // [T][B][A]
   const float* att; int softmax;   // softmax mode: the saved attention weights [T][B][F]
-  float* G2;                       // [T][B][DCB_KS][H] exchange (by chain step): the K parts of the recurrent part of dh (ll: stamped 8-byte words)
-  unsigned* epoch; int ll; int master; float* poison;
-  int partial;                     // 1 (needs ll, excludes master): phase A' waits for the captions of ITS row part only (below)
-  unsigned* rep;                   // partial: [8 XCDs][DCB_PARTS][32] arrival words, a 128-byte line per (XCD, row part)
+  float* G2;                       // [T][B][DCB_KS][H] exchange (by chain step): the K parts of the recurrent part of dh as stamped 8-byte words
+  unsigned* epoch; float* poison;
+  unsigned* rep;                   // [8 XCDs][DCB_PARTS][32] arrival words, a 128-byte line per (XCD, row part): phase A' waits for the captions of ITS row part only (below)
   bf16_t* Pan;                     // [T][rc_pan_elems(4H + A)] exchange (by chain step): rows [dgates | dWh]
   bf16_t* dGx; int ld_dgx;         // [T][B][ld_dgx]
   float* dUv; bf16_t* dUv_lp; int ld_dUv;                   // [B][F][A], [B F][ld_dUv]
@@ -765,19 +659,15 @@ __global__ __launch_bounds__(256) void dec_chain_bwd_kernel(const DecChainBwdArg
   for (int j = tid; j < 64; j += 256) srow[W4 + 128 + j] = (bf16_t)0.f;
   unsigned ph = 0;
   const unsigned ep0 = rc_epoch_read(p.epoch), ep = ep0 << 6, fb = ep0 << 7;   // see rec_chain.hpp
-  if (p.master && wg == (int)gridDim.x - 1) {
-    rc_master_loop(p.bar, p.bar + 256, (int)gridDim.x - 1, fb, (p.ll ? 1 : 2) * (p.T - 1));
-    return;
-  }
   // Partial hand-over B' -> A' (round 5).  A phase-A' workgroup reads only the `own` = 28 panel rows of its row part, i.e. the rows
   // [dgates | dWh] of 28 captions, and phase B' of a caption polls the stamped words of the 32 unit groups of ITS part: the
-  // dependencies close inside a row part, so nothing needs the whole grid.  Arrive -> master sees all 128 -> release word -> waiter
-  // becomes arrive -> waiter: one memory round trip instead of two, and a part does not wait for the stragglers of the other three.
+  // dependencies close inside a row part, so nothing needs the whole grid.  Against a relayed grid barrier (arrive -> master sees all
+  // 128 -> release word -> waiter) that is one memory round trip instead of two, and a part does not wait for the stragglers of the
+  // other three.
   // A caption writes its arrival into one replica of its part's flag line per XCD that hosts the part's phase-A' workgroups (p.rep:
   // [8][DCB_PARTS][32] words, a 128-byte line per (XCD, part)); a waiter polls the replica of its own XCD (blockIdx % 8) with one wave load.
   // With ONE copy polled by all 128 workgroups the step got 0.9 us LONGER (measured: 315 against 288 us per launch) — a line that is
-  // written from eight XCDs and read from eight is the worst case for the L2s; in this form every line has its readers in one XCD,
-  // like the arrival flags (read by the master only) and the release words (one line per XCD) of the relayed barrier.
+  // written from eight XCDs and read from eight is the worst case for the L2s; in this form every line has its readers in one XCD.
   // Workgroups without a phase A' do not wait.
   auto wait_part = [&](unsigned target) {
     if (isA && tid < 64) {
@@ -864,24 +754,12 @@ __global__ __launch_bounds__(256) void dec_chain_bwd_kernel(const DecChainBwdArg
             const float v0 = red[rl * DCB_RLD + pc] + red[32 * DCB_RLD + rl * DCB_RLD + pc];
             const float v1 = red[rl * DCB_RLD + pc + 1] + red[32 * DCB_RLD + rl * DCB_RLD + pc + 1];
             const size_t widx = (((size_t)s * B + rg) * DCB_KS + kp) * H + un;
-            if (p.ll) {
-              // two stamped words = 16 contiguous, 16-byte-aligned bytes: one store (each 8-byte word lies inside one 32-byte
-              // sector, which is what its reader's 8-byte load observes as a unit)
-              const unsigned st = ep | (unsigned)s;
-              rc_store16f(reinterpret_cast<float*>(reinterpret_cast<uint64_t*>(p.G2) + widx), f32x4{v0, __builtin_bit_cast(float, st), v1, __builtin_bit_cast(float, st)});
-            } else {
-              union { float f[2]; uint64_t q; } pk; pk.f[0] = v0; pk.f[1] = v1;
-              __hip_atomic_store(reinterpret_cast<uint64_t*>(p.G2 + widx), pk.q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+            // two stamped words = 16 contiguous, 16-byte-aligned bytes: one store (each 8-byte word lies inside one 32-byte
+            // sector, which is what its reader's 8-byte load observes as a unit)
+            const unsigned st = ep | (unsigned)s;
+            rc_store16f(reinterpret_cast<float*>(reinterpret_cast<uint64_t*>(p.G2) + widx), f32x4{v0, __builtin_bit_cast(float, st), v1, __builtin_bit_cast(float, st)});
           }
         }
-        if (!p.ll) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
-      if (!p.ll) {
-        __syncthreads();
-        ++ph;
-        rc_arrive(p.bar, fb + ph);
-        { if (p.master) rc_wait_release(p.bar + 256, fb + ph); else rc_wait(p.bar, fb + ph); }
       }
     }
     // ================= phase B': caption b
@@ -889,7 +767,7 @@ __global__ __launch_bounds__(256) void dec_chain_bwd_kernel(const DecChainBwdArg
       // (1) cell backward of the thread's two units -> dgates (bf16) into the row buffer
       DCB_TS(1);
       float grec[2] = {0.f, 0.f};
-      if (s > 0 && p.ll) {
+      if (s > 0) {
         const uint64_t* L = reinterpret_cast<const uint64_t*>(p.G2) + ((size_t)s * B + b) * DCB_KS * H;
         const uint64_t* l0 = L + (tid < H ? tid : 0);
         const uint64_t* l1 = L + (tid + 256 < H ? tid + 256 : 0);
@@ -911,15 +789,6 @@ __global__ __launch_bounds__(256) void dec_chain_bwd_kernel(const DecChainBwdArg
         // (K order, whoever arrived last)
         grec[0] = (__builtin_bit_cast(float, (unsigned)w0[0]) + __builtin_bit_cast(float, (unsigned)w0[1])) + (__builtin_bit_cast(float, (unsigned)w0[2]) + __builtin_bit_cast(float, (unsigned)w0[3]));
         grec[1] = (__builtin_bit_cast(float, (unsigned)w1[0]) + __builtin_bit_cast(float, (unsigned)w1[1])) + (__builtin_bit_cast(float, (unsigned)w1[2]) + __builtin_bit_cast(float, (unsigned)w1[3]));
-      } else if (s > 0) {
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          const int u = tid + 256 * q;
-          if (u < H) {
-            const float* gp = p.G2 + ((size_t)s * B + b) * DCB_KS * H + u;
-            grec[q] = (gp[0] + gp[H]) + (gp[2 * (size_t)H] + gp[3 * (size_t)H]);
-          }
-        }
       }
 #pragma unroll
       for (int q = 0; q < 2; ++q) {
@@ -1025,27 +894,24 @@ __global__ __launch_bounds__(256) void dec_chain_bwd_kernel(const DecChainBwdArg
       for (int kg = tid; kg < (KA >> 3); kg += 256) {
         rc_store16(p.Pan + (size_t)s * pan_t + ((size_t)kg * RC_PAN_ROWS + b) * 8, srow + kg * 8);
       }
-      if (more) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads(); ++ph; if (p.partial) arrive_part(fb + ph); else rc_arrive(p.bar, fb + ph); }
+      if (more) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads(); ++ph; arrive_part(fb + ph); }
       DCB_TS(5);
       // ---- off the critical path: the row-major copy [dgates | dWh | 0 ..] for the deferred GEMMs
       bf16_t* Gt = p.dGx + ((size_t)t * Bs + b) * p.ld_dgx;
       for (int kg = tid; kg < (p.ld_dgx >> 3); kg += 256)
         *reinterpret_cast<bf16x8*>(Gt + kg * 8) = kg < (KA >> 3) ? *reinterpret_cast<const bf16x8*>(srow + kg * 8) : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-      if (more) { prefetch(t - 1); { if (p.partial) wait_part(fb + ph); else if (p.master) rc_wait_release(p.bar + 256, fb + ph); else rc_wait(p.bar, fb + ph); } }
+      if (more) { prefetch(t - 1); wait_part(fb + ph); }
       DCB_TS(6);
     } else if (s + 1 < p.T) {
       __syncthreads();
       ++ph;
-      if (!p.partial) rc_arrive(p.bar, fb + ph);
-      { if (p.partial) wait_part(fb + ph); else if (p.master) rc_wait_release(p.bar + 256, fb + ph); else rc_wait(p.bar, fb + ph); }
+      wait_part(fb + ph);
     }
   }
-  if (p.partial) {
-    // the launch epoch may only move once every workgroup has read it: a full barrier, once, at the end (phase T: above every step's)
-    __syncthreads();
-    rc_arrive(p.bar, fb + (unsigned)p.T);
-    if (wg == 0) rc_wait(p.bar, fb + (unsigned)p.T);
-  }
+  // the launch epoch may only move once every workgroup has read it: a full barrier, once, at the end (phase T: above every step's)
+  __syncthreads();
+  rc_arrive(p.bar, fb + (unsigned)p.T);
+  if (wg == 0) rc_wait(p.bar, fb + (unsigned)p.T);
   // ---- the accumulators: dUv (+ operand copy, zero padded), dw
   if (isB) {
     if (fk_on) {

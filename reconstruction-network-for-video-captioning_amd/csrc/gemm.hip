@@ -140,30 +140,23 @@ void rn_launch_gemm(int prec, const void* A, int a_bf16, int a_col, int lda, con
     else if (!a_bf16 && b_bf16) launch_layout<bf16_t, float, bf16_t>(a, a_col, b_col, grid, st, tag);
     else if (a.a_vec && a.b_vec) {
       // forward-form chain launches (activations x weights^T, M <= 128, K slice <= 6 k-tiles): single round trip kernel
-      static int chain_on = 1;
-      static int chain_ng = 0;
-      if (chain_on && tag_chain && !a_col && !b_col && M <= 128 && per <= GC_MAX_KT && !c_bf16 && !c2) {
+      if (tag_chain && !a_col && !b_col && M <= 128 && per <= GC_MAX_KT && !c_bf16 && !c2) {
         // 128-column workgroups unless that leaves half the chip idle (e.g. the decoder's N = 4H + A = 2176)
-        const int ng = chain_ng ? chain_ng : ((((N + 127) / 128) * splitk >= 128) ? 2 : 1);
+        const int ng = (((N + 127) / 128) * splitk >= 128) ? 2 : 1;
         const bool done = ng == 1 ? launch_chain<1>(a, per, st, tag_chain) : launch_chain<2>(a, per, st, tag_chain);
         if (done) goto after_launch;
       }
       // both operands bf16 in memory: the DMA-staged ring kernel.  Chain launches (tag > 0) run ~1 block
-      // per CU and want the deepest ring; batched GEMMs trade ring depth for 2 resident blocks per CU.
-      static const int ns_chain = 4;
-      static int ns_batch = 2;
-      const int ns = tag ? ns_chain : ns_batch;
+      // per CU and want the deepest ring (4 stages); batched GEMMs trade ring depth for 2 resident blocks per CU (2 stages).
       {
         // chain launch, row/row: 96-column workgroups when that turns a partial wave of workgroups into one per CU
-        static int bn96 = 1;
         const int t128 = ((N + 127) / 128) * ((M + 127) / 128) * splitk, t96 = ((N + 95) / 96) * ((M + 127) / 128) * splitk;
-        if (bn96 && tag == RN_TAG_REC_FWD && !a_col && !b_col && ns >= 4 && N % 96 == 0 && t128 < 224 && t96 <= 256) {
+        if (tag == RN_TAG_REC_FWD && !a_col && !b_col && N % 96 == 0 && t128 < 224 && t96 <= 256) {
           launch_lds_96<4, RN_TAG_REC_FWD>(a, st);
           goto after_launch;
         }
       }
-      if (ns >= 4) launch_lds<4>(a, a_col, b_col, grid, st, tag);
-      else if (ns == 3) launch_lds<3>(a, a_col, b_col, grid, st, tag);
+      if (tag) launch_lds<4>(a, a_col, b_col, grid, st, tag);
       else launch_lds<2>(a, a_col, b_col, grid, st, tag);
     } else launch_layout<bf16_t, bf16_t, bf16_t>(a, a_col, b_col, grid, st, 0);   // unaligned bf16 operands
   } else {

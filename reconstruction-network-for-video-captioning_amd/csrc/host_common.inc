@@ -125,11 +125,8 @@ static int gemm_slabs(recnet_handle* h, int tag, const void* A, int lda, const v
   float* slab = dst ? dst : h->slab;
   // split-K caps per site: more slices than this buy nothing for the GEMM (measured) and every slab is re-read by
   // the consumer kernel
-  static const int cap_env = 0;
-  static const int dbwd_cap = 16;
-  int cap = (tag == RN_TAG_DEC_FWD) ? 4 : (tag == RN_TAG_DEC_BWD ? (b_col ? 8 : dbwd_cap) : 16);
+  int cap = (tag == RN_TAG_DEC_FWD) ? 4 : ((tag == RN_TAG_DEC_BWD && b_col) ? 8 : 16);
   if (dst) cap = 8;
-  if (cap_env) cap = cap_env;
   int s = rn_pick_splitk(h->prec, M, N, K, cap, 1);
   while (s > 1 && (size_t)s * M * N > h->slab_floats) s >>= 1;
   if (s < 2) s = 2;  // always use the slab path so the consumer code is uniform
@@ -352,8 +349,7 @@ static int pack_weights(recnet_handle* h, hipStream_t st) {
 }
 
 static void launch_dec_cell(recnet_handle* h, const DecCellArgs& a, hipStream_t st) {
-  static const int vec_env = 1;
-  if (vec_env && h->lp && (h->H & 7) == 0 && h->F <= 32 && h->A <= 128 && (h->ld4H & 7) == 0) {
+  if (h->lp && (h->H & 7) == 0 && h->F <= 32 && h->A <= 128 && (h->ld4H & 7) == 0) {
     const size_t smv = (size_t)(h->A + ((h->F + 3) & ~3) + 4 * 512 + 16) * 4;
     hipLaunchKernelGGL(dec_cell_vec_kernel<bf16_t>, dim3(h->B, cdiv(h->H, 512)), dim3(256), smv, st, a);
     return;

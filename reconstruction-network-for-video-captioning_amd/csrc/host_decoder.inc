@@ -13,20 +13,13 @@ static int dec_fwd_chain(recnet_handle* h, const float* enc, const int64_t* targ
   if (!h->norms_hoisted) param_norms(h, 0, h->scal + 1, st);
   // The input part of the gates (embeddings -> Xe) does not depend on the features: in the fused step it runs on the side
   // stream beside the feature products Uv / P (ev[8] joins it in front of the chain)
-  static const int f_pro = 1;
-  const bool fork_xe = f_pro && !free_tokens && h->overlap && h->s2 && h->hoist_pending && h->hoist_par;
+  const bool fork_xe = !free_tokens && h->overlap && h->s2 && h->hoist_pending && h->hoist_par;
   // bf16 path, round 4: the three products of the prologue — Xe, Uv, P — are ONE grouped launch (774 tiles in one hardware
   // queue instead of launches of 400, 22 and 352 workgroups): only the embedding gather runs beside the feature cast
-  static const int f_pg = 1;
-  const bool pro_group = f_pg && fork_xe && h->lp;
-  static const int f_ps = 0;      // (measured: 1.748 against 1.720 ms at C2 — off)
-  if (pro_group && f_ps) {
-    // three small kernels in a row on the step's own stream: ~20 us, and no cross-queue join in front of the grouped launch
-    gate_bias(h->dP.rnn_bias_ih_l0, h->dP.rnn_bias_hh_l0, h->bsum_d, H, h->dgru, st);   // Xe's bias
-    embed_fwd(h, targets, nullptr, T * B, train, 0, st);
-    pack_block(h, h->enc_lp, h->ldD, enc, h->D, B * F, h->D, 1.f, st);
-  } else if (pro_group) {
+  const bool pro_group = fork_xe && h->lp;
+  if (pro_group) {
     // gate bias, embedding gather and feature cast in one launch (kernels_util.hpp: prologue_pack_kernel)
+    // (measured and rejected: the three as separate kernels on the step's own stream, 1.748 against 1.720 ms at C2)
     ProPackArgs a;
     a.enc_lp = (bf16_t*)h->enc_lp; a.ld_enc = h->ldD; a.enc = enc; a.rowsE = B * F; a.D = h->D;
     a.Emb = h->dP.embedding_weight; a.targets = targets; a.emb = (bf16_t*)h->emb_lp; a.ld_emb = h->ldE; a.B = B; a.E = E; a.V = V;
@@ -68,8 +61,7 @@ static int dec_fwd_chain(recnet_handle* h, const float* enc, const int64_t* targ
   // captured in this order the chain stays on the prologue's hardware queue (the first-captured successor of a graph node does)
   // instead of paying a cross-queue hand-over of ~20 us on the critical path; the branches wait for the chain's residency anyway
   // (wait_chain_kernel)
-  static const int f_hac = 1;
-  const bool hoist_late = f_hac && h->hoist_pending && h->persist_dec && !free_tokens && (h->ld4H & 7) == 0 && h->overlap && h->s2;
+  const bool hoist_late = h->hoist_pending && h->persist_dec && !free_tokens && (h->ld4H & 7) == 0 && h->overlap && h->s2;
   if (hoist_late) { hipEventRecord(h->ev[4], st); hipEventRecord(h->ev[11], st); h->hoist_fork_recorded = 1; }
   else if (h->hoist_pending) hoist_side_work(h, st);     // forked here: beside the chain, behind the prologue (fwd_bwd_impl)
   if (h->persist_dec && !free_tokens && (h->ld4H & 7) == 0) {
@@ -85,13 +77,10 @@ static int dec_fwd_chain(recnet_handle* h, const float* enc, const int64_t* targ
     c.Xe = h->Xe + (size_t)b0 * 4 * H; c.G1 = h->dc_G1; c.Pan = (bf16_t*)h->dc_pan;
     c.Hs = h->Hs + (size_t)b0 * H; c.Cs = h->Cs + (size_t)b0 * H; c.acts = h->acts + (size_t)b0 * 4 * H; c.Hlp = (bf16_t*)h->Hs_lp + (size_t)b0 * h->ldH; c.ld_hlp = h->ldH;
     c.Wh = h->Wh + (size_t)b0 * A; c.att = h->att + (size_t)b0 * F; c.bar = h->gbar + 1024; c.ts = h->lc_ts + 4096; c.softmax = h->c.decoder_attn_normalize == RECNET_ATTN_SOFTMAX;
-    static const int f_ll = 1;
-    c.epoch = h->gbar + 2048; c.ll = f_ll && T <= 63;
-    static const int f_master = 1;
-    c.master = f_master; c.poison = h->scal + 15;
+    c.epoch = h->gbar + 2048; c.rep = h->gbar + 5376; c.poison = h->scal + 15;
     c.mp = h->kind == RECNET_REC_GLOBAL ? h->mp + (size_t)b0 * H : nullptr; c.mp_scale = (float)h->cml / ((float)T * (float)T);   // global_reconstructor.py:33-37
     h->mp_done = c.mp ? 1 : 0;
-    // RN_DEC_XCAT=1: the chain also writes the global reconstructor's input operand [h_t ; drop_t(mp)] (no xcat_global_kernel behind it)
+    // dec_xcat: the chain also writes the global reconstructor's input operand [h_t ; drop_t(mp)] (no xcat_global_kernel behind it)
     const int f_xcat = h->sw.dec_xcat;
     c.Xcat = nullptr; c.ld_xcat = 0; c.xdd = mkdrop(h, RN_SITE_REC_INPUT, h->c.reconstructor_decoder_dropout, train);
     // (not with the deferred reconstructor update: its pending weight-gradient products read the PREVIOUS step's operand while this chain runs)
@@ -100,39 +89,19 @@ static int dec_fwd_chain(recnet_handle* h, const float* enc, const int64_t* targ
       h->xcat_done = 1;
     }
     // LW (F <= 32): the attention projection is formed by the caption's own workgroup from an LDS-resident attn_W (dec_chain.hpp)
-    const int f_lw = h->sw.dec_lw;
-    // RP: phase A as 64 columns x one of 4 row parts, the B -> A hand-over inside the part (RN_DEC_PARTIAL, read per call like the BPTT's)
-    const int f_rp = h->sw.dec_rp;
-    const int f_partial = h->sw.dec_partial;
-    const bool lw = f_lw && c.ll && A <= 128 && H <= 512 && (H & 31) == 0 && F <= 32;
-    const bool rp = f_rp && c.ll && H <= 512;
-    c.partial = rp && f_partial; c.rep = h->gbar + 5376;
-    if (c.partial) c.master = 0;
-    const int NN = lw ? 4 * H : 4 * H + A;
-    const int NAx = rp ? DCF_NA(NN) : NN / 16;
-    const dim3 grid((NAx > nb ? NAx : nb) + (c.master ? 1 : 0));
+    const bool lw = h->sw.dec_lw && A <= 128 && H <= 512 && (H & 31) == 0 && F <= 32;
+    const int NAx = DCF_NA(lw ? 4 * H : 4 * H + A);
+    const dim3 grid(NAx > nb ? NAx : nb);
     if (F > 32) {      // frames 32 .. 47 from LDS
       const size_t dyn = (size_t)DC_XF * 2048 * 2 + (size_t)DC_XF * 128 * 4;
-      if (rp) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(dec_chain_kernel<true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
-        hipLaunchKernelGGL((dec_chain_kernel<true, false, true>), grid, dim3(256), dyn, st, c);
-      } else {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(dec_chain_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
-        hipLaunchKernelGGL(dec_chain_kernel<true>, grid, dim3(256), dyn, st, c);
-      }
-    } else if (lw && (c.master || c.partial)) {
+      hipFuncSetAttribute(reinterpret_cast<const void*>(dec_chain_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
+      hipLaunchKernelGGL((dec_chain_kernel<true, false>), grid, dim3(256), dyn, st, c);
+    } else if (lw) {
       const size_t dyn = (size_t)128 * 512 * 2;
-      if (rp) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(dec_chain_kernel<false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
-        hipLaunchKernelGGL((dec_chain_kernel<false, true, true>), grid, dim3(256), dyn, st, c);
-      } else {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(dec_chain_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
-        hipLaunchKernelGGL((dec_chain_kernel<false, true>), grid, dim3(256), dyn, st, c);
-      }
-    } else if (rp) {
-      hipLaunchKernelGGL((dec_chain_kernel<false, false, true>), grid, dim3(256), 0, st, c);
+      hipFuncSetAttribute(reinterpret_cast<const void*>(dec_chain_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
+      hipLaunchKernelGGL((dec_chain_kernel<false, true>), grid, dim3(256), dyn, st, c);
     } else {
-      hipLaunchKernelGGL(dec_chain_kernel<false>, grid, dim3(256), 0, st, c);
+      hipLaunchKernelGGL((dec_chain_kernel<false, false>), grid, dim3(256), 0, st, c);
     }
    }
     if (pe) hipEventRecord(pe, st);
@@ -249,20 +218,16 @@ static int dec_bwd_chain(recnet_handle* h, const float* dhid, hipStream_t st) {
     c.G2 = h->dc_G2; c.Pan = (bf16_t*)h->dc_pan2; c.dGx = (bf16_t*)h->dGx + (size_t)b0 * ldWS; c.ld_dgx = ldWS;
     c.dUv = h->dUv + (size_t)b0 * F * A; c.dUv_lp = (bf16_t*)h->dUv_lp + (size_t)b0 * F * h->ldA; c.ld_dUv = h->ldA; c.dwacc = h->dwacc + (size_t)b0 * A;
     c.bar = h->gbar + 1536; c.ts = h->lc_ts + 4096 + 512;
-    static const int f_ll = 1;
-    c.epoch = h->gbar + 2049; c.ll = f_ll && T <= 63;
-    static const int f_master = 1;
-    // partial B' -> A' hand-over (dec_chain.hpp): the arrival flags of a row part polled by the part's own unit owners, no master
-    const int f_partial = h->sw.dec_partial;
-    c.partial = f_partial && c.ll; c.rep = h->gbar + 4352;
-    c.master = c.partial ? 0 : f_master; c.poison = h->scal + 15;
+    // the B' -> A' hand-over (dec_chain.hpp): the arrival flags of a row part polled by the part's own unit owners
+    c.epoch = h->gbar + 2049; c.rep = h->gbar + 4352; c.poison = h->scal + 15;
     const int NAb = DCB_NA(H);
+    const dim3 grid(NAb > nb ? NAb : nb);
     if (F > 32) {
       const size_t dyn = (size_t)DC_XF * DCB_PLD * 2 + (size_t)2 * DC_XF * 128 * 4;
       hipFuncSetAttribute(reinterpret_cast<const void*>(dec_chain_bwd_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
-      hipLaunchKernelGGL(dec_chain_bwd_kernel<true>, dim3((NAb > nb ? NAb : nb) + (c.master ? 1 : 0)), dim3(256), dyn, st, c);
+      hipLaunchKernelGGL(dec_chain_bwd_kernel<true>, grid, dim3(256), dyn, st, c);
     } else {
-      hipLaunchKernelGGL(dec_chain_bwd_kernel<false>, dim3((NAb > nb ? NAb : nb) + (c.master ? 1 : 0)), dim3(256), 0, st, c);
+      hipLaunchKernelGGL(dec_chain_bwd_kernel<false>, grid, dim3(256), 0, st, c);
     }
    }
     if (pe) hipEventRecord(pe, st);
@@ -320,26 +285,17 @@ static int dec_bwd_deferred_rows(recnet_handle* h, const float* enc, const int64
   const int GH = (h->dgru ? 3 : 4) * H;   // rows of the master W_ih / W_hh: gate blocks (r, z, n) or (i, f, g, o)
   void* dG = at_off(h, h->dGx, r0 * ldWS);
   // dgates live in columns [0,4H) of dGx, dWh chunks behind them
-  // RN_TAIL_EMB_SIDE=1: the embedding branch (d emb product + the two scatter kernels, ~120 us in a row) goes with the second
-  // stream's half when there is one (the first stream's half is ~320 us of kernels against ~130 us).  Measured and rejected
-  // (round 3): C2 1.979 against 1.931 ms, C3 2.329 against 2.295 ms — the side stream is still busy with the reconstructor's
-  // Adam step when the chain ends, so the branch only starts later there.
-  static const int f_embside = 0;
-  const bool emb_side = f_embside && st2 && st2 != st;
-  auto embedding_branch = [&](hipStream_t st) {
-    gemm(h, dG, 0, ldWS, h->We_w, 1, h->ldE, h->demb + r0 * E, E, nullptr, nrow, E, 4 * H, 1.f, 0, st);
-    if (!acc && !h->prezeroed) hipMemsetAsync(h->dGd.embedding_weight, 0, (size_t)V * E * 4, st);
-    hipLaunchKernelGGL(embed_bwd_kernel, dim3(nrow), dim3(128), 0, st, h->dGd.embedding_weight, targets, h->demb, B, E, V,
-                       h->c.embedding_scale, mkdrop(h, RN_SITE_DEC_EMBED, h->c.embedding_dropout, train), (int)r0,
-                       (const int64_t*)(h->free_fwd ? h->in_tok : nullptr));
-    hipLaunchKernelGGL(embed_bwd_hot_kernel, dim3(cdiv(E, 128), cdiv(nrow, RN_HOT_ROWS)), dim3(128), 0, st, h->dGd.embedding_weight, targets, h->demb, B, E, V,
-                       h->c.embedding_scale, mkdrop(h, RN_SITE_DEC_EMBED, h->c.embedding_dropout, train), (int)r0, nrow,
-                       (const int64_t*)(h->free_fwd ? h->in_tok : nullptr));
-  };
-  {
-    if (!emb_side) embedding_branch(st);
-    gemm(h, dG, 1, ldWS, at_off(h, h->emb_lp, r0 * h->ldE), 1, h->ldE, h->dGd.rnn_weight_ih_l0, E + D, nullptr, GH, E, nrow, 1.f, acc, st);
-  }
+  // the embedding branch: d emb product + the two scatter kernels (measured and rejected, round 3: on the second stream's half,
+  // C2 1.979 against 1.931 ms — the side stream is still busy with the reconstructor's Adam step when the chain ends)
+  gemm(h, dG, 0, ldWS, h->We_w, 1, h->ldE, h->demb + r0 * E, E, nullptr, nrow, E, 4 * H, 1.f, 0, st);
+  if (!acc && !h->prezeroed) hipMemsetAsync(h->dGd.embedding_weight, 0, (size_t)V * E * 4, st);
+  hipLaunchKernelGGL(embed_bwd_kernel, dim3(nrow), dim3(128), 0, st, h->dGd.embedding_weight, targets, h->demb, B, E, V,
+                     h->c.embedding_scale, mkdrop(h, RN_SITE_DEC_EMBED, h->c.embedding_dropout, train), (int)r0,
+                     (const int64_t*)(h->free_fwd ? h->in_tok : nullptr));
+  hipLaunchKernelGGL(embed_bwd_hot_kernel, dim3(cdiv(E, 128), cdiv(nrow, RN_HOT_ROWS)), dim3(128), 0, st, h->dGd.embedding_weight, targets, h->demb, B, E, V,
+                     h->c.embedding_scale, mkdrop(h, RN_SITE_DEC_EMBED, h->c.embedding_dropout, train), (int)r0, nrow,
+                     (const int64_t*)(h->free_fwd ? h->in_tok : nullptr));
+  gemm(h, dG, 1, ldWS, at_off(h, h->emb_lp, r0 * h->ldE), 1, h->ldE, h->dGd.rnn_weight_ih_l0, E + D, nullptr, GH, E, nrow, 1.f, acc, st);
   // ctx_t = (1/F) sum_f a_t[f] enc[b,f] for these steps (only needed here), then dW_ih[:, E:] (+)= dgates^T . ctx
   {
     if (!h->ctx_done) dec_ctx_rows(h, enc, t0, t1, st);
@@ -349,7 +305,6 @@ static int dec_bwd_deferred_rows(recnet_handle* h, const float* enc, const int64
   // the rest touches other gradient tensors: on a second stream (with the second split-K workspace) when the caller has one
   float* const gws_keep = h->gws_cur;
   if (st2 && st2 != st) { st = st2; h->gws_cur = h->gws2; }
-  if (emb_side) embedding_branch(st);
   // dWh_t = sum of its RN_FCH frame-chunk partials (operand of dW_attn and source of d attn_b)
   {
     const size_t n = (size_t)nrow * h->ldA;
@@ -451,8 +406,7 @@ static int dec_bwd_deferred_grouped(recnet_handle* h, const float* enc, const in
 }
 static int dec_bwd_deferred(recnet_handle* h, const float* enc, const int64_t* targets, hipStream_t st, hipStream_t st2 = nullptr, hipStream_t st3 = nullptr) {
   RN_RANGE("recnet: decoder deferred weight gradients");
-  static const int f_tg = 1;
-  if (f_tg && h->lp) return dec_bwd_deferred_grouped(h, enc, targets, st, st2, st3);
+  if (h->lp) return dec_bwd_deferred_grouped(h, enc, targets, st, st2, st3);
   int r = dec_bwd_deferred_rows(h, enc, targets, 0, h->T_last, 0, st, st2); if (r) return r;
   if (st2 && st2 != st) {
     float* const keep = h->gws_cur;

@@ -65,16 +65,13 @@ static int fwd_rec_global(recnet_handle* h, const float* enc, int T, int train, 
   }
   // Xg = [h_t ; drop_t(mp)] . W_ih^T + b_ih + b_hh, batched over T (only h_r . W_hh^T is recurrent)
   gemm(h, h->Xcat_g, 0, h->ld2H, h->Wih_f, 0, h->ld2H, h->Xg, 4 * R, h->bsum_r, T * B, 4 * R, 2 * H, 1.f, 0, st);
-  // RN_SIDE_AFTER_CHAIN=1: the side work (vocabulary projection, CE, ...) is enqueued BEHIND the chain launch, with its fork
-  // event recorded in front of it — so that the chain's workgroups, which need whole CUs, are dispatched before the
-  // projection's workgroups start filling every CU partly
-  // (C2: 1.926 -> 1.913 ms)
-  static const int f_sac = 1;
+  // The side work (vocabulary projection, CE, ...) is enqueued BEHIND the chain launch, with its fork event recorded in front of
+  // it — so that the chain's workgroups, which need whole CUs, are dispatched before the projection's workgroups start filling
+  // every CU partly (C2: 1.926 -> 1.913 ms)
   // (one-graph step only: in the data-parallel three-graph form it costs 0.17 ms — 2.31 against 2.14 ms at one rank)
-  const bool side_late = f_sac && h->in_fused && h->side_pending && h->overlap && h->s2 && h->persist_rec;
+  const bool side_late = h->in_fused && h->side_pending && h->overlap && h->s2 && h->persist_rec;
   if (side_late) { hipEventRecord(h->ev[0], st); h->side_fork_recorded = 1; }
-  else if (h->side_pending) side_after_decoder_fwd(h, st);       // see fwd_bwd_impl (RN_SIDE_LATE)
-  if (h->join_pending && h->join_early) { join_from(h, 1, st, h->s2); h->join_pending = 0; }   // see fwd_bwd_impl (RN_SIDE_JOIN)
+  else if (h->side_pending) side_after_decoder_fwd(h, st);       // see fwd_bwd_impl
   if (h->rec_wait_pending) { hipStreamWaitEvent(st, h->ev[12], 0); h->rec_wait_pending = 0; }      // W_hh's pending update (mode 2)
   // batches above RC_PAN_ROWS captions run the chain once per row group (h->bgrp rows each, csrc/api.hip): a group is an
   // independent batch for the chain — same weights, its own rows of every [T][B][.] tensor (row stride Bs = B)
@@ -88,8 +85,7 @@ static int fwd_rec_global(recnet_handle* h, const float* enc, int T, int train, 
     a.Xg = h->Xg + (size_t)b0 * 4 * R; a.H = h->Hr + (size_t)b0 * R; a.C = h->Cr + (size_t)b0 * R; a.acts = h->acts_r + (size_t)b0 * 4 * R;
     a.hmean = h->hrmean + (size_t)b0 * R; a.hmean_lp = (bf16_t*)h->hrmean_lp + (size_t)b0 * h->ldR; a.ld_hmean = h->ldR;
     a.bar = h->gbar; a.epoch = h->gbar + 2050;
-    static const int f_master = 1;
-    a.master = f_master && R / 8 + 1 <= h->ncu;      // the master needs a CU of its own
+    a.master = R / 8 + 1 <= h->ncu;      // the master needs a CU of its own
     a.poison = h->scal + 15;
     const int steps = (R + 127) / 128;
     a.epi = 0;
@@ -99,7 +95,7 @@ static int fwd_rec_global(recnet_handle* h, const float* enc, int T, int train, 
     if (split && (R & 15) == 0) {
       const dim3 g(R / 16 + a.master, 2);
       const size_t sm = rc_smem_bytes<4, 4>();
-      // RN_REC_EPILOGUE=1: output layer + MSE + d out as an epilogue of the chain (rec_chain.hpp) instead of a split-K GEMM, its
+      // rec_epi 1: output layer + MSE + d out as an epilogue of the chain (rec_chain.hpp) instead of a split-K GEMM, its
       // reduction and the MSE kernel between the two chains (C2: 1.837 -> 1.815 ms)
       const int f_epi = h->sw.rec_epi;
       if (f_epi && a.master && h->lp && h->ldR == R && nb == B && h->hm_pan) {
@@ -109,7 +105,7 @@ static int fwd_rec_global(recnet_handle* h, const float* enc, int T, int train, 
         a.epi = 1; a.Wo = (const bf16_t*)h->Wor_w; a.ldwo = h->ldR; a.obias = h->rP.out_bias; a.target = h->encmean;
         a.dout = h->outm; a.dout_lp = (bf16_t*)h->dout_lp; a.PanM = (bf16_t*)h->hm_pan; a.mse_part = h->msep;
         a.gcoef = (float)(2.0 / (cnt * T)); a.lp_scale = h->c.lambda_recon;
-        // RN_REC_EPILOGUE=2: + d loss / d mean_t h_t = dout . W_o behind one more barrier phase (no product between the two chains)
+        // rec_epi 2: + d loss / d mean_t h_t = dout . W_o behind one more barrier phase (no product between the two chains)
         a.WoT = nullptr; a.ldwot = 0; a.PanD = nullptr; a.dhr = nullptr;
         if (f_epi > 1 && h->WoT && h->hd_pan && h->persist_rec_bwd) {
           a.epi = 2; a.WoT = (const bf16_t*)h->WoT; a.ldwot = h->ldR; a.PanD = (bf16_t*)h->hd_pan; a.dhr = h->dhrmean;
@@ -218,14 +214,13 @@ static int bwd_rec_global(recnet_handle* h, float gscale, float* dhid_out, hipSt
     a.dh_direct = h->dhrmean + (size_t)b0 * R; a.dh_scale = 1.0f / (float)T;
     a.acts = h->acts_r + (size_t)b0 * 4 * R; a.C = h->Cr + (size_t)b0 * R; a.H = h->Hr + (size_t)b0 * R;
     a.bar = h->gbar + 512; a.epoch = h->gbar + 2051;
-    static const int f_master = 1;
-    a.master = f_master && (R / 16) * (nb > 64 ? 2 : 1) + 1 <= h->ncu;
+    a.master = (R / 16) * (nb > 64 ? 2 : 1) + 1 <= h->ncu;
     a.poison = h->scal + 15;
     const int steps = (4 * R + 127) / 128;
     // above 64 captions and up to R = 1536: 32 units x 32 rows per workgroup (a third of its weights in LDS), four row parts
     const int f_wide = h->sw.rec_wide;
     const bool wide = f_wide && nb > 64 && (R & 31) == 0 && steps > 32 && steps <= 48 && (R / 32) * 4 + 1 <= h->ncu;
-    if (wide) a.master = f_master;
+    if (wide) a.master = 1;
     const dim3 g((wide ? R / 32 : R / 16) + a.master, wide ? 4 : (nb > 64 ? 2 : 1));
     const size_t sm = rc_bwd_smem_bytes<4, 1>();
     if (wide) {
@@ -406,7 +401,6 @@ static int bwd_rec_local(recnet_handle* h, float gscale, float* dhid_out, hipStr
     c.bar = h->gbar + 3072; c.epoch = h->gbar + 2053; c.poison = h->scal + 15;
     c.dd = mkdrop(h, RN_SITE_REC_INPUT, h->c.reconstructor_decoder_dropout, train); c.dd.boff += b0; c.ts = h->lc_ts;
     const dim3 g(c.NWG);
-    static const int f_nl = 1;      // 0: no LDS-resident k-steps (measurement knob)
     // (round 4: every even R / 128 in 18 ... 32, i.e. R = 2304 ... 4096 in steps of 256 — round 3 had the benchmark's 24 / 28 / 32 only)
     if (h->lb_steps == 18) rc_launch(h, RN_SITE_REC_CHAIN_BWD, (lcbig_bwd_kernel<18, LB_SR(18), LB_PF, LB_NL>), g, lcbig_smem_bytes<LB_NL>(), st, c);
     else if (h->lb_steps == 20) rc_launch(h, RN_SITE_REC_CHAIN_BWD, (lcbig_bwd_kernel<20, LB_SR(20), LB_PF, LB_NL>), g, lcbig_smem_bytes<LB_NL>(), st, c);
@@ -414,8 +408,7 @@ static int bwd_rec_local(recnet_handle* h, float gscale, float* dhid_out, hipStr
     else if (h->lb_steps == 24) rc_launch(h, RN_SITE_REC_CHAIN_BWD, (lcbig_bwd_kernel<24, LB_SR(24), LB_PF, LB_NL>), g, lcbig_smem_bytes<LB_NL>(), st, c);
     else if (h->lb_steps == 26) rc_launch(h, RN_SITE_REC_CHAIN_BWD, (lcbig_bwd_kernel<26, LB_SR(26), LB_PF, LB_NL>), g, lcbig_smem_bytes<LB_NL>(), st, c);
     else if (h->lb_steps == 30) rc_launch(h, RN_SITE_REC_CHAIN_BWD, (lcbig_bwd_kernel<30, LB_SR(30), LB_PF, LB_NL>), g, lcbig_smem_bytes<LB_NL>(), st, c);
-    else if (h->lb_steps == 28 && f_nl) rc_launch(h, RN_SITE_REC_CHAIN_BWD, (lcbig_bwd_kernel<28, LB_SR(28), LB_PF, LB_NL>), g, lcbig_smem_bytes<LB_NL>(), st, c);
-    else if (h->lb_steps == 28) rc_launch(h, RN_SITE_REC_CHAIN_BWD, (lcbig_bwd_kernel<28, LB_SR(28), LB_PF, 0>), g, lcbig_smem_bytes<0>(), st, c);
+    else if (h->lb_steps == 28) rc_launch(h, RN_SITE_REC_CHAIN_BWD, (lcbig_bwd_kernel<28, LB_SR(28), LB_PF, LB_NL>), g, lcbig_smem_bytes<LB_NL>(), st, c);
     else rc_launch(h, RN_SITE_REC_CHAIN_BWD, (lcbig_bwd_kernel<32, LB_SR(32), LB_PF, LB_NL>), g, lcbig_smem_bytes<LB_NL>(), st, c);
    }
     hipLaunchKernelGGL(lcbig_dhs_kernel, dim3(B, cdiv(H, 256), 2), dim3(256), 0, st, (const float*)h->beta, (const float*)h->lb_dxm, dhid_out, F, T, B, H);
@@ -438,8 +431,8 @@ static int bwd_rec_local(recnet_handle* h, float gscale, float* dhid_out, hipStr
     c.PanG = (bf16_t*)h->lc_pang; c.PanW = (bf16_t*)h->lc_panw; c.Dx = h->lc_dx;
     c.bar = h->gbar + 3072; c.epoch = h->gbar + 2053; c.poison = h->scal + 15;
     c.dd = mkdrop(h, RN_SITE_REC_INPUT, h->c.reconstructor_decoder_dropout, train); c.dd.boff += b0; c.ts = h->lc_ts;
-    static const int f_defer = 0;   // measured: +0.08 ms at B = 100 (X' is bound by its own CU's L1 fill rate, not by U')
-    c.defer_big = f_defer;
+    // (measured and rejected: U' waiting for X' to publish dx before its recurrent product, +0.08 ms at B = 100 — X' is bound by its
+    // own CU's L1 fill rate, not by U')
     const dim3 g(c.NGU * c.MSU + c.NGX * c.MSX * c.KSX + c.NC + 1);
     const int steps = (4 * R + 127) / 128;
     if (h->lcb_xs) {      // X' with the contraction split over workgroups (lcb_xsplit_role)
@@ -488,37 +481,20 @@ static int bwd_rec_local(recnet_handle* h, float gscale, float* dhid_out, hipStr
     const int Asz = RA <= 256 ? 256 : RA;
     const size_t sm = (size_t)(H + 2 * T + 2 * Asz + 16) * 4;
     // per step: LSTM backward -> GEMM dGr_s . [W_ih | W_hh] -> attention backward -> GEMM dWhr_s . W_r
-    // Split form (large R, where the product streams 117 MB per step): only its dx columns (N = H, W_ih) feed the attention
-    // backward and the small product behind it; the dhr columns (N = R, W_hh) feed nothing but the next LSTM backward.  The
-    // two branches run on two streams: [dG . W_ih -> attention backward -> dWhr . W_r] beside [dG . W_hh].
-    // RN_LOC_BWD_SPLIT=1 — measured and rejected (round 3, C5): 4.31 against 4.21 ms; a fork and a join per step in the
-    // replayed graph cost more than the ~20 us of overlap return (the same result as the forward's third-stream trial).
-    const int f_split = 0;
-    const bool split = f_split && h->overlap && h->s3 && h->slab3 && R >= 2048 && (H & 7) == 0;
-    a.slab_w = split ? H : 0;
+    // (measured and rejected, round 3, C5: the dx and dhr columns of the product on two streams, 4.31 against 4.21 ms)
+    a.slab_w = 0;
     int S1 = 0, S2 = 0;
     for (int s = F - 1; s >= 0; --s) {
-      lstm_bwd(h, R, S1, split ? R : H + R, split ? 0 : H, h->dHr + (size_t)s * B * R, R, 1.0f, h->acts_r + (size_t)s * B * 4 * R, h->Cr + (size_t)s * B * R,
+      lstm_bwd(h, R, S1, H + R, H, h->dHr + (size_t)s * B * R, R, 1.0f, h->acts_r + (size_t)s * B * 4 * R, h->Cr + (size_t)s * B * R,
                s > 0 ? (h->rgru ? h->Hr : h->Cr) + (size_t)(s - 1) * B * R : nullptr, h->dcr_carry, s == F - 1, at_off(h, h->dGr, (size_t)s * B * ld4R), ld4R, st,
                h->slab2, S2);
-      hipStream_t sa = st;            // stream of the attention branch
-      int Sx;
-      if (split) {
-        sa = h->s3;
-        fork_to(h, 13, st, sa);
-        Sx = gemm_slabs(h, RN_TAG_REC_ATT_BWD, at_off(h, h->dGr, (size_t)s * B * ld4R), ld4R, h->Wihh_w, 1, ldHR, B, H, 4 * R, sa, h->slab3);
-        if (s > 0) S1 = gemm_slabs(h, RN_TAG_REC_BWD, at_off(h, h->dGr, (size_t)s * B * ld4R), ld4R, at_off(h, h->Wihh_w, (size_t)H), 1, ldHR, B, R, 4 * R, st);
-      } else {
-        S1 = gemm_slabs(h, RN_TAG_REC_BWD, at_off(h, h->dGr, (size_t)s * B * ld4R), ld4R, h->Wihh_w, 1, ldHR, B, H + R, 4 * R, st);
-        Sx = S1;
-      }
-      a.s = s; a.S = Sx; a.slab = split ? h->slab3 : h->slab; a.first = (s == F - 1); a.last = (s == 0);
+      S1 = gemm_slabs(h, RN_TAG_REC_BWD, at_off(h, h->dGr, (size_t)s * B * ld4R), ld4R, h->Wihh_w, 1, ldHR, B, H + R, 4 * R, st);
+      a.s = s; a.S = S1; a.slab = h->slab; a.first = (s == F - 1); a.last = (s == 0);
       a.Whr = h->Whr + (size_t)s * B * RA; a.beta = h->beta + (size_t)s * B * T;
       a.dWhr = at_off(h, h->dWhr, (size_t)s * B * h->ldRA4);
-      LAUNCH_AT(h, loc_attn_bwd_kernel, dim3(B, RN_TCH), dim3(256), sm, sa, a);
+      LAUNCH_AT(h, loc_attn_bwd_kernel, dim3(B, RN_TCH), dim3(256), sm, st, a);
       if (s > 0)   // d hr_{s-1} (attention path) = (dWhr_s chunk partials) . [W_r ; .. ; W_r]
-        S2 = gemm_slabs(h, RN_TAG_REC_ATT_BWD, at_off(h, h->dWhr, (size_t)s * B * h->ldRA4), h->ldRA4, h->Wr4_w, 1, h->ldR, B, R, RN_TCH * RA, sa, h->slab2);
-      if (split) join_from(h, 12, st, sa);
+        S2 = gemm_slabs(h, RN_TAG_REC_ATT_BWD, at_off(h, h->dWhr, (size_t)s * B * h->ldRA4), h->ldRA4, h->Wr4_w, 1, h->ldR, B, R, RN_TCH * RA, st, h->slab2);
     }
   }
   { const int rr = rec_deferred_fork(h, st); if (rr) return rr; }

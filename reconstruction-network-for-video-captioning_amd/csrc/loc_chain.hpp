@@ -605,7 +605,6 @@ struct LocChainBwdArgs {
   bf16_t* PanG; bf16_t* PanW; float* Dx;    // exchange: [F][rc_pan_elems(4R)], [F][rc_pan_elems(A)], [F][KSX][B][H]
   unsigned* bar; unsigned* epoch; float* poison;
   DropDesc dd;
-  int defer_big;                     // 1: U' starts its recurrent product after X' has finished with the same panel (L2 bandwidth)
   unsigned long long* ts;            // probe builds only
 };
 
@@ -1041,9 +1040,8 @@ __global__ __launch_bounds__(256) void loc_chain_bwd_kernel(const LocChainBwdArg
       f32x4 acc[RBU];
 #pragma unroll
       for (int i = 0; i < RBU; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-      // dG_{s+1} is complete.  X' (on the critical path) streams the same 1.4 MB panel out of the L2s at the same time: with
-      // defer_big U' waits until X' has published dx (its own product is only needed after C' has finished as well)
-      if (p.defer_big) lc_wait(relX, fb + (unsigned)q, p.bar); else lc_wait(relG, fb + (unsigned)q, p.bar);
+      // dG_{s+1} is complete (X', on the critical path, streams the same 1.4 MB panel out of the L2s at the same time)
+      lc_wait(relG, fb + (unsigned)q, p.bar);
       if (wg == 0) LC_TS(4, q, 0);
       lcb_product<STEPS, PF, RBU>(acc, wb, p.PanG + (size_t)(q - 1) * pan_g + lane_off, K, kw0, rot);
       if (wg == 0) LC_TS(4, q, 1);

@@ -98,6 +98,25 @@ def test_bad_configs_are_rejected(lib, over, msg):
     assert msg in lib.recnet_last_error()
 
 
+@pytest.mark.parametrize("var,value", [("RN_ALT", "dec_all_rows"), ("RN_ALT", "bogus"), ("RN_PER_STEP", "rec,decoder")])
+def test_unknown_switch_names_are_rejected(lib, monkeypatch, var, value):
+    monkeypatch.setenv(var, value)
+    h = C.c_void_p()
+    c = _cfg()
+    assert lib.recnet_create(C.byref(c), C.byref(h)) == -1
+    msg = lib.recnet_last_error()
+    assert var.encode() in msg and value.split(",")[-1].encode() in msg, msg
+
+
+@pytest.mark.parametrize("var,value", [("RN_PER_STEP", "rec, dec"), ("RN_PER_STEP", "all"), ("RN_ALT", " dec_no_xcat ,loc_no_hybrid")])
+def test_known_switch_names_are_accepted(lib, monkeypatch, var, value):
+    monkeypatch.setenv(var, value)
+    h = C.c_void_p()
+    c = _cfg()
+    assert lib.recnet_create(C.byref(c), C.byref(h)) == 0, lib.recnet_last_error()
+    lib.recnet_destroy(h)
+
+
 def test_product_path_fails_loudly_without_gpu():
     import torch
     if torch.cuda.is_available():

@@ -68,8 +68,6 @@ RN_GEMM_GROUP=0 timeout -k 10 600 python3 bench.py $x > $O/bench_c2_no_grouped_l
 RN_ALT=dec_wh_in_phase_a timeout -k 10 600 python3 bench.py $x > $O/bench_c2_attention_projection_in_phase_A.json 2>/dev/null
 RN_ADAM_EPILOGUE=0 timeout -k 10 600 python3 bench.py $x > $O/bench_c2_adam_kernel_instead_of_epilogue.json 2>/dev/null
 RN_WAIT_CHAIN=0 timeout -k 10 600 python3 bench.py $x > $O/bench_c2_no_residency_waits.json 2>/dev/null
-RN_ALT=dec_relayed_barrier timeout -k 10 600 python3 bench.py $x > $O/bench_c2_relayed_barrier_in_decoder_chains.json 2>/dev/null
-RN_ALT=dec_all_rows timeout -k 10 600 python3 bench.py $x > $O/bench_c2_forward_phase_A_all_rows.json 2>/dev/null
 # the data-parallel step at ONE rank (no byte crosses xGMI): one captured graph with the collectives inside / three graphs
 timeout -k 10 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --force-allreduce $x > $O/bench_c2_dp_one_rank_one_graph.json 2>/dev/null
 RN_DP_ONE_GRAPH=0 timeout -k 10 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29518 bench.py --gpus 1 --force-allreduce $x > $O/bench_c2_dp_one_rank_three_graphs.json 2>/dev/null

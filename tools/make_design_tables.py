@@ -45,8 +45,7 @@ print()
 var = [("update inside the step", "c2_update_inside_the_step"), ("C3, update inside the step", "c3_update_inside_the_step"),
        ("whole update deferred (mode 1)", "c2_deferred_reconstructor_update"), ("no grouped launches", "c2_no_grouped_launches"),
        ("`RN_ADAM_EPILOGUE=0`", "c2_adam_kernel_instead_of_epilogue"), ("no residency waits", "c2_no_residency_waits"),
-       ("attention projection in phase A", "c2_attention_projection_in_phase_A"), ("relayed barrier in the decoder chains", "c2_relayed_barrier_in_decoder_chains"),
-       ("phase A over all rows", "c2_forward_phase_A_all_rows"), ("host feed", "c2_host_feed"), ("host feed (2)", "c2_host_feed_2"), ("resident (2)", "c2_resident_2"),
+       ("attention projection in phase A", "c2_attention_projection_in_phase_A"), ("host feed", "c2_host_feed"), ("host feed (2)", "c2_host_feed_2"), ("resident (2)", "c2_resident_2"),
        ("resident (3)", "c2_resident_3"), ("one rank, all-reduce forced, one graph", "c2_dp_one_rank_one_graph"),
        ("one rank, three graphs", "c2_dp_one_rank_three_graphs"), ("C2 at B = 200, per-step kernels", "c2_B200_per_step_kernels"),
        ("C4 weak, per-step kernels", "c4_weak_B256_per_step_kernels"), ("C5, per-step forward", "c5_per_step_forward"), ("C5, per-step kernels", "c5_per_step_kernels"),

@@ -1,9 +1,9 @@
-// gemm_wide_kernel (csrc/gemm_wide.hpp) against gemm_lds_kernel (128 x 128 tiles) and hipBLASLt (fp32 output) on the step's
+// gemm_wide_kernel (gemm_wide.hpp, beside this file) against gemm_lds_kernel (128 x 128 tiles) and hipBLASLt (fp32 output) on the step's
 // large products: correctness of every (tile width, split) candidate against a plain fp32 reference kernel on random operands,
 // then warm (20 back-to-back launches) and cold (each launch behind a 640 MB streaming kernel) times.
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -I../../include tools/micro/gemm_wide_probe.hip -o tools/micro/gemm_wide_probe -lhipblaslt
 // The vendor library is linked into this TOOL only (the yardstick); the product library does not use it.
-#include "../../reconstruction-network-for-video-captioning_amd/csrc/gemm_wide.hpp"
+#include "gemm_wide.hpp"
 #include <hipblaslt/hipblaslt.h>
 #include <stdio.h>
 #include <stdlib.h>
