@@ -389,7 +389,7 @@ int recnet_dp_reduce(const void* recv, int32_t world, int64_t chunk, void* red, 
 int recnet_read_step_ring(recnet_handle* h, uint64_t* out16, void* stream);
 int recnet_chain_status(recnet_handle* h, int32_t* status_out, void* stream);
 int recnet_chain_reset(recnet_handle* h, int32_t disable_persistent, void* stream);
-/* Test hook: what a chain kernel does when it gives up a bounded wait (rec_chain.hpp: rc_give_up) — raises the sticky word
+/* Test hook: what a chain kernel does when it gives up a bounded wait (chain_sync.hpp: rc_give_up) — raises the sticky word
  * of chain `chain_bit` (one of 1, 2, 4, 8, 32, 64) and the poison word, stream-ordered. */
 int recnet_debug_raise_give_up(recnet_handle* h, int32_t chain_bit, void* stream);
 /* Test hook: a kernel of `n_workgroups` workgroups that each take a whole CU (160 KB of LDS) and spin for `microseconds` —

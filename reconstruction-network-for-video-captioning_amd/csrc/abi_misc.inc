@@ -86,21 +86,20 @@ int32_t recnet_dim(const recnet_handle* h, int32_t which) {
 }
 
 // Health of the persistent chain kernels.  Every wait inside them is bounded; a waiter that gives up raises a sticky word
-// in its chain's barrier block and the step's total loss becomes NaN (rec_chain.hpp: rc_give_up / rc_poison), and the
+// in its chain's barrier block and the step's total loss becomes NaN (chain_sync.hpp: rc_give_up / cs_finish), and the
 // optimiser kernels leave the parameters alone from then on.  recnet_chain_status synchronises the stream and returns a
 // bit per chain (1 reconstructor fwd, 2 reconstructor bwd, 4 decoder fwd, 8 decoder BPTT, 32 / 64 local reconstructor
 // fwd / bwd, 256 the poisoned-loss word); recnet_chain_reset clears the words and, with disable_persistent != 0, makes
 // every later launch sequence of this handle use the per-step kernels (graphs captured earlier must be re-captured).
-#define RN_CHAIN_BLOCKS 7
 int recnet_chain_status(recnet_handle* h, int32_t* status_out, void* stream) {
   REQUIRE_WS(h);
   if (!status_out) return fail(RECNET_EINVAL, "null argument");
-  uint32_t w[RN_CHAIN_BLOCKS]; float poison = 0.f;
+  uint32_t w[CS_WS_BLOCKS]; float poison = 0.f;
   HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-  for (int k = 0; k < RN_CHAIN_BLOCKS; ++k) HIPCHK(hipMemcpy(&w[k], h->gbar + 512 * k + 257, 4, hipMemcpyDeviceToHost));
+  for (int k = 0; k < CS_WS_BLOCKS; ++k) HIPCHK(hipMemcpy(&w[k], cs_ws_sticky(h->gbar, k), 4, hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(&poison, h->scal + 15, 4, hipMemcpyDeviceToHost));
   int32_t s = 0;
-  for (int k = 0; k < RN_CHAIN_BLOCKS; ++k) if (w[k]) s |= 1 << k;
+  for (int k = 0; k < CS_WS_BLOCKS; ++k) if (w[k]) s |= 1 << k;
   if (poison != 0.f) s |= 256;      // NaN != 0
   *status_out = s;
   return RECNET_OK;
@@ -112,9 +111,9 @@ int recnet_read_stamps(recnet_handle* h, uint64_t* out, int32_t n, void* stream)
   // (every copy BEHIND the synchronisation: the library's and torch's streams do not block on the null stream, so a blocking copy in
   // front of it could return the stamps of a step that has not finished)
   HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-  if (n >= 30) HIPCHK(hipMemcpy(&out[14], h->gbar + 2048 + 128, 16 * 8, hipMemcpyDeviceToHost));      // grouped launches: 8 x (start, end)
+  if (n >= 30) HIPCHK(hipMemcpy(&out[14], h->gbar + CS_WS_GROUP_STAMPS, 16 * 8, hipMemcpyDeviceToHost));      // grouped launches: 8 x (start, end)
   HIPCHK(hipMemcpy(&out[0], h->ctrl + 32, 8, hipMemcpyDeviceToHost));                       // step start (advance_step_kernel)
-  HIPCHK(hipMemcpy(&out[1], h->gbar + 2048 + 64, 12 * 8, hipMemcpyDeviceToHost));           // six chains x (begin, end): rc_stamp_slot
+  HIPCHK(hipMemcpy(&out[1], h->gbar + CS_WS_STAMPS, 12 * 8, hipMemcpyDeviceToHost));           // six chains x (begin, end): rc_stamp_slot
   HIPCHK(hipMemcpy(&out[13], h->scal + 32, 8, hipMemcpyDeviceToHost));                      // step end (export_scalars_kernel)
   return RECNET_OK;
 }
@@ -153,7 +152,7 @@ int recnet_read_step_ring(recnet_handle* h, uint64_t* out16, void* stream) {
 int recnet_chain_reset(recnet_handle* h, int32_t disable_persistent, void* stream) {
   REQUIRE_WS(h);
   hipStream_t st = (hipStream_t)stream;
-  for (int k = 0; k < RN_CHAIN_BLOCKS; ++k) HIPCHK(hipMemsetAsync(h->gbar + 512 * k + 257, 0, 4, st));
+  for (int k = 0; k < CS_WS_BLOCKS; ++k) HIPCHK(hipMemsetAsync(cs_ws_sticky(h->gbar, k), 0, 4, st));
   HIPCHK(hipMemsetAsync(h->scal + 15, 0, 4, st));
   // a pending deferred reconstructor update belongs to a step whose results are void: drop it (the poison word that made its
   // Adam kernel a no-op is cleared above, so a later flush would otherwise apply the garbage step's gradients)
@@ -169,10 +168,10 @@ int recnet_chain_reset(recnet_handle* h, int32_t disable_persistent, void* strea
 int recnet_debug_raise_give_up(recnet_handle* h, int32_t chain_bit, void* stream) {
   REQUIRE_WS(h);
   int k = -1;
-  for (int i = 0; i < RN_CHAIN_BLOCKS; ++i) if (chain_bit == (1 << i)) k = i;
+  for (int i = 0; i < CS_WS_BLOCKS; ++i) if (chain_bit == (1 << i)) k = i;
   if (k < 0) return fail(RECNET_EINVAL, "chain_bit must be one chain's status bit");
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(set_u32_kernel, dim3(1), dim3(1), 0, st, h->gbar + 512 * k + 257, 1u);
+  hipLaunchKernelGGL(set_u32_kernel, dim3(1), dim3(1), 0, st, cs_ws_sticky(h->gbar, k), 1u);
   hipLaunchKernelGGL(set_u32_kernel, dim3(1), dim3(1), 0, st, (uint32_t*)(h->scal + 15), 0x7fc00000u);
   LAUNCH_OK();
   return RECNET_OK;

@@ -15,7 +15,7 @@
 //   abi_step.inc             sequence-level entry points and the fused train step (stream orchestration)
 //   abi_misc.inc             profiling hooks, bare GEMM entry points
 // Device code: kernels.hpp -> kernels_{util,decoder,reconstructor,search,optim}.hpp, gemm*.hpp (GEMMs),
-// rec_chain.hpp / loc_chain.hpp / dec_chain.hpp (the recurrent chains as persistent kernels), common.hpp.
+// rec_chain.hpp / loc_chain.hpp / dec_chain.hpp (the recurrent chains as persistent kernels; chain_sync.hpp: their hand-over protocol), common.hpp.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -67,7 +67,7 @@ struct recnet_handle {
   // workspace
   char* ws = nullptr; size_t ws_bytes = 0; size_t need = 0;
   uint32_t* ctrl;        // [0] seed slot, [1] step slot (int32)
-  uint32_t* gbar;        // [256] grid-barrier flags of rec_chain_kernel
+  uint32_t* gbar;        // barrier workspace of the chain kernels (chain_sync.hpp: CS_WS_*)
   float* scal;           // [0] dec_ce [1] dec_reg [2] dec_loss [3] rec_mse [4] rec_reg [5] rec_loss [6] total [7] gnorm [8] clip
   // ---- decoder: fp32 state
   float *slab2 = nullptr;   // second slab buffer (local reconstructor backward: dWhr . W_r)
@@ -182,7 +182,7 @@ static size_t carve(recnet_handle* h, char* base) {
   const size_t ldD = h->ldD, ldE = h->ldE, ldH = h->ldH, ldV = h->ldV, ldA = h->ldA, ld4H = h->ld4H, ldWS = h->ldWS,
                ldR = h->ldR, ld4R = h->ld4R, ldRA = h->ldRA, ldHR = h->ldHR;
   h->ctrl = (uint32_t*)take(64);
-  h->gbar = (uint32_t*)take(4096 + 64 + 2240);   // (floats: 16 KB) per chain kernel 256 arrival flags + 256 release words; epochs behind   // up to four persistent launches x 256 flags, then the launch-epoch words
+  h->gbar = (uint32_t*)take(CS_WS_WORDS);   // the barrier blocks of the chain kernels, their epochs and stamps, the decoder chains' replica lines (chain_sync.hpp)
   h->dc_G1 = take(2 * Tm * B * (4 * H + A));   // fp32, or 8-byte stamped words
   h->dc_pan = takev(Tm * rc_pan_elems((int)H) / 2 + 64);
   h->dc_G2 = take(2 * Tm * B * H * DCB_KS); h->dc_pan2 = takev(Tm * rc_pan_elems((int)(4 * H + A)) / 2 + 64);
@@ -407,7 +407,7 @@ int recnet_create(const recnet_config* cfg, recnet_handle** out) {
     hipGetDevice(&dev);
     hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
     h->ncu = ncu;
-    // Tm <= 60: stamped words carry epoch << 6 | step and barrier words epoch << 7 | phase (rec_chain.hpp) — a longer
+    // Tm <= 60: stamped words carry epoch << 6 | step and barrier words epoch << 7 | phase (chain_sync.hpp) — a longer
     // caption limit would let one launch's values run into the next epoch's, so it takes the per-step kernels
     h->persist_rec = chain_on("rec") && h->lp && h->kind == RECNET_REC_GLOBAL && Bg <= RC_PAN_ROWS && h->Tm <= 60 &&
                      (h->R & 7) == 0 && h->R <= 2048 && h->R / 8 <= ncu;   // <= 16 k-steps of resident weights per wave
@@ -576,7 +576,7 @@ int recnet_bind_workspace(recnet_handle* h, void* workspace, size_t bytes) {
   // gradients — by the fixed-shape products of a deferred reconstructor update, and 0 x NaN bit patterns would not be 0
   HIPCHK(hipMemset(h->ws, 0, h->need));
   // stamped exchange buffers and the launch-epoch words start from zero (a stamp is never zero)
-  HIPCHK(hipMemset(h->gbar, 0, (4096 + 64 + 2240) * 4)); HIPCHK(hipMemset(h->scal, 0, 64 * 4)); HIPCHK(hipMemset(h->dc_G1, 0, (size_t)2 * h->Tm * h->B * (4 * h->H + h->A) * 4));
+  HIPCHK(hipMemset(h->gbar, 0, CS_WS_WORDS * 4)); HIPCHK(hipMemset(h->scal, 0, 64 * 4)); HIPCHK(hipMemset(h->dc_G1, 0, (size_t)2 * h->Tm * h->B * (4 * h->H + h->A) * 4));
   HIPCHK(hipMemset(h->dc_G2, 0, (size_t)2 * h->Tm * h->B * h->H * DCB_KS * 4));
   h->gws_cur = h->gws;
   if (!h->s2) {

@@ -13,7 +13,7 @@
 //            cell, publishes h_t (bf16) for phase A of the next step and writes everything the backward needs.
 // A workgroup takes part in both phases (grid = max(NA, B) <= CU count, one workgroup per CU).  The roles are laid out XCD-aware
 // (DCF_NA below).  Hand-overs: A -> B through stamped words (G1), B -> A through the arrival line of the caption's row part
-// (arrive_part / wait_part), and one full grid barrier at the end of the launch that guards the epoch (rec_chain.hpp).
+// (cs_arrive_part / cs_wait_part), and one full grid barrier at the end of the launch that guards the epoch (chain_sync.hpp).
 // Limits: bf16 path, H % 8 == 0, H <= 512, F <= 32, A <= 128, (4H + A) % 16 == 0, B <= 112, T <= 63.
 #pragma once
 #include "common.hpp"
@@ -28,8 +28,8 @@ struct DecChainArgs {
   const float* Xe;                 // [T][B][4H] emb . W_e^T + biases
   float* G1;                       // [T][B][4H + A] exchange: recurrent pre-activations as 8-byte words {value, stamp}
   unsigned* epoch;
-  unsigned* rep;                   // phase A waits for the captions of its row part only, through per-XCD replicas of the part's arrival line (see dec_chain_bwd_kernel)
-  float* poison;                   // see rc_give_up (rec_chain.hpp)
+  unsigned* rep;                   // phase A waits for the captions of its row part only, through per-XCD replicas of the part's arrival line (cs_wait_part)
+  float* poison;                   // see rc_give_up (chain_sync.hpp)
   float* mp; float mp_scale;       // optional: mp_scale * sum_t h_t [B][H] (the global reconstructor's mean-pooled input)
   bf16_t* Xcat; int ld_xcat; DropDesc xdd;   // optional (global reconstructor, ld_xcat == 2H): its LSTM input operand [T][Bs][2H] = [h_t ; drop_t(mp)]
                                    // (global_reconstructor.py:38-41) written by the chain itself instead of xcat_global_kernel behind it
@@ -63,7 +63,7 @@ struct DecChainArgs {
 // number of workgroups and (almost) of MFMAs, but a workgroup pulls 32 rows x H of the h_{t-1} panel through its CU's 64 B/clk L1 path
 // instead of 112 (32 KB instead of 115 KB per step: 0.2 us instead of 0.75), and its consumers and producers all lie in ITS row part, so
 // the B -> A hand-over is partial (as in dec_chain_bwd_kernel).
-#define DCF_PARTS 4
+#define DCF_PARTS CS_PARTS
 #define DCF_RLD 68      // (multiple of 4: an accumulator fragment of the TRANSPOSED product is four consecutive columns of one row = one ds_write_b128, round 6)
 // XCD-aware roles: workgroup i runs on XCD i % 8 (rec_chain.hpp), and every XCD fetches what its workgroups read into its own L2.
 // Row part = (i % 8) / 2: the two XCDs of a part read only that part's 28 panel rows (a quarter of h_{t-1}) — with the column block
@@ -115,13 +115,7 @@ __global__ __launch_bounds__(256) void dec_chain_kernel(const DecChainArgs p) {
       wb[s][gq] = (k + kq < H && n < NN) ? *reinterpret_cast<const bf16x8*>(wrow + k) : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
     }
   }
-  if ((H & 31) && wg == 0) {     // zero the k-groups that pad H to a multiple of 32 in every step's panel (see rec_chain.hpp)
-    const int pad0 = H >> 3, padn = (((H + 31) >> 5) << 2) - pad0;
-    for (int t = 0; t < p.T; ++t)
-      for (int j = tid; j < padn * RC_PAN_ROWS * 2; j += 256)
-        __hip_atomic_store(reinterpret_cast<uint64_t*>(p.Pan + (size_t)t * pan_t + (size_t)pad0 * RC_PAN_ROWS * 8) + j, (uint64_t)0,
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  if ((H & 31) && wg == 0) rc_pan_zero_pad(p.Pan, H, p.T, tid);
   // ---- phase B residents (caption b = wg): P block, Uv rows, attention vectors; wave = gate g, lane = 8 units
   const int b = isB ? wg : 0, g = wave;
   const int u = lane * 8;
@@ -177,22 +171,7 @@ __global__ __launch_bounds__(256) void dec_chain_kernel(const DecChainArgs p) {
   // acknowledgement wait, no flag, no barrier between phase A and phase B.  The epoch (one more per launch, kept in device memory)
   // makes the words of earlier launches stale.
   const unsigned ep0 = rc_epoch_read(p.epoch), ep = ep0 << 6, fb = ep0 << 7;
-  // the B -> A hand-over inside a row part (the comment at dec_chain_bwd_kernel's wait_part has the measurements)
-  auto wait_part = [&](unsigned target) {
-    if (isA && tid < 64) {
-      const int n = B - own_lo < own ? B - own_lo : own;
-      if (n > 0) {
-        const unsigned* f = p.rep + ((wg & 7) * DCF_PARTS + part) * 32 + (tid < n ? tid : n - 1);
-        unsigned spin = 0;
-        while (!__all((int)(__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - target) >= 0)) { if (rc_give_up(p.bar, spin)) break; }
-        if (RC_ACQUIRE_INV) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      }
-    }
-    __syncthreads();
-  };
-  auto arrive_part = [&](unsigned v) {      // the replicas of the part's two XCDs
-    if (isB && tid < 2) __hip_atomic_store(p.rep + ((2 * (b / own) + tid) * DCF_PARTS + b / own) * 32 + b % own, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  };
+  const int npart = B - own_lo < own ? B - own_lo : own;      // captions of this row part (the B -> A hand-over stays inside it: cs_wait_part)
 
   // LW: attention projection and scores of step tt, from this caption's own h_{tt-1} (hl, bf16) — no other workgroup involved
   auto lw_scores = [&](const int tt) {
@@ -473,7 +452,7 @@ __global__ __launch_bounds__(256) void dec_chain_kernel(const DecChainArgs p) {
       }
       if (t + 1 < p.T) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       // (the stores below are issued after the arrive, see the end of the loop body)
-      if (t + 1 < p.T) { __syncthreads(); DC_TS(6); ++ph; arrive_part(fb + ph); }
+      if (t + 1 < p.T) { __syncthreads(); DC_TS(6); ++ph; cs_arrive_part(p.rep, b / own, b % own, fb + ph); }
       bf16_t* Lt = p.Hlp + ((size_t)t * Bs + b) * p.ld_hlp;
       if (tid < (H >> 3)) *reinterpret_cast<bf16x8*>(Lt + tid * 8) = *reinterpret_cast<const bf16x8*>(hl + tid * 8);
       if (p.Xcat && tid < (H >> 3)) *reinterpret_cast<bf16x8*>(p.Xcat + ((size_t)t * Bs + b) * p.ld_xcat + tid * 8) = *reinterpret_cast<const bf16x8*>(hl + tid * 8);
@@ -490,18 +469,18 @@ __global__ __launch_bounds__(256) void dec_chain_kernel(const DecChainArgs p) {
         }
       }
       if (LW && t + 1 < p.T) lw_scores(t + 1);      // from hl = h_t, while the barrier completes
-      if (t + 1 < p.T) wait_part(fb + ph);
+      if (t + 1 < p.T) cs_wait_part(isA, p.rep, part, npart, fb + ph, p.bar);
       DC_TS(7);
     } else if (t + 1 < p.T) {
       __syncthreads();
       ++ph;
-      wait_part(fb + ph);
+      cs_wait_part(isA, p.rep, part, npart, fb + ph, p.bar);
     }
   }
   // the launch epoch may only move once every workgroup has read it: one full barrier at the end
   __syncthreads();
-  rc_arrive(p.bar, fb + (unsigned)p.T);
-  if (wg == 0) rc_wait(p.bar, fb + (unsigned)p.T);
+  cs_arrive(p.bar + cs_wg(), fb + (unsigned)p.T);
+  if (wg == 0) cs_wait_grid(p.bar, fb + (unsigned)p.T);
   if (p.mp && isB) {
 #pragma unroll
     for (int jj = 0; jj < 2; ++jj) { const int uu = tid + 256 * jj; if (uu < H) p.mp[(size_t)b * H + uu] = hs_sum[jj] * p.mp_scale; }
@@ -517,8 +496,7 @@ __global__ __launch_bounds__(256) void dec_chain_kernel(const DecChainArgs p) {
       }
     }
   }
-  rc_epoch_bump(p.epoch, ep0);
-  rc_poison(p.bar, p.poison);
+  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) cs_finish(p.epoch, ep0, p.bar, p.poison);
 }
 
 // =============================================================================================
@@ -545,7 +523,7 @@ struct DecChainBwdArgs {
   const float* att; int softmax;   // softmax mode: the saved attention weights [T][B][F]
   float* G2;                       // [T][B][DCB_KS][H] exchange (by chain step): the K parts of the recurrent part of dh as stamped 8-byte words
   unsigned* epoch; float* poison;
-  unsigned* rep;                   // [8 XCDs][DCB_PARTS][32] arrival words, a 128-byte line per (XCD, row part): phase A' waits for the captions of ITS row part only (below)
+  unsigned* rep;                   // [8 XCDs][DCB_PARTS][32] arrival words, a 128-byte line per (XCD, row part): phase A' waits for the captions of ITS row part only (cs_wait_part)
   bf16_t* Pan;                     // [T][rc_pan_elems(4H + A)] exchange (by chain step): rows [dgates | dWh]
   bf16_t* dGx; int ld_dgx;         // [T][B][ld_dgx]
   float* dUv; bf16_t* dUv_lp; int ld_dUv;                   // [B][F][A], [B F][ld_dUv]
@@ -560,7 +538,7 @@ struct DecChainBwdArgs {
 #define DCB_TS(i) do { } while (0)
 #endif
 #define DCB_RB 2              // 32 rows per workgroup in phase A', 4 row parts
-#define DCB_PARTS 4
+#define DCB_PARTS CS_PARTS
 // Phase A' tiling (round 5): workgroup = (64 output units, one of 4 row parts, one of DCB_KS parts of K = 4H + A) instead of
 // (16 units, row part, all of K) — the same number of workgroups (128 at H = 512) and 40 instead of 34 MFMAs per wave, but a
 // workgroup pulls 32 rows x K / 4 of the panel through its CU's 64 B/clk L1 path per step instead of 32 rows x K (35 KB instead of
@@ -611,13 +589,7 @@ __global__ __launch_bounds__(256) void dec_chain_bwd_kernel(const DecChainBwdArg
       wb[j][gq] = (ks >= 0 && n < H && k + kq < KA) ? *reinterpret_cast<const bf16x8*>(wrow + k) : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
     }
   }
-  if ((KA & 31) && wg == 0) {    // zero the k-groups that pad KA to a multiple of 32 in every step's panel
-    const int pad0 = KA >> 3, padn = (((KA + 31) >> 5) << 2) - pad0;
-    for (int t = 0; t < p.T; ++t)
-      for (int j = tid; j < padn * RC_PAN_ROWS * 2; j += 256)
-        __hip_atomic_store(reinterpret_cast<uint64_t*>(p.Pan + (size_t)t * pan_t + (size_t)pad0 * RC_PAN_ROWS * 8) + j, (uint64_t)0,
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  if ((KA & 31) && wg == 0) rc_pan_zero_pad(p.Pan, KA, p.T, tid);
   // ---- phase B' residents (caption b = wg)
   const int b = isB ? wg : 0, g = wave;
   // P as MFMA A-operand fragments: rows = frames (2 blocks of 16), K = this wave's gate block [g H, (g+1) H)
@@ -658,32 +630,8 @@ __global__ __launch_bounds__(256) void dec_chain_bwd_kernel(const DecChainBwdArg
   const int lane_off = ((lane >> 4) * RC_PAN_ROWS + r0 + (lane & 15)) * 8;
   for (int j = tid; j < 64; j += 256) srow[W4 + 128 + j] = (bf16_t)0.f;
   unsigned ph = 0;
-  const unsigned ep0 = rc_epoch_read(p.epoch), ep = ep0 << 6, fb = ep0 << 7;   // see rec_chain.hpp
-  // Partial hand-over B' -> A' (round 5).  A phase-A' workgroup reads only the `own` = 28 panel rows of its row part, i.e. the rows
-  // [dgates | dWh] of 28 captions, and phase B' of a caption polls the stamped words of the 32 unit groups of ITS part: the
-  // dependencies close inside a row part, so nothing needs the whole grid.  Against a relayed grid barrier (arrive -> master sees all
-  // 128 -> release word -> waiter) that is one memory round trip instead of two, and a part does not wait for the stragglers of the
-  // other three.
-  // A caption writes its arrival into one replica of its part's flag line per XCD that hosts the part's phase-A' workgroups (p.rep:
-  // [8][DCB_PARTS][32] words, a 128-byte line per (XCD, part)); a waiter polls the replica of its own XCD (blockIdx % 8) with one wave load.
-  // With ONE copy polled by all 128 workgroups the step got 0.9 us LONGER (measured: 315 against 288 us per launch) — a line that is
-  // written from eight XCDs and read from eight is the worst case for the L2s; in this form every line has its readers in one XCD.
-  // Workgroups without a phase A' do not wait.
-  auto wait_part = [&](unsigned target) {
-    if (isA && tid < 64) {
-      const int n = B - own_lo < own ? B - own_lo : own;
-      if (n > 0) {
-        const unsigned* f = p.rep + ((wg & 7) * DCB_PARTS + part) * 32 + (tid < n ? tid : n - 1);
-        unsigned spin = 0;
-        while (!__all((int)(__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - target) >= 0)) { if (rc_give_up(p.bar, spin)) break; }
-        if (RC_ACQUIRE_INV) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      }
-    }
-    __syncthreads();
-  };
-  auto arrive_part = [&](unsigned v) {       // caption b = wg: its part, its slot in the part's line, the replicas of the part's two XCDs
-    if (isB && tid < 2) __hip_atomic_store(p.rep + ((2 * (b / own) + tid) * DCB_PARTS + b / own) * 32 + b % own, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  };
+  const unsigned ep0 = rc_epoch_read(p.epoch), ep = ep0 << 6, fb = ep0 << 7;   // see chain_sync.hpp
+  const int npart = B - own_lo < own ? B - own_lo : own;      // captions of this row part (the B' -> A' hand-over stays inside it: cs_wait_part)
 
   // saved tensors of step t for this thread's two units, and Wh[t][b][kk]
   float d1[2], d2[2], av[2][4], cv[2], cpv[2], whk;
@@ -894,24 +842,24 @@ __global__ __launch_bounds__(256) void dec_chain_bwd_kernel(const DecChainBwdArg
       for (int kg = tid; kg < (KA >> 3); kg += 256) {
         rc_store16(p.Pan + (size_t)s * pan_t + ((size_t)kg * RC_PAN_ROWS + b) * 8, srow + kg * 8);
       }
-      if (more) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads(); ++ph; arrive_part(fb + ph); }
+      if (more) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads(); ++ph; cs_arrive_part(p.rep, b / own, b % own, fb + ph); }
       DCB_TS(5);
       // ---- off the critical path: the row-major copy [dgates | dWh | 0 ..] for the deferred GEMMs
       bf16_t* Gt = p.dGx + ((size_t)t * Bs + b) * p.ld_dgx;
       for (int kg = tid; kg < (p.ld_dgx >> 3); kg += 256)
         *reinterpret_cast<bf16x8*>(Gt + kg * 8) = kg < (KA >> 3) ? *reinterpret_cast<const bf16x8*>(srow + kg * 8) : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-      if (more) { prefetch(t - 1); wait_part(fb + ph); }
+      if (more) { prefetch(t - 1); cs_wait_part(isA, p.rep, part, npart, fb + ph, p.bar); }
       DCB_TS(6);
     } else if (s + 1 < p.T) {
       __syncthreads();
       ++ph;
-      wait_part(fb + ph);
+      cs_wait_part(isA, p.rep, part, npart, fb + ph, p.bar);
     }
   }
   // the launch epoch may only move once every workgroup has read it: a full barrier, once, at the end (phase T: above every step's)
   __syncthreads();
-  rc_arrive(p.bar, fb + (unsigned)p.T);
-  if (wg == 0) rc_wait(p.bar, fb + (unsigned)p.T);
+  cs_arrive(p.bar + cs_wg(), fb + (unsigned)p.T);
+  if (wg == 0) cs_wait_grid(p.bar, fb + (unsigned)p.T);
   // ---- the accumulators: dUv (+ operand copy, zero padded), dw
   if (isB) {
     if (fk_on) {
@@ -946,6 +894,5 @@ __global__ __launch_bounds__(256) void dec_chain_bwd_kernel(const DecChainBwdArg
       for (int ch = 1; ch < RN_FCH; ++ch) p.dwacc[((size_t)ch * Bs + b) * A + tid] = 0.f;
     }
   }
-  rc_epoch_bump(p.epoch, ep0);
-  rc_poison(p.bar, p.poison);
+  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) cs_finish(p.epoch, ep0, p.bar, p.poison);
 }

@@ -17,15 +17,13 @@
 // between the logical extent and its multiple of 8.
 #pragma once
 #include "gemm.hpp"
+#include "chain_sync.hpp"      // RC_ACQUIRE_INV (1: cross-check build with the conventional acquire fences; Makefile: acqinv)
 #include <type_traits>
 
 #ifndef GL_TR_ASM
 #define GL_TR_ASM 1      // col-operand fragments through asm transposing reads (gl_frag_tr_asm below); 0: the builtin
 #endif
 #define GL_STAGE_BYTES 32768   // A image 16 KiB + B image 16 KiB
-#ifndef RC_ACQUIRE_INV
-#define RC_ACQUIRE_INV 0       // 1: cross-check build with the conventional acquire fences (rec_chain.hpp; Makefile: acqinv)
-#endif
 
 __device__ __forceinline__ int gl_col_swz(int k) { return ((k & 3) << 1) | (k & 8); }
 
@@ -275,7 +273,7 @@ __device__ __forceinline__ void gemm_lds_tile(const ArgsT& p, const int bx, cons
     // tile's counter; the slice that draws the last ticket reads all slabs back in slice order (sc1 loads: served by L2 /
     // memory, never by this CU's L1) and runs the epilogue.  Slab addresses are written once and read once per launch, and
     // the kernel boundary in front of the launch has dropped whatever an L2 held of them — the same argument as for the
-    // exchange panels of the chain kernels (rec_chain.hpp); RC_ACQUIRE_INV builds add the conventional acquire fence.
+    // exchange panels of the chain kernels (chain_sync.hpp); RC_ACQUIRE_INV builds add the conventional acquire fence.
     // The sum runs in slice order whoever arrives last: results do not depend on the schedule.  The host splits only products
     // with N % 4 == 0 (every slab access is a whole 16-byte quad).
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)p.ws, 0, 0x7ffffffc, 0x00020000);

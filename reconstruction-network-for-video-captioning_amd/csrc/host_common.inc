@@ -80,7 +80,7 @@ static unsigned* gg_counters(recnet_handle* h) {
 static bool gg_run(recnet_handle* h, GemmGroup& g, hipStream_t st, const AdamShared* adam = nullptr) {
   if (g.n == 0) { h->gg_site = 0; return true; }
   // h->gg_site (1..8, 0 = none): this launch stamps its start / end into slot gg_site of the handle's group stamps
-  unsigned long long* stamp = h->gg_site > 0 ? reinterpret_cast<unsigned long long*>(h->gbar + 2048 + 128) + 2 * (h->gg_site - 1) : nullptr;
+  unsigned long long* stamp = h->gg_site > 0 ? reinterpret_cast<unsigned long long*>(h->gbar + CS_WS_GROUP_STAMPS) + 2 * (h->gg_site - 1) : nullptr;
   h->gg_site = 0;
   if (h->lp && h->sw.gemm_group && !rn_launch_gemm_group(g.a_col, g.b_col, g.d, g.n, h->gws_cur, h->gws_floats, gg_counters(h), RN_GCNT_WORDS, st, h->gg_slots, adam, stamp)) { g.n = 0; return true; }
   if (adam) { g.n = 0; return false; }
@@ -210,7 +210,7 @@ __global__ void fill_i64_kernel(int64_t* p, int64_t v, int n) {
 __global__ void axpb_kernel(const float* a, const float* b, float k, float* out) { *out = *a + k * *b; }
 __global__ void export_scalars_kernel(const float* scal, recnet_scalars* out) {
   out->dec_ce = scal[0]; out->dec_reg = scal[1]; out->dec_loss = scal[2]; out->rec_mse = scal[3];
-  out->rec_reg = scal[4]; out->rec_loss = scal[5]; out->total_loss = scal[6] + scal[15]; out->dec_grad_norm = scal[7];   // scal[15]: 0, or NaN after a chain kernel gave up waiting (rec_chain.hpp)
+  out->rec_reg = scal[4]; out->rec_loss = scal[5]; out->total_loss = scal[6] + scal[15]; out->dec_grad_norm = scal[7];   // scal[15]: 0, or NaN after a chain kernel gave up waiting (chain_sync.hpp)
   const unsigned long long now = (unsigned long long)wall_clock64();
   reinterpret_cast<unsigned long long*>(const_cast<float*>(scal) + 32)[0] = now;      // phase stamp: step end (recnet_read_stamps)
   rn_ring_push(reinterpret_cast<unsigned long long*>(const_cast<float*>(scal) + 34), now);      // scal[34 .. 49]
@@ -238,11 +238,11 @@ static hipEvent_t prof_bracket_begin(recnet_handle* h, int site, hipStream_t st)
   if (prof_take(h, st, &e0, &e1)) hipEventRecord(e0, st);
   return e1;
 }
-// see wait_chain_kernel (rec_chain.hpp); k = 0 decoder forward chain, 1 decoder BPTT, 2 / 3 global fwd / bwd, 4 / 5 local fwd / bwd
+// see wait_chain_kernel (rec_chain.hpp); k = the chain's CsChain (chain_sync.hpp): 0 decoder forward chain, 1 decoder BPTT, 2 / 3 global fwd / bwd, 4 / 5 local fwd / bwd
 static void wait_chain(recnet_handle* h, int k, hipStream_t st) {
   const int on = h->sw.wait_chain;
   if (!on || !h->in_fused) return;      // (the step-start stamp is written by the fused step's first kernel)
-  const unsigned long long* stamps = reinterpret_cast<const unsigned long long*>(h->gbar + 2048 + 64);
+  const unsigned long long* stamps = reinterpret_cast<const unsigned long long*>(h->gbar + CS_WS_STAMPS);
   hipLaunchKernelGGL(wait_chain_kernel, dim3(1), dim3(64), 0, st, reinterpret_cast<const unsigned long long*>(h->ctrl + 32), stamps + 2 * k, 30000u);
 }
 static void hoist_side_work(recnet_handle* h, hipStream_t st);   // abi_step.inc

@@ -76,8 +76,8 @@ static int dec_fwd_chain(recnet_handle* h, const float* enc, const int64_t* targ
     c.P = (const bf16_t*)h->P + (size_t)b0 * F * h->ld4H; c.ldp = h->ld4H; c.Uv = h->Uv + (size_t)b0 * F * A; c.ab = h->dP.attn_b; c.w = h->dP.attn_w_weight;
     c.Xe = h->Xe + (size_t)b0 * 4 * H; c.G1 = h->dc_G1; c.Pan = (bf16_t*)h->dc_pan;
     c.Hs = h->Hs + (size_t)b0 * H; c.Cs = h->Cs + (size_t)b0 * H; c.acts = h->acts + (size_t)b0 * 4 * H; c.Hlp = (bf16_t*)h->Hs_lp + (size_t)b0 * h->ldH; c.ld_hlp = h->ldH;
-    c.Wh = h->Wh + (size_t)b0 * A; c.att = h->att + (size_t)b0 * F; c.bar = h->gbar + 1024; c.ts = h->lc_ts + 4096; c.softmax = h->c.decoder_attn_normalize == RECNET_ATTN_SOFTMAX;
-    c.epoch = h->gbar + 2048; c.rep = h->gbar + 5376; c.poison = h->scal + 15;
+    c.Wh = h->Wh + (size_t)b0 * A; c.att = h->att + (size_t)b0 * F; c.bar = cs_ws_bar(h->gbar, CS_DEC_FWD); c.ts = h->lc_ts + 4096; c.softmax = h->c.decoder_attn_normalize == RECNET_ATTN_SOFTMAX;
+    c.epoch = cs_ws_epoch(h->gbar, CS_DEC_FWD); c.rep = h->gbar + CS_WS_REP_DEC_FWD; c.poison = h->scal + 15;
     c.mp = h->kind == RECNET_REC_GLOBAL ? h->mp + (size_t)b0 * H : nullptr; c.mp_scale = (float)h->cml / ((float)T * (float)T);   // global_reconstructor.py:33-37
     h->mp_done = c.mp ? 1 : 0;
     // dec_xcat: the chain also writes the global reconstructor's input operand [h_t ; drop_t(mp)] (no xcat_global_kernel behind it)
@@ -217,9 +217,9 @@ static int dec_bwd_chain(recnet_handle* h, const float* dhid, hipStream_t st) {
     c.Wh = h->Wh + (size_t)b0 * A; c.att = h->att + (size_t)b0 * F; c.softmax = h->c.decoder_attn_normalize == RECNET_ATTN_SOFTMAX;
     c.G2 = h->dc_G2; c.Pan = (bf16_t*)h->dc_pan2; c.dGx = (bf16_t*)h->dGx + (size_t)b0 * ldWS; c.ld_dgx = ldWS;
     c.dUv = h->dUv + (size_t)b0 * F * A; c.dUv_lp = (bf16_t*)h->dUv_lp + (size_t)b0 * F * h->ldA; c.ld_dUv = h->ldA; c.dwacc = h->dwacc + (size_t)b0 * A;
-    c.bar = h->gbar + 1536; c.ts = h->lc_ts + 4096 + 512;
+    c.bar = cs_ws_bar(h->gbar, CS_DEC_BWD); c.ts = h->lc_ts + 4096 + 512;
     // the B' -> A' hand-over (dec_chain.hpp): the arrival flags of a row part polled by the part's own unit owners
-    c.epoch = h->gbar + 2049; c.rep = h->gbar + 4352; c.poison = h->scal + 15;
+    c.epoch = cs_ws_epoch(h->gbar, CS_DEC_BWD); c.rep = h->gbar + CS_WS_REP_DEC_BWD; c.poison = h->scal + 15;
     const int NAb = DCB_NA(H);
     const dim3 grid(NAb > nb ? NAb : nb);
     if (F > 32) {

@@ -84,7 +84,7 @@ static int fwd_rec_global(recnet_handle* h, const float* enc, int T, int train, 
     a.Hlp = (bf16_t*)h->Hr_lp + (size_t)b0 * h->ldR; a.ld_hlp = h->ldR; a.Pan = (bf16_t*)h->Hr_pan;
     a.Xg = h->Xg + (size_t)b0 * 4 * R; a.H = h->Hr + (size_t)b0 * R; a.C = h->Cr + (size_t)b0 * R; a.acts = h->acts_r + (size_t)b0 * 4 * R;
     a.hmean = h->hrmean + (size_t)b0 * R; a.hmean_lp = (bf16_t*)h->hrmean_lp + (size_t)b0 * h->ldR; a.ld_hmean = h->ldR;
-    a.bar = h->gbar; a.epoch = h->gbar + 2050;
+    a.bar = cs_ws_bar(h->gbar, CS_REC_FWD); a.epoch = cs_ws_epoch(h->gbar, CS_REC_FWD);
     a.master = R / 8 + 1 <= h->ncu;      // the master needs a CU of its own
     a.poison = h->scal + 15;
     const int steps = (R + 127) / 128;
@@ -213,7 +213,7 @@ static int bwd_rec_global(recnet_handle* h, float gscale, float* dhid_out, hipSt
     a.Pan = (bf16_t*)h->dG_pan; a.dG = (bf16_t*)h->dGr + (size_t)b0 * ld4R; a.ld_dg = ld4R;
     a.dh_direct = h->dhrmean + (size_t)b0 * R; a.dh_scale = 1.0f / (float)T;
     a.acts = h->acts_r + (size_t)b0 * 4 * R; a.C = h->Cr + (size_t)b0 * R; a.H = h->Hr + (size_t)b0 * R;
-    a.bar = h->gbar + 512; a.epoch = h->gbar + 2051;
+    a.bar = cs_ws_bar(h->gbar, CS_REC_BWD); a.epoch = cs_ws_epoch(h->gbar, CS_REC_BWD);
     a.master = (R / 16) * (nb > 64 ? 2 : 1) + 1 <= h->ncu;
     a.poison = h->scal + 15;
     const int steps = (4 * R + 127) / 128;
@@ -306,7 +306,7 @@ static int fwd_rec_local(recnet_handle* h, const float* enc, int T, int train, h
     a.Hr = h->Hr + (size_t)b0 * R; a.Cr = h->Cr + (size_t)b0 * R; a.acts = h->acts_r + (size_t)b0 * 4 * R; a.Hlp = (bf16_t*)h->Hr_lp + (size_t)b0 * h->ldR; a.ld_hlp = h->ldR;
     a.Xcat = (bf16_t*)h->Xcat_r + (size_t)b0 * ldHR; a.ld_xcat = ldHR; a.beta = h->beta + (size_t)b0 * T; a.Whr = h->Whr + (size_t)b0 * RA;
     a.PanH = (bf16_t*)h->lc_panh; a.PanX = (bf16_t*)h->lc_panx; a.Pw = h->lc_pw;
-    a.bar = h->gbar + 2560; a.epoch = h->gbar + 2052; a.poison = h->scal + 15;
+    a.bar = cs_ws_bar(h->gbar, CS_LOC_FWD); a.epoch = cs_ws_epoch(h->gbar, CS_LOC_FWD); a.poison = h->scal + 15;
     a.dd = mkdrop(h, RN_SITE_REC_INPUT, h->c.reconstructor_decoder_dropout, train); a.dd.boff += b0; a.ts = h->lc_ts;
     const dim3 g(a.NU + a.NC + a.relay);
     const int steps = (R + 127) / 128;
@@ -398,7 +398,7 @@ static int bwd_rec_local(recnet_handle* h, float gscale, float* dhid_out, hipStr
     c.dG = (bf16_t*)h->dGr + (size_t)b0 * ld4R; c.ld_dg = ld4R; c.dWhrs = (bf16_t*)h->dWhrs + (size_t)b0 * h->ldRA; c.ld_dwhr = h->ldRA;
     c.dxm = h->lb_dxm + (size_t)b0 * H; c.dbeta = h->lb_dbeta + (size_t)b0 * T;
     c.PanG = (bf16_t*)h->lc_pang; c.PanW = (bf16_t*)h->lc_panw; c.Part = h->lb_part;
-    c.bar = h->gbar + 3072; c.epoch = h->gbar + 2053; c.poison = h->scal + 15;
+    c.bar = cs_ws_bar(h->gbar, CS_LOC_BWD); c.epoch = cs_ws_epoch(h->gbar, CS_LOC_BWD); c.poison = h->scal + 15;
     c.dd = mkdrop(h, RN_SITE_REC_INPUT, h->c.reconstructor_decoder_dropout, train); c.dd.boff += b0; c.ts = h->lc_ts;
     const dim3 g(c.NWG);
     // (round 4: every even R / 128 in 18 ... 32, i.e. R = 2304 ... 4096 in steps of 256 — round 3 had the benchmark's 24 / 28 / 32 only)
@@ -429,7 +429,7 @@ static int bwd_rec_local(recnet_handle* h, float gscale, float* dhid_out, hipStr
     c.dG = (bf16_t*)h->dGr + (size_t)b0 * ld4R; c.ld_dg = ld4R; c.dWhrs = (bf16_t*)h->dWhrs + (size_t)b0 * h->ldRA; c.ld_dwhr = h->ldRA;
     c.dHs = dhid_out + (size_t)b0 * H; c.dUd = h->dUd + (size_t)b0 * RA; c.dUd_lp = (bf16_t*)h->dUd_lp + (size_t)b0 * h->ldRA; c.ld_dUd = h->ldRA; c.dwacc = h->dwacc_r + (size_t)b0 * RA; c.nch = RN_TCH;
     c.PanG = (bf16_t*)h->lc_pang; c.PanW = (bf16_t*)h->lc_panw; c.Dx = h->lc_dx;
-    c.bar = h->gbar + 3072; c.epoch = h->gbar + 2053; c.poison = h->scal + 15;
+    c.bar = cs_ws_bar(h->gbar, CS_LOC_BWD); c.epoch = cs_ws_epoch(h->gbar, CS_LOC_BWD); c.poison = h->scal + 15;
     c.dd = mkdrop(h, RN_SITE_REC_INPUT, h->c.reconstructor_decoder_dropout, train); c.dd.boff += b0; c.ts = h->lc_ts;
     // (measured and rejected: U' waiting for X' to publish dx before its recurrent product, +0.08 ms at B = 100 — X' is bound by its
     // own CU's L1 fill rate, not by U')

@@ -154,7 +154,7 @@ __global__ __launch_bounds__(256) void adam_chunk_kernel(const TensorDesc* __res
                                                          const float* __restrict__ poison,
                                                          const uint32_t* __restrict__ pending = nullptr, int step_off = 0,
                                                          uint32_t skip_mask = 0u) {
-  // A persistent chain kernel of this step gave up waiting (rec_chain.hpp: rc_give_up) and marked the step: its gradients
+  // A persistent chain kernel of this step gave up waiting (chain_sync.hpp: rc_give_up) and marked the step: its gradients
   // are garbage, so parameters, moments and the packed images stay as they are (the host sees the flag through
   // recnet_chain_status and the NaN total loss).
   if (poison && *poison != 0.f) return;

@@ -11,7 +11,7 @@ __global__ void stamp_u64_kernel(unsigned long long* slot, int take_max) {
   else __hip_atomic_store(slot, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 __global__ void set_u32_kernel(uint32_t* p, uint32_t v) { *p = v; }
-// Data parallel: a rank whose chain kernel gave up (rec_chain.hpp: the poison word is NaN, else 0) marks one element of the
+// Data parallel: a rank whose chain kernel gave up (chain_sync.hpp: the poison word is NaN, else 0) marks one element of the
 // gradient bucket that is all-reduced LAST; after the SUM every rank sees the NaN and raises its own poison word, so all
 // ranks skip the optimiser update together (adam_chunk_kernel tests the word) instead of the healthy ones applying garbage.
 __global__ void poison_mark_kernel(float* g0, const float* poison) { if (*poison != 0.f) *g0 = __int_as_float(0x7fc00000); }

@@ -74,7 +74,6 @@ __global__ __launch_bounds__(256) void lcbig_bwd_kernel(const LocBigBwdArgs p) {
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wg = blockIdx.x, R = p.R, B = p.B, Bs = p.Bs, H = p.H, A = p.A, F = p.F, T = p.T, K = 4 * R, NT = H + R;
   const unsigned ep = rc_epoch_read(p.epoch), fb = ep << 7;
-  unsigned* rel = p.bar + 256;
   const size_t pan_g = rc_pan_elems(K), pan_w = rc_pan_elems(A);
   const bool relay = wg == p.NWG - 1;
   const int kq = (lane >> 4) * 8;
@@ -91,20 +90,9 @@ __global__ __launch_bounds__(256) void lcbig_bwd_kernel(const LocBigBwdArgs p) {
   auto bar_arrive = [&](unsigned phase) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    lc_arrive(myflag, fb + phase);
+    cs_arrive(myflag, fb + phase);
   };
-  auto bar_wait = [&](unsigned phase) { lc_wait_or_relay(relay, rel, p.bar, p.NWG, fb + phase, p.bar); };
-  // wave-level wait for n <= 64 consecutive arrival flags (lane i polls flag i)
-  auto flags_wait = [&](const unsigned* f, int n, unsigned target) {
-    const unsigned* fl = f + (lane < n ? lane : 0);
-    unsigned spin = 0;
-    for (;;) {
-      const bool ok = (int)(__hip_atomic_load(fl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - target) >= 0;
-      if (__all(ok)) break;
-      if (rc_give_up(p.bar, spin)) break;
-    }
-    if (RC_ACQUIRE_INV) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  };
+  auto bar_wait = [&](unsigned phase) { lc_wait_or_relay(relay, p.bar, CS_REL_A, p.bar, p.NWG, fb + phase); };
 
   // ---------------------------------------------------------------- P: residents
   const int kw0 = kqi * R + wave * (STEPS * 32);            // this wave's K range inside the quarter (K quarter = R gate rows)
@@ -229,7 +217,7 @@ __global__ __launch_bounds__(256) void lcbig_bwd_kernel(const LocBigBwdArgs p) {
         const int col = gq * R + u0 + kgi * 8;
         const bf16_t* src = hl + ((size_t)rg * 4 + gq) * UW + kgi * 8;
         if (rg < B) {
-          lc_store16(p.PanG + (size_t)q * pan_g + ((size_t)(col >> 3) * RC_PAN_ROWS + rg) * 8, src);
+          rc_store16(p.PanG + (size_t)q * pan_g + ((size_t)(col >> 3) * RC_PAN_ROWS + rg) * 8, src);
           *reinterpret_cast<bf16x8*>(Gt + (size_t)rg * p.ld_dg + col) = *reinterpret_cast<const bf16x8*>(src);
         }
       }
@@ -315,7 +303,7 @@ __global__ __launch_bounds__(256) void lcbig_bwd_kernel(const LocBigBwdArgs p) {
           for (int w = 0; w < 4; ++w)
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] += red[w * (RED_ROWS * RED_LD) + (rr * 16 + prow) * RED_LD + pc0 + e];
-          lc_store16f(dst + (size_t)(half * 32 + rr * 16) * NT, v);
+          rc_store16f(dst + (size_t)(half * 32 + rr * 16) * NT, v);
         }
       }
     }
@@ -352,7 +340,7 @@ __global__ __launch_bounds__(256) void lcbig_bwd_kernel(const LocBigBwdArgs p) {
     }
     LB_WTS(q, 3);
     if (isC) {
-      if (tid < 64) flags_wait(p.bar, 4 * NXB, fb + 3u * (unsigned)q + 2u);
+      if (tid < 64) cs_poll_wave(p.bar + (lane < 4 * NXB ? lane : 0), fb + 3u * (unsigned)q + 2u, p.bar);
       LB_WTS(q, 4);
       __syncthreads();
     }
@@ -417,7 +405,7 @@ __global__ __launch_bounds__(256) void lcbig_bwd_kernel(const LocBigBwdArgs p) {
       if (tid < 128) swl[tid] = (bf16_t)(tid < A ? sdw[tid] + sdw[128 + tid] : 0.f);
       __syncthreads();
       // publish dWhr_s[b] (k-groups up to the next multiple of 32 columns; swl holds zeros beyond A) + the row-major copy
-      if (tid < (((A + 31) >> 5) << 2)) lc_store16(p.PanW + (size_t)q * pan_w + ((size_t)tid * RC_PAN_ROWS + b) * 8, swl + tid * 8);
+      if (tid < (((A + 31) >> 5) << 2)) rc_store16(p.PanW + (size_t)q * pan_w + ((size_t)tid * RC_PAN_ROWS + b) * 8, swl + tid * 8);
       if (tid < (p.ld_dwhr >> 3) && tid < 16)
         *reinterpret_cast<bf16x8*>(p.dWhrs + ((size_t)s * Bs + b) * p.ld_dwhr + tid * 8) = *reinterpret_cast<const bf16x8*>(swl + tid * 8);
     }
@@ -426,16 +414,7 @@ __global__ __launch_bounds__(256) void lcbig_bwd_kernel(const LocBigBwdArgs p) {
     if (isL && q + 1 < F) {
       l_prefetch(s - 1, tl);
       // the K partials of this workgroup's columns of dhr: their four producers finished P(q) a caption phase ago
-      {
-        const unsigned* f = p.bar + 4 * NXB + ((H + u0) >> 6) - NXB + (lane & 3) * (p.NCB - NXB);
-        unsigned spin = 0;
-        for (;;) {
-          const bool ok = (int)(__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - (fb + 3u * (unsigned)q + 2u)) >= 0;
-          if (__all(ok)) break;
-          if (rc_give_up(p.bar, spin)) break;
-        }
-        if (RC_ACQUIRE_INV) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      }
+      cs_poll_wave(p.bar + 4 * NXB + ((H + u0) >> 6) - NXB + (lane & 3) * (p.NCB - NXB), fb + 3u * (unsigned)q + 2u, p.bar);
 #pragma unroll
       for (int z = 0; z < 4; ++z)
         pk[z] = *(lc_gf32x4)(lc_launder_s(p.Part + ((size_t)q * 4 + z) * ROWS * NT + H + u0) + (unsigned)lrow * (unsigned)NT + (unsigned)luq);
@@ -451,10 +430,7 @@ __global__ __launch_bounds__(256) void lcbig_bwd_kernel(const LocBigBwdArgs p) {
     LB_TS(q, 7);
   }
   // everybody has passed the last barrier (and read the epoch long ago)
-  if (relay && tid == 0) {
-    __hip_atomic_store(p.epoch, ep + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); rc_stamp_slot(p.epoch)[1] = wall_clock64();
-    if (__hip_atomic_load(p.bar + 257, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) *p.poison = __builtin_nanf("");
-  }
+  if (relay && tid == 0) cs_finish(p.epoch, ep, p.bar, p.poison);
 }
 template <int NL> constexpr size_t lcbig_smem_bytes() { return (size_t)4 * 32 * 65 * 4 + (size_t)4 * NL * 4 * 1024 + (size_t)64 * 4 * 16 * 2; }
 

@@ -3,7 +3,7 @@
 //               gates = x . W_ih^T + hr_{s-1} . W_hh^T + bias ;  (hr_s, cr_s) = cell
 // The per-launch path runs four kernels per step (attention GEMM, attention, gate GEMM, cell: 33 us per step at
 // B = 100, R = 1536) and re-streams [W_ih | W_hh] (25 MB) every step.  Here the weights are read once and a step is two
-// hand-overs between two kinds of resident workgroups (one per CU, rec_chain.hpp's exchange discipline):
+// hand-overs between two kinds of resident workgroups (one per CU, chain_sync.hpp's exchange discipline):
 //   U (unit owner): 16 hidden units x one row part.  Its 64 gate rows of W_hh stay in MFMA B-operand registers, its
 //      rows of W_ih as B fragments in LDS, its 16 columns of W_r in registers.  Per step: (x_s arrived) x_s . W_ih^T on top
 //      of the recurrent part, 4-wave K reduction, cell pointwise, publishes hr_s (k-group-major panel) AND its rank-16
@@ -58,56 +58,20 @@ struct LocChainArgs {
 #endif
 #define LC_HYB_SR(STEPS) ((STEPS) == 28 ? LC_HYB_SR28 : 12)
 #define LC_MAX_PHASE 128       // barrier words are (launch epoch << 7) + phase: every phase number of a launch stays below this
-__device__ __forceinline__ void lc_poll(const unsigned* flags, int n, unsigned target, unsigned* bar, unsigned& spin) {
-  // wave 0 of the relay workgroup: all n <= 256 flags have reached `target`
-  const int l = threadIdx.x;
-  const unsigned* f0 = flags + (l < n ? l : n - 1);
-  const unsigned* f1 = flags + (l + 64 < n ? l + 64 : n - 1);
-  const unsigned* f2 = flags + (l + 128 < n ? l + 128 : n - 1);
-  const unsigned* f3 = flags + (l + 192 < n ? l + 192 : n - 1);
-  for (;;) {
-    const unsigned a0 = __hip_atomic_load(f0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned a1 = __hip_atomic_load(f1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned a2 = __hip_atomic_load(f2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned a3 = __hip_atomic_load(f3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const bool ok = (int)(a0 - target) >= 0 && (int)(a1 - target) >= 0 && (int)(a2 - target) >= 0 && (int)(a3 - target) >= 0;
-    if (__all(ok)) break;
-    if (rc_give_up(bar, spin)) break;
-  }
-}
-__device__ __forceinline__ void lc_release(unsigned* rel, unsigned v) {
-  if (threadIdx.x < 8) __hip_atomic_store(rel + threadIdx.x * 32, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// workers: wave 0 polls this workgroup's copy of a release word (one 128-byte line per group of workgroups)
-__device__ __forceinline__ void lc_wait(const unsigned* rel, unsigned target, unsigned* bar) {
-  if (threadIdx.x < 64) {
-    const unsigned* r = rel + (blockIdx.x & 7) * 32;
-    unsigned spin = 0;
-    while ((int)(__hip_atomic_load(r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - target) < 0) { if (rc_give_up(bar, spin)) break; }
-    if (RC_ACQUIRE_INV) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  }
-  __syncthreads();
-}
 // A launch without a CU for the relay workgroup (NU + NC = CU count) folds the relay into the LAST caption workgroup, in
 // the time it would spend waiting anyway: where the others wait for a release word it polls the arrival flags itself and
 // then writes the release words (`me` = this workgroup is that relay).  One poller, as with the dedicated relay — with every
 // waiter polling the 224 flags the U -> C hand-over took 4.3 us instead of ~2.
-__device__ __forceinline__ void lc_wait_or_relay(bool me, unsigned* rel, const unsigned* flags, int n, unsigned target, unsigned* bar) {
-  if (!me) { lc_wait(rel, target, bar); return; }
+__device__ __forceinline__ void lc_wait_or_relay(bool me, unsigned* bar, int slot, const unsigned* flags, int n, unsigned target) {
+  if (!me) { cs_wait_release(bar, slot, blockIdx.x, target); return; }
   if (threadIdx.x < 64) {
     unsigned spin = 0;
-    lc_poll(flags, n, target, bar, spin);
-    lc_release(rel, target);
+    cs_poll<false>(flags, n, target, bar, spin);
+    cs_release(bar, slot, target);
     if (RC_ACQUIRE_INV) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
   }
   __syncthreads();
 }
-__device__ __forceinline__ void lc_arrive(unsigned* flag, unsigned v) {
-  if (threadIdx.x == 0) __hip_atomic_store(flag, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// (16-byte write-through stores: rc_store16f / rc_store16, rec_chain.hpp)
-__device__ __forceinline__ void lc_store16f(float* dst, f32x4 v) { rc_store16f(dst, v); }
-__device__ __forceinline__ void lc_store16(bf16_t* dst, const bf16_t* src) { rc_store16(dst, src); }
 // A pointer that went through an empty asm (to keep its address arithmetic out of loop-invariant hoisting) has lost its address
 // space: loads through it are FLAT loads, which may return out of order with global loads, so every wait next to them becomes
 // vmcnt(0) and a register ring of loads drains at each use.  These put the address space back.
@@ -121,7 +85,7 @@ typedef short lc_s4 __attribute__((ext_vector_type(4)));
 typedef _Float16 lc_h4 __attribute__((ext_vector_type(4)));
 
 // release words: relU (word 0 of each line) = "every U workgroup has finished step .", relC (word 16) = "every C ...".
-// Flag / release values are fb + phase, fb = launch epoch << 7 (rec_chain.hpp).  Phases: U arrives with s + 1 after
+// Flag / release values are fb + phase, fb = launch epoch << 7 (chain_sync.hpp).  Phases: U arrives with s + 1 after
 // publishing hr_s, C arrives with s + 1 after publishing x_s; both arrive with F + 1 when they are done, after which the
 // relay bumps the launch epoch (every workgroup has read it by then).
 // SR < STEPS (R above 2048, BASELINE configs[4]: R = 3584): the hybrid form.  64 gate rows x (H + R) of [W_ih | W_hh] are
@@ -139,7 +103,7 @@ __global__ __launch_bounds__(256) void loc_chain_kernel(const LocChainArgs p) {
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wg = blockIdx.x, R = p.R, B = p.B, Bs = p.Bs, H = p.H, A = p.A, F = p.F, T = p.T;
   const unsigned ep = rc_epoch_read(p.epoch), fb = ep << 7;
-  unsigned* relU = p.bar + 256; unsigned* relC = p.bar + 256 + 16;
+  constexpr int relU = CS_REL_A, relC = CS_REL_C;
   const size_t pan_h = rc_pan_elems(R), pan_x = rc_pan_elems(H);
 
   // ================================================================================== relay workgroup
@@ -147,16 +111,13 @@ __global__ __launch_bounds__(256) void loc_chain_kernel(const LocChainArgs p) {
     if (tid < 64) {
       unsigned spin = 0;
       for (int s = 0; s < F; ++s) {
-        if (s >= 1) { lc_poll(p.bar, p.NU, fb + (unsigned)s, p.bar, spin); lc_release(relU, fb + (unsigned)s); }
+        if (s >= 1) { cs_poll<false>(p.bar, p.NU, fb + (unsigned)s, p.bar, spin); cs_release(p.bar, relU, fb + (unsigned)s); }
         LC_TS(2, s, 0);
-        lc_poll(p.bar + p.NU, p.NC, fb + (unsigned)(s + 1), p.bar, spin); lc_release(relC, fb + (unsigned)(s + 1));
+        cs_poll<false>(p.bar + p.NU, p.NC, fb + (unsigned)(s + 1), p.bar, spin); cs_release(p.bar, relC, fb + (unsigned)(s + 1));
         LC_TS(2, s, 1);
       }
-      lc_poll(p.bar, p.NU + p.NC, fb + (unsigned)(F + 1), p.bar, spin);      // everybody is done (and has read the epoch)
-      if (tid == 0) {
-        __hip_atomic_store(p.epoch, ep + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); rc_stamp_slot(p.epoch)[1] = wall_clock64();
-        if (__hip_atomic_load(p.bar + 257, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) *p.poison = __builtin_nanf("");
-      }
+      cs_poll<false>(p.bar, p.NU + p.NC, fb + (unsigned)(F + 1), p.bar, spin);      // everybody is done (and has read the epoch)
+      if (tid == 0) cs_finish(p.epoch, ep, p.bar, p.poison);
     }
     return;
   }
@@ -199,7 +160,7 @@ __global__ __launch_bounds__(256) void loc_chain_kernel(const LocChainArgs p) {
       // ---- Whr_s[b][j] = sum over the unit groups' rank-16 contributions (fixed order; zero at s = 0: hr_{-1} = 0)
       float whr = 0.f;
       if (s >= 1) {
-        lc_wait_or_relay(fold, relU, p.bar, p.NU, fb + (unsigned)s, p.bar);
+        lc_wait_or_relay(fold, p.bar, relU, p.bar, p.NU, fb + (unsigned)s);
         if (ci == 0) LC_TS(1, s, 0);
         // thread = (attention columns 4 aq .. 4 aq + 3, unit groups gg, gg + 4, ..): every load of the step is issued before
         // the first use (one memory round trip; the blocks were written by other XCDs a moment ago and come from memory)
@@ -260,27 +221,24 @@ __global__ __launch_bounds__(256) void loc_chain_kernel(const LocChainArgs p) {
       // publish x_s[b]: 16 bytes per k-group, written through; then the row-major copy for the deferred dW_ih GEMM
       const int pc = tid >> 6, kg = tid & 63, pb = ci * LC_CPW + pc;
       const bool pon = tid < LC_CPW * 64 && pb < B && kg < (H >> 3);
-      if (pon) lc_store16(p.PanX + (size_t)s * pan_x + ((size_t)kg * RC_PAN_ROWS + pb) * 8, xl + pc * 512 + kg * 8);
+      if (pon) rc_store16(p.PanX + (size_t)s * pan_x + ((size_t)kg * RC_PAN_ROWS + pb) * 8, xl + pc * 512 + kg * 8);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
-      lc_arrive(p.bar + p.NU + ci, fb + (unsigned)(s + 1));
+      cs_arrive(p.bar + p.NU + ci, fb + (unsigned)(s + 1));
       if (ci == 0) LC_TS(1, s, 3);
       if (pon) *reinterpret_cast<bf16x8*>(p.Xcat + ((size_t)s * Bs + pb) * p.ld_xcat + kg * 8) = *reinterpret_cast<const bf16x8*>(xl + pc * 512 + kg * 8);
       if (fold && tid < 64) {      // "every caption workgroup has published x_s": release the unit owners
         unsigned spin = 0;
-        lc_poll(p.bar + p.NU, p.NC, fb + (unsigned)(s + 1), p.bar, spin);
-        lc_release(relC, fb + (unsigned)(s + 1));
+        cs_poll<false>(p.bar + p.NU, p.NC, fb + (unsigned)(s + 1), p.bar, spin);
+        cs_release(p.bar, relC, fb + (unsigned)(s + 1));
       }
     }
     __syncthreads();
-    lc_arrive(p.bar + p.NU + ci, fb + (unsigned)(F + 1));
+    cs_arrive(p.bar + p.NU + ci, fb + (unsigned)(F + 1));
     if (!p.relay && ci == 0 && tid < 64) {      // no relay workgroup: this one closes the launch (everybody is done and has read the epoch)
       unsigned spin = 0;
-      lc_poll(p.bar, p.NU + p.NC, fb + (unsigned)(F + 1), p.bar, spin);
-      if (tid == 0) {
-        __hip_atomic_store(p.epoch, ep + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); rc_stamp_slot(p.epoch)[1] = wall_clock64();
-        if (__hip_atomic_load(p.bar + 257, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) *p.poison = __builtin_nanf("");
-      }
+      cs_poll<false>(p.bar, p.NU + p.NC, fb + (unsigned)(F + 1), p.bar, spin);
+      if (tid == 0) cs_finish(p.epoch, ep, p.bar, p.poison);
     }
     return;
   }
@@ -334,12 +292,11 @@ __global__ __launch_bounds__(256) void loc_chain_kernel(const LocChainArgs p) {
   }
   constexpr int CPT = (ROWS * UW + 255) / 256;
   static_assert(CPT == 4 || CPT == 2, "RB = 4 or 2");
-#define LCU_CELL(c) (((tid / UW) * CPT + (c)) * UW + tid % UW)
   float xb[CPT][4], cpv[CPT];
   bool mine[CPT];
 #pragma unroll
   for (int c = 0; c < CPT; ++c) {
-    const int cell = LCU_CELL(c), rg = r0 + cell / UW;
+    const int cell = RC_CELL(c), rg = r0 + cell / UW;
     mine[c] = cell < ROWS * UW && rg >= own_lo && rg < own_lo + own && rg < B;
     cpv[c] = 0.f;
 #pragma unroll
@@ -357,7 +314,7 @@ __global__ __launch_bounds__(256) void loc_chain_kernel(const LocChainArgs p) {
 
   for (int s = 0; s < F; ++s) {
     // ---- x_s . W_ih^T on top of the recurrent part (this wave's K slice of both)
-    lc_wait(relC, fb + (unsigned)(s + 1), p.bar);
+    cs_wait_release(p.bar, relC, wg, fb + (unsigned)(s + 1));
     if (wg == 0) LC_TS(0, s, 0);
     {
       const bf16_t* Ax = p.PanX + (size_t)s * pan_x + lane_off;
@@ -413,7 +370,7 @@ __global__ __launch_bounds__(256) void loc_chain_kernel(const LocChainArgs p) {
     float hv[CPT], av[CPT][4];
 #pragma unroll
     for (int c = 0; c < CPT; ++c) {
-      const int cell = LCU_CELL(c);
+      const int cell = RC_CELL(c);
       float g4[4];
 #pragma unroll
       for (int q = 0; q < 4; ++q) g4[q] = xb[c][q] + gsum[q][c];
@@ -431,7 +388,7 @@ __global__ __launch_bounds__(256) void loc_chain_kernel(const LocChainArgs p) {
     const bool more = s + 1 < F;
     if (more) {
       // publish hr_s (what the recurrent product of the next step reads)
-      if (it_on) lc_store16(p.PanH + (size_t)s * pan_h + ((size_t)(ug * KG + it_j) * RC_PAN_ROWS + it_rg) * 8, it_src);
+      if (it_on) rc_store16(p.PanH + (size_t)s * pan_h + ((size_t)(ug * KG + it_j) * RC_PAN_ROWS + it_rg) * 8, it_src);
       // this workgroup's rank-16 contribution to Whr_{s+1}, transposed: W_r[:, own units] . [ROWS x 16 units]^T as 16x16x16
       // MFMAs (wave -> attention columns [32 wave, 32 wave + 32)): a lane then holds four consecutive attention columns of
       // one caption - one 8-byte fp16 store straight from the accumulator, no staging through LDS
@@ -460,7 +417,7 @@ __global__ __launch_bounds__(256) void loc_chain_kernel(const LocChainArgs p) {
       if (wg == 0) LC_TS(0, s, 3);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
-      lc_arrive(p.bar + wg, fb + (unsigned)(s + 1));
+      cs_arrive(p.bar + wg, fb + (unsigned)(s + 1));
       if (wg == 0) LC_TS(0, s, 4);
     }
     // ---- off the critical path: what the backward and the output layer read
@@ -471,7 +428,7 @@ __global__ __launch_bounds__(256) void loc_chain_kernel(const LocChainArgs p) {
     if (it_on) *reinterpret_cast<bf16x8*>(Lt + (size_t)it_rg * p.ld_hlp + u0 + it_j * 8) = *reinterpret_cast<const bf16x8*>(it_src);
 #pragma unroll
     for (int c = 0; c < CPT; ++c) {
-      const int cell = LCU_CELL(c);
+      const int cell = RC_CELL(c);
       if (mine[c]) {
         const int row = r0 + cell / UW, u = u0 + cell % UW;
         const size_t o = (size_t)row * R + u;
@@ -507,7 +464,7 @@ __global__ __launch_bounds__(256) void loc_chain_kernel(const LocChainArgs p) {
         for (int i = 0; i < PF; ++i)
           if (i < NPS) issue_w(i % PF, i);
       }
-      lc_wait(relU, fb + (unsigned)(s + 1), p.bar);
+      cs_wait_release(p.bar, relU, wg, fb + (unsigned)(s + 1));
       if (wg == 0) LC_TS(0, s, 5);
       const bf16_t* Ah = p.PanH + (size_t)s * pan_h + lane_off;
       bf16x8 fa[PF][2][RB];
@@ -550,11 +507,10 @@ __global__ __launch_bounds__(256) void loc_chain_kernel(const LocChainArgs p) {
     }
   }
   __syncthreads();
-  lc_arrive(p.bar + wg, fb + (unsigned)(F + 1));
+  cs_arrive(p.bar + wg, fb + (unsigned)(F + 1));
 }
 // The streamed k-steps of the hybrid forward chain as MFMA B fragments, in the order loc_chain_kernel<STEPS, ., ., SR> consumes
 // them (pair NPR + i of its rotated sequence, i = 0 ..): dst[ug][wave][js][g][lane][8].  Run after every update of W_hh.
-#undef LCU_CELL
 __global__ __launch_bounds__(256) void lc_pack_stream_kernel(const bf16_t* __restrict__ W, int ldw, int R, int H, int STEPS, int SR, bf16_t* __restrict__ dst, size_t n_frag) {
   const size_t f = (size_t)blockIdx.x * 256 + threadIdx.x;       // one 16-byte fragment piece per thread
   if (f >= n_frag) return;
@@ -584,7 +540,7 @@ template <int RB> constexpr size_t lc_smem_bytes() {
 //      it runs while X' and C' work), then the small product with dWhr (K = A), cell backward, publishes dG_s;
 //   X' (16 columns of dx x one row part): the same product with the W_ih rows of WT; publishes dx_s (fp32, masked);
 //   C' (two captions): h_t, Ud[t] and the dHs / dUd / dw accumulators live in registers for all F steps; publishes dWhr_s.
-// The panels are indexed by chain step (fresh addresses every step, rec_chain.hpp).
+// The panels are indexed by chain step (fresh addresses every step, chain_sync.hpp).
 struct LocChainBwdArgs {
   int F, T, B, R, H, A, gru;
   int Bs;                            // see LocChainArgs (Dx / panels are private to the launch)
@@ -660,7 +616,7 @@ __device__ __forceinline__ void lcb_load_weights(bf16x8 (&wb)[STEPS], const bf16
 // what bounds the whole-K form.  The KSX partial dx (each masked: the dropout mask is a per-element factor) are summed by
 // the caption workgroups when they read them.
 template <int XS, int PF>
-__device__ __forceinline__ void lcb_xsplit_role(const LocChainBwdArgs& p, float* red, int xi, int wg, unsigned fb, const unsigned* relG) {
+__device__ __forceinline__ void lcb_xsplit_role(const LocChainBwdArgs& p, float* red, int xi, int wg, unsigned fb, int relG) {
   constexpr int CG = 4, RB = 2, UWX = 16 * CG, ROWS = RB * 16, RED_LD = UWX + 1, NP = XS / 2, OWN = ROWS;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int R = p.R, B = p.B, H = p.H, F = p.F, K = 4 * R;
@@ -695,7 +651,7 @@ __device__ __forceinline__ void lcb_xsplit_role(const LocChainBwdArgs& p, float*
   const uint32_t key = drop_key(p.dd);
   for (int q = 0; q < F; ++q) {
     const int s = F - 1 - q;
-    lc_wait(relG, fb + (unsigned)(q + 1), p.bar);
+    cs_wait_release(p.bar, relG, wg, fb + (unsigned)(q + 1));
     if (xi == 0) LC_TS(5, q, 0);
     const bf16_t* A = p.PanG + (size_t)q * pan_g + lane_off;
     bf16x8 fa[PF][2][RB];
@@ -752,7 +708,7 @@ __device__ __forceinline__ void lcb_xsplit_role(const LocChainBwdArgs& p, float*
         // step's [KSX][B][H] block — a violation raises the chain's sticky word (the step reports NaN) instead of writing
         const bool ok = rl >= 0 && rl < ROWS && j0 + pc + 3 < H && (((uintptr_t)dst) & 15) == 0 &&
                         ((size_t)q * p.KSX + kp) * B * H + (size_t)rg * H + j0 + pc + 3 < (size_t)F * p.KSX * B * H;
-        if (!ok) { __hip_atomic_store(p.bar + 257, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); continue; }
+        if (!ok) { cs_raise(p.bar); continue; }
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int w = 0; w < 4; ++w)
@@ -765,11 +721,11 @@ __device__ __forceinline__ void lcb_xsplit_role(const LocChainBwdArgs& p, float*
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    lc_arrive(p.bar + wg, fb + (unsigned)(q + 1));
+    cs_arrive(p.bar + wg, fb + (unsigned)(q + 1));
     if (xi == 0) LC_TS(5, q, 2);
   }
   __syncthreads();
-  lc_arrive(p.bar + wg, fb + (unsigned)(F + 1));
+  cs_arrive(p.bar + wg, fb + (unsigned)(F + 1));
 }
 
 template <int STEPS, int PF, int RBU, int RBX, int XS = 0>
@@ -780,7 +736,7 @@ __global__ __launch_bounds__(256) void loc_chain_bwd_kernel(const LocChainBwdArg
   const int wg = blockIdx.x, R = p.R, B = p.B, Bs = p.Bs, H = p.H, A = p.A, F = p.F, T = p.T, K = 4 * R;
   const int NU = p.NGU * p.MSU, NX = p.NGX * p.MSX * p.KSX;
   const unsigned ep = rc_epoch_read(p.epoch), fb = ep << 7;
-  unsigned* relG = p.bar + 256; unsigned* relX = p.bar + 256 + 8; unsigned* relW = p.bar + 256 + 16;
+  constexpr int relG = CS_REL_A, relX = CS_REL_B, relW = CS_REL_C;
   const size_t pan_g = rc_pan_elems(K), pan_w = rc_pan_elems(A);
   const int kq = (lane >> 4) * 8, kw0 = wave * (STEPS * 32);
 
@@ -789,18 +745,15 @@ __global__ __launch_bounds__(256) void loc_chain_bwd_kernel(const LocChainBwdArg
     if (tid < 64) {
       unsigned spin = 0;
       for (int q = 0; q < F; ++q) {
-        lc_poll(p.bar, NU, fb + (unsigned)(q + 1), p.bar, spin); lc_release(relG, fb + (unsigned)(q + 1));
+        cs_poll<false>(p.bar, NU, fb + (unsigned)(q + 1), p.bar, spin); cs_release(p.bar, relG, fb + (unsigned)(q + 1));
         LC_TS(3, q, 0);
-        lc_poll(p.bar + NU, NX, fb + (unsigned)(q + 1), p.bar, spin); lc_release(relX, fb + (unsigned)(q + 1));
+        cs_poll<false>(p.bar + NU, NX, fb + (unsigned)(q + 1), p.bar, spin); cs_release(p.bar, relX, fb + (unsigned)(q + 1));
         LC_TS(3, q, 1);
-        lc_poll(p.bar + NU + NX, p.NC, fb + (unsigned)(q + 1), p.bar, spin); lc_release(relW, fb + (unsigned)(q + 1));
+        cs_poll<false>(p.bar + NU + NX, p.NC, fb + (unsigned)(q + 1), p.bar, spin); cs_release(p.bar, relW, fb + (unsigned)(q + 1));
         LC_TS(3, q, 2);
       }
-      lc_poll(p.bar, NU + NX + p.NC, fb + (unsigned)(F + 1), p.bar, spin);
-      if (tid == 0) {
-        __hip_atomic_store(p.epoch, ep + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); rc_stamp_slot(p.epoch)[1] = wall_clock64();
-        if (__hip_atomic_load(p.bar + 257, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) *p.poison = __builtin_nanf("");
-      }
+      cs_poll<false>(p.bar, NU + NX + p.NC, fb + (unsigned)(F + 1), p.bar, spin);
+      if (tid == 0) cs_finish(p.epoch, ep, p.bar, p.poison);
     }
     return;
   }
@@ -843,7 +796,7 @@ __global__ __launch_bounds__(256) void loc_chain_bwd_kernel(const LocChainBwdArg
       float tzr[32];
 #pragma unroll
       for (int t = 0; t < 32; ++t) tzr[t] = rn_tanh(whk + ud[t]);
-      lc_wait(relX, fb + (unsigned)(q + 1), p.bar);
+      cs_wait_release(p.bar, relX, wg, fb + (unsigned)(q + 1));
       if (ci == 0) LC_TS(6, q, 0);
       {   // the KSX <= 4 partial dx of the X' workgroups: every load in flight before the first add
         float pv[4][4];
@@ -893,10 +846,10 @@ __global__ __launch_bounds__(256) void loc_chain_bwd_kernel(const LocChainBwdArg
       const int pc = tid >> 6, kg = tid & 63, pb = ci * LC_CPW + pc;
       const bool pon = tid < LC_CPW * 64 && pb < B;
       // (k-groups up to the next multiple of 32 columns: the consumer's k-step reads them; swl holds zeros beyond A)
-      if (pon && kg < (((A + 31) >> 5) << 2)) lc_store16(p.PanW + (size_t)q * pan_w + ((size_t)kg * RC_PAN_ROWS + pb) * 8, swl + pc * 128 + kg * 8);
+      if (pon && kg < (((A + 31) >> 5) << 2)) rc_store16(p.PanW + (size_t)q * pan_w + ((size_t)kg * RC_PAN_ROWS + pb) * 8, swl + pc * 128 + kg * 8);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
-      lc_arrive(p.bar + NU + NX + ci, fb + (unsigned)(q + 1));
+      cs_arrive(p.bar + NU + NX + ci, fb + (unsigned)(q + 1));
       if (ci == 0) LC_TS(6, q, 2);
       if (pon && kg < (p.ld_dwhr >> 3) && kg < 16)
         *reinterpret_cast<bf16x8*>(p.dWhrs + ((size_t)s * Bs + pb) * p.ld_dwhr + kg * 8) = *reinterpret_cast<const bf16x8*>(swl + pc * 128 + kg * 8);
@@ -923,7 +876,7 @@ __global__ __launch_bounds__(256) void loc_chain_bwd_kernel(const LocChainBwdArg
       }
     }
     __syncthreads();
-    lc_arrive(p.bar + NU + NX + ci, fb + (unsigned)(F + 1));
+    cs_arrive(p.bar + NU + NX + ci, fb + (unsigned)(F + 1));
     return;
   }
 
@@ -946,7 +899,7 @@ __global__ __launch_bounds__(256) void loc_chain_bwd_kernel(const LocChainBwdArg
     const uint32_t key = drop_key(p.dd);
     for (int q = 0; q < F; ++q) {
       const int s = F - 1 - q;
-      lc_wait(relG, fb + (unsigned)(q + 1), p.bar);
+      cs_wait_release(p.bar, relG, wg, fb + (unsigned)(q + 1));
       if (xi == 0) LC_TS(5, q, 0);
       f32x4 acc[RBX];
 #pragma unroll
@@ -972,11 +925,11 @@ __global__ __launch_bounds__(256) void loc_chain_bwd_kernel(const LocChainBwdArg
       }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
-      lc_arrive(p.bar + wg, fb + (unsigned)(q + 1));
+      cs_arrive(p.bar + wg, fb + (unsigned)(q + 1));
       if (xi == 0) LC_TS(5, q, 2);
     }
     __syncthreads();
-    lc_arrive(p.bar + wg, fb + (unsigned)(F + 1));
+    cs_arrive(p.bar + wg, fb + (unsigned)(F + 1));
     return;
   }
 
@@ -1041,11 +994,11 @@ __global__ __launch_bounds__(256) void loc_chain_bwd_kernel(const LocChainBwdArg
 #pragma unroll
       for (int i = 0; i < RBU; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
       // dG_{s+1} is complete (X', on the critical path, streams the same 1.4 MB panel out of the L2s at the same time)
-      lc_wait(relG, fb + (unsigned)q, p.bar);
+      cs_wait_release(p.bar, relG, wg, fb + (unsigned)q);
       if (wg == 0) LC_TS(4, q, 0);
       lcb_product<STEPS, PF, RBU>(acc, wb, p.PanG + (size_t)(q - 1) * pan_g + lane_off, K, kw0, rot);
       if (wg == 0) LC_TS(4, q, 1);
-      lc_wait(relW, fb + (unsigned)q, p.bar);                        // dWhr_{s+1} is complete
+      cs_wait_release(p.bar, relW, wg, fb + (unsigned)q);                        // dWhr_{s+1} is complete
       if (wg == 0) LC_TS(4, q, 2);
       {
         const int k = wave * 32;
@@ -1087,10 +1040,10 @@ __global__ __launch_bounds__(256) void loc_chain_bwd_kernel(const LocChainBwdArg
     if (wg == 0) LC_TS(4, q, 3);
 #pragma unroll
     for (int jj = 0; jj < IPT; ++jj)
-      if (it_on[jj]) lc_store16(p.PanG + (size_t)q * pan_g + ((size_t)(it_col[jj] >> 3) * RC_PAN_ROWS + it_rg[jj]) * 8, it_src[jj]);
+      if (it_on[jj]) rc_store16(p.PanG + (size_t)q * pan_g + ((size_t)(it_col[jj] >> 3) * RC_PAN_ROWS + it_rg[jj]) * 8, it_src[jj]);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    lc_arrive(p.bar + wg, fb + (unsigned)(q + 1));
+    cs_arrive(p.bar + wg, fb + (unsigned)(q + 1));
     if (wg == 0) LC_TS(4, q, 4);
     // ---- off the critical path: the row-major copy for the deferred weight-gradient GEMMs
     bf16_t* Gt = p.dG + (size_t)s * Bs * p.ld_dg;
@@ -1102,7 +1055,7 @@ __global__ __launch_bounds__(256) void loc_chain_bwd_kernel(const LocChainBwdArg
     if (q + 1 < F) prefetch(s - 1);
   }
   __syncthreads();
-  lc_arrive(p.bar + wg, fb + (unsigned)(F + 1));
+  cs_arrive(p.bar + wg, fb + (unsigned)(F + 1));
 }
 template <int RBU, int RBX, int XS = 0> constexpr size_t lcb_smem_bytes() {
   constexpr int RB = RBU > RBX ? RBU : RBX;

@@ -15,6 +15,7 @@
 //   * the weight rows come from the ordinary gate-major packed image (row gate*R + u): the gather happens once.
 #pragma once
 #include "common.hpp"
+#include "chain_sync.hpp"
 
 struct RecChainArgs {
   int T, B, R, gru;
@@ -28,7 +29,7 @@ struct RecChainArgs {
   unsigned* bar;                  // grid barrier flags, one word per workgroup (never cleared: see rc_epoch_read)
   unsigned* epoch;
   int master;                     // 1: gridDim.x has one extra column; block (gridDim.x - 1, 0) is the barrier master
-  float* poison;                  // see rc_give_up
+  float* poison;                  // see rc_give_up (chain_sync.hpp)
   float* hmean; bf16_t* hmean_lp; int ld_hmean;   // mean_t h_t [B][R] (+ operand copy, zero padded): what the output layer reads
   // Output-layer epilogue (epi = 1; global reconstructor, train.py:96-103): after the last step the launch also computes
   //   out = mean_t h_t . W_o^T + b_o ;  d = out - target ;  partial sums of d^2 ;  dout = gcoef d (fp32) and lp_scale gcoef d (operand copy)
@@ -49,57 +50,10 @@ struct RecChainArgs {
   float* dhr;                     // [B][R]
 };
 
-#define RC_MB 7               // 16-row blocks: B <= 112
-// Acquire side of the barriers.  An agent-scope acquire fence is `buffer_inv sc1`: it drops every non-local line of the
-// XCD's L2 — under all other workgroups of the chain and under the batched GEMMs of the side stream — 120-190 times
-// per time step (measured: 0.12 ms of a 2.29 ms train step).  It is not needed here: (a) every exchange block has its own
-// address per time step and nobody touches it before the barrier that publishes it, so no L1 / L2 can hold a line of it
-// from an earlier step of this launch; (b) lines from an earlier LAUNCH are dropped by the acquire of the kernel dispatch
-// itself (the same mechanism every producer -> consumer pair of kernels on different XCDs relies on); (c) producers write
-// through (sc1 stores) and are acknowledged before they arrive at the barrier, so memory holds the data when the
-// consumer's first — necessarily missing — load goes out; (d) flags, release words and stamped words are read with sc1
-// loads.  RC_ACQUIRE_INV=1 compiles the fences back in (same results on every test).
-#ifndef RC_ACQUIRE_INV
-#define RC_ACQUIRE_INV 0
-#endif
-// Layout of the copy of h_t that the chain itself reads back.  An MFMA A-fragment load (16 rows x 32 k, 16 bytes per
-// lane) is issued by the texture unit 16 lanes at a time, and in a row-major matrix those 16 lanes are 16 different
-// rows = 16 different cache lines for 256 bytes (measured: ~58 clocks per wave load, 8 us per step for the 307 KB
-// block).  Stored as [k / 8][row][8] the same 16 lanes read 256 contiguous bytes (two full lines), and a workgroup's
-// 8 units x B rows are one contiguous run for the writer.
-#define RC_PAN_ROWS (RC_MB * 16)
-// elements of one step's panel for a contraction length K (k-groups padded to whole 32-k steps)
-__host__ __device__ inline size_t rc_pan_elems(int K) { return (size_t)(((K + 31) >> 5) << 2) * RC_PAN_ROWS * 8; }
+// this thread's cells of a [ROWS][UW] tile: unit tid % UW, CPT CONSECUTIVE tile rows (tid / UW) CPT + c (cell = row * UW + unit: cell / UW and
+// cell % UW keep their meaning); UW and CPT are the using kernel's constants
+#define RC_CELL(c) (((tid / UW) * CPT + (c)) * UW + tid % UW)
 
-// Grid barrier, split in two so that the stores nobody waits for are issued between the halves.
-//   arrive: the caller has already waited for its write-through stores of h_t (s_waitcnt vmcnt(0) + __syncthreads);
-//           one agent-scope store of the step number into this workgroup's own flag — no read-modify-write, so the
-//           arrivals of the R / 8 workgroups do not serialise on one address;
-//   wait:   wave 0 polls all flags (one agent-scope load per 64 workgroups) until every one has reached the step, then
-//           invalidates this CU's L1 and this XCD's L2 (acquire) so that the next loads of h_t come from memory.
-// Launch epoch: one word per chain kernel in device memory, read by every workgroup at the start and incremented by
-// workgroup 0 at the end (a workgroup that has passed a barrier knows every other one has started).  Barrier flags are
-// epoch << 7 | phase and stamped words carry epoch << 6 | step, so neither needs clearing between launches — in a replayed
-// hipGraph each clearing memset was a 6 us node on the critical path.
-// Phase stamps (recnet_read_stamps): the launch-epoch words of the six chain kernels are consecutive words at the start of a
-// 256-byte line; the line behind it holds one pair of 100 MHz wall-clock stamps per chain — written by workgroup 0 when it starts
-// running and when it leaves — so that a REPLAYED hipGraph, which no tracer has to be attached to, reports where its step went
-// (prologue / chains / gaps / tail) at the cost of two 8-byte stores per launch.
-__device__ __forceinline__ unsigned long long* rc_stamp_slot(const unsigned* epoch) {
-  const unsigned long long a = (unsigned long long)epoch;
-  return reinterpret_cast<unsigned long long*>((a & ~255ull) + 256ull) + 2 * ((a >> 2) & 7ull);
-}
-__device__ __forceinline__ unsigned rc_epoch_read(const unsigned* epoch) {
-  // (written through: wait_chain_kernel on another XCD polls it)
-  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) __hip_atomic_store(rc_stamp_slot(epoch), (unsigned long long)wall_clock64(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  return __hip_atomic_load(epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void rc_epoch_bump(unsigned* epoch, unsigned e) {
-  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
-    __hip_atomic_store(epoch, e + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    rc_stamp_slot(epoch)[1] = wall_clock64();
-  }
-}
 // Ordering tool for the streams BESIDE a chain: a chain kernel's workgroups need whole CUs (up to 512 registers per lane), so
 // ordinary workgroups that are already running when it launches delay its residency by as long as they run.  Work that may run
 // beside chain k is therefore enqueued behind this one-wave kernel, which returns once workgroup 0 of chain k has started in the
@@ -115,92 +69,13 @@ __global__ void wait_chain_kernel(const unsigned long long* step_start, const un
     __builtin_amdgcn_s_sleep(8);
   }
 }
-// Every wait in the chain kernels is bounded: a launch whose workgroups are not all resident (two such launches sharing
-// the GPU) would otherwise spin forever and take the device with it.  After ~2^22 polls (seconds) a waiter raises the
-// sticky word bar[257]; every wait of this and of later launches then falls through, and the kernel poisons the step's
-// total loss with NaN (rc_poison) — wrong loudly instead of hung.
-#define RC_SPIN_LIMIT (1u << 22)
-// 16 bytes per lane, written through to the agent's coherence point: the instruction an agent-scope relaxed atomic store compiles
-// to (global_store_dwordx2 ... sc1), in its 16-byte form — one request per lane instead of two
-// (the s_nop 1 = the TWO wait states a VMEM store of more than 8 bytes needs before a VALU instruction may overwrite its data
-// registers: the compiler's hazard recognizer inserts `s_nop 1` behind its own dwordx4 stores and does not look inside inline asm —
-// without it the next loop iteration's adds corrupted the stored values; `s_nop 0` was one state short)
-__device__ __forceinline__ void rc_store16f(float* dst, f32x4 v) {
-  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(dst), "v"(v) : "memory");
-}
-__device__ __forceinline__ void rc_store16(bf16_t* dst, const bf16_t* src) {
-  rc_store16f(reinterpret_cast<float*>(dst), *reinterpret_cast<const f32x4*>(src));
-}
-__device__ __forceinline__ bool rc_give_up(unsigned* bar, unsigned& spin) {
-  if ((++spin & 0x3ffu) != 0) return false;
-  if (spin <= RC_SPIN_LIMIT && __hip_atomic_load(bar + 257, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) return false;
-  __hip_atomic_store(bar + 257, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  return true;
-}
-__device__ __forceinline__ void rc_poison(unsigned* bar, float* poison) {
-  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0 && __hip_atomic_load(bar + 257, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)
-    *poison = __builtin_nanf("");
-}
-__device__ __forceinline__ void rc_arrive(unsigned* flags, unsigned step) {
-  if (threadIdx.x == 0) __hip_atomic_store(flags + blockIdx.y * gridDim.x + blockIdx.x, step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void rc_arrive_at(unsigned* flags, int idx, unsigned step) {
-  if (threadIdx.x == 0) __hip_atomic_store(flags + idx, step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void rc_wait(unsigned* flags, unsigned step) {
-#ifndef RC_PROBE_NO_BARRIER
-  if (threadIdx.x < 64) {
-    // n <= 256 flags: four loads per lane, all in flight together (a loop that folds each flag into a running minimum
-    // waits for every load before issuing the next one: three memory round trips per poll instead of one)
-    const int n = gridDim.x * gridDim.y;
-    const unsigned* f0 = flags + (threadIdx.x < n ? threadIdx.x : n - 1);
-    const unsigned* f1 = flags + (threadIdx.x + 64 < n ? threadIdx.x + 64 : n - 1);
-    const unsigned* f2 = flags + (threadIdx.x + 128 < n ? threadIdx.x + 128 : n - 1);
-    const unsigned* f3 = flags + (threadIdx.x + 192 < n ? threadIdx.x + 192 : n - 1);
-    unsigned spin = 0;
-    for (;;) {
-      const unsigned a0 = __hip_atomic_load(f0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const unsigned a1 = __hip_atomic_load(f1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const unsigned a2 = __hip_atomic_load(f2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const unsigned a3 = __hip_atomic_load(f3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      // flags count up across launches (base = launch epoch << 7, see rc_epoch_base): signed distance, wrap-safe
-      const bool ok = (int)(a0 - step) >= 0 && (int)(a1 - step) >= 0 && (int)(a2 - step) >= 0 && (int)(a3 - step) >= 0;
-      if (__all(ok)) break;
-      if (rc_give_up(flags, spin)) break;
-      __builtin_amdgcn_s_sleep(1);
-    }
-#ifndef RC_PROBE_NO_FENCE
-    if (RC_ACQUIRE_INV) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-#endif
-  }
-#endif
-  __syncthreads();
-}
-
-// Barrier through a master workgroup.  With every workgroup polling every flag, the 130-190 pollers (four wave loads each
-// per round, all to the same six lines) queue up at the memory side: the flag round cost 2.7 us, while an uncontended
-// store -> load hand-over between two CUs is 0.3-0.4 us (tools/micro/xcd_pingpong.hip).  Here one extra workgroup does
-// nothing but poll the arrival flags and, when all have reached a phase, write that phase into eight release words (one
-// 128-byte line per XCD-sized group of workgroups); the workers poll only their release word.
-__device__ __forceinline__ void rc_master_loop(unsigned* flags, unsigned* release, int n, unsigned fb, int phases) {
+// the barrier master of a chain (see cs_release): relays `phases` barriers of its n workers
+__device__ __forceinline__ void rc_master_loop(unsigned* bar, int n, unsigned fb, int phases) {
   if (threadIdx.x >= 64) return;
-  const unsigned* f0 = flags + (threadIdx.x < n ? threadIdx.x : n - 1);
-  const unsigned* f1 = flags + (threadIdx.x + 64 < n ? threadIdx.x + 64 : n - 1);
-  const unsigned* f2 = flags + (threadIdx.x + 128 < n ? threadIdx.x + 128 : n - 1);
-  const unsigned* f3 = flags + (threadIdx.x + 192 < n ? threadIdx.x + 192 : n - 1);
   unsigned spin = 0;
   for (int ph = 1; ph <= phases; ++ph) {
-    const unsigned step = fb + (unsigned)ph;
-    for (;;) {
-      const unsigned a0 = __hip_atomic_load(f0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const unsigned a1 = __hip_atomic_load(f1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const unsigned a2 = __hip_atomic_load(f2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const unsigned a3 = __hip_atomic_load(f3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const bool ok = (int)(a0 - step) >= 0 && (int)(a1 - step) >= 0 && (int)(a2 - step) >= 0 && (int)(a3 - step) >= 0;
-      if (__all(ok)) break;
-      if (rc_give_up(flags, spin)) break;
-    }
-    if (threadIdx.x < 8) __hip_atomic_store(release + threadIdx.x * 32, step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    cs_poll<false>(bar, n, fb + (unsigned)ph, bar, spin);
+    cs_release(bar, CS_REL_A, fb + (unsigned)ph);
   }
 }
 // XCD-aware roles of a (unit groups x row parts) grid (round 5).  Workgroup L = blockIdx.y * gridDim.x + blockIdx.x runs on XCD L % 8
@@ -225,17 +100,6 @@ __device__ __forceinline__ RcRole rc_role(int nwx, int has_master) {
     r.idle = has_master && (int)blockIdx.x == nwx && blockIdx.y != 0;
   }
   return r;
-}
-__device__ __forceinline__ void rc_wait_release(const unsigned* release, unsigned step) {
-#ifndef RC_PROBE_NO_BARRIER
-  if (threadIdx.x < 64) {
-    const unsigned* r = release + ((blockIdx.y * gridDim.x + blockIdx.x) & 7) * 32;      // the line of this workgroup's XCD
-    unsigned spin = 0;
-    while ((int)(__hip_atomic_load(r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - step) < 0) { if (rc_give_up(const_cast<unsigned*>(release) - 256, spin)) break; }
-    if (RC_ACQUIRE_INV) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  }
-#endif
-  __syncthreads();
 }
 
 // STEPS = k32-steps per wave (R <= 4 * 32 * STEPS, even); PF = activation prefetch distance in pairs of k-steps.
@@ -267,7 +131,7 @@ __global__ __launch_bounds__(256) void rec_chain_kernel(const RecChainArgs p) {
   constexpr int NP = STEPS / 2;
   const unsigned ep = rc_epoch_read(p.epoch), fb = ep << 7;
   const int widx = vy * nwx + vx;                        // my flag
-  if (role.master) { rc_master_loop(p.bar, p.bar + 256, nwx * (int)gridDim.y, fb, p.T - 1 + p.epi); return; }
+  if (role.master) { rc_master_loop(p.bar, nwx * (int)gridDim.y, fb, p.T - 1 + p.epi); return; }
   if (role.idle) return;
   const int rot = vx % NP;                               // workgroups start at different k: spreads the L2 channels
   auto k_of = [&](int pr, int hh) { int prr = pr + rot; prr = prr >= NP ? prr - NP : prr; return kw0 + (prr * 2 + hh) * 32; };
@@ -286,9 +150,7 @@ __global__ __launch_bounds__(256) void rec_chain_kernel(const RecChainArgs p) {
         wb[pr * 2 + hh][g] = (k + kq < R) ? *reinterpret_cast<const bf16x8*>(wrow + k) : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
       }
   }
-  // ---- this thread's cells: unit u0 + tid % UW, CPT CONSECUTIVE tile rows (tid / UW) CPT + c (round 6: the K partials of a unit's
-  // four rows are one 16-byte LDS read per gate and wave; cell = row * UW + unit as before, so cell / UW and cell % UW keep their meaning)
-#define RC_CELL(c) (((tid / UW) * CPT + (c)) * UW + tid % UW)
+  // ---- this thread's cells (RC_CELL; round 6: the K partials of a unit's four rows are one 16-byte LDS read per gate and wave)
   constexpr int CPT = (ROWS * UW + 255) / 256;
   float xg[CPT][4], cpv[CPT];
   bool mine[CPT];
@@ -313,15 +175,7 @@ __global__ __launch_bounds__(256) void rec_chain_kernel(const RecChainArgs p) {
 
   const int lane_off = ((lane >> 4) * RC_PAN_ROWS + r0 + (lane & 15)) * 8;   // k-group (lane / 16), row r0 + lane % 16
   const size_t pan_t = rc_pan_elems(R);                                      // elements per time step
-  if ((R & 31) && blockIdx.x == 0 && blockIdx.y == 0) {
-    // zero the k-groups that pad R to a multiple of 32, in every step's panel: a partly live k-step reads them
-    // (against zero weights — but 0 x garbage could be NaN).  Published by the first barrier like h_0.
-    const int pad0 = R >> 3, padn = (((R + 31) >> 5) << 2) - pad0;
-    for (int t = 0; t < p.T; ++t)
-      for (int j = tid; j < padn * RC_PAN_ROWS * 2; j += 256)
-        __hip_atomic_store(reinterpret_cast<uint64_t*>(p.Pan + (size_t)t * pan_t + (size_t)pad0 * RC_PAN_ROWS * 8) + j, (uint64_t)0,
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  if ((R & 31) && blockIdx.x == 0 && blockIdx.y == 0) rc_pan_zero_pad(p.Pan, R, p.T, tid);
 
   for (int t = 0; t < p.T; ++t) {
     if (t > 0) {
@@ -420,7 +274,7 @@ __global__ __launch_bounds__(256) void rec_chain_kernel(const RecChainArgs p) {
     if (more) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
-      rc_arrive_at(p.bar, widx, fb + (unsigned)(t + 1));
+      cs_arrive(p.bar + widx, fb + (unsigned)(t + 1));
     }
     // ---- everything below is off the critical path of the chain
     float* Ht = p.H + (size_t)t * Bs * R;
@@ -449,7 +303,7 @@ __global__ __launch_bounds__(256) void rec_chain_kernel(const RecChainArgs p) {
       }
     if (more) {
       load_x(t + 1);                                     // independent of the other workgroups: in flight across the barrier
-      if (p.master) rc_wait_release(p.bar + 256, fb + (unsigned)(t + 1)); else rc_wait(p.bar, fb + (unsigned)(t + 1));
+      if (p.master) cs_wait_release(p.bar, CS_REL_A, cs_wg(), fb + (unsigned)(t + 1)); else cs_wait_grid(p.bar, fb + (unsigned)(t + 1));
     }
   }
   // mean_t h_t (train.py:96-98 averages the outputs; the output layer is linear, so it runs once on the mean)
@@ -486,7 +340,7 @@ __global__ __launch_bounds__(256) void rec_chain_kernel(const RecChainArgs p) {
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    rc_arrive_at(p.bar, widx, fb + (unsigned)p.T);
+    cs_arrive(p.bar + widx, fb + (unsigned)p.T);
     // ... W_o rows of its 16 output columns into the registers W_hh has left, the target and the bias while the barrier completes
     bf16x8 wo[STEPS];
     {
@@ -505,7 +359,7 @@ __global__ __launch_bounds__(256) void rec_chain_kernel(const RecChainArgs p) {
       tg[c] = p.target[(size_t)row * R + u];
       ob[c] = p.obias[u];
     }
-    rc_wait_release(p.bar + 256, fb + (unsigned)p.T);
+    cs_wait_release(p.bar, CS_REL_A, cs_wg(), fb + (unsigned)p.T);
     {
       const bf16_t* A = p.PanM + lane_off;
       f32x4 acc[RB];
@@ -579,7 +433,7 @@ __global__ __launch_bounds__(256) void rec_chain_kernel(const RecChainArgs p) {
       }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
-      rc_arrive_at(p.bar, widx, fb + (unsigned)p.T + 1u);
+      cs_arrive(p.bar + widx, fb + (unsigned)p.T + 1u);
       bf16x8 wt[STEPS];
       {
         const bf16_t* wrow = p.WoT + (size_t)(u0 + (lane & 15)) * p.ldwot + kq;
@@ -589,7 +443,7 @@ __global__ __launch_bounds__(256) void rec_chain_kernel(const RecChainArgs p) {
           wt[ks] = (k + kq < R) ? *reinterpret_cast<const bf16x8*>(wrow + k) : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
         }
       }
-      rc_wait_release(p.bar + 256, fb + (unsigned)p.T + 1u);
+      cs_wait_release(p.bar, CS_REL_A, cs_wg(), fb + (unsigned)p.T + 1u);
       {
         const bf16_t* A = p.PanD + lane_off;
         f32x4 acc[RB];
@@ -634,9 +488,7 @@ __global__ __launch_bounds__(256) void rec_chain_kernel(const RecChainArgs p) {
       }
     }
   }
-#undef RC_CELL
-  rc_epoch_bump(p.epoch, ep);
-  rc_poison(p.bar, p.poison);
+  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) cs_finish(p.epoch, ep, p.bar, p.poison);
 }
 template <int RB, int CG> constexpr size_t rc_smem_bytes() { return (size_t)4 * (CG * 16) * (RB * 16 + 4) * 4 + (size_t)RB * 16 * 4 * CG * 2; }
 
@@ -682,7 +534,7 @@ __global__ __launch_bounds__(256) void rec_chain_bwd_kernel(const RecChainBwdArg
   const int kq = (lane >> 4) * 8;
   const unsigned ep = rc_epoch_read(p.epoch), fb = ep << 7;
   const int widx = vy * nwx + vx;
-  if (role.master) { rc_master_loop(p.bar, p.bar + 256, nwx * (int)gridDim.y, fb, p.T - 1); return; }
+  if (role.master) { rc_master_loop(p.bar, nwx * (int)gridDim.y, fb, p.T - 1); return; }
   if (role.idle) return;
   const int rot = vx % NP;
   auto k_of = [&](int pr, int hh) { int prr = pr + rot; prr = prr >= NP ? prr - NP : prr; return kw0 + (prr * 2 + hh) * 32; };
@@ -702,13 +554,11 @@ __global__ __launch_bounds__(256) void rec_chain_bwd_kernel(const RecChainBwdArg
   }
   constexpr int CPT = (ROWS * UW + 255) / 256;
   static_assert(CPT == 4, "four consecutive rows per thread");
-  // this thread's cells: unit u0 + tid % UW, rows (tid / UW) CPT + c (cell = row * UW + unit: cell / UW and cell % UW as before)
-#define RCB_CELL(c) (((tid / UW) * CPT + (c)) * UW + tid % UW)
   bool mine[CPT];
   float direct[CPT], carry[CPT], av[CPT][4], cc[CPT], cp[CPT];
 #pragma unroll
   for (int c = 0; c < CPT; ++c) {
-    const int cell = RCB_CELL(c), rg = r0 + cell / UW;
+    const int cell = RC_CELL(c), rg = r0 + cell / UW;
     mine[c] = cell < ROWS * UW && rg >= own_lo && rg < own_lo + own && rg < B;
     direct[c] = mine[c] ? p.dh_scale * p.dh_direct[(size_t)rg * R + u0 + cell % UW] : 0.f;
     carry[c] = 0.f;
@@ -716,7 +566,7 @@ __global__ __launch_bounds__(256) void rec_chain_bwd_kernel(const RecChainBwdArg
   auto prefetch = [&](int t) {                            // saved activations and states of step t
 #pragma unroll
     for (int c = 0; c < CPT; ++c) {
-      const int cell = RCB_CELL(c);
+      const int cell = RC_CELL(c);
       const size_t row = mine[c] ? r0 + cell / UW : 0;
       const int u = u0 + cell % UW;
       const float* a = p.acts + ((size_t)t * Bs + row) * 4 * R + u;
@@ -802,7 +652,7 @@ __global__ __launch_bounds__(256) void rec_chain_bwd_kernel(const RecChainBwdArg
     }
 #pragma unroll
     for (int c = 0; c < CPT; ++c) {
-      const int cell = RCB_CELL(c);
+      const int cell = RC_CELL(c);
       const int row = cell < ROWS * UW ? cell / UW : 0, ul = cell % UW;
       const float dh = direct[c] + dsum[c];
       const LstmGrad g = p.gru ? gru_point_bwd(dh + carry[c], av[c][0], av[c][1], av[c][2], av[c][3], cp[c])
@@ -824,7 +674,7 @@ __global__ __launch_bounds__(256) void rec_chain_bwd_kernel(const RecChainBwdArg
     if (more) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
-      rc_arrive_at(p.bar, widx, fb + (unsigned)(s + 1));
+      cs_arrive(p.bar + widx, fb + (unsigned)(s + 1));
     }
     // ---- off the critical path: the row-major copy for the deferred weight-gradient GEMMs
     bf16_t* Gt = p.dG + (size_t)t * Bs * p.ld_dg;
@@ -838,12 +688,10 @@ __global__ __launch_bounds__(256) void rec_chain_bwd_kernel(const RecChainBwdArg
       }
     if (more) {
       prefetch(t - 1);
-      if (p.master) rc_wait_release(p.bar + 256, fb + (unsigned)(s + 1)); else rc_wait(p.bar, fb + (unsigned)(s + 1));
+      if (p.master) cs_wait_release(p.bar, CS_REL_A, cs_wg(), fb + (unsigned)(s + 1)); else cs_wait_grid(p.bar, fb + (unsigned)(s + 1));
     }
   }
-#undef RCB_CELL
-  rc_epoch_bump(p.epoch, ep);
-  rc_poison(p.bar, p.poison);
+  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) cs_finish(p.epoch, ep, p.bar, p.poison);
 }
 template <int RB, int CG, int KL = 0> constexpr size_t rc_bwd_smem_bytes() {
   return (size_t)4 * (16 * CG) * (RB * 16 + 4) * 4 + (size_t)RB * 16 * 4 * 16 * CG * 2 + (size_t)KL * CG * 256 * 16;

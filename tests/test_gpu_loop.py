@@ -162,6 +162,39 @@ def test_chain_give_up_skips_the_update_and_is_reported():
     assert any(not torch.equal(v, before[k]) for k, v in tr.decoder["model"].state_dict().items())
 
 
+def test_chain_status_bits_map_to_their_barrier_blocks():
+    """The table of csrc/chain_sync.hpp through the ABI: status bit 1 << k is the sticky word of barrier block k.  Raising a
+    chain's bit (recnet_debug_raise_give_up) shows up as exactly that bit plus the poisoned-loss bit 256, and a reset that leaves
+    the persistent kernels on clears both.  No chain kernel runs while a word is raised."""
+    from tests import golden_util as GU
+    from tests.gpu_util import make_models
+    dims = [24, 6, 64, 61, 16, 32, 16, 16]                  # the persistent-chain shape of tests/test_gpu_knobs.py
+    B, F, D, Vc, E, H, A, RA = dims
+    decP = GU.formula_params(GU.decoder_shapes(Vc, E, H, A, D), 3)
+    recP = GU.formula_params(GU.rec_shapes("global", H, D, RA), 4)
+    _, dec, rec = make_models(list(dims), "global", "bf16", decP, recP)
+    step = R.TrainStep(dec, rec)
+    enc, targets = GU.make_batch(B, F, D, Vc, [30] + list(range(1, B)), 11)
+    T, w = step.prepare(targets.numpy())
+    step(enc.cuda(), targets.cuda(), T, w)                  # one healthy eager step
+    eng = step.engine
+    assert eng.chain_status() == 0
+    for bit in (1, 2, 4, 8, 32, 64):
+        eng.debug_raise_give_up(bit)
+        assert eng.chain_status() == bit | 256, bit
+        eng.chain_reset(False)
+        assert eng.chain_status() == 0, bit
+    with pytest.raises(RuntimeError, match="chain_bit"):              # (_lib.RecNetError)
+        eng.debug_raise_give_up(3)                           # not a single bit
+    assert eng.chain_status() == 0
+    # 16 is no chain's bit — block 4 holds the launch epochs and the phase stamps — but the ABI has always taken it as the
+    # spare word CS_STICKY of that block, which no kernel reads: raised, reported and cleared like the others
+    eng.debug_raise_give_up(16)
+    assert eng.chain_status() == 16 | 256
+    eng.chain_reset(False)
+    assert eng.chain_status() == 0
+
+
 def test_teacher_forcing_ratio_below_one_runs_eager_steps_with_the_host_draw():
     """config.py:71 decoder_teacher_forcing_ratio < 1: the draw of train.py:38 is a host decision per iteration, so the Trainer
     keeps to eager steps (a replayed graph makes no draw; GraphedStep refuses such a step) — and the same seven iterations
