@@ -13,7 +13,7 @@ int recnet_profile_null_launch(recnet_handle* h, int32_t count, void* stream) {
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (!prof_take(h, st, &e0, &e1)) return fail(RECNET_ESTATE, "profile brackets are taken around eager launches only (the stream is capturing)");
   HIPCHK(hipEventRecord(e0, st));
-  for (int i = 0; i < count; ++i) hipLaunchKernelGGL(set_u32_kernel, dim3(1), dim3(1), 0, st, h->ctrl + 8, 0u);
+  for (int i = 0; i < count; ++i) hipLaunchKernelGGL(set_u32_kernel, dim3(1), dim3(1), 0, st, h->ctrl + RN_CTRL_SINK_LAUNCH, 0u);
   HIPCHK(hipEventRecord(e1, st));
   LAUNCH_OK();
   return RECNET_OK;
@@ -74,7 +74,7 @@ __global__ __launch_bounds__(256) void lds_poison_kernel(unsigned* sink) {
 int recnet_debug_poison_lds(recnet_handle* h, void* stream) {
   REQUIRE_WS(h);
   hipFuncSetAttribute(reinterpret_cast<const void*>(lds_poison_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-  hipLaunchKernelGGL(lds_poison_kernel, dim3(h->ncu > 0 ? 8 * h->ncu : 2048), dim3(256), 65536, (hipStream_t)stream, h->ctrl + 16);
+  hipLaunchKernelGGL(lds_poison_kernel, dim3(h->ncu > 0 ? 8 * h->ncu : 2048), dim3(256), 65536, (hipStream_t)stream, h->ctrl + RN_CTRL_SINK_LDS);
   LAUNCH_OK();
   return RECNET_OK;
 }
@@ -97,7 +97,7 @@ int recnet_chain_status(recnet_handle* h, int32_t* status_out, void* stream) {
   uint32_t w[CS_WS_BLOCKS]; float poison = 0.f;
   HIPCHK(hipStreamSynchronize((hipStream_t)stream));
   for (int k = 0; k < CS_WS_BLOCKS; ++k) HIPCHK(hipMemcpy(&w[k], cs_ws_sticky(h->gbar, k), 4, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(&poison, h->scal + 15, 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(&poison, h->scal + RN_SCAL_POISON, 4, hipMemcpyDeviceToHost));
   int32_t s = 0;
   for (int k = 0; k < CS_WS_BLOCKS; ++k) if (w[k]) s |= 1 << k;
   if (poison != 0.f) s |= 256;      // NaN != 0
@@ -112,9 +112,9 @@ int recnet_read_stamps(recnet_handle* h, uint64_t* out, int32_t n, void* stream)
   // front of it could return the stamps of a step that has not finished)
   HIPCHK(hipStreamSynchronize((hipStream_t)stream));
   if (n >= 30) HIPCHK(hipMemcpy(&out[14], h->gbar + CS_WS_GROUP_STAMPS, 16 * 8, hipMemcpyDeviceToHost));      // grouped launches: 8 x (start, end)
-  HIPCHK(hipMemcpy(&out[0], h->ctrl + 32, 8, hipMemcpyDeviceToHost));                       // step start (advance_step_kernel)
+  HIPCHK(hipMemcpy(&out[0], h->ctrl + RN_CTRL_STAMP_START, 8, hipMemcpyDeviceToHost));                       // step start (advance_step_kernel)
   HIPCHK(hipMemcpy(&out[1], h->gbar + CS_WS_STAMPS, 12 * 8, hipMemcpyDeviceToHost));           // six chains x (begin, end): rc_stamp_slot
-  HIPCHK(hipMemcpy(&out[13], h->scal + 32, 8, hipMemcpyDeviceToHost));                      // step end (export_scalars_kernel)
+  HIPCHK(hipMemcpy(&out[13], h->scal + RN_SCAL_STAMP_END, 8, hipMemcpyDeviceToHost));                      // step end (export_scalars_kernel)
   return RECNET_OK;
 }
 // ---- staging kernels of the direct gradient transport (include/recnet_hip.h; kernels_util.hpp)
@@ -145,18 +145,18 @@ int recnet_read_step_ring(recnet_handle* h, uint64_t* out16, void* stream) {
   REQUIRE_WS(h);
   if (!out16) return fail(RECNET_EINVAL, "null argument");
   HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-  HIPCHK(hipMemcpy(&out16[0], h->ctrl + 34, 8 * 8, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(&out16[8], h->scal + 34, 8 * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(&out16[0], h->ctrl + RN_CTRL_RING, 8 * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(&out16[8], h->scal + RN_SCAL_RING, 8 * 8, hipMemcpyDeviceToHost));
   return RECNET_OK;
 }
 int recnet_chain_reset(recnet_handle* h, int32_t disable_persistent, void* stream) {
   REQUIRE_WS(h);
   hipStream_t st = (hipStream_t)stream;
   for (int k = 0; k < CS_WS_BLOCKS; ++k) HIPCHK(hipMemsetAsync(cs_ws_sticky(h->gbar, k), 0, 4, st));
-  HIPCHK(hipMemsetAsync(h->scal + 15, 0, 4, st));
+  HIPCHK(hipMemsetAsync(h->scal + RN_SCAL_POISON, 0, 4, st));
   // a pending deferred reconstructor update belongs to a step whose results are void: drop it (the poison word that made its
   // Adam kernel a no-op is cleared above, so a later flush would otherwise apply the garbage step's gradients)
-  HIPCHK(hipMemsetAsync(h->ctrl + 2, 0, 4, st));
+  HIPCHK(hipMemsetAsync(h->ctrl + RN_CTRL_PENDING, 0, 4, st));
   h->maybe_pending = 0;
   if (disable_persistent) {
     h->persist_rec = h->persist_rec_bwd = h->persist_dec = h->persist_dec_bwd = 0; h->persist_loc = h->persist_loc_bwd = 0;
@@ -172,7 +172,7 @@ int recnet_debug_raise_give_up(recnet_handle* h, int32_t chain_bit, void* stream
   if (k < 0) return fail(RECNET_EINVAL, "chain_bit must be one chain's status bit");
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(set_u32_kernel, dim3(1), dim3(1), 0, st, cs_ws_sticky(h->gbar, k), 1u);
-  hipLaunchKernelGGL(set_u32_kernel, dim3(1), dim3(1), 0, st, (uint32_t*)(h->scal + 15), 0x7fc00000u);
+  hipLaunchKernelGGL(set_u32_kernel, dim3(1), dim3(1), 0, st, (uint32_t*)(h->scal + RN_SCAL_POISON), 0x7fc00000u);
   LAUNCH_OK();
   return RECNET_OK;
 }
@@ -267,7 +267,7 @@ int recnet_debug_occupy(recnet_handle* h, int32_t n_workgroups, int32_t microsec
   if (n_workgroups < 1 || n_workgroups > 1024 || microseconds < 1 || microseconds > 100000) return fail(RECNET_EINVAL, "bad occupy argument");
   const int lds = 160 * 1024;     // the whole LDS of a CU: nothing else is co-resident with one of these workgroups
   hipFuncSetAttribute(reinterpret_cast<const void*>(occupy_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  hipLaunchKernelGGL(occupy_kernel, dim3(n_workgroups), dim3(256), lds, (hipStream_t)stream, (unsigned long long)microseconds * 100ull, h->ctrl + 17);
+  hipLaunchKernelGGL(occupy_kernel, dim3(n_workgroups), dim3(256), lds, (hipStream_t)stream, (unsigned long long)microseconds * 100ull, h->ctrl + RN_CTRL_SINK_OCCUPY);
   LAUNCH_OK();
   return RECNET_OK;
 }

@@ -69,7 +69,7 @@ int recnet_reconstructor_step(recnet_handle* h, const float* input, const float*
   gate_bias(h->rP.rnn_bias_ih_l0, h->rP.rnn_bias_hh_l0, h->bsum_r, R, h->rgru, st);
   const float* c_prev = h->rgru ? hr_in : cr_in;
   if (hr_in) pack_block(h, h->Hr_lp, h->ldR, hr_in, R, B, R, 1.f, st);
-  h->fwd_dec_done = h->fwd_rec_done = 0; h->mp_done = 0;     // Hs / Hs_lp / Hr_lp no longer hold a sequence-level forward
+  h->fwd_dec_done = h->fwd_rec_done = 0; h->ss.mp_done = 0;     // Hs / Hs_lp / Hr_lp no longer hold a sequence-level forward
   const DropDesc dd = mkdrop(h, RN_SITE_REC_INPUT, h->c.reconstructor_decoder_dropout, train);
   if (h->kind == RECNET_REC_GLOBAL) {
     if (decoder_hiddens)   // (caption_max_len / T^2) sum_t h_t: mean over T and L, rescaled (global_reconstructor.py:33-37)

@@ -32,6 +32,7 @@
 #include "dec_chain.hpp"
 #include "loc_chain.hpp"
 #include "loc_big.hpp"
+#include "step_sched.hpp"
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string& m) { g_err = m; return code; }
@@ -66,13 +67,12 @@ struct recnet_handle {
   int ldD, ldE, ldH, ldV, ldA, ld4H, ldWS, ldR, ld4R, ldRA, ldHR, ldRA4, ld2H;
   // workspace
   char* ws = nullptr; size_t ws_bytes = 0; size_t need = 0;
-  uint32_t* ctrl;        // [0] seed slot, [1] step slot (int32)
+  uint32_t* ctrl;        // control words: the RN_CTRL_* slots (common.hpp)
   uint32_t* gbar;        // barrier workspace of the chain kernels (chain_sync.hpp: CS_WS_*)
-  float* scal;           // [0] dec_ce [1] dec_reg [2] dec_loss [3] rec_mse [4] rec_reg [5] rec_loss [6] total [7] gnorm [8] clip
+  float* scal;           // loss scalars, poison word, step-end stamps: the RN_SCAL_* slots (common.hpp)
   // ---- decoder: fp32 state
   float *slab2 = nullptr;   // second slab buffer (local reconstructor backward: dWhr . W_r)
   float *bsum4 = nullptr, *bsum4r = nullptr;   // [4H], [4R] column sums of the gate gradients (source of both bias gradients)
-  int prezeroed = 0;        // the step's atomic-sum targets were zeroed by one hoisted kernel (fwd_bwd)
   float *bsum_d, *Uv, *Xe, *Hs, *Cs, *acts, *Wh, *att, *logits, *rowloss, *slab, *gws, *dHs, *dHsrec, *dc_carry, *dUv,
       *dwacc, *demb, *stepw, *msep;
   // ---- decoder: operand copies (AT = bf16 | float)
@@ -86,7 +86,7 @@ struct recnet_handle {
   float *Ud, *beta, *Whr, *outl, *dHr, *dUd, *dwacc_r;
   void* Hr_pan = nullptr;
   void* hm_pan = nullptr;   // exchange copy of mean_t hr_t (rec_chain_kernel's output-layer epilogue)
-  void* hd_pan = nullptr; void* WoT = nullptr; int dhr_done = 0;   // ... of the scaled dout; W_o^T image; dhrmean computed by the epilogue
+  void* hd_pan = nullptr; void* WoT = nullptr;   // ... of the scaled dout; W_o^T image
   // backward chain for R > 2048 (loc_big.hpp): K partials, per-step masked dx / dbeta for the post-chain sums, streamed fragments of W^T
   float *lb_part = nullptr, *lb_dxm = nullptr, *lb_dbeta = nullptr; void* WstT = nullptr; int persist_big_bwd = 0, lb_steps = 0, lb_sr = 0, lb_ncb = 0;
   void* Wst = nullptr; int lc_steps = 0, lc_sr = 0;   // hybrid forward chain (R > 2048): streamed fragments image, k-steps per wave / resident
@@ -94,9 +94,8 @@ struct recnet_handle {
   void *lc_pang = nullptr, *lc_panw = nullptr; float* lc_dx = nullptr; void* WihhT = nullptr;   // ... of the backward chain; [W_ih | W_hh]^T
   int lcb_msx = 1, lcb_rbu = 4, lc_bwd_done = 0;
   int lcb_xs = 0;           // X' of the backward chain with K split over workgroups: k-steps per wave (0: whole K per workgroup)
-  int deferred_early = 0, deferred_early_flags = -1, deferred_done = 0, join_recorded = 0;   // rec_deferred_fork (host_reconstructor.inc)
   float mse_scale = 0.f; int mse_nb = 0;   // pending MSE partials: fwd_rec finalises the loss scalars in one launch
-  float dout_scale = 0.f; int dout_ready = 0;   // dout_lp already holds dout_scale * d loss / d out (written by the MSE kernel)
+  float dout_scale = 0.f;   // the scale of d loss / d out in dout_lp while ss.dout_ready
   unsigned long long* lc_ts = nullptr;   // probe builds (make probe): wall-clock stamps of the local chain kernels
   int lc_ms = 1, lc_rb = 4, lc_ng = 0, lc_nc = 0;
   void* dG_pan = nullptr;   // exchange copies of the gate gradients, rec_chain_bwd_kernel
@@ -106,33 +105,15 @@ struct recnet_handle {
   int persist_dec = 0;      // dec_chain.hpp: the decoder's teacher-forced forward chain as one launch
   float* dc_G1 = nullptr; void* dc_pan = nullptr;
   int persist_dec_bwd = 0;  // ... and its BPTT chain
-  int side_pending = 0, side_T = 0, side_phase = 0, side_err = 0;   // side_after_decoder_fwd (abi_step.inc)
-  const int64_t* side_targets = nullptr; const float* side_stepw = nullptr; const float* side_enc = nullptr;
   int bgrp_loc = 0;              // ... of the local reconstructor's chains (<= 64 rows where more do not fit: recnet_create)
   int bgrp = 0;                  // rows per launch of the persistent chain kernels: B for B <= RC_PAN_ROWS, else B split evenly into ceil(B / 112) row groups
-  // deferred reconstructor update (recnet_set_deferred_reconstructor_update): ctrl[2] on the device says whether an update is
-  // pending; maybe_pending is the host's conservative shadow (replayed graphs do not run host code)
-  int in_fused = 0, side_fork_recorded = 0;
-  // Deferred refresh of the reconstructor's DERIVED weight images (round 5; opt-in with the deferred-update modes, applies where the
-  // split update does not — 28 x 3584, row groups): the fused step skips the transposes / fragment packs behind its reconstructor
-  // Adam step (183 us at the end of the step at 28 x 3584) and runs them at the start of the NEXT fused step, on the third stream
-  // beside the decoder's forward chain; the reconstructor's chains wait for them (ev[12]).  The refresh is idempotent, so a captured
-  // step is correct behind any other; images_maybe_stale is the host's shadow for the non-fused entry points (flush_pending).
-  int img_defer_now = 0, images_maybe_stale = 0, s3_late = 0;
-  int dp_overlap = 0, side_open = 0;   // recnet_set_dp_overlap: part 1 of the data-parallel step leaves the side stream's weight-gradient products unjoined (recnet_join_side)
-  int hoist_fork_recorded = 0;   // dec_fwd_chain recorded the fork events of hoist_side_work itself, in front of the chain launch
-  int rec_loss_defer = 0, rec_loss_late = 0;   // fused step: the reconstructor's loss scalars are formed beside the BPTT (rec_loss_scalars) instead of between its two chains
-  int rec_norm_late = 0;   // mode 2: the norm of the pending-updated W_hh is joined in front of the loss scalars (ev[21]), not in front of the chain
-  int side_tail_open = 0;  // decoder-only: dec_bwd_out recorded the BPTT's join in front of the rest of the side branch (ev[18] covers the rest)
-  int total_late = 0;      // the total-loss scalar is formed on the side stream behind the BPTT's fork (fwd_bwd_impl)
+  // deferred reconstructor update (recnet_set_deferred_reconstructor_update): RN_CTRL_PENDING on the device says whether an update is
+  // pending; maybe_pending is the host's conservative shadow (replayed graphs do not run host code), defer_flags the optimiser flags
+  // of the step that left it (flush_pending of a LATER call reads them: they outlive the step, unlike ss)
+  int defer_rec = 0, maybe_pending = 0, def_rows = 0, defer_flags = 3; hipStream_t s3 = nullptr; float* gws3 = nullptr;
+  int images_maybe_stale = 0;    // the host's shadow of a deferred refresh of the derived weight images (step_sched.hpp: img_defer_now)
   int split_ok = 0;              // the pending half of a split reconstructor update fits beside the decoder forward chain (recnet_create)
-  int rec_wait_pending = 0;      // fwd_rec_global waits for ev[12] (the pending W_hh update, mode 2) in front of its recurrent chain
-  int defer_rec = 0, defer_now = 0, defer_err = 0, maybe_pending = 0, def_rows = 0, defer_flags = 3; hipStream_t s3 = nullptr; float* gws3 = nullptr;
-  int mp_done = 0;          // h->mp holds the mean-pooled decoder states of the last decoder forward (dec_chain_kernel)
   int ncu = 0;
-  int ctx_done = 0;         // the attended features of all steps were computed early (fwd_bwd_impl)
-  int hoist_pending = 0, hoist_par = 0, encmean_hoisted = 0; const float* hoist_enc = nullptr;   // see hoist_side_work (abi_step.inc)
-  int xcat_done = 0;        // dec_chain_kernel wrote the global reconstructor's input operand itself (host_decoder.inc)
   float* dc_G2 = nullptr; void* dc_pan2 = nullptr;
   void *Xcat_g, *Hr_lp, *hrmean_lp, *dout_lp, *dGr, *Xcat_r, *dUd_lp, *dWhr, *dWhrs, *Wr4_w;
   void *Wih_f, *Whh_w, *Wor_w, *Ur_w, *Wr_w, *Wihh_w;
@@ -143,26 +124,27 @@ struct recnet_handle {
   int64_t* in_tok = nullptr;   // [Tm][B] tokens fed by the last free-running forward (its backward scatters the embedding gradient by them)
   int free_fwd = 0;
   size_t gws_floats, slab_floats;
-  float* gws2 = nullptr; float* gws_cur = nullptr;   // the side stream's split-K slabs / the one gemm() uses now
+  float* gws2 = nullptr;   // the side stream's split-K slabs (ss.gws_cur: the ones gemm() uses now)
   unsigned* gcnt = nullptr;      // tile counters of the grouped launches' in-launch split-K sums: one block of RN_GCNT_WORDS per slab workspace
   int gg_site = 0;               // the next grouped launch stamps its start / end into this slot (1..8) of the group stamps
   // environment switches, read ONCE per handle in recnet_create (round 6: no getenv on any enqueue path; a test that flips one creates
   // a new handle).  Each selects between two tested forms of one piece of the schedule, never the arithmetic (tests/test_gpu_knobs.py,
   // tests/test_gpu_parity.py: _chain_variants).
   struct RnSw { int wait_chain = 1, mse_epi = 1, adam_epi = 1, dec_lw = 1, dec_xcat = 1, rec_epi = 2, rec_wide = 1, persist_ms = 0, gemm_group = 1; } sw;
-  int gg_slots = 0;              // workgroup slots the next grouped launches can expect (0 = whole chip): see host_common.inc
-  int gemm_single_group = 0;     // set around a single product whose K slices are to be summed inside its launch (host_decoder.inc: the embedding branch)
-  hipStream_t s2 = nullptr; hipEvent_t ev[24] = {}; int overlap = 1;
+  hipStream_t s2 = nullptr; hipEvent_t ev[RN_EV_COUNT] = {}; int overlap = 1;   // the events by name: RnEvent (step_sched.hpp)
+  StepSched ss;                  // the step's enqueue-time schedule state (step_sched.hpp); sched_reset = between two steps
   // bindings
   recnet_decoder_tensors dP{}, dGd{}, dM{}, dV{}, dVm{};
   recnet_reconstructor_tensors rP{}, rG{}, rM{}, rV{}, rVm{};
   bool dec_bound = false, rec_bound = false;
   OptGroup og[2];
   // state between forward and backward
-  int T_last = 0, train_last = 0, fwd_dec_done = 0, fwd_rec_done = 0, rec_bwd_done = 0, early_opt_done = 0, norms_hoisted = 0, join_pending = 0;
+  int T_last = 0, train_last = 0, fwd_dec_done = 0, fwd_rec_done = 0, rec_bwd_done = 0;
   // optional per-launch timing of the recurrent-step GEMM (recnet_profile_*)
   int prof_on = 0; std::vector<hipEvent_t> prof_ev; size_t prof_used = 0;
 };
+// the schedule state back to "between two steps"
+static void sched_reset(recnet_handle* h) { h->ss = StepSched{}; h->ss.gws_cur = h->gws; }
 
 // ------------------------------------------------------------------------------------------------
 static size_t carve(recnet_handle* h, char* base) {
@@ -181,12 +163,12 @@ static size_t carve(recnet_handle* h, char* base) {
   h->ldRA4 = pad8(RN_TCH * h->RA); h->ld2H = pad8(2 * h->H);
   const size_t ldD = h->ldD, ldE = h->ldE, ldH = h->ldH, ldV = h->ldV, ldA = h->ldA, ld4H = h->ld4H, ldWS = h->ldWS,
                ldR = h->ldR, ld4R = h->ld4R, ldRA = h->ldRA, ldHR = h->ldHR;
-  h->ctrl = (uint32_t*)take(64);
+  h->ctrl = (uint32_t*)take(RN_CTRL_WORDS);
   h->gbar = (uint32_t*)take(CS_WS_WORDS);   // the barrier blocks of the chain kernels, their epochs and stamps, the decoder chains' replica lines (chain_sync.hpp)
   h->dc_G1 = take(2 * Tm * B * (4 * H + A));   // fp32, or 8-byte stamped words
   h->dc_pan = takev(Tm * rc_pan_elems((int)H) / 2 + 64);
   h->dc_G2 = take(2 * Tm * B * H * DCB_KS); h->dc_pan2 = takev(Tm * rc_pan_elems((int)(4 * H + A)) / 2 + 64);
-  h->scal = take(64);
+  h->scal = take(RN_SCAL_WORDS);
   h->lc_ts = (unsigned long long*)take(2 * (2 * 8 * 64 * 8));   // 8192 u64 entries (take counts floats): local chains [8 roles][64][8], decoder chains at +4096 / +4608
   h->stepw = take(Tm);
   h->msep = take(1024);
@@ -380,7 +362,6 @@ int recnet_create(const recnet_config* cfg, recnet_handle** out) {
   h->RA = c.reconstructor_type == RECNET_REC_LOCAL ? c.reconstructor_attn_size : 0;
   h->cml = c.caption_max_len; h->Tm = c.caption_max_len + 1;
   h->kind = c.reconstructor_type; h->prec = c.precision; h->lp = c.precision == RECNET_PREC_BF16;
-  h->gemm_single_group = 0;
   {
     auto env = [](const char* n, int dflt) { const char* e = getenv(n); return e ? atoi(e) : dflt; };
     h->sw.wait_chain = env("RN_WAIT_CHAIN", 1); h->sw.mse_epi = env("RN_MSE_EPILOGUE", 1); h->sw.adam_epi = env("RN_ADAM_EPILOGUE", 1);
@@ -502,7 +483,7 @@ int recnet_create(const recnet_config* cfg, recnet_handle** out) {
 void recnet_destroy(recnet_handle* h) {
   if (!h) return;
   for (auto e : h->prof_ev) hipEventDestroy(e);
-  for (int i = 0; i < 24; ++i) if (h->ev[i]) hipEventDestroy(h->ev[i]);
+  for (int i = 0; i < RN_EV_COUNT; ++i) if (h->ev[i]) hipEventDestroy(h->ev[i]);
   if (h->s2) hipStreamDestroy(h->s2);
   if (h->s3) hipStreamDestroy(h->s3);
   delete h;
@@ -576,16 +557,16 @@ int recnet_bind_workspace(recnet_handle* h, void* workspace, size_t bytes) {
   // gradients — by the fixed-shape products of a deferred reconstructor update, and 0 x NaN bit patterns would not be 0
   HIPCHK(hipMemset(h->ws, 0, h->need));
   // stamped exchange buffers and the launch-epoch words start from zero (a stamp is never zero)
-  HIPCHK(hipMemset(h->gbar, 0, CS_WS_WORDS * 4)); HIPCHK(hipMemset(h->scal, 0, 64 * 4)); HIPCHK(hipMemset(h->dc_G1, 0, (size_t)2 * h->Tm * h->B * (4 * h->H + h->A) * 4));
+  HIPCHK(hipMemset(h->gbar, 0, CS_WS_WORDS * 4)); HIPCHK(hipMemset(h->scal, 0, RN_SCAL_WORDS * 4)); HIPCHK(hipMemset(h->dc_G1, 0, (size_t)2 * h->Tm * h->B * (4 * h->H + h->A) * 4));
   HIPCHK(hipMemset(h->dc_G2, 0, (size_t)2 * h->Tm * h->B * h->H * DCB_KS * 4));
-  h->gws_cur = h->gws;
+  sched_reset(h);
   if (!h->s2) {
     h->overlap = 1;
     // (a lowest-priority side stream was measured in round 4: 2.63 against 1.82 ms — the side work is on the critical path often enough)
     // (non-default stream priorities for the side streams — lowest or highest — cost 0.12 ms at C2 and 0.07 at C3, round 6: default priority)
     HIPCHK(hipStreamCreateWithFlags(&h->s2, hipStreamNonBlocking));
     HIPCHK(hipStreamCreateWithFlags(&h->s3, hipStreamNonBlocking));
-    for (int i = 0; i < 24; ++i) HIPCHK(hipEventCreateWithFlags(&h->ev[i], hipEventDisableTiming));
+    for (int i = 0; i < RN_EV_COUNT; ++i) HIPCHK(hipEventCreateWithFlags(&h->ev[i], hipEventDisableTiming));
   }
   h->fwd_dec_done = h->fwd_rec_done = h->rec_bwd_done = 0;
   int r = upload_tables(h, 0); if (r) return r;

@@ -11,6 +11,26 @@ typedef int i32x4_t __attribute__((ext_vector_type(4)));
 
 #define RN_WAVE 64
 
+// ---------------------------------------------------------------- scalar and control slots of a handle's workspace
+// scal: RN_SCAL_WORDS floats.  The loss scalars of recnet_scalars in its order, the decoder's gradient norm and clip factor, the
+// poison word (0, or NaN after a chain kernel gave up waiting: chain_sync.hpp), and behind them as 64-bit words the step-end stamp
+// (export_scalars_kernel) and the ring of the last step-end stamps (rn_ring_push: a count + 7 stamps).
+enum {
+  RN_SCAL_DEC_CE = 0, RN_SCAL_DEC_REG = 1, RN_SCAL_DEC_LOSS = 2, RN_SCAL_REC_MSE = 3, RN_SCAL_REC_REG = 4, RN_SCAL_REC_LOSS = 5,
+  RN_SCAL_TOTAL = 6, RN_SCAL_GNORM = 7, RN_SCAL_CLIP = 8, RN_SCAL_POISON = 15, RN_SCAL_STAMP_END = 32, RN_SCAL_RING = 34,
+  RN_SCAL_WORDS = 64
+};
+// ctrl: RN_CTRL_WORDS 32-bit words.  The dropout seed, the step counter (int32), the device's "a deferred reconstructor update is
+// pending" word, three words that the timing / debugging kernels of abi_misc.inc write to, and as 64-bit words the step-start stamp
+// (advance_step_kernel, set_step_kernel; wait_chain_kernel reads it) and the ring of the last step-start stamps.
+enum {
+  RN_CTRL_SEED = 0, RN_CTRL_STEP = 1, RN_CTRL_PENDING = 2, RN_CTRL_SINK_LAUNCH = 8, RN_CTRL_SINK_LDS = 16, RN_CTRL_SINK_OCCUPY = 17,
+  RN_CTRL_STAMP_START = 32, RN_CTRL_RING = 34, RN_CTRL_WORDS = 64
+};
+#define RN_RING_WORDS 16      // 32-bit words of one stamp ring: 8 x 64 bit
+static_assert(RN_SCAL_RING + RN_RING_WORDS <= RN_SCAL_WORDS && RN_CTRL_RING + RN_RING_WORDS <= RN_CTRL_WORDS, "the stamp rings end inside the words carved for scal / ctrl");
+static_assert(RN_SCAL_STAMP_END % 2 == 0 && RN_SCAL_RING % 2 == 0 && RN_CTRL_STAMP_START % 2 == 0 && RN_CTRL_RING % 2 == 0, "64-bit slots are 8-byte aligned");
+
 // ---------------------------------------------------------------- dropout (counter-based)
 // keep(seed, site, t, b, j): see oracle/dropmask.py (the numpy restatement used by the tests).
 #define RN_SITE_DEC_EMBED 0u

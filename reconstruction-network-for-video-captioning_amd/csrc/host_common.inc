@@ -65,7 +65,7 @@ struct RnRange {
 // last-arriving slice (no reduction launch).  bf16 path only; the exact-fp32 path runs the members one by one.
 struct GemmGroup { int a_col, b_col, n; RnGemmDesc d[GG_MAX]; };
 static GemmGroup gg_begin(int a_col, int b_col) { GemmGroup g; g.a_col = a_col; g.b_col = b_col; g.n = 0; return g; }
-// h->gg_slots: workgroup slots the next launches can expect (0: the whole chip) — set by the call sites that run beside a chain
+// h->ss.gg_slots: workgroup slots the next launches can expect (0: the whole chip) — set by the call sites that run beside a chain
 // kernel or beside another grouped launch (launch.hpp: rn_launch_gemm_group)
 static void gemm(recnet_handle* h, const void* A, int a_col, int lda, const void* Bm, int b_col, int ldb, float* C, int ldc,
                  const float* bias, int M, int N, int K, float alpha, int acc, hipStream_t st);
@@ -73,7 +73,7 @@ static void gemm_to_at(recnet_handle* h, const void* A, int a_col, int lda, cons
                        int ldc, int M, int N, int K, hipStream_t st);
 // the tile counters that go with the split-K slabs in use (one block per slab workspace: launches on different streams never share)
 static unsigned* gg_counters(recnet_handle* h) {
-  return h->gcnt + (h->gws_cur == h->gws2 ? RN_GCNT_WORDS : (h->gws_cur == h->gws3 ? 2 * RN_GCNT_WORDS : 0));
+  return h->gcnt + (h->ss.gws_cur == h->gws2 ? RN_GCNT_WORDS : (h->ss.gws_cur == h->gws3 ? 2 * RN_GCNT_WORDS : 0));
 }
 // adam != null: members with ad_p set apply their Adam update in the epilogue (returns false if the launch did not qualify —
 // nothing was enqueued then, and the caller runs the plain products and the optimiser kernel instead)
@@ -82,7 +82,7 @@ static bool gg_run(recnet_handle* h, GemmGroup& g, hipStream_t st, const AdamSha
   // h->gg_site (1..8, 0 = none): this launch stamps its start / end into slot gg_site of the handle's group stamps
   unsigned long long* stamp = h->gg_site > 0 ? reinterpret_cast<unsigned long long*>(h->gbar + CS_WS_GROUP_STAMPS) + 2 * (h->gg_site - 1) : nullptr;
   h->gg_site = 0;
-  if (h->lp && h->sw.gemm_group && !rn_launch_gemm_group(g.a_col, g.b_col, g.d, g.n, h->gws_cur, h->gws_floats, gg_counters(h), RN_GCNT_WORDS, st, h->gg_slots, adam, stamp)) { g.n = 0; return true; }
+  if (h->lp && h->sw.gemm_group && !rn_launch_gemm_group(g.a_col, g.b_col, g.d, g.n, h->ss.gws_cur, h->gws_floats, gg_counters(h), RN_GCNT_WORDS, st, h->ss.gg_slots, adam, stamp)) { g.n = 0; return true; }
   if (adam) { g.n = 0; return false; }
   for (int i = 0; i < g.n; ++i) {
     const RnGemmDesc& e = g.d[i];
@@ -103,15 +103,15 @@ static void gg_add(recnet_handle* h, GemmGroup& g, const void* A, int lda, const
 // batched GEMM on operand buffers (AT) with automatic split-K; fp32 output
 static void gemm(recnet_handle* h, const void* A, int a_col, int lda, const void* Bm, int b_col, int ldb, float* C, int ldc,
                  const float* bias, int M, int N, int K, float alpha, int acc, hipStream_t st) {
-  if (h->lp && h->gemm_single_group) {      // a group of one: same kernel, split products summed inside the launch
+  if (h->lp && h->ss.gemm_single_group) {      // a group of one: same kernel, split products summed inside the launch
     RnGemmDesc e;
     e.A = A; e.lda = lda; e.B = Bm; e.ldb = ldb; e.C = C; e.ldc = ldc; e.bias = bias; e.M = M; e.N = N; e.K = K; e.alpha = alpha;
     e.accumulate = acc; e.c_bf16 = 0; e.c2 = nullptr; e.ldc2 = 0; e.ad_p = nullptr;
-    if (h->sw.gemm_group && !rn_launch_gemm_group(a_col, b_col, &e, 1, h->gws_cur, h->gws_floats, gg_counters(h), RN_GCNT_WORDS, st, h->gg_slots)) return;
+    if (h->sw.gemm_group && !rn_launch_gemm_group(a_col, b_col, &e, 1, h->ss.gws_cur, h->gws_floats, gg_counters(h), RN_GCNT_WORDS, st, h->ss.gg_slots)) return;
   }
   int s = rn_pick_splitk(h->prec, M, N, K, 16, 0);
   while (s > 1 && (size_t)s * M * N > h->gws_floats) s >>= 1;
-  rn_launch_gemm(h->prec, A, h->lp, a_col, lda, Bm, h->lp, b_col, ldb, C, ldc, bias, M, N, K, alpha, acc, s, h->gws_cur, 1, st);
+  rn_launch_gemm(h->prec, A, h->lp, a_col, lda, Bm, h->lp, b_col, ldb, C, ldc, bias, M, N, K, alpha, acc, s, h->ss.gws_cur, 1, st);
 }
 // same, output written as an operand buffer (AT) — direct epilogue only
 static void gemm_to_at(recnet_handle* h, const void* A, int a_col, int lda, const void* Bm, int b_col, int ldb, void* C,
@@ -165,7 +165,7 @@ static void colsum_at(recnet_handle* h, const void* X, int rows, int cols, int l
 // stream capture these become graph edges, so independent work runs in parallel branches of the hipGraph.
 static void gate_bias_grad(recnet_handle* h, const void* dG, int rows, int Hd, int ld, float* dbih, float* dbhh, int gru, hipStream_t st) {
   float* tmp = (dbih == h->dGd.rnn_bias_ih_l0) ? h->bsum4 : h->bsum4r;      // decoder / reconstructor
-  colsum_at(h, dG, rows, 4 * Hd, ld, tmp, st, h->prezeroed);
+  colsum_at(h, dG, rows, 4 * Hd, ld, tmp, st, h->ss.prezeroed);
   hipLaunchKernelGGL(gate_bias_grad_kernel, dim3(cdiv(4 * Hd, 256)), dim3(256), 0, st, tmp, dbih, dbhh, Hd, gru);
 }
 // dW_hh = dG^T . Hprev over `rows` rows.  LSTM: the 4 gate blocks as they are.  GRU: master blocks (r, z) come from
@@ -176,10 +176,10 @@ static void dW_hh(recnet_handle* h, int gru, int Hd, const void* dG, int ld_dg, 
   gemm(h, dG, 1, ld_dg, Hprev, 1, ld_h, dW, Hd, nullptr, 2 * Hd, Hd, rows, 1.f, acc, st);
   gemm(h, at_off(h, (void*)dG, (size_t)3 * Hd), 1, ld_dg, Hprev, 1, ld_h, dW + (size_t)2 * Hd * Hd, Hd, nullptr, Hd, Hd, rows, 1.f, acc, st);
 }
-static void fork_to(recnet_handle* h, int e, hipStream_t main, hipStream_t side) {
+static void fork_to(recnet_handle* h, RnEvent e, hipStream_t main, hipStream_t side) {
   hipEventRecord(h->ev[e], main); hipStreamWaitEvent(side, h->ev[e], 0);
 }
-static void join_from(recnet_handle* h, int e, hipStream_t main, hipStream_t side) {
+static void join_from(recnet_handle* h, RnEvent e, hipStream_t main, hipStream_t side) {
   hipEventRecord(h->ev[e], side); hipStreamWaitEvent(main, h->ev[e], 0);
 }
 static void copyf(const float* x, float* y, size_t n, hipStream_t st) {
@@ -209,11 +209,11 @@ __global__ void fill_i64_kernel(int64_t* p, int64_t v, int n) {
 // out = a + k * b
 __global__ void axpb_kernel(const float* a, const float* b, float k, float* out) { *out = *a + k * *b; }
 __global__ void export_scalars_kernel(const float* scal, recnet_scalars* out) {
-  out->dec_ce = scal[0]; out->dec_reg = scal[1]; out->dec_loss = scal[2]; out->rec_mse = scal[3];
-  out->rec_reg = scal[4]; out->rec_loss = scal[5]; out->total_loss = scal[6] + scal[15]; out->dec_grad_norm = scal[7];   // scal[15]: 0, or NaN after a chain kernel gave up waiting (chain_sync.hpp)
+  out->dec_ce = scal[RN_SCAL_DEC_CE]; out->dec_reg = scal[RN_SCAL_DEC_REG]; out->dec_loss = scal[RN_SCAL_DEC_LOSS]; out->rec_mse = scal[RN_SCAL_REC_MSE];
+  out->rec_reg = scal[RN_SCAL_REC_REG]; out->rec_loss = scal[RN_SCAL_REC_LOSS]; out->total_loss = scal[RN_SCAL_TOTAL] + scal[RN_SCAL_POISON]; out->dec_grad_norm = scal[RN_SCAL_GNORM];   // the poison word: 0, or NaN after a chain kernel gave up waiting (chain_sync.hpp)
   const unsigned long long now = (unsigned long long)wall_clock64();
-  reinterpret_cast<unsigned long long*>(const_cast<float*>(scal) + 32)[0] = now;      // phase stamp: step end (recnet_read_stamps)
-  rn_ring_push(reinterpret_cast<unsigned long long*>(const_cast<float*>(scal) + 34), now);      // scal[34 .. 49]
+  reinterpret_cast<unsigned long long*>(const_cast<float*>(scal) + RN_SCAL_STAMP_END)[0] = now;      // phase stamp: step end (recnet_read_stamps)
+  rn_ring_push(reinterpret_cast<unsigned long long*>(const_cast<float*>(scal) + RN_SCAL_RING), now);
 }
 
 static inline GateMap gmap_ih(int gru) { GateMap m; m.m[0] = 0; m.m[1] = 1; m.m[2] = 2; m.m[3] = gru ? -1 : 3; return m; }
@@ -241,9 +241,9 @@ static hipEvent_t prof_bracket_begin(recnet_handle* h, int site, hipStream_t st)
 // see wait_chain_kernel (rec_chain.hpp); k = the chain's CsChain (chain_sync.hpp): 0 decoder forward chain, 1 decoder BPTT, 2 / 3 global fwd / bwd, 4 / 5 local fwd / bwd
 static void wait_chain(recnet_handle* h, int k, hipStream_t st) {
   const int on = h->sw.wait_chain;
-  if (!on || !h->in_fused) return;      // (the step-start stamp is written by the fused step's first kernel)
+  if (!on || !h->ss.in_fused) return;      // (the step-start stamp is written by the fused step's first kernel)
   const unsigned long long* stamps = reinterpret_cast<const unsigned long long*>(h->gbar + CS_WS_STAMPS);
-  hipLaunchKernelGGL(wait_chain_kernel, dim3(1), dim3(64), 0, st, reinterpret_cast<const unsigned long long*>(h->ctrl + 32), stamps + 2 * k, 30000u);
+  hipLaunchKernelGGL(wait_chain_kernel, dim3(1), dim3(64), 0, st, reinterpret_cast<const unsigned long long*>(h->ctrl + RN_CTRL_STAMP_START), stamps + 2 * k, 30000u);
 }
 static void hoist_side_work(recnet_handle* h, hipStream_t st);   // abi_step.inc
 static void side_after_decoder_fwd(recnet_handle* h, hipStream_t st);   // abi_step.inc
@@ -303,7 +303,7 @@ static void refresh_rec_images(recnet_handle* h, hipStream_t st) {
 // (global), the W_ih rows of [W_ih | W_hh]^T (local).  (Round 4 transposed all of W_hh^T here as well, 30 us of the BPTT window
 // at C2 for an image the next step's pending update overwrites, and W_o^T twice.)
 static void rec_images_after_update(recnet_handle* h, hipStream_t st, bool whh_skipped = false) {
-  if (h->img_defer_now) { h->images_maybe_stale = 1; return; }      // the next fused step refreshes them beside its decoder chain (api.hip)
+  if (h->ss.img_defer_now) { h->images_maybe_stale = 1; return; }      // the next fused step refreshes them beside its decoder chain (api.hip)
   if (!whh_skipped || h->persist_big_bwd) { refresh_rec_images(h, st); return; }
   if (h->kind == RECNET_REC_GLOBAL) { refresh_whh_t(h, st, 2); return; }
   if (h->kind == RECNET_REC_LOCAL && h->persist_loc_bwd) {

@@ -9,11 +9,11 @@ static int dec_fwd_chain(recnet_handle* h, const float* enc, const int64_t* targ
                          int64_t* free_tokens = nullptr) {
   RN_RANGE("recnet: decoder forward chain (decoder.py:45-70 x T)");
   const int B = h->B, F = h->F, E = h->E, H = h->H, A = h->A, V = h->V;
-  h->mp_done = 0;
-  if (!h->norms_hoisted) param_norms(h, 0, h->scal + 1, st);
+  h->ss.mp_done = 0;
+  if (!h->ss.norms_hoisted) param_norms(h, 0, h->scal + RN_SCAL_DEC_REG, st);
   // The input part of the gates (embeddings -> Xe) does not depend on the features: in the fused step it runs on the side
-  // stream beside the feature products Uv / P (ev[8] joins it in front of the chain)
-  const bool fork_xe = !free_tokens && h->overlap && h->s2 && h->hoist_pending && h->hoist_par;
+  // stream beside the feature products Uv / P (EV_XE_FORK joins it in front of the chain)
+  const bool fork_xe = !free_tokens && h->overlap && h->s2 && h->ss.hoist_pending && h->ss.hoist_par;
   // bf16 path, round 4: the three products of the prologue — Xe, Uv, P — are ONE grouped launch (774 tiles in one hardware
   // queue instead of launches of 400, 22 and 352 workgroups): only the embedding gather runs beside the feature cast
   const bool pro_group = fork_xe && h->lp;
@@ -36,18 +36,18 @@ static int dec_fwd_chain(recnet_handle* h, const float* enc, const int64_t* targ
     h->gg_site = 1;
     gg_run(h, g, st);
   } else if (fork_xe) {
-    fork_to(h, 8, st, h->s2);
-    h->gws_cur = h->gws2;
+    fork_to(h, EV_XE_FORK, st, h->s2);
+    h->ss.gws_cur = h->gws2;
     gate_bias(h->dP.rnn_bias_ih_l0, h->dP.rnn_bias_hh_l0, h->bsum_d, H, h->dgru, h->s2);   // Xe's bias
     embed_fwd(h, targets, nullptr, T * B, train, 0, h->s2);
     gemm(h, h->emb_lp, 0, h->ldE, h->We_w, 0, h->ldE, h->Xe, 4 * H, h->bsum_d, T * B, 4 * H, E, 1.f, 0, h->s2);
-    h->gws_cur = h->gws;
-    hipEventRecord(h->ev[9], h->s2);
+    h->ss.gws_cur = h->gws;
+    hipEventRecord(h->ev[EV_XE_JOIN], h->s2);
   }
   if (!pro_group) dec_invariants(h, enc, st, !fork_xe);   // (Uv on the side stream as well: measured +10 us, the two products share the chip anyway)
   if (pro_group) {
   } else if (fork_xe) {
-    hipStreamWaitEvent(st, h->ev[9], 0);
+    hipStreamWaitEvent(st, h->ev[EV_XE_JOIN], 0);
   } else if (!free_tokens) {
     // all T teacher-forced input embeddings at once    (decoder.py:46-48, train.py:25,45)
     embed_fwd(h, targets, nullptr, T * B, train, 0, st);
@@ -61,9 +61,9 @@ static int dec_fwd_chain(recnet_handle* h, const float* enc, const int64_t* targ
   // captured in this order the chain stays on the prologue's hardware queue (the first-captured successor of a graph node does)
   // instead of paying a cross-queue hand-over of ~20 us on the critical path; the branches wait for the chain's residency anyway
   // (wait_chain_kernel)
-  const bool hoist_late = h->hoist_pending && h->persist_dec && !free_tokens && (h->ld4H & 7) == 0 && h->overlap && h->s2;
-  if (hoist_late) { hipEventRecord(h->ev[4], st); hipEventRecord(h->ev[11], st); h->hoist_fork_recorded = 1; }
-  else if (h->hoist_pending) hoist_side_work(h, st);     // forked here: beside the chain, behind the prologue (fwd_bwd_impl)
+  const bool hoist_late = h->ss.hoist_pending && h->persist_dec && !free_tokens && (h->ld4H & 7) == 0 && h->overlap && h->s2;
+  if (hoist_late) { hipEventRecord(h->ev[EV_HOIST_FORK], st); hipEventRecord(h->ev[EV_S3_FORK], st); h->ss.hoist_fork_recorded = 1; }
+  else if (h->ss.hoist_pending) hoist_side_work(h, st);     // forked here: beside the chain, behind the prologue (fwd_bwd_impl)
   if (h->persist_dec && !free_tokens && (h->ld4H & 7) == 0) {
    hipEvent_t pe = prof_bracket_begin(h, RN_SITE_DEC_CHAIN_FWD, st);
    // batches above RC_PAN_ROWS captions: one launch per row group of h->bgrp captions (csrc/api.hip) — a group is an
@@ -77,16 +77,16 @@ static int dec_fwd_chain(recnet_handle* h, const float* enc, const int64_t* targ
     c.Xe = h->Xe + (size_t)b0 * 4 * H; c.G1 = h->dc_G1; c.Pan = (bf16_t*)h->dc_pan;
     c.Hs = h->Hs + (size_t)b0 * H; c.Cs = h->Cs + (size_t)b0 * H; c.acts = h->acts + (size_t)b0 * 4 * H; c.Hlp = (bf16_t*)h->Hs_lp + (size_t)b0 * h->ldH; c.ld_hlp = h->ldH;
     c.Wh = h->Wh + (size_t)b0 * A; c.att = h->att + (size_t)b0 * F; c.bar = cs_ws_bar(h->gbar, CS_DEC_FWD); c.ts = h->lc_ts + 4096; c.softmax = h->c.decoder_attn_normalize == RECNET_ATTN_SOFTMAX;
-    c.epoch = cs_ws_epoch(h->gbar, CS_DEC_FWD); c.rep = h->gbar + CS_WS_REP_DEC_FWD; c.poison = h->scal + 15;
+    c.epoch = cs_ws_epoch(h->gbar, CS_DEC_FWD); c.rep = h->gbar + CS_WS_REP_DEC_FWD; c.poison = h->scal + RN_SCAL_POISON;
     c.mp = h->kind == RECNET_REC_GLOBAL ? h->mp + (size_t)b0 * H : nullptr; c.mp_scale = (float)h->cml / ((float)T * (float)T);   // global_reconstructor.py:33-37
-    h->mp_done = c.mp ? 1 : 0;
+    h->ss.mp_done = c.mp ? 1 : 0;
     // dec_xcat: the chain also writes the global reconstructor's input operand [h_t ; drop_t(mp)] (no xcat_global_kernel behind it)
     const int f_xcat = h->sw.dec_xcat;
     c.Xcat = nullptr; c.ld_xcat = 0; c.xdd = mkdrop(h, RN_SITE_REC_INPUT, h->c.reconstructor_decoder_dropout, train);
     // (not with the deferred reconstructor update: its pending weight-gradient products read the PREVIOUS step's operand while this chain runs)
     if (f_xcat && c.mp && h->lp && h->ld2H == 2 * H && h->Xcat_g && h->defer_rec != 1) {
       c.Xcat = (bf16_t*)h->Xcat_g + (size_t)b0 * h->ld2H; c.ld_xcat = h->ld2H; c.xdd.boff += b0;
-      h->xcat_done = 1;
+      h->ss.xcat_done = 1;
     }
     // LW (F <= 32): the attention projection is formed by the caption's own workgroup from an LDS-resident attn_W (dec_chain.hpp)
     const bool lw = h->sw.dec_lw && A <= 128 && H <= 512 && (H & 31) == 0 && F <= 32;
@@ -105,8 +105,8 @@ static int dec_fwd_chain(recnet_handle* h, const float* enc, const int64_t* targ
     }
    }
     if (pe) hipEventRecord(pe, st);
-    if (hoist_late && h->hoist_pending) hoist_side_work(h, st);
-    h->hoist_fork_recorded = 0;
+    if (hoist_late && h->ss.hoist_pending) hoist_side_work(h, st);
+    h->ss.hoist_fork_recorded = 0;
     h->T_last = T; h->train_last = train;
     return RECNET_OK;
   }
@@ -189,15 +189,15 @@ static int dec_bwd_out(recnet_handle* h, float gscale, hipStream_t st, int part 
   if (part & 1) gemm(h, h->dlog_lp, 0, h->ldV, h->Wo_w, 1, h->ldH, h->dHs, H, nullptr, TB, H, V, 1.f, 0, st);
   // Decoder-only step: the BPTT waits for this branch only up to here (d hiddens of the output layer, and the CE loss in front of
   // it) — the output layer's own gradients and the attended features that follow run beside the BPTT chain, whose 129 workgroups
-  // leave half the chip idle and which nothing else shares in this configuration (ev[18] covers them for the step's tail).  With a
+  // leave half the chip idle and which nothing else shares in this configuration (EV_SIDE_TAIL covers them for the step's tail).  With a
   // reconstructor the same was measured in round 4 and is off: there the BPTT waits for the reconstructor's d-hiddens product.
-  if ((part & 1) && h->kind == RECNET_REC_NONE && h->join_pending && !h->join_recorded && st == h->s2 && h->side_phase == 0) {
-    hipEventRecord(h->ev[1], st); h->join_recorded = 1; h->side_tail_open = 1;
+  if ((part & 1) && h->kind == RECNET_REC_NONE && h->ss.join_pending && !h->ss.join_recorded && st == h->s2 && h->ss.side_phase == 0) {
+    hipEventRecord(h->ev[EV_SIDE_JOIN], st); h->ss.join_recorded = 1; h->ss.side_tail_open = 1;
   }
   if (!(part & 2)) return RECNET_OK;
   // dW_o = dlogits^T . Hs ; db_o = colsum(dlogits)
   gemm(h, h->dlog_lp, 1, h->ldV, h->Hs_lp, 1, h->ldH, h->dGd.out_weight, H, nullptr, V, H, TB, 1.f, 0, st);
-  colsum_at(h, h->dlog_lp, TB, V, h->ldV, h->dGd.out_bias, st, h->prezeroed);
+  colsum_at(h, h->dlog_lp, TB, V, h->ldV, h->dGd.out_bias, st, h->ss.prezeroed);
   return RECNET_OK;
 }
 // BPTT chain; dh_t (direct) = dHs_out[t] + dhid[t] (the reconstructor's gradient w.r.t. the hidden states)
@@ -219,7 +219,7 @@ static int dec_bwd_chain(recnet_handle* h, const float* dhid, hipStream_t st) {
     c.dUv = h->dUv + (size_t)b0 * F * A; c.dUv_lp = (bf16_t*)h->dUv_lp + (size_t)b0 * F * h->ldA; c.ld_dUv = h->ldA; c.dwacc = h->dwacc + (size_t)b0 * A;
     c.bar = cs_ws_bar(h->gbar, CS_DEC_BWD); c.ts = h->lc_ts + 4096 + 512;
     // the B' -> A' hand-over (dec_chain.hpp): the arrival flags of a row part polled by the part's own unit owners
-    c.epoch = cs_ws_epoch(h->gbar, CS_DEC_BWD); c.rep = h->gbar + CS_WS_REP_DEC_BWD; c.poison = h->scal + 15;
+    c.epoch = cs_ws_epoch(h->gbar, CS_DEC_BWD); c.rep = h->gbar + CS_WS_REP_DEC_BWD; c.poison = h->scal + RN_SCAL_POISON;
     const int NAb = DCB_NA(H);
     const dim3 grid(NAb > nb ? NAb : nb);
     if (F > 32) {
@@ -288,7 +288,7 @@ static int dec_bwd_deferred_rows(recnet_handle* h, const float* enc, const int64
   // the embedding branch: d emb product + the two scatter kernels (measured and rejected, round 3: on the second stream's half,
   // C2 1.979 against 1.931 ms — the side stream is still busy with the reconstructor's Adam step when the chain ends)
   gemm(h, dG, 0, ldWS, h->We_w, 1, h->ldE, h->demb + r0 * E, E, nullptr, nrow, E, 4 * H, 1.f, 0, st);
-  if (!acc && !h->prezeroed) hipMemsetAsync(h->dGd.embedding_weight, 0, (size_t)V * E * 4, st);
+  if (!acc && !h->ss.prezeroed) hipMemsetAsync(h->dGd.embedding_weight, 0, (size_t)V * E * 4, st);
   hipLaunchKernelGGL(embed_bwd_kernel, dim3(nrow), dim3(128), 0, st, h->dGd.embedding_weight, targets, h->demb, B, E, V,
                      h->c.embedding_scale, mkdrop(h, RN_SITE_DEC_EMBED, h->c.embedding_dropout, train), (int)r0,
                      (const int64_t*)(h->free_fwd ? h->in_tok : nullptr));
@@ -298,13 +298,13 @@ static int dec_bwd_deferred_rows(recnet_handle* h, const float* enc, const int64
   gemm(h, dG, 1, ldWS, at_off(h, h->emb_lp, r0 * h->ldE), 1, h->ldE, h->dGd.rnn_weight_ih_l0, E + D, nullptr, GH, E, nrow, 1.f, acc, st);
   // ctx_t = (1/F) sum_f a_t[f] enc[b,f] for these steps (only needed here), then dW_ih[:, E:] (+)= dgates^T . ctx
   {
-    if (!h->ctx_done) dec_ctx_rows(h, enc, t0, t1, st);
+    if (!h->ss.ctx_done) dec_ctx_rows(h, enc, t0, t1, st);
     void* ctx = at_off(h, h->ctx_lp, r0 * h->ldD);
     gemm(h, dG, 1, ldWS, ctx, 1, h->ldD, h->dGd.rnn_weight_ih_l0 + E, E + D, nullptr, GH, D, nrow, 1.f, acc, st);
   }
   // the rest touches other gradient tensors: on a second stream (with the second split-K workspace) when the caller has one
-  float* const gws_keep = h->gws_cur;
-  if (st2 && st2 != st) { st = st2; h->gws_cur = h->gws2; }
+  float* const gws_keep = h->ss.gws_cur;
+  if (st2 && st2 != st) { st = st2; h->ss.gws_cur = h->gws2; }
   // dWh_t = sum of its RN_FCH frame-chunk partials (operand of dW_attn and source of d attn_b)
   {
     const size_t n = (size_t)nrow * h->ldA;
@@ -323,7 +323,7 @@ static int dec_bwd_deferred_rows(recnet_handle* h, const float* enc, const int64
     hipMemsetAsync(h->dGd.rnn_weight_hh_l0, 0, (size_t)GH * H * 4, st);
     hipMemsetAsync(h->dGd.attn_W_weight, 0, (size_t)A * H * 4, st);
   }
-  h->gws_cur = gws_keep;
+  h->ss.gws_cur = gws_keep;
   return RECNET_OK;
 }
 // what needs the whole chain: bias gradients (column sums over all rows), d attn_U (dUv is complete after step 0), d attn_w
@@ -331,8 +331,8 @@ static int dec_bwd_deferred_tail(recnet_handle* h, hipStream_t st) {
   const int B = h->B, F = h->F, D = h->D, H = h->H, A = h->A, T = h->T_last, TB = T * B, ldWS = h->ldWS;
   gate_bias_grad(h, h->dGx, TB, H, ldWS, h->dGd.rnn_bias_ih_l0, h->dGd.rnn_bias_hh_l0, h->dgru, st);
   gemm(h, h->dUv_lp, 1, h->ldA, h->enc_lp, 1, h->ldD, h->dGd.attn_U_weight, D, nullptr, A, D, B * F, 1.f, 0, st);
-  colsum_t<float>(h->dwacc, RN_FCH * B, A, A, h->dGd.attn_w_weight, st, h->prezeroed);
-  colsum_at(h, h->dWhs, TB, A, h->ldA, h->dGd.attn_b, st, h->prezeroed);
+  colsum_t<float>(h->dwacc, RN_FCH * B, A, A, h->dGd.attn_w_weight, st, h->ss.prezeroed);
+  colsum_at(h, h->dWhs, TB, A, h->ldA, h->dGd.attn_b, st, h->ss.prezeroed);
   return RECNET_OK;
 }
 // bf16 path, round 4: the five weight-gradient products (dW_ih[:, :E], dW_ih[:, E:], dW_hh, dW_att, dU — every one dY^T . X) are
@@ -350,14 +350,14 @@ static int dec_bwd_deferred_grouped(recnet_handle* h, const float* enc, const in
     hipLaunchKernelGGL(sum_chunks_kernel<bf16_t>, dim3(ew_blocks(n)), dim3(256), 0, st, (bf16_t*)h->dWhs, h->ldA, (const bf16_t*)dG + 4 * H, ldWS, TB, A, RN_FCH);
     dWh = h->dWhs; ld_dwh = h->ldA;
   }
-  if (!h->ctx_done) dec_ctx_rows(h, enc, 0, T, st);
-  if (h->side_tail_open) { hipStreamWaitEvent(st, h->ev[18], 0); h->side_tail_open = 0; }      // (the side branch's output-layer gradients and attended features)
+  if (!h->ss.ctx_done) dec_ctx_rows(h, enc, 0, T, st);
+  if (h->ss.side_tail_open) { hipStreamWaitEvent(st, h->ev[EV_SIDE_TAIL], 0); h->ss.side_tail_open = 0; }      // (the side branch's output-layer gradients and attended features)
   const bool two = st2 && st2 != st;
-  if (two) fork_to(h, 15, st, st2);      // (behind sum_chunks: the column sum of dWh on st2 reads its output)
+  if (two) fork_to(h, EV_TAIL2_FORK, st, st2);      // (behind sum_chunks: the column sum of dWh on st2 reads its output)
   // the bias gradients (column sums of dG / dWh / the attention vector's partials: four short launches that read only what the
   // BPTT left) on a third stream beside both branches — behind the embedding branch they were the last 40 us before the norms
   const bool three = two && st3 && st3 != st && st3 != st2;
-  if (three) fork_to(h, 16, st, st3);
+  if (three) fork_to(h, EV_TAIL3_FORK, st, st3);
   GemmGroup g = gg_begin(1, 1);
   gg_add(h, g, dG, ldWS, h->ctx_lp, h->ldD, h->dGd.rnn_weight_ih_l0 + E, E + D, nullptr, GH, D, TB, 1.f, 0, st);
   gg_add(h, g, dG, ldWS, h->emb_lp, h->ldE, h->dGd.rnn_weight_ih_l0, E + D, nullptr, GH, E, TB, 1.f, 0, st);
@@ -382,14 +382,14 @@ static int dec_bwd_deferred_grouped(recnet_handle* h, const float* enc, const in
   // longest thing beside the grouped launch) takes the THIRD one, which is idle when the BPTT ends — the second still runs the
   // reconstructor's in-step optimiser for ~20 us then —, and the short column sums queue behind that
   hipStream_t sb = three ? st3 : (two ? st2 : st);
-  float* const gws_keep = h->gws_cur;
-  if (three) h->gws_cur = h->gws3; else if (two) h->gws_cur = h->gws2;
-  if (two) h->gg_slots = h->ncu > 0 ? h->ncu / 2 : 128;      // (beside the grouped launch above)
-  h->gemm_single_group = 1;      // (K slices summed inside the launch: no reduction launch in front of the embedding scatter)
+  float* const gws_keep = h->ss.gws_cur;
+  if (three) h->ss.gws_cur = h->gws3; else if (two) h->ss.gws_cur = h->gws2;
+  if (two) h->ss.gg_slots = h->ncu > 0 ? h->ncu / 2 : 128;      // (beside the grouped launch above)
+  h->ss.gemm_single_group = 1;      // (K slices summed inside the launch: no reduction launch in front of the embedding scatter)
   gemm(h, dG, 0, ldWS, h->We_w, 1, h->ldE, h->demb, E, nullptr, TB, E, 4 * H, 1.f, 0, sb);
-  h->gemm_single_group = 0;
-  h->gg_slots = 0;
-  if (!h->prezeroed) hipMemsetAsync(h->dGd.embedding_weight, 0, (size_t)V * E * 4, sb);
+  h->ss.gemm_single_group = 0;
+  h->ss.gg_slots = 0;
+  if (!h->ss.prezeroed) hipMemsetAsync(h->dGd.embedding_weight, 0, (size_t)V * E * 4, sb);
   hipLaunchKernelGGL(embed_bwd_kernel, dim3(TB), dim3(128), 0, sb, h->dGd.embedding_weight, targets, h->demb, B, E, V,
                      h->c.embedding_scale, mkdrop(h, RN_SITE_DEC_EMBED, h->c.embedding_dropout, train), 0,
                      (const int64_t*)(h->free_fwd ? h->in_tok : nullptr));
@@ -398,10 +398,10 @@ static int dec_bwd_deferred_grouped(recnet_handle* h, const float* enc, const in
                      (const int64_t*)(h->free_fwd ? h->in_tok : nullptr));
   hipStream_t sc = three ? st2 : sb;
   gate_bias_grad(h, dG, TB, H, ldWS, h->dGd.rnn_bias_ih_l0, h->dGd.rnn_bias_hh_l0, h->dgru, sc);
-  colsum_t<float>(h->dwacc, RN_FCH * B, A, A, h->dGd.attn_w_weight, sc, h->prezeroed);
-  colsum_at(h, dWh, TB, A, ld_dwh, h->dGd.attn_b, sc, h->prezeroed);
-  if (three) join_from(h, 17, st, st3);
-  h->gws_cur = gws_keep;
+  colsum_t<float>(h->dwacc, RN_FCH * B, A, A, h->dGd.attn_w_weight, sc, h->ss.prezeroed);
+  colsum_at(h, dWh, TB, A, ld_dwh, h->dGd.attn_b, sc, h->ss.prezeroed);
+  if (three) join_from(h, EV_TAIL3_JOIN, st, st3);
+  h->ss.gws_cur = gws_keep;
   return RECNET_OK;
 }
 static int dec_bwd_deferred(recnet_handle* h, const float* enc, const int64_t* targets, hipStream_t st, hipStream_t st2 = nullptr, hipStream_t st3 = nullptr) {
@@ -409,10 +409,10 @@ static int dec_bwd_deferred(recnet_handle* h, const float* enc, const int64_t* t
   if (h->lp) return dec_bwd_deferred_grouped(h, enc, targets, st, st2, st3);
   int r = dec_bwd_deferred_rows(h, enc, targets, 0, h->T_last, 0, st, st2); if (r) return r;
   if (st2 && st2 != st) {
-    float* const keep = h->gws_cur;
-    h->gws_cur = h->gws2;
+    float* const keep = h->ss.gws_cur;
+    h->ss.gws_cur = h->gws2;
     r = dec_bwd_deferred_tail(h, st2);
-    h->gws_cur = keep;
+    h->ss.gws_cur = keep;
     return r;
   }
   return dec_bwd_deferred_tail(h, st);

@@ -37,10 +37,10 @@ static void rc_launch(recnet_handle* h, int site, K kern, dim3 grid, size_t smem
 static void mse_and_dout(recnet_handle* h, float* out, const float* ref, int Sn, int rows_b, int R, size_t bstride, size_t sstride,
                          float gcoef, int nb, hipStream_t st) {
   const bool vec = (R & 3) == 0 && (((uintptr_t)out) & 15) == 0 && (((uintptr_t)ref) & 15) == 0 && (bstride & 3) == 0 && (sstride & 3) == 0;
-  h->dout_ready = 0;
+  h->ss.dout_ready = 0;
   if (!vec) { hipLaunchKernelGGL(mse_kernel, dim3(nb), dim3(256), 0, st, out, ref, Sn, rows_b, R, bstride, sstride, gcoef, h->msep); return; }
   const bool lp = h->ldR == R;          // no padding columns to zero
-  h->dout_scale = h->c.lambda_recon; h->dout_ready = lp;
+  h->dout_scale = h->c.lambda_recon; h->ss.dout_ready = lp;
   if (h->lp) hipLaunchKernelGGL(mse_vec_kernel<bf16_t>, dim3(nb), dim3(256), 0, st, out, ref, Sn, rows_b, R, bstride, sstride, gcoef, h->msep,
                                 lp ? (bf16_t*)h->dout_lp : (bf16_t*)nullptr, h->c.lambda_recon);
   else hipLaunchKernelGGL(mse_vec_kernel<float>, dim3(nb), dim3(256), 0, st, out, ref, Sn, rows_b, R, bstride, sstride, gcoef, h->msep,
@@ -48,16 +48,16 @@ static void mse_and_dout(recnet_handle* h, float* out, const float* ref, int Sn,
 }
 static int fwd_rec_global(recnet_handle* h, const float* enc, int T, int train, hipStream_t st) {
   const int B = h->B, F = h->F, D = h->D, H = h->H, R = h->R;
-  if (!h->norms_hoisted) {
-    param_norms(h, 1, h->scal + 4, st);
+  if (!h->ss.norms_hoisted) {
+    param_norms(h, 1, h->scal + RN_SCAL_REC_REG, st);
     gate_bias(h->rP.rnn_bias_ih_l0, h->rP.rnn_bias_hh_l0, h->bsum_r, R, h->rgru, st);
   }
   // mean-pooled decoder states, rescaled by caption_max_len / T (global_reconstructor.py:33-37): (cml / T^2) sum_t h_t
-  if (!h->mp_done) mean_over_t(h, h->Hs, T, H, (float)h->cml / ((float)T * (float)T), h->mp, nullptr, 0, st);   // else: accumulated by dec_chain_kernel
-  if (h->xcat_done && h->mp_done) {
-    h->xcat_done = 0;          // (dec_chain_kernel wrote the operand)
+  if (!h->ss.mp_done) mean_over_t(h, h->Hs, T, H, (float)h->cml / ((float)T * (float)T), h->mp, nullptr, 0, st);   // else: accumulated by dec_chain_kernel
+  if (h->ss.xcat_done && h->ss.mp_done) {
+    h->ss.xcat_done = 0;          // (dec_chain_kernel wrote the operand)
   } else {
-    h->xcat_done = 0;
+    h->ss.xcat_done = 0;
     const size_t n = (size_t)T * B * h->ld2H;
     const DropDesc dd = mkdrop(h, RN_SITE_REC_INPUT, h->c.reconstructor_decoder_dropout, train);
     if (h->lp) hipLaunchKernelGGL(xcat_global_kernel<bf16_t>, dim3(ew_blocks(n)), dim3(256), 0, st, (const bf16_t*)h->Hs_lp, h->ldH, h->mp, (bf16_t*)h->Xcat_g, h->ld2H, T, B, H, dd, 0);
@@ -69,10 +69,10 @@ static int fwd_rec_global(recnet_handle* h, const float* enc, int T, int train, 
   // it — so that the chain's workgroups, which need whole CUs, are dispatched before the projection's workgroups start filling
   // every CU partly (C2: 1.926 -> 1.913 ms)
   // (one-graph step only: in the data-parallel three-graph form it costs 0.17 ms — 2.31 against 2.14 ms at one rank)
-  const bool side_late = h->in_fused && h->side_pending && h->overlap && h->s2 && h->persist_rec;
-  if (side_late) { hipEventRecord(h->ev[0], st); h->side_fork_recorded = 1; }
-  else if (h->side_pending) side_after_decoder_fwd(h, st);       // see fwd_bwd_impl
-  if (h->rec_wait_pending) { hipStreamWaitEvent(st, h->ev[12], 0); h->rec_wait_pending = 0; }      // W_hh's pending update (mode 2)
+  const bool side_late = h->ss.in_fused && h->ss.side_pending && h->overlap && h->s2 && h->persist_rec;
+  if (side_late) { hipEventRecord(h->ev[EV_SIDE_FORK], st); h->ss.side_fork_recorded = 1; }
+  else if (h->ss.side_pending) side_after_decoder_fwd(h, st);       // see fwd_bwd_impl
+  if (h->ss.rec_wait_pending) { hipStreamWaitEvent(st, h->ev[EV_PENDING_DONE], 0); h->ss.rec_wait_pending = 0; }      // W_hh's pending update (mode 2)
   // batches above RC_PAN_ROWS captions run the chain once per row group (h->bgrp rows each, csrc/api.hip): a group is an
   // independent batch for the chain — same weights, its own rows of every [T][B][.] tensor (row stride Bs = B)
   bool epi_done = false;
@@ -86,7 +86,7 @@ static int fwd_rec_global(recnet_handle* h, const float* enc, int T, int train, 
     a.hmean = h->hrmean + (size_t)b0 * R; a.hmean_lp = (bf16_t*)h->hrmean_lp + (size_t)b0 * h->ldR; a.ld_hmean = h->ldR;
     a.bar = cs_ws_bar(h->gbar, CS_REC_FWD); a.epoch = cs_ws_epoch(h->gbar, CS_REC_FWD);
     a.master = R / 8 + 1 <= h->ncu;      // the master needs a CU of its own
-    a.poison = h->scal + 15;
+    a.poison = h->scal + RN_SCAL_POISON;
     const int steps = (R + 127) / 128;
     a.epi = 0;
     // <4, 4>: two row halves x 16 units (less L2 -> L1 traffic per CU), when the batch has rows in both halves
@@ -99,8 +99,8 @@ static int fwd_rec_global(recnet_handle* h, const float* enc, int T, int train, 
       // reduction and the MSE kernel between the two chains (C2: 1.837 -> 1.815 ms)
       const int f_epi = h->sw.rec_epi;
       if (f_epi && a.master && h->lp && h->ldR == R && nb == B && h->hm_pan) {
-        if (!h->encmean_hoisted) hipLaunchKernelGGL(mean_over_f_kernel, dim3(ew_blocks((size_t)B * D)), dim3(256), 0, st, enc, B, F, D, h->encmean);
-        h->encmean_hoisted = 1;
+        if (!h->ss.encmean_hoisted) hipLaunchKernelGGL(mean_over_f_kernel, dim3(ew_blocks((size_t)B * D)), dim3(256), 0, st, enc, B, F, D, h->encmean);
+        h->ss.encmean_hoisted = 1;
         const double cnt = (double)h->c.global_batch_size * R;
         a.epi = 1; a.Wo = (const bf16_t*)h->Wor_w; a.ldwo = h->ldR; a.obias = h->rP.out_bias; a.target = h->encmean;
         a.dout = h->outm; a.dout_lp = (bf16_t*)h->dout_lp; a.PanM = (bf16_t*)h->hm_pan; a.mse_part = h->msep;
@@ -109,7 +109,7 @@ static int fwd_rec_global(recnet_handle* h, const float* enc, int T, int train, 
         a.WoT = nullptr; a.ldwot = 0; a.PanD = nullptr; a.dhr = nullptr;
         if (f_epi > 1 && h->WoT && h->hd_pan && h->persist_rec_bwd) {
           a.epi = 2; a.WoT = (const bf16_t*)h->WoT; a.ldwot = h->ldR; a.PanD = (bf16_t*)h->hd_pan; a.dhr = h->dhrmean;
-          h->dhr_done = 1;
+          h->ss.dhr_done = 1;
         }
         epi_done = true;
       }
@@ -126,7 +126,7 @@ static int fwd_rec_global(recnet_handle* h, const float* enc, int T, int train, 
       else rc_launch(h, RN_SITE_REC_CHAIN_FWD, (rec_chain_kernel<16, 2, 7, 2>), g, sm, st, a);
     }
   }
-  if (side_late && h->side_pending) side_after_decoder_fwd(h, st);
+  if (side_late && h->ss.side_pending) side_after_decoder_fwd(h, st);
   for (int t = 0; t < T && !h->persist_rec; ++t) {
     int S = 0;
     if (t > 0) S = gemm_slabs(h, RN_TAG_REC_FWD, at_off(h, h->Hr_lp, (size_t)(t - 1) * B * h->ldR), h->ldR, h->Whh_w, 0, h->ldR, B, 4 * R, R, st);
@@ -139,14 +139,14 @@ static int fwd_rec_global(recnet_handle* h, const float* enc, int T, int train, 
   if (!h->persist_rec) mean_over_t(h, h->Hr, T, R, 1.0f / (float)T, h->hrmean, h->hrmean_lp, h->ldR, st);   // (the chain kernel accumulates it)
   const double cnt = (double)h->c.global_batch_size * R;
   if (epi_done) {      // the chain's epilogue has done all of it
-    h->encmean_hoisted = 0;
-    h->dout_scale = h->c.lambda_recon; h->dout_ready = 1;
+    h->ss.encmean_hoisted = 0;
+    h->dout_scale = h->c.lambda_recon; h->ss.dout_ready = 1;
     h->mse_nb = (R / 16) * 2; h->mse_scale = (float)(1.0 / (cnt * T));
     return RECNET_OK;
   }
   gemm(h, h->hrmean_lp, 0, h->ldR, h->Wor_w, 0, h->ldR, h->outm, R, h->rP.out_bias, B, R, R, 1.f, 0, st);
-  if (!h->encmean_hoisted) hipLaunchKernelGGL(mean_over_f_kernel, dim3(ew_blocks((size_t)B * D)), dim3(256), 0, st, enc, B, F, D, h->encmean);
-  h->encmean_hoisted = 0;
+  if (!h->ss.encmean_hoisted) hipLaunchKernelGGL(mean_over_f_kernel, dim3(ew_blocks((size_t)B * D)), dim3(256), 0, st, enc, B, F, D, h->encmean);
+  h->ss.encmean_hoisted = 0;
   const int nb = 256;
   mse_and_dout(h, h->outm, h->encmean, 1, B, R, (size_t)R, (size_t)0, (float)(2.0 / (cnt * T)), nb, st);
   h->mse_nb = nb; h->mse_scale = (float)(1.0 / (cnt * T));
@@ -177,19 +177,19 @@ static bool rec_pending_hh_fused(recnet_handle* h, hipStream_t s, int step_off, 
 // they get a head start of ~130 us over forking them in front of the decoder's BPTT, which is what the side stream was
 // still busy with when the BPTT ended.  The join the BPTT needs (vocabulary-projection side work) is recorded first.
 static int rec_deferred_fork(recnet_handle* h, hipStream_t st) {
-  if (!h->deferred_early) return RECNET_OK;
-  h->deferred_early = 0;
+  if (!h->ss.deferred_early) return RECNET_OK;
+  h->ss.deferred_early = 0;
   hipStream_t sd = h->s2;
-  if (h->join_pending) { hipEventRecord(h->ev[1], sd); h->join_recorded = 1; }
-  fork_to(h, 10, st, sd);
-  h->gws_cur = h->gws2;
+  if (h->ss.join_pending) { hipEventRecord(h->ev[EV_SIDE_JOIN], sd); h->ss.join_recorded = 1; }
+  fork_to(h, EV_REC_DW_FORK, st, sd);
+  h->ss.gws_cur = h->gws2;
   int r = bwd_rec_deferred(h, sd, 0);
-  h->gws_cur = h->gws;
+  h->ss.gws_cur = h->gws;
   if (r) return r;
-  h->deferred_done = 1;
-  if (h->deferred_early_flags >= 0) {
-    r = optimizer_step(h, h->deferred_early_flags, sd, 1); if (r) return r;
-    h->early_opt_done = 1;
+  h->ss.deferred_done = 1;
+  if (h->ss.deferred_early_flags >= 0) {
+    r = optimizer_step(h, h->ss.deferred_early_flags, sd, 1); if (r) return r;
+    h->ss.early_opt_done = 1;
   }
   return RECNET_OK;
 }
@@ -199,11 +199,11 @@ static int bwd_rec_global(recnet_handle* h, float gscale, float* dhid_out, hipSt
   const int train = h->train_last;
   // dout (operand copy) = gscale * d loss / d out_mean
   // (the output layer's own gradients do not feed the chain: bwd_rec_global_deferred)
-  const bool had_dout = h->dout_ready && h->dout_scale == gscale;      // (else the epilogue's dhrmean carries another scale)
+  const bool had_dout = h->ss.dout_ready && h->dout_scale == gscale;      // (else the epilogue's dhrmean carries another scale)
   if (!had_dout) pack_block(h, h->dout_lp, h->ldR, h->outm, R, B, R, gscale, st);
-  h->dout_ready = 0;
-  if (!(h->dhr_done && had_dout)) gemm(h, h->dout_lp, 0, h->ldR, h->Wor_w, 1, h->ldR, h->dhrmean, R, nullptr, B, R, R, 1.f, 0, st);
-  h->dhr_done = 0;
+  h->ss.dout_ready = 0;
+  if (!(h->ss.dhr_done && had_dout)) gemm(h, h->dout_lp, 0, h->ldR, h->Wor_w, 1, h->ldR, h->dhrmean, R, nullptr, B, R, R, 1.f, 0, st);
+  h->ss.dhr_done = 0;
   int S = 0;
   for (int b0 = 0; b0 < B && h->persist_rec_bwd; b0 += h->bgrp) {      // one launch per row group (see fwd_rec_global)
     const int nb = B - b0 < h->bgrp ? B - b0 : h->bgrp;
@@ -215,7 +215,7 @@ static int bwd_rec_global(recnet_handle* h, float gscale, float* dhid_out, hipSt
     a.acts = h->acts_r + (size_t)b0 * 4 * R; a.C = h->Cr + (size_t)b0 * R; a.H = h->Hr + (size_t)b0 * R;
     a.bar = cs_ws_bar(h->gbar, CS_REC_BWD); a.epoch = cs_ws_epoch(h->gbar, CS_REC_BWD);
     a.master = (R / 16) * (nb > 64 ? 2 : 1) + 1 <= h->ncu;
-    a.poison = h->scal + 15;
+    a.poison = h->scal + RN_SCAL_POISON;
     const int steps = (4 * R + 127) / 128;
     // above 64 captions and up to R = 1536: 32 units x 32 rows per workgroup (a third of its weights in LDS), four row parts
     const int f_wide = h->sw.rec_wide;
@@ -244,9 +244,9 @@ static int bwd_rec_global(recnet_handle* h, float gscale, float* dhid_out, hipSt
   // decoder's BPTT — was measured in round 4: no change, 1.699 against 1.683 ms within the box's spread; not kept.)
   // (a group of one: the K slices are summed inside the launch by the last-arriving slice — the separate reduction kernel was 17 us of the
   //  gap in front of the decoder's BPTT, where the side stream's weight-gradient products still run)
-  h->gemm_single_group = 1;
+  h->ss.gemm_single_group = 1;
   gemm(h, h->dGr, 0, ld4R, h->Wih_f, 1, h->ld2H, h->dmpd, 2 * H, nullptr, TB, 2 * H, 4 * R, 1.f, 0, st);
-  h->gemm_single_group = 0;
+  h->ss.gemm_single_group = 0;
   hipLaunchKernelGGL(global_dhid_kernel, dim3((unsigned)(((size_t)B * H + 63) / 64)), dim3(256), 0, st, h->dmpd, dhid_out, T, B, H,
                      (float)h->cml / ((float)T * (float)T), mkdrop(h, RN_SITE_REC_INPUT, h->c.reconstructor_decoder_dropout, train));
   return RECNET_OK;
@@ -277,7 +277,7 @@ static int bwd_rec_global_deferred(recnet_handle* h, hipStream_t st, int which =
   gg_add(h, g, h->dout_lp, h->ldR, h->hrmean_lp, h->ldR, h->rG.out_weight, R, nullptr, R, R, B, 1.f, 0, st);            // d W_o = dout^T . mean_t hr_t
   // the column sums first: in the fused step this stream runs beside the decoder's BPTT chain, whose whole-CU workgroups must
   // be resident before the grouped launch's ~1000 workgroups start filling every CU (they were 480 instead of 325 us otherwise)
-  colsum_at(h, h->dout_lp, B, R, h->ldR, h->rG.out_bias, st, h->prezeroed);
+  colsum_at(h, h->dout_lp, B, R, h->ldR, h->rG.out_bias, st, h->ss.prezeroed);
   gate_bias_grad(h, h->dGr, TB, R, ld4R, h->rG.rnn_bias_ih_l0, h->rG.rnn_bias_hh_l0, h->rgru, st);
   h->gg_site = 2;
   gg_run(h, g, st);
@@ -288,13 +288,13 @@ static int bwd_rec_global_deferred(recnet_handle* h, hipStream_t st, int which =
 static int fwd_rec_local(recnet_handle* h, const float* enc, int T, int train, hipStream_t st) {
   const int B = h->B, F = h->F, D = h->D, H = h->H, R = h->R, RA = h->RA, ldHR = h->ldHR;
   const size_t esz = h->lp ? 2 : 4;
-  if (!h->norms_hoisted) {
-    param_norms(h, 1, h->scal + 4, st);
+  if (!h->ss.norms_hoisted) {
+    param_norms(h, 1, h->scal + RN_SCAL_REC_REG, st);
     gate_bias(h->rP.rnn_bias_ih_l0, h->rP.rnn_bias_hh_l0, h->bsum_r, R, h->rgru, st);
   }
   // Ud = hiddens . U_r^T   (local_reconstructor.py:42, hoisted)
   gemm(h, h->Hs_lp, 0, h->ldH, h->Ur_w, 0, h->ldH, h->Ud, RA, nullptr, T * B, RA, H, 1.f, 0, st);
-  if (h->rec_wait_pending) { hipStreamWaitEvent(st, h->ev[12], 0); h->rec_wait_pending = 0; }      // W_hh's pending update (mode 2)
+  if (h->ss.rec_wait_pending) { hipStreamWaitEvent(st, h->ev[EV_PENDING_DONE], 0); h->ss.rec_wait_pending = 0; }      // W_hh's pending update (mode 2)
   if (h->persist_loc) for (int b0 = 0; b0 < B; b0 += h->bgrp_loc) {      // one launch per row group (see fwd_rec_global; bgrp_loc: recnet_create)
     const int nb = B - b0 < h->bgrp_loc ? B - b0 : h->bgrp_loc;
     LocChainArgs a;
@@ -306,7 +306,7 @@ static int fwd_rec_local(recnet_handle* h, const float* enc, int T, int train, h
     a.Hr = h->Hr + (size_t)b0 * R; a.Cr = h->Cr + (size_t)b0 * R; a.acts = h->acts_r + (size_t)b0 * 4 * R; a.Hlp = (bf16_t*)h->Hr_lp + (size_t)b0 * h->ldR; a.ld_hlp = h->ldR;
     a.Xcat = (bf16_t*)h->Xcat_r + (size_t)b0 * ldHR; a.ld_xcat = ldHR; a.beta = h->beta + (size_t)b0 * T; a.Whr = h->Whr + (size_t)b0 * RA;
     a.PanH = (bf16_t*)h->lc_panh; a.PanX = (bf16_t*)h->lc_panx; a.Pw = h->lc_pw;
-    a.bar = cs_ws_bar(h->gbar, CS_LOC_FWD); a.epoch = cs_ws_epoch(h->gbar, CS_LOC_FWD); a.poison = h->scal + 15;
+    a.bar = cs_ws_bar(h->gbar, CS_LOC_FWD); a.epoch = cs_ws_epoch(h->gbar, CS_LOC_FWD); a.poison = h->scal + RN_SCAL_POISON;
     a.dd = mkdrop(h, RN_SITE_REC_INPUT, h->c.reconstructor_decoder_dropout, train); a.dd.boff += b0; a.ts = h->lc_ts;
     const dim3 g(a.NU + a.NC + a.relay);
     const int steps = (R + 127) / 128;
@@ -366,7 +366,7 @@ static int fwd_rec_local(recnet_handle* h, const float* enc, int T, int train, h
     RnMse m; m.ref = enc; m.part = h->msep; m.bstride = (size_t)F * D; m.sstride = (size_t)D; m.B = B; m.gcoef = (float)(2.0 / cnt); m.lp = h->c.lambda_recon;
     rn_launch_gemm(h->prec, h->Hr_lp, 1, 0, h->ldR, h->Wor_w, 1, 0, h->ldR, h->outl, R, h->rP.out_bias, F * B, R, R, 1.f, 0, 1, nullptr, 0, st, 0, 0,
                    h->dout_lp, h->ldR, &m);
-    h->dout_scale = h->c.lambda_recon; h->dout_ready = 1;
+    h->dout_scale = h->c.lambda_recon; h->ss.dout_ready = 1;
     h->mse_nb = tiles; h->mse_scale = (float)(1.0 / cnt);
     return RECNET_OK;
   }
@@ -381,8 +381,8 @@ static int bwd_rec_local(recnet_handle* h, float gscale, float* dhid_out, hipStr
   const int B = h->B, F = h->F, H = h->H, R = h->R, RA = h->RA, T = h->T_last, TB = T * B, FB = F * B;
   const int train = h->train_last, ld4R = h->ld4R, ldHR = h->ldHR;
   // (the output layer's own gradients do not feed the chain: bwd_rec_local_deferred)
-  if (!(h->dout_ready && h->dout_scale == gscale)) pack_block(h, h->dout_lp, h->ldR, h->outl, R, FB, R, gscale, st);
-  h->dout_ready = 0;
+  if (!(h->ss.dout_ready && h->dout_scale == gscale)) pack_block(h, h->dout_lp, h->ldR, h->outl, R, FB, R, gscale, st);
+  h->ss.dout_ready = 0;
   gemm(h, h->dout_lp, 0, h->ldR, h->Wor_w, 1, h->ldR, h->dHr, R, nullptr, FB, R, R, 1.f, 0, st);
   h->lc_bwd_done = 0;
   if (h->persist_big_bwd) {
@@ -398,7 +398,7 @@ static int bwd_rec_local(recnet_handle* h, float gscale, float* dhid_out, hipStr
     c.dG = (bf16_t*)h->dGr + (size_t)b0 * ld4R; c.ld_dg = ld4R; c.dWhrs = (bf16_t*)h->dWhrs + (size_t)b0 * h->ldRA; c.ld_dwhr = h->ldRA;
     c.dxm = h->lb_dxm + (size_t)b0 * H; c.dbeta = h->lb_dbeta + (size_t)b0 * T;
     c.PanG = (bf16_t*)h->lc_pang; c.PanW = (bf16_t*)h->lc_panw; c.Part = h->lb_part;
-    c.bar = cs_ws_bar(h->gbar, CS_LOC_BWD); c.epoch = cs_ws_epoch(h->gbar, CS_LOC_BWD); c.poison = h->scal + 15;
+    c.bar = cs_ws_bar(h->gbar, CS_LOC_BWD); c.epoch = cs_ws_epoch(h->gbar, CS_LOC_BWD); c.poison = h->scal + RN_SCAL_POISON;
     c.dd = mkdrop(h, RN_SITE_REC_INPUT, h->c.reconstructor_decoder_dropout, train); c.dd.boff += b0; c.ts = h->lc_ts;
     const dim3 g(c.NWG);
     // (round 4: every even R / 128 in 18 ... 32, i.e. R = 2304 ... 4096 in steps of 256 — round 3 had the benchmark's 24 / 28 / 32 only)
@@ -429,7 +429,7 @@ static int bwd_rec_local(recnet_handle* h, float gscale, float* dhid_out, hipStr
     c.dG = (bf16_t*)h->dGr + (size_t)b0 * ld4R; c.ld_dg = ld4R; c.dWhrs = (bf16_t*)h->dWhrs + (size_t)b0 * h->ldRA; c.ld_dwhr = h->ldRA;
     c.dHs = dhid_out + (size_t)b0 * H; c.dUd = h->dUd + (size_t)b0 * RA; c.dUd_lp = (bf16_t*)h->dUd_lp + (size_t)b0 * h->ldRA; c.ld_dUd = h->ldRA; c.dwacc = h->dwacc_r + (size_t)b0 * RA; c.nch = RN_TCH;
     c.PanG = (bf16_t*)h->lc_pang; c.PanW = (bf16_t*)h->lc_panw; c.Dx = h->lc_dx;
-    c.bar = cs_ws_bar(h->gbar, CS_LOC_BWD); c.epoch = cs_ws_epoch(h->gbar, CS_LOC_BWD); c.poison = h->scal + 15;
+    c.bar = cs_ws_bar(h->gbar, CS_LOC_BWD); c.epoch = cs_ws_epoch(h->gbar, CS_LOC_BWD); c.poison = h->scal + RN_SCAL_POISON;
     c.dd = mkdrop(h, RN_SITE_REC_INPUT, h->c.reconstructor_decoder_dropout, train); c.dd.boff += b0; c.ts = h->lc_ts;
     // (measured and rejected: U' waiting for X' to publish dx before its recurrent product, +0.08 ms at B = 100 — X' is bound by its
     // own CU's L1 fill rate, not by U')
@@ -526,7 +526,7 @@ static int bwd_rec_local_deferred(recnet_handle* h, hipStream_t st, int part = 0
     return RECNET_OK;
   }
   gg_add(h, g, h->dout_lp, h->ldR, h->Hr_lp, h->ldR, h->rG.out_weight, R, nullptr, R, R, FB, 1.f, 0, st);              // d W_o = dout^T . hr
-  colsum_at(h, h->dout_lp, FB, R, h->ldR, h->rG.out_bias, st, h->prezeroed);
+  colsum_at(h, h->dout_lp, FB, R, h->ldR, h->rG.out_bias, st, h->ss.prezeroed);
   if (!h->lc_bwd_done) {   // (loc_chain_bwd_kernel writes dWhrs itself)
     const size_t n = (size_t)FB * h->ldRA;
     if (h->lp) hipLaunchKernelGGL(sum_chunks_kernel<bf16_t>, dim3(ew_blocks(n)), dim3(256), 0, st, (bf16_t*)h->dWhrs, h->ldRA, (const bf16_t*)h->dWhr, h->ldRA4, FB, RA, RN_TCH);
@@ -555,12 +555,12 @@ static int bwd_rec_local_deferred(recnet_handle* h, hipStream_t st, int part = 0
   return RECNET_OK;
 }
 
-// rec_loss = mse + lambda_reg * reg from the chain's partial sums (and the norm of the pending-updated W_hh, hoist_side_work: ev[21])
+// rec_loss = mse + lambda_reg * reg from the chain's partial sums (and the norm of the pending-updated W_hh, hoist_side_work: EV_WHH_NORM)
 static void rec_loss_scalars(recnet_handle* h, hipStream_t st) {
-  if (h->rec_norm_late) { hipStreamWaitEvent(st, h->ev[21], 0); h->rec_norm_late = 0; }
+  if (h->ss.rec_norm_late) { hipStreamWaitEvent(st, h->ev[EV_WHH_NORM], 0); h->ss.rec_norm_late = 0; }
   hipLaunchKernelGGL(rec_loss_finalize_kernel, dim3(1), dim3(256), 0, st, h->msep, h->mse_nb, h->mse_scale, h->scal,
                      h->c.reconstructor_lambda_reg, h->c.lambda_recon);
-  h->rec_loss_late = 0;
+  h->ss.rec_loss_late = 0;
 }
 static int fwd_rec(recnet_handle* h, const float* enc, int T, int train, hipStream_t st) {
   RN_RANGE("recnet: reconstructor forward (train.py:78-131)");
@@ -568,7 +568,7 @@ static int fwd_rec(recnet_handle* h, const float* enc, int T, int train, hipStre
   if (r) return r;
   // rec_loss = mse + lambda_reg * reg ; total = dec_loss + lambda_recon * rec_loss
   // (launching it on the fused step's side stream behind the BPTT's fork, like the total-loss scalar, was measured: no change)
-  if (h->rec_loss_defer) h->rec_loss_late = 1;      // fused step: launched on the side stream behind the BPTT's fork (rec_loss_scalars), not between the two chains
+  if (h->ss.rec_loss_defer) h->ss.rec_loss_late = 1;      // fused step: launched on the side stream behind the BPTT's fork (rec_loss_scalars), not between the two chains
   else rec_loss_scalars(h, st);
   h->T_last = T; h->train_last = train; h->fwd_rec_done = 1;
   return RECNET_OK;
@@ -585,29 +585,29 @@ static int bwd_rec_deferred(recnet_handle* h, hipStream_t st, int part, int whic
 }
 // Deferred reconstructor update (include/recnet_hip.h: recnet_set_deferred_reconstructor_update): the weight-gradient
 // products of the step that left an update pending, its Adam step and the re-transposed weight images, on stream s.  The
-// Adam kernel reads the device's pending word (ctrl[2]) and does nothing when no step left one; the products then ran on
+// Adam kernel reads the device's pending word (RN_CTRL_PENDING) and does nothing when no step left one; the products then ran on
 // stale operands into gradient buffers nobody reads.  step_off = -1 when the step counter was already advanced.
 static int rec_pending_update(recnet_handle* h, hipStream_t s, int step_off, int flags) {
-  float* const keep = h->gws_cur;
-  if (s == h->s3) h->gws_cur = h->gws3;
-  const int pz = h->prezeroed; h->prezeroed = 0;          // the column sums' atomic targets: colsum_at zeroes them itself
+  float* const keep = h->ss.gws_cur;
+  if (s == h->s3) h->ss.gws_cur = h->gws3;
+  const int pz = h->ss.prezeroed; h->ss.prezeroed = 0;          // the column sums' atomic targets: colsum_at zeroes them itself
   const bool split = h->defer_rec == 2;      // only the recurrent weights were left pending (mode 2)
   if (split && rec_pending_hh_fused(h, s, step_off, flags)) {
     // product + Adam update + both operand images of W_hh in one launch (W_o^T was refreshed inside the step that updated W_o)
-    h->prezeroed = pz; h->gws_cur = keep;
-    hipLaunchKernelGGL(set_u32_kernel, dim3(1), dim3(1), 0, s, h->ctrl + 2, 0u);
+    h->ss.prezeroed = pz; h->ss.gws_cur = keep;
+    hipLaunchKernelGGL(set_u32_kernel, dim3(1), dim3(1), 0, s, h->ctrl + RN_CTRL_PENDING, 0u);
     return RECNET_OK;
   }
   h->def_rows = 1;
   int r = bwd_rec_deferred(h, s, 2, split ? 1 : 3);
-  h->def_rows = 0; h->prezeroed = pz;
+  h->def_rows = 0; h->ss.prezeroed = pz;
   // (the derived weight images are refreshed right behind this update, on its stream)
-  const int fused = h->in_fused; h->in_fused = 0;
+  const int fused = h->ss.in_fused; h->ss.in_fused = 0;
   if (!r) r = optimizer_step(h, flags, s, 1, 1, step_off, split ? ~(1u << RN_REC_T_WHH(h)) : 0u);
-  h->in_fused = fused;
-  h->gws_cur = keep;
+  h->ss.in_fused = fused;
+  h->ss.gws_cur = keep;
   if (r) return r;
-  hipLaunchKernelGGL(set_u32_kernel, dim3(1), dim3(1), 0, s, h->ctrl + 2, 0u);
+  hipLaunchKernelGGL(set_u32_kernel, dim3(1), dim3(1), 0, s, h->ctrl + RN_CTRL_PENDING, 0u);
   return RECNET_OK;
 }
 static int bwd_rec(recnet_handle* h, float gscale, float* dhid_out, hipStream_t st) {
@@ -651,8 +651,8 @@ static bool rec_pending_hh_fused(recnet_handle* h, hipStream_t s, int step_off, 
   const int ti = RN_REC_T_WHH(h);
   const TensorDesc& td = o.tab[ti];      // rnn.weight_hh_l0
   AdamShared sh;
-  sh.hp = adam_hyper(h, 1, flags); sh.step_ptr = (const int32_t*)(h->ctrl + 1); sh.poison = h->scal + 15;
-  sh.pending = (const uint32_t*)(h->ctrl + 2); sh.step_off = step_off; sh.pad = 0;
+  sh.hp = adam_hyper(h, 1, flags); sh.step_ptr = (const int32_t*)(h->ctrl + RN_CTRL_STEP); sh.poison = h->scal + RN_SCAL_POISON;
+  sh.pending = (const uint32_t*)(h->ctrl + RN_CTRL_PENDING); sh.step_off = step_off; sh.pad = 0;
 #ifdef RN_FAULT_INJECT
   sh.pad = getenv("RN_FAULT") ? atoi(getenv("RN_FAULT")) : 0;      // (fault-injection build only: gemm_lds.hpp)
 #endif
@@ -696,17 +696,17 @@ static int optimizer_step(recnet_handle* h, int flags, hipStream_t st, int only_
     if (g == 0 && (flags & RECNET_OPT_CLIP) && h->c.gradient_clip > 0.f) {
       hipLaunchKernelGGL(sumsq_chunk_kernel, dim3(o.nchunks), dim3(256), 0, st, o.d_tab, o.d_chunks, 1, o.d_pnorm, coef, o.d_partial);
       if (o.ntens <= 16) {
-        hipLaunchKernelGGL(norm_all_kernel, dim3(1), dim3(256), 0, st, o.d_tab, o.d_partial, o.ntens, o.d_gnorm, h->c.gradient_clip, h->scal + 7, h->scal + 8, (float*)nullptr);
+        hipLaunchKernelGGL(norm_all_kernel, dim3(1), dim3(256), 0, st, o.d_tab, o.d_partial, o.ntens, o.d_gnorm, h->c.gradient_clip, h->scal + RN_SCAL_GNORM, h->scal + RN_SCAL_CLIP, (float*)nullptr);
       } else {
         hipLaunchKernelGGL(tensor_norm_kernel, dim3(o.ntens), dim3(256), 0, st, o.d_tab, o.d_partial, o.d_gnorm);
-        hipLaunchKernelGGL(norm_finalize_kernel, dim3(1), dim3(64), 0, st, o.d_gnorm, o.ntens, h->c.gradient_clip, h->scal + 7, h->scal + 8, (float*)nullptr);
+        hipLaunchKernelGGL(norm_finalize_kernel, dim3(1), dim3(64), 0, st, o.d_gnorm, o.ntens, h->c.gradient_clip, h->scal + RN_SCAL_GNORM, h->scal + RN_SCAL_CLIP, (float*)nullptr);
       }
-      clip = h->scal + 8;
+      clip = h->scal + RN_SCAL_CLIP;
     }
     // the kernel also writes the packed operand images of the tensors it updates (no separate re-pack pass)
     hipLaunchKernelGGL(adam_chunk_kernel, dim3(o.nchunks), dim3(256), 0, st, o.d_tab, o.d_chunks, hp, o.d_pnorm, clip,
-                       (const int32_t*)(h->ctrl + 1), (const PackDesc*)o.d_pack, h->lp, (const float*)(h->scal + 15),
-                       deferred ? (const uint32_t*)(h->ctrl + 2) : (const uint32_t*)nullptr, step_off, g == 1 ? skip_mask : 0u);
+                       (const int32_t*)(h->ctrl + RN_CTRL_STEP), (const PackDesc*)o.d_pack, h->lp, (const float*)(h->scal + RN_SCAL_POISON),
+                       deferred ? (const uint32_t*)(h->ctrl + RN_CTRL_PENDING) : (const uint32_t*)nullptr, step_off, g == 1 ? skip_mask : 0u);
     if (g == 0) refresh_wcomb_t(h, st);
     if (g == 1) rec_images_after_update(h, st, (skip_mask >> RN_REC_T_WHH(h)) & 1u);
   }

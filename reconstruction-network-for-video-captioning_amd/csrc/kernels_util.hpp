@@ -27,14 +27,14 @@ __device__ __forceinline__ void rn_ring_push(unsigned long long* ring, unsigned 
 __global__ void advance_step_kernel(int32_t* step, uint32_t* seed_slot, uint32_t seed_base) {
   int s = *step + 1; *step = s; *seed_slot = seed_base + (uint32_t)s;
   const unsigned long long now = (unsigned long long)wall_clock64();
-  __hip_atomic_store(reinterpret_cast<unsigned long long*>(seed_slot + 32), now, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // phase stamp: step start (recnet_read_stamps, wait_chain_kernel)
-  rn_ring_push(reinterpret_cast<unsigned long long*>(seed_slot + 34), now);      // ctrl[34 .. 49]
+  __hip_atomic_store(reinterpret_cast<unsigned long long*>(seed_slot + (RN_CTRL_STAMP_START - RN_CTRL_SEED)), now, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // phase stamp: step start (recnet_read_stamps, wait_chain_kernel)
+  rn_ring_push(reinterpret_cast<unsigned long long*>(seed_slot + (RN_CTRL_RING - RN_CTRL_SEED)), now);
 }
 
 // step counter = step (host-numbered train step), with the step-start stamp of advance_step_kernel
 __global__ void set_step_kernel(int32_t* step, int32_t v) {
   *step = v;
-  __hip_atomic_store(reinterpret_cast<unsigned long long*>(step + 31), (unsigned long long)wall_clock64(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_store(reinterpret_cast<unsigned long long*>(step + (RN_CTRL_STAMP_START - RN_CTRL_STEP)), (unsigned long long)wall_clock64(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // sum_{z<n} p[z*stride] over the split-K slabs.  All (<= 16) loads are issued back to back and reduced as a
@@ -137,7 +137,7 @@ __device__ __forceinline__ float drop_at(const DropDesc& dd, uint32_t key, int t
 }
 
 // The reconstructor's loss scalars in one launch: mse = scale * sum_j x[j] ; rec_loss = mse + lam_reg * reg ;
-// total = dec_loss + lam_recon * rec_loss   (scal: [2] dec_loss [3] mse [4] reg [5] rec_loss [6] total)
+// total = dec_loss + lam_recon * rec_loss   (scal: the RN_SCAL_* slots, common.hpp)
 __global__ __launch_bounds__(256) void rec_loss_finalize_kernel(const float* __restrict__ x, int n, float scale, float* scal, float lam_reg,
                                                                 float lam_recon) {
   __shared__ float sm[4];
@@ -145,8 +145,8 @@ __global__ __launch_bounds__(256) void rec_loss_finalize_kernel(const float* __r
   for (int i = threadIdx.x; i < n; i += 256) s += x[i];
   s = block_sum256(s, sm);
   if (threadIdx.x == 0) {
-    const float mse = s * scale, rl = mse + lam_reg * scal[4];
-    scal[3] = mse; scal[5] = rl; scal[6] = scal[2] + lam_recon * rl;
+    const float mse = s * scale, rl = mse + lam_reg * scal[RN_SCAL_REC_REG];
+    scal[RN_SCAL_REC_MSE] = mse; scal[RN_SCAL_REC_LOSS] = rl; scal[RN_SCAL_TOTAL] = scal[RN_SCAL_DEC_LOSS] + lam_recon * rl;
   }
 }
 // out[i] = scale * sum_j x[j]   (single block; deterministic order)
@@ -190,14 +190,14 @@ __global__ __launch_bounds__(256) void dp_reduce_kernel(const WT* __restrict__ r
   }
 }
 
-// The decoder's loss scalars in one launch (round 5: a row-sum kernel and two one-thread kernels before): scal[0] = CE = sum of the
-// weighted row losses, scal[2] = dec_loss = CE + lambda_reg * reg (scal[1], from the parameter norms), scal[6] = total so far
+// The decoder's loss scalars in one launch (round 5: a row-sum kernel and two one-thread kernels before): RN_SCAL_DEC_CE = sum of the
+// weighted row losses, RN_SCAL_DEC_LOSS = CE + lambda_reg * reg (RN_SCAL_DEC_REG, from the parameter norms), RN_SCAL_TOTAL = total so far
 __global__ __launch_bounds__(256) void dec_loss_finalize_kernel(const float* __restrict__ rowloss, int n, float* scal, float lambda_reg) {
   __shared__ float sm[4];
   float s = 0.f;
   for (int i = threadIdx.x; i < n; i += 256) s += rowloss[i];
   s = block_sum256(s, sm);
-  if (threadIdx.x == 0) { scal[0] = s; const float dl = s + lambda_reg * scal[1]; scal[2] = dl; scal[6] = dl + 0.f * dl; }
+  if (threadIdx.x == 0) { scal[RN_SCAL_DEC_CE] = s; const float dl = s + lambda_reg * scal[RN_SCAL_DEC_REG]; scal[RN_SCAL_DEC_LOSS] = dl; scal[RN_SCAL_TOTAL] = dl + 0.f * dl; }
 }
 
 // out[c] (+)= sum_r X[r*ld + c].  grid (ceil(cols/64), RS); with RS > 1 `out` must be pre-zeroed (atomics).

@@ -67,3 +67,60 @@ def test_config_validation():
         Engine(dict(B=0, F=2, D=8, E=4, H=8, A=4, V=8), None, "bf16")
     with pytest.raises(KeyError):
         Engine(dict(B=2, F=2, D=8, E=4, H=8, A=4, V=8, dec_cell="RNN"), None, "bf16")
+
+
+# ---- an abandoned step leaves nothing behind (recnet_abort_step)
+CHAIN_DIMS = [24, 6, 64, 61, 16, 32, 16, 16]      # the persistent-chain shape of tests/test_gpu_knobs.py
+CHAIN_LR = 1e-2
+
+
+def _chain_step(kind):
+    B, F, D, V, E, H, A, RA = CHAIN_DIMS
+    decP = GU.formula_params(GU.decoder_shapes(V, E, H, A, D), 3)
+    recP = GU.formula_params(GU.rec_shapes(kind, H, D, RA), 4)
+    _, dec, rec = make_models(list(CHAIN_DIMS), kind, "bf16", decP, recP, decoder_learning_rate=CHAIN_LR,
+                              reconstructor_learning_rate=CHAIN_LR)
+    return R.TrainStep(dec, rec), dec, rec, decP, recP
+
+
+def _params(dec, rec, decP, recP):
+    out = {}
+    for name, md, P in (("dec", dec, decP), ("rec", rec, recP)):
+        for k, v in md["model"].state_dict().items():
+            out[name + "." + k] = (v.detach().double().cpu(), P[k].double())
+    return out
+
+
+@pytest.mark.parametrize("kind", ["global", "local"])
+def test_abort_step_after_part_one_leaves_no_trace(kind):
+    """Part 1 of a data-parallel step with the side stream left open (recnet_set_dp_overlap), abandoned with recnet_abort_step: the
+    fused step that follows computes what it computes on a fresh handle — the same schedule state, so the same arithmetic (the bars
+    are those of tests/test_gpu_knobs.py, which compares two schedules of one arithmetic)."""
+    B, F, D, V = CHAIN_DIMS[:4]
+    rs = np.random.RandomState(2)
+    enc, targets = GU.make_batch(B, F, D, V, [30] + [int(x) for x in rs.randint(1, 30, size=B - 1)], 11)
+    encd, tgd = enc.cuda(), targets.cuda()
+    res = []
+    for abandoned in (True, False):
+        step, dec, rec, decP, recP = _chain_step(kind)
+        eng = step.engine
+        T, w = step.prepare(targets.numpy())
+        if abandoned:
+            eng.set_dp_overlap(True)
+            eng.train_step_part_dev(1, encd, tgd, T, w, 7)
+            torch.cuda.synchronize()
+            eng.abort_step()
+        eng.train_step(encd, tgd, T, w, seed=5, step=1)
+        torch.cuda.synchronize()
+        assert eng.chain_status() == 0
+        res.append((_params(dec, rec, decP, recP), eng.scalars.cpu().numpy()[:7].copy()))
+    (pa, la), (pb, lb) = res
+    print("losses after abort:", la, "fresh:", lb)
+    assert np.allclose(la, lb, rtol=1e-4, atol=0), (la, lb)
+    for k in pa:
+        (a, init), (b, _) = pa[k], pb[k]
+        moved = float((a - init).norm())
+        diff = float((a - b).norm())
+        print(k, "moved", moved, "diff", diff)
+        assert moved > 3e-3 * np.sqrt(a.numel()), (k, moved)
+        assert diff <= 2e-3 * moved, (k, diff, moved)
