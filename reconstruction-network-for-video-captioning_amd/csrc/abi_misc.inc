@@ -161,6 +161,7 @@ int recnet_chain_reset(recnet_handle* h, int32_t disable_persistent, void* strea
   if (disable_persistent) {
     h->persist_rec = h->persist_rec_bwd = h->persist_dec = h->persist_dec_bwd = 0; h->persist_loc = h->persist_loc_bwd = 0;
     h->persist_big_bwd = 0;      // (lcbig_bwd_kernel, R > 2048; the hybrid forward chain follows persist_loc)
+    build_weight_images(h);      // the derived images of those chains are no longer kept
   }
   return RECNET_OK;
 }
@@ -200,34 +201,16 @@ __global__ void count_diff_u16_kernel(const uint16_t* a, const uint16_t* b, size
 // captures and replays of the tests' graphs, coincided with rare segmentation faults inside hipGraphLaunch — three of eight runs of
 // tests/test_gpu_deferred.py in round 5, never under the debugger)
 struct RnImg { void* p; size_t bytes; };
+// every live image of the bound groups, from the handle's table (weight_images.hpp)
 static int rn_image_list(recnet_handle* h, RnImg* im) {
   int n = 0;
-  const size_t esz = h->lp ? 2 : 4;
-  auto add = [&](void* p, size_t elems, size_t es) { if (p && elems && n < 24) { im[n].p = p; im[n].bytes = elems * es; ++n; } };
-  const size_t H = h->H, A = h->A, V = h->V, R = h->R, RA = h->RA;
-  if (h->dec_bound) {
-    add(h->U_w, A * h->ldD, esz); add(h->Wc_w, 4 * H * h->ldD, esz); add(h->We_w, 4 * H * h->ldE, esz);
-    add(h->Wcomb, (4 * H + RN_FCH * A) * h->ldH, esz); add(h->Wo_w, V * h->ldH, esz);
-    if (h->use_wcomb_t) add(h->WcombT, H * (size_t)h->ldKW, esz);
-  }
-  if (h->rec_bound && h->kind != RECNET_REC_NONE) {
-    add(h->Wor_w, R * h->ldR, esz);
-    if (h->kind == RECNET_REC_GLOBAL) {
-      add(h->Wih_f, 4 * R * (size_t)h->ld2H, esz); add(h->Whh_w, 4 * R * h->ldR, esz);
-      if (h->persist_rec_bwd) { add(h->WhhT, R * (size_t)h->ld4R, esz); add(h->WoT, R * (size_t)h->ldR, esz); }
-    } else {
-      add(h->Ur_w, RA * h->ldH, esz); add(h->Wr_w, RA * h->ldR, esz); add(h->Wr4_w, RN_TCH * RA * h->ldR, esz);
-      add(h->Wihh_w, 4 * R * h->ldHR, esz);
-      if (h->persist_loc_bwd || h->persist_big_bwd) add(h->WihhT, (H + R) * (size_t)h->ld4R, esz);
-      if (h->persist_big_bwd && h->WstT) add(h->WstT, (size_t)h->lb_ncb * 4 * 4 * (h->lb_steps - h->lb_sr) * 4 * 64, 16);
-      if (h->persist_loc && h->lc_steps && h->Wst) add(h->Wst, (size_t)(R / 16) * 4 * (h->lc_steps - h->lc_sr) * 4 * 64, 16);
-    }
-  }
+  for (const WImage& w : h->wimg)
+    if (w.live && h->og[w.group].bound && h->*w.field) { im[n].p = h->*w.field; im[n].bytes = wimg_bytes(w, h->lp); ++n; }
   return n;
 }
 int64_t recnet_debug_images_bytes(recnet_handle* h) {
   if (!h || !h->ws) return -1;
-  RnImg im[24];
+  RnImg im[WI_COUNT];
   const int n = rn_image_list(h, im);
   size_t total = 0;
   for (int i = 0; i < n; ++i) total += (im[i].bytes + 255) & ~(size_t)255;
@@ -238,7 +221,7 @@ int recnet_debug_images_stale(recnet_handle* h, void* scratch_dev, int64_t scrat
   if (!n_diff_out || !scratch_dev) return fail(RECNET_EINVAL, "null argument");
   FLUSH_PENDING(h, stream);
   hipStream_t st = (hipStream_t)stream;
-  RnImg im[24];
+  RnImg im[WI_COUNT];
   const int n = rn_image_list(h, im);
   size_t total = 0;
   for (int i = 0; i < n; ++i) total += (im[i].bytes + 255) & ~(size_t)255;

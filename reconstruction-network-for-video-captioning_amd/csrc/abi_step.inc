@@ -193,7 +193,7 @@ static void hoist_side_work(recnet_handle* h, hipStream_t st) {
     // stream beside the decoder's chain; EV_PENDING_DONE = done (the reconstructor's chains wait for it, fwd_rec_*: rec_wait_pending)
     if (h->ss.hoist_fork_recorded) hipStreamWaitEvent(h->s3, h->ev[EV_S3_FORK], 0); else fork_to(h, EV_S3_FORK, st, h->s3);
     if (h->persist_dec) wait_chain(h, 0, h->s3);
-    refresh_rec_images(h, h->s3);
+    refresh_images(h, 1, h->s3);
     hipEventRecord(h->ev[EV_PENDING_DONE], h->s3);
   }
   const bool rec = h->kind != RECNET_REC_NONE && !h->ss.defer_now;

@@ -7,7 +7,7 @@
 // every hot-path entry point only enqueues on the caller's stream.
 //
 // One translation unit, laid out over several files:
-//   api.hip                  handle, workspace carving, create / bind / pack tables (this file)
+//   api.hip                  handle, workspace carving, the weight image table (weight_images.hpp), create / bind (this file)
 //   host_common.inc          GEMM wrappers, split-K slabs of the chain sites, column sums, weight packing, invariants
 //   host_decoder.inc         decoder forward chain + loss, backward chain + deferred weight gradients
 //   host_reconstructor.inc   global / local reconstructor forward + backward, optimiser step
@@ -33,6 +33,7 @@
 #include "loc_chain.hpp"
 #include "loc_big.hpp"
 #include "step_sched.hpp"
+#include "weight_images.hpp"
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string& m) { g_err = m; return code; }
@@ -138,6 +139,7 @@ struct recnet_handle {
   recnet_reconstructor_tensors rP{}, rG{}, rM{}, rV{}, rVm{};
   bool dec_bound = false, rec_bound = false;
   OptGroup og[2];
+  WImage wimg[WI_COUNT];         // the packed weight images of this handle (weight_images.hpp; build_weight_images)
   // state between forward and backward
   int T_last = 0, train_last = 0, fwd_dec_done = 0, fwd_rec_done = 0, rec_bwd_done = 0;
   // optional per-launch timing of the recurrent-step GEMM (recnet_profile_*)
@@ -145,6 +147,86 @@ struct recnet_handle {
 };
 // the schedule state back to "between two steps"
 static void sched_reset(recnet_handle* h) { h->ss = StepSched{}; h->ss.gws_cur = h->gws; }
+
+// leading dimensions of the operand buffers and the k-step counts of the R > 2048 chains (recnet_create, before the image table)
+static void set_dims(recnet_handle* h) {
+  h->ldD = pad8(h->D); h->ldE = pad8(h->E); h->ldH = pad8(h->H); h->ldV = pad8(h->V); h->ldA = pad8(h->A);
+  h->ld4H = pad8(4 * h->H); h->ldWS = pad8(4 * h->H + RN_FCH * h->A); h->ldKW = pad8(4 * h->H + RN_FCH * h->A);
+  h->ldR = pad8(h->R); h->ld4R = pad8(4 * h->R); h->ldRA = pad8(h->RA); h->ldHR = pad8(h->H + h->R);
+  h->ldRA4 = pad8(RN_TCH * h->RA); h->ld2H = pad8(2 * h->H);
+  if (h->kind != RECNET_REC_LOCAL) return;
+  // hybrid forward chain: 12 of the (R / 128 rounded up to even) k-steps per wave resident, the others streamed
+  int steps = (h->R + 127) / 128; steps += steps & 1;
+  h->lc_steps = steps > 16 ? (steps <= 28 ? 28 : 32) : 0; h->lc_sr = LC_HYB_SR(h->lc_steps);
+  if (h->R > 2048 && h->R % 128 == 0 && h->B <= 64 * 2 * RN_MAX_ROW_GROUPS) {     // the large-R backward chain (loc_big.hpp; eligibility: recnet_create; row groups of <= 64 captions)
+    h->lb_steps = h->R / 128; h->lb_sr = LB_SR(h->lb_steps); h->lb_ncb = (h->H + h->R) / 64;
+  }
+}
+
+// The weight image table (weight_images.hpp).  Tensor indices are those of dec_list / rec_list.
+static void build_weight_images(recnet_handle* h) {
+  const int H = h->H, D = h->D, E = h->E, A = h->A, V = h->V, R = h->R, RA = h->RA;
+  const bool global = h->kind == RECNET_REC_GLOBAL, local = h->kind == RECNET_REC_LOCAL;
+  for (WImage& im : h->wimg) im = WImage();
+  auto image = [&](int id, void* recnet_handle::* field, int group, size_t rows, int cols, int ld) -> WImage& {
+    WImage& im = h->wimg[id];
+    im.field = field; im.group = group; im.rows = rows; im.cols = cols; im.ld = ld; im.carved = im.live = true;
+    return im;
+  };
+  auto derived = [&](int id, void* recnet_handle::* field, size_t rows, int cols, int ld, int how, int from, bool carved, bool live) {
+    WImage& im = image(id, field, h->wimg[from].group, rows, cols, ld);
+    im.how = how; im.from = from; im.carved = carved; im.live = carved && live;
+    im.frag = how != WI_TRANSPOSE;
+  };
+  auto window = [&](WImage& im, int t, int tcols, int c0, int nc, size_t dr = 0, int dc = 0, int r0 = 0, int nr = 1 << 30) {
+    im.src[im.nsrc++] = WImageSrc{t, tcols, c0, nc, r0, nr, dr, dc};
+  };
+  // W_hh [4 Hd | 3 Hd][Hd] into the 4-block gate layout
+  auto window_hh = [&](WImage& im, int gru, int Hd, int t, int dc = 0) {
+    if (!gru) { window(im, t, Hd, 0, Hd, 0, dc); return; }
+    window(im, t, Hd, 0, Hd, 0, dc, 0, 2 * Hd);
+    window(im, t, Hd, 0, Hd, (size_t)3 * Hd, dc, 2 * Hd, Hd);
+  };
+  const int KW = 4 * H + RN_FCH * A;
+  window(image(WI_U_W, &recnet_handle::U_w, 0, A, D, h->ldD), 3, D, 0, D);                        // attn_U
+  window(image(WI_WC_W, &recnet_handle::Wc_w, 0, 4 * H, D, h->ldD), 5, E + D, E, D);              // rnn.weight_ih_l0, context columns
+  window(image(WI_WE_W, &recnet_handle::We_w, 0, 4 * H, E, h->ldE), 5, E + D, 0, E);              // ... embedding columns
+  {
+    WImage& im = image(WI_WCOMB, &recnet_handle::Wcomb, 0, KW, H, h->ldH);                        // [W_hh ; W ; W ; W ; W]
+    window_hh(im, h->dgru, H, 6);
+    for (int j = 0; j < RN_FCH; ++j) window(im, 2, H, 0, H, (size_t)4 * H + j * A);               // attn_W
+  }
+  derived(WI_WCOMBT, &recnet_handle::WcombT, H, KW, h->ldKW, WI_TRANSPOSE, WI_WCOMB, true, h->use_wcomb_t);
+  window(image(WI_WO_W, &recnet_handle::Wo_w, 0, V, H, h->ldH), 9, H, 0, H);                      // out.weight
+  if (global || local) window(image(WI_WOR_W, &recnet_handle::Wor_w, 1, R, R, h->ldR), local ? 8 : 4, R, 0, R);
+  if (global) {
+    window(image(WI_WIH_F, &recnet_handle::Wih_f, 1, 4 * R, 2 * H, h->ld2H), 0, 2 * H, 0, 2 * H);
+    window_hh(image(WI_WHH_W, &recnet_handle::Whh_w, 1, 4 * R, R, h->ldR), h->rgru, R, 1);
+    // W_o^T for the forward chain's epilogue (rec_chain.hpp, epi = 2), W_hh^T (K contiguous) for rec_chain_bwd_kernel
+    derived(WI_WOT, &recnet_handle::WoT, R, R, h->ldR, WI_TRANSPOSE, WI_WOR_W, true, h->persist_rec_bwd);
+    derived(WI_WHHT, &recnet_handle::WhhT, R, 4 * R, h->ld4R, WI_TRANSPOSE, WI_WHH_W, true, h->persist_rec_bwd);
+  }
+  if (local) {
+    {
+      WImage& im = image(WI_WR4_W, &recnet_handle::Wr4_w, 1, RN_TCH * RA, R, h->ldR);            // [W_r ; W_r ; W_r ; W_r]: sums the per-chunk dWhr partials in the GEMM's K loop
+      for (int j = 0; j < RN_TCH; ++j) window(im, 1, R, 0, R, (size_t)j * RA);
+    }
+    window(image(WI_UR_W, &recnet_handle::Ur_w, 1, RA, H, h->ldH), 2, H, 0, H);
+    window(image(WI_WR_W, &recnet_handle::Wr_w, 1, RA, R, h->ldR), 1, R, 0, R);
+    {
+      WImage& im = image(WI_WIHH_W, &recnet_handle::Wihh_w, 1, 4 * R, H + R, h->ldHR);           // [W_ih | W_hh]
+      window(im, 4, H, 0, H);
+      window_hh(im, h->rgru, R, 5, H);
+    }
+    // the streamed k-steps of W_hh (hybrid forward chain, loc_chain.hpp); [W_ih | W_hh]^T (K = 4R contiguous), the resident operand
+    // of loc_chain_bwd_kernel, and its streamed k-steps (loc_big.hpp)
+    derived(WI_WST, &recnet_handle::Wst, wimg_stream_fragments(R / 16, h->lc_steps - h->lc_sr), 8, 8, WI_STREAM_FWD, WI_WIHH_W, h->lc_steps != 0,
+            h->persist_loc);
+    derived(WI_WIHHT, &recnet_handle::WihhT, H + R, 4 * R, h->ld4R, WI_TRANSPOSE, WI_WIHH_W, true, h->persist_loc_bwd || h->persist_big_bwd);
+    derived(WI_WSTT, &recnet_handle::WstT, wimg_stream_fragments(h->lb_ncb * 4, h->lb_steps - h->lb_sr), 8, 8, WI_STREAM_BWD, WI_WIHHT, h->lb_steps != 0,
+            h->persist_big_bwd);
+  }
+}
 
 // ------------------------------------------------------------------------------------------------
 static size_t carve(recnet_handle* h, char* base) {
@@ -156,11 +238,12 @@ static size_t carve(recnet_handle* h, char* base) {
   };
   // operand buffers are sized as if fp32 (the bf16 path uses half of each)
   auto takev = [&](size_t n) -> void* { return (void*)take(n); };
+  // rows first .. last of the weight image table, in its order (sizes: weight_images.hpp)
+  auto take_images = [&](int first, int last) {
+    for (int i = first; i <= last; ++i)
+      if (h->wimg[i].carved) h->*(h->wimg[i].field) = takev(wimg_take_floats(h->wimg[i]));
+  };
   const size_t B = h->B, F = h->F, D = h->D, E = h->E, H = h->H, A = h->A, V = h->V, R = h->R, RA = h->RA, Tm = h->Tm;
-  h->ldD = pad8(h->D); h->ldE = pad8(h->E); h->ldH = pad8(h->H); h->ldV = pad8(h->V); h->ldA = pad8(h->A);
-  h->ld4H = pad8(4 * h->H); h->ldWS = pad8(4 * h->H + RN_FCH * h->A);
-  h->ldR = pad8(h->R); h->ld4R = pad8(4 * h->R); h->ldRA = pad8(h->RA); h->ldHR = pad8(h->H + h->R);
-  h->ldRA4 = pad8(RN_TCH * h->RA); h->ld2H = pad8(2 * h->H);
   const size_t ldD = h->ldD, ldE = h->ldE, ldH = h->ldH, ldV = h->ldV, ldA = h->ldA, ld4H = h->ld4H, ldWS = h->ldWS,
                ldR = h->ldR, ld4R = h->ld4R, ldRA = h->ldRA, ldHR = h->ldHR;
   h->ctrl = (uint32_t*)take(RN_CTRL_WORDS);
@@ -198,13 +281,7 @@ static size_t carve(recnet_handle* h, char* base) {
   h->ctx_lp = takev(Tm * B * ldD);
   h->dUv_lp = takev(B * F * ldA);
   h->dWhs = takev(Tm * B * ldA);
-  h->U_w = takev(A * ldD);
-  h->Wc_w = takev(4 * H * ldD);
-  h->We_w = takev(4 * H * ldE);
-  h->Wcomb = takev((4 * H + RN_FCH * A) * ldH);
-  h->ldKW = pad8(4 * h->H + RN_FCH * h->A);
-  h->WcombT = takev(H * (size_t)h->ldKW);
-  h->Wo_w = takev(V * ldH);
+  take_images(WI_U_W, WI_WO_W);
   size_t maxN = 4 * H + A;
   if (h->kind != RECNET_REC_NONE) {
     if (4 * R > maxN) maxN = 4 * R;
@@ -230,7 +307,7 @@ static size_t carve(recnet_handle* h, char* base) {
   if (h->kind != RECNET_REC_NONE) {
     h->bsum_r = take(4 * R);
     h->dcr_carry = take(B * R);
-    h->Wor_w = takev(R * ldR);
+    take_images(WI_WOR_W, WI_WOR_W);
   }
   if (h->kind == RECNET_REC_GLOBAL) {
     h->mp = take(B * H); h->Xg = take(Tm * B * 4 * R);
@@ -240,11 +317,11 @@ static size_t carve(recnet_handle* h, char* base) {
     h->Xcat_g = takev(Tm * B * (size_t)h->ld2H); h->Hr_lp = takev(Tm * B * ldR); h->hrmean_lp = takev(B * ldR);
     h->Hr_pan = takev(Tm * rc_pan_elems((int)R) / 2 + 64);       // bf16: k-group-major copies of h_t for rec_chain_kernel
     h->hm_pan = takev(rc_pan_elems((int)R) / 2 + 64);
-    h->hd_pan = takev(rc_pan_elems((int)R) / 2 + 64); h->WoT = takev(R * (size_t)h->ldR);
+    h->hd_pan = takev(rc_pan_elems((int)R) / 2 + 64); take_images(WI_WOT, WI_WOT);
     h->dG_pan = takev(Tm * rc_pan_elems((int)(4 * R)) / 2 + 64);
-    h->WhhT = takev(R * (size_t)h->ld4R);
+    take_images(WI_WHHT, WI_WHHT);
     h->dout_lp = takev(B * ldR); h->dGr = takev(Tm * B * ld4R);
-    h->Wih_f = takev(4 * R * (size_t)h->ld2H); h->Whh_w = takev(4 * R * ldR);
+    take_images(WI_WIH_F, WI_WHH_W);
   } else if (h->kind == RECNET_REC_LOCAL) {
     h->Ud = take(Tm * B * RA);
     h->Hr = take(F * B * R); h->Cr = take(F * B * R); h->acts_r = take(F * B * 4 * R);
@@ -252,27 +329,21 @@ static size_t carve(recnet_handle* h, char* base) {
     h->dUd = take(Tm * B * RA); h->dwacc_r = take(RN_TCH * B * RA);
     h->Xcat_r = takev(F * B * ldHR); h->Hr_lp = takev(F * B * ldR); h->dout_lp = takev(F * B * ldR);
     h->dGr = takev(F * B * ld4R); h->dUd_lp = takev(Tm * B * ldRA); h->dWhr = takev(F * B * (size_t)h->ldRA4);
-    h->dWhrs = takev(F * B * ldRA); h->Wr4_w = takev(RN_TCH * RA * ldR);
-    h->Ur_w = takev(RA * ldH); h->Wr_w = takev(RA * ldR); h->Wihh_w = takev(4 * R * ldHR);
+    h->dWhrs = takev(F * B * ldRA);
+    take_images(WI_WR4_W, WI_WIHH_W);
     h->slab2 = take(16 * B * R);
     h->lc_panh = takev(F * rc_pan_elems((int)R) / 2 + 64);
     h->lc_panx = takev(F * rc_pan_elems((int)H) / 2 + 64);
     h->lc_pw = (_Float16*)take(F * B * ((R + 15) / 16) * RA / 2 + 64);
-    {   // hybrid forward chain: 12 of the (R / 128 rounded up to even) k-steps per wave resident, the others streamed from this image
-      int steps = (int)(R + 127) / 128; steps += steps & 1;
-      h->lc_steps = steps > 16 ? (steps <= 28 ? 28 : 32) : 0; h->lc_sr = LC_HYB_SR(h->lc_steps);
-      if (h->lc_steps) h->Wst = takev((R / 16) * 4 * (size_t)(h->lc_steps - h->lc_sr) * 4 * 512 / 2 + 64);
-    }
+    take_images(WI_WST, WI_WST);       // hybrid forward chain: the streamed k-steps of W_hh
     h->lc_pang = takev(F * rc_pan_elems((int)(4 * R)) / 2 + 64);
     h->lc_panw = takev(F * rc_pan_elems((int)RA) / 2 + 64);
     h->lc_dx = take(F * 4 * B * H);     // up to 4 K parts (lcb_xsplit_role)
-    h->WihhT = takev((H + R) * (size_t)h->ld4R);
-    if (R > 2048 && R % 128 == 0 && B <= 64 * 2 * RN_MAX_ROW_GROUPS) {     // the large-R backward chain (loc_big.hpp; eligibility: recnet_create; row groups of <= 64 captions)
-      const int steps = (int)R / 128;
-      h->lb_steps = steps; h->lb_sr = LB_SR(steps); h->lb_ncb = (int)(H + R) / 64;
+    take_images(WI_WIHHT, WI_WIHHT);
+    if (h->lb_steps) {     // the large-R backward chain (loc_big.hpp; set_dims)
       h->lb_part = take(F * 4 * 64 * (H + R));
       h->lb_dxm = take(F * B * H); h->lb_dbeta = take(F * B * Tm);
-      h->WstT = takev((size_t)h->lb_ncb * 4 * 4 * (size_t)(steps - h->lb_sr) * 4 * 512 / 2 + 64);
+      take_images(WI_WSTT, WI_WSTT);
     }
   }
   // optimiser tables (sizes are upper bounds; filled at bind time)
@@ -475,6 +546,8 @@ int recnet_create(const recnet_config* cfg, recnet_handle** out) {
     // (one row group only: at B = 200, two groups of 100, the split form measured 3.21 ms against 3.10 ms for the immediate one)
     h->split_ok = h->kind != RECNET_REC_NONE && h->persist_dec && h->lp && Bg == h->B && t_pending <= t_chain;
   }
+  set_dims(h);
+  build_weight_images(h);
   h->need = carve(h, nullptr);
   *out = h;
   return RECNET_OK;
@@ -498,43 +571,18 @@ int recnet_set_shard(recnet_handle* h, int32_t global_batch_size, int32_t batch_
 size_t recnet_workspace_bytes(const recnet_handle* h) { return h ? h->need : 0; }
 
 static inline void* at_off(const recnet_handle* h, void* p, size_t elems);
-// destinations of the packed operand images, per parameter tensor (same order as dec_list / rec_list)
+// the optimiser's pack descriptors, per parameter tensor: the windows of the weight image table with their addresses
 static void build_pack_tables(recnet_handle* h, int g) {
   OptGroup& o = h->og[g];
   o.pack.assign(o.ntens, PackDesc());
   for (auto& pd : o.pack) { pd.ndst = 0; pd.cols = 1; }
-  auto addr = [&](int t, int cols, void* dst, int ld, int c0, int nc, int r0, int nr) {
-    PackDesc& pd = o.pack[t]; pd.cols = cols;
-    PackDst& d = pd.d[pd.ndst++]; d.dst = dst; d.ld = ld; d.c0 = c0; d.nc = nc; d.r0 = r0; d.nr = nr; d.mode = 0; d.pad = 0;
-  };
-  auto add = [&](int t, int cols, void* dst, int ld, int c0, int nc) { addr(t, cols, dst, ld, c0, nc, 0, 1 << 30); };
-  // recurrent weights into the 4-block gate layout: W_ih rows as they are (GRU: 3 blocks, the 4th stays zero);
-  // W_hh of a GRU: blocks (r, z) in place, block n -> packed block 3, packed block 2 stays zero
-  auto add_ih = [&](int t, int cols, void* dst, int ld, int c0, int nc) { add(t, cols, dst, ld, c0, nc); };
-  auto add_hh = [&](int gru, int Hd, int t, int cols, void* dst, int ld, int c0, int nc) {
-    if (!gru) { add(t, cols, dst, ld, c0, nc); return; }
-    addr(t, cols, dst, ld, c0, nc, 0, 2 * Hd);
-    addr(t, cols, at_off(h, dst, (size_t)3 * Hd * ld), ld, c0, nc, 2 * Hd, Hd);
-  };
-  const int H = h->H, D = h->D, E = h->E, A = h->A, R = h->R, RA = h->RA;
-  if (g == 0) {
-    for (int j = 0; j < RN_FCH; ++j) add(2, H, at_off(h, h->Wcomb, (size_t)(4 * H + j * A) * h->ldH), h->ldH, 0, H);   // attn_W
-    add(3, D, h->U_w, h->ldD, 0, D);                                        // attn_U
-    add_ih(5, E + D, h->We_w, h->ldE, 0, E); add_ih(5, E + D, h->Wc_w, h->ldD, E, D);   // rnn.weight_ih_l0
-    add_hh(h->dgru, H, 6, H, h->Wcomb, h->ldH, 0, H);                       // rnn.weight_hh_l0
-    add(9, H, h->Wo_w, h->ldH, 0, H);                                       // out.weight
-  } else if (h->kind == RECNET_REC_GLOBAL) {
-    add_ih(0, 2 * H, h->Wih_f, h->ld2H, 0, 2 * H);
-    add_hh(h->rgru, R, 1, R, h->Whh_w, h->ldR, 0, R);
-    add(4, R, h->Wor_w, h->ldR, 0, R);
-  } else if (h->kind == RECNET_REC_LOCAL) {
-    add(1, R, h->Wr_w, h->ldR, 0, R);
-    for (int j = 0; j < RN_TCH; ++j) add(1, R, at_off(h, h->Wr4_w, (size_t)j * RA * h->ldR), h->ldR, 0, R);
-    add(2, H, h->Ur_w, h->ldH, 0, H);
-    add_ih(4, H, h->Wihh_w, h->ldHR, 0, H);
-    add_hh(h->rgru, R, 5, R, at_off(h, h->Wihh_w, (size_t)H), h->ldHR, 0, R);
-    add(8, R, h->Wor_w, h->ldR, 0, R);
-  }
+  for (const WImage& im : h->wimg)
+    for (int k = 0; k < im.nsrc && im.group == g; ++k) {
+      const WImageSrc& w = im.src[k];
+      PackDesc& pd = o.pack[w.t]; pd.cols = w.tcols;
+      PackDst& d = pd.d[pd.ndst++];
+      d = PackDst{at_off(h, h->*im.field, w.dr * im.ld + w.dc), im.ld, w.c0, w.nc, w.r0, w.nr, {0, 0}};
+    }
 }
 
 static int upload_tables(recnet_handle* h, int g) {
@@ -665,9 +713,9 @@ extern "C" {
 
 // A pending deferred reconstructor update (recnet_set_deferred_reconstructor_update) is completed before anything else
 // reads the reconstructor's parameters, packed images, gradients or Adam state.
-static void refresh_rec_images(recnet_handle* h, hipStream_t st);
+static void refresh_images(recnet_handle* h, int group, hipStream_t st);
 static int flush_pending(recnet_handle* h, hipStream_t st, int explicit_call = 0) {
-  if (h->images_maybe_stale && h->rec_bound) { refresh_rec_images(h, st); h->images_maybe_stale = 0; }      // (deferred image refresh)
+  if (h->images_maybe_stale && h->rec_bound) { refresh_images(h, 1, st); h->images_maybe_stale = 0; }      // (deferred image refresh)
   // maybe_pending is the host's shadow of the device's pending word: set when a deferred step is enqueued or captured, and
   // by recnet_mark_pending when a captured one is replayed.  An explicit recnet_flush also runs while the mode is on (the
   // device word decides whether the Adam step happens; the products are recomputed from the step's own operands either way).

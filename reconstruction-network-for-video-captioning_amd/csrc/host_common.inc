@@ -216,15 +216,6 @@ __global__ void export_scalars_kernel(const float* scal, recnet_scalars* out) {
   rn_ring_push(reinterpret_cast<unsigned long long*>(const_cast<float*>(scal) + RN_SCAL_RING), now);
 }
 
-static inline GateMap gmap_ih(int gru) { GateMap m; m.m[0] = 0; m.m[1] = 1; m.m[2] = 2; m.m[3] = gru ? -1 : 3; return m; }
-static inline GateMap gmap_hh(int gru) { GateMap m; m.m[0] = 0; m.m[1] = 1; m.m[2] = gru ? -1 : 2; m.m[3] = gru ? 2 : 3; return m; }
-// recurrent weight image in the 4-block gate layout: dst[4 Hd][ld] = [src1 cols | src2 cols | 0]
-static void pack_gates(recnet_handle* h, void* dst, int ld_dst, int Hd, const float* src1, int ld1, int c1, GateMap m1,
-                       const float* src2, int ld2, int c2, GateMap m2, hipStream_t st) {
-  const size_t n = (size_t)4 * Hd * ld_dst;
-  if (h->lp) hipLaunchKernelGGL(pack_gates_kernel<bf16_t>, dim3(ew_blocks(n)), dim3(256), 0, st, (bf16_t*)dst, ld_dst, Hd, src1, ld1, c1, m1, src2, ld2, c2, m2);
-  else hipLaunchKernelGGL(pack_gates_kernel<float>, dim3(ew_blocks(n)), dim3(256), 0, st, (float*)dst, ld_dst, Hd, src1, ld1, c1, m1, src2, ld2, c2, m2);
-}
 static void gate_bias(const float* bih, const float* bhh, float* out, int Hd, int gru, hipStream_t st) {
   hipLaunchKernelGGL(gate_bias_kernel, dim3(cdiv(4 * Hd, 256)), dim3(256), 0, st, bih, bhh, out, Hd, gru);
 }
@@ -247,54 +238,28 @@ static void wait_chain(recnet_handle* h, int k, hipStream_t st) {
 }
 static void hoist_side_work(recnet_handle* h, hipStream_t st);   // abi_step.inc
 static void side_after_decoder_fwd(recnet_handle* h, hipStream_t st);   // abi_step.inc
-// WcombT = Wcomb^T (after Wcomb changed: pack_weights, the decoder's Adam step)
-static void refresh_wcomb_t(recnet_handle* h, hipStream_t st) {
-  if (!h->use_wcomb_t) return;
-  const int KW = 4 * h->H + RN_FCH * h->A, H = h->H;
-  dim3 grid(cdiv(H, 32), cdiv(h->ldKW, 32));           // source = Wcomb [KW][ldH] (rows beyond KW read as zero -> pad)
-  hipLaunchKernelGGL(transpose_at_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)h->Wcomb, h->ldH, KW, H, (bf16_t*)h->WcombT, h->ldKW);
+// ---- the images DERIVED from the packed weights (weight_images.hpp): shapes, sources and existence come from the handle's table.
+// A transposed image = (its source image)^T, K contiguous (source rows beyond its extent read as zero -> the padding of the
+// transposed rows); src_cols > 0: only the first src_cols columns of the source.  A fragment image: one 16-byte fragment per thread.
+static void refresh_image(recnet_handle* h, int id, hipStream_t st, int src_cols = 0) {
+  const WImage& d = h->wimg[id];
+  if (!d.live || !(h->*d.field)) return;
+  const WImage& s = h->wimg[d.from];
+  const bf16_t* src = (const bf16_t*)(h->*s.field);
+  bf16_t* dst = (bf16_t*)(h->*d.field);
+  const int cols = src_cols ? src_cols : s.cols;
+  const dim3 grid((unsigned)cdiv((long)d.rows, 256));
+  if (d.how == WI_TRANSPOSE)
+    hipLaunchKernelGGL(transpose_at_kernel<bf16_t>, dim3(cdiv(cols, 32), cdiv(d.ld, 32)), dim3(256), 0, st, src, s.ld, (int)s.rows, cols, dst, d.ld);
+  else if (d.how == WI_STREAM_FWD)
+    hipLaunchKernelGGL(lc_pack_stream_kernel, grid, dim3(256), 0, st, src, s.ld, h->R, h->H, h->lc_steps, h->lc_sr, dst, d.rows);
+  else if (d.how == WI_STREAM_BWD)
+    hipLaunchKernelGGL(lcbig_pack_stream_kernel, grid, dim3(256), 0, st, src, s.ld, h->R, h->lb_ncb, h->lb_steps, h->lb_sr, dst, d.rows);
 }
-
-// WhhT = Whh_w^T of the global reconstructor (after Whh_w changed: pack_weights, the reconstructor's Adam step)
-// (which: bit 0 = W_hh^T, bit 1 = W_o^T)
-static void refresh_whh_t(recnet_handle* h, hipStream_t st, int which = 3) {
-  if (!h->persist_rec_bwd) return;
-  const int R = h->R;
-  dim3 grid(cdiv(R, 32), cdiv(h->ld4R, 32));            // source = Whh_w [4R][ldR]
-  if (which & 1) hipLaunchKernelGGL(transpose_at_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)h->Whh_w, h->ldR, 4 * R, R, (bf16_t*)h->WhhT, h->ld4R);
-  if (h->WoT && (which & 2)) {       // W_o^T for the forward chain's epilogue (rec_chain.hpp, epi = 2)
-    dim3 g2(cdiv(R, 32), cdiv(h->ldR, 32));           // source = Wor_w [R][ldR]
-    hipLaunchKernelGGL(transpose_at_kernel<bf16_t>, g2, dim3(256), 0, st, (const bf16_t*)h->Wor_w, h->ldR, R, R, (bf16_t*)h->WoT, h->ldR);
-  }
-}
-
-// WihhT = [W_ih | W_hh]^T of the local reconstructor (K = 4R contiguous): the resident operand of loc_chain_bwd_kernel
-// (which: bit 0 = the transpose, bit 1 = the streamed fragments derived from it)
-static void refresh_wihh_t(recnet_handle* h, hipStream_t st, int which = 3) {
-  if (!h->persist_loc_bwd && !h->persist_big_bwd) return;
-  const int R = h->R, H = h->H;
-  dim3 grid(cdiv(H + R, 32), cdiv(h->ld4R, 32));       // source = Wihh_w [4R][ldHR]
-  if (which & 1) hipLaunchKernelGGL(transpose_at_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)h->Wihh_w, h->ldHR, 4 * R, H + R, (bf16_t*)h->WihhT, h->ld4R);
-  if (!(which & 2)) return;
-  if (h->persist_big_bwd && h->WstT) {     // ... and the streamed fragments of it (loc_big.hpp)
-    const size_t nf = (size_t)h->lb_ncb * 4 * 4 * (h->lb_steps - h->lb_sr) * 4 * 64;
-    hipLaunchKernelGGL(lcbig_pack_stream_kernel, dim3((unsigned)cdiv((long)nf, 256)), dim3(256), 0, st, (const bf16_t*)h->WihhT, h->ld4R, R, h->lb_ncb,
-                       h->lb_steps, h->lb_sr, (bf16_t*)h->WstT, nf);
-  }
-}
-
-// hybrid forward chain of the local reconstructor: the streamed part of W_hh as fragments (loc_chain.hpp)
-static void refresh_wst(recnet_handle* h, hipStream_t st) {
-  if (!h->persist_loc || !h->lc_steps || !h->Wst) return;
-  const size_t nf = (size_t)(h->R / 16) * 4 * (h->lc_steps - h->lc_sr) * 4 * 64;
-  hipLaunchKernelGGL(lc_pack_stream_kernel, dim3((unsigned)cdiv((long)nf, 256)), dim3(256), 0, st, (const bf16_t*)h->Wihh_w, h->ldHR, h->R, h->H,
-                     h->lc_steps, h->lc_sr, (bf16_t*)h->Wst, nf);
-}
-
-// every image DERIVED from the reconstructor's packed weights (what the chain kernels keep resident / stream)
-static void refresh_rec_images(recnet_handle* h, hipStream_t st) {
-  if (h->kind == RECNET_REC_GLOBAL) refresh_whh_t(h, st);
-  else if (h->kind == RECNET_REC_LOCAL) { refresh_wihh_t(h, st); refresh_wst(h, st); }
+// every derived image of one optimiser group's weights (table order: a source comes before what derives from it)
+static void refresh_images(recnet_handle* h, int group, hipStream_t st) {
+  for (int id = 0; id < WI_COUNT; ++id)
+    if (h->wimg[id].how != WI_DIRECT && h->wimg[id].group == group) refresh_image(h, id, st);
 }
 // ... after the reconstructor's Adam step (a lazy refresh under the next step's decoder chain existed in rounds 3-4; the split
 // update's epilogue, which writes both images itself, replaced it)
@@ -304,46 +269,20 @@ static void refresh_rec_images(recnet_handle* h, hipStream_t st) {
 // at C2 for an image the next step's pending update overwrites, and W_o^T twice.)
 static void rec_images_after_update(recnet_handle* h, hipStream_t st, bool whh_skipped = false) {
   if (h->ss.img_defer_now) { h->images_maybe_stale = 1; return; }      // the next fused step refreshes them beside its decoder chain (api.hip)
-  if (!whh_skipped || h->persist_big_bwd) { refresh_rec_images(h, st); return; }
-  if (h->kind == RECNET_REC_GLOBAL) { refresh_whh_t(h, st, 2); return; }
-  if (h->kind == RECNET_REC_LOCAL && h->persist_loc_bwd) {
-    const int R = h->R, H = h->H;
-    dim3 grid(cdiv(H, 32), cdiv(h->ld4R, 32));       // source = the W_ih columns of Wihh_w [4R][ldHR]
-    hipLaunchKernelGGL(transpose_at_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)h->Wihh_w, h->ldHR, 4 * R, H, (bf16_t*)h->WihhT, h->ld4R);
-  }
+  if (!whh_skipped || h->persist_big_bwd) { refresh_images(h, 1, st); return; }
+  if (h->kind == RECNET_REC_GLOBAL) { refresh_image(h, WI_WOT, st); return; }
+  if (h->kind == RECNET_REC_LOCAL && h->persist_loc_bwd) refresh_image(h, WI_WIHHT, st, h->wimg[WI_WIHH_W].src[0].nc);      // the W_ih window of [W_ih | W_hh]
 }
 
-// Packed operand images of the weights (AT, zero padded leading dimensions), refreshed after every optimiser step.
+// Packed operand images of the weights (AT, zero padded leading dimensions) from the master parameters: one launch per bound
+// group through the pack descriptors the Adam kernel also stores by, then the derived images.  Padding and a GRU's empty gate block
+// stay zero from the workspace's memset: every writer (this kernel, Adam, the split update's GEMM epilogue) stays inside the windows.
 static int pack_weights(recnet_handle* h, hipStream_t st) {
-  const int H = h->H, D = h->D, E = h->E, A = h->A, V = h->V, R = h->R, RA = h->RA;
-  if (h->dec_bound) {
-    pack_block(h, h->U_w, h->ldD, h->dP.attn_U_weight, D, A, D, 1.f, st);
-    const GateMap none = gmap_ih(0);
-    pack_gates(h, h->Wc_w, h->ldD, H, h->dP.rnn_weight_ih_l0 + E, E + D, D, gmap_ih(h->dgru), nullptr, 0, 0, none, st);
-    pack_gates(h, h->We_w, h->ldE, H, h->dP.rnn_weight_ih_l0, E + D, E, gmap_ih(h->dgru), nullptr, 0, 0, none, st);
-    pack_gates(h, h->Wcomb, h->ldH, H, h->dP.rnn_weight_hh_l0, H, H, gmap_hh(h->dgru), nullptr, 0, 0, none, st);   // [W_hh ; W ; W ; W ; W]
-    for (int j = 0; j < RN_FCH; ++j)
-      pack_block(h, at_off(h, h->Wcomb, (size_t)(4 * H + j * A) * h->ldH), h->ldH, h->dP.attn_W_weight, H, A, H, 1.f, st);
-    pack_block(h, h->Wo_w, h->ldH, h->dP.out_weight, H, V, H, 1.f, st);
-    refresh_wcomb_t(h, st);
-  }
-  if (h->rec_bound) {
-    pack_block(h, h->Wor_w, h->ldR, h->rP.out_weight, R, R, R, 1.f, st);
-    if (h->kind == RECNET_REC_GLOBAL) {
-      const GateMap none = gmap_ih(0);
-      pack_gates(h, h->Wih_f, h->ld2H, R, h->rP.rnn_weight_ih_l0, 2 * H, 2 * H, gmap_ih(h->rgru), nullptr, 0, 0, none, st);
-      pack_gates(h, h->Whh_w, h->ldR, R, h->rP.rnn_weight_hh_l0, R, R, gmap_hh(h->rgru), nullptr, 0, 0, none, st);
-      refresh_whh_t(h, st);
-    } else {
-      pack_block(h, h->Ur_w, h->ldH, h->rP.attn_U_weight, H, RA, H, 1.f, st);
-      pack_block(h, h->Wr_w, h->ldR, h->rP.attn_W_weight, R, RA, R, 1.f, st);
-      for (int j = 0; j < RN_TCH; ++j)   // [W_r ; W_r ; W_r ; W_r]: sums the per-chunk dWhr partials in the GEMM's K loop
-        pack_block(h, at_off(h, h->Wr4_w, (size_t)j * RA * h->ldR), h->ldR, h->rP.attn_W_weight, R, RA, R, 1.f, st);
-      // [W_ih | W_hh | 0]
-      pack_gates(h, h->Wihh_w, h->ldHR, R, h->rP.rnn_weight_ih_l0, H, H, gmap_ih(h->rgru), h->rP.rnn_weight_hh_l0, R, R, gmap_hh(h->rgru), st);
-      refresh_wihh_t(h, st);
-      refresh_wst(h, st);
-    }
+  for (int g = 0; g < 2; ++g) {
+    const OptGroup& o = h->og[g];
+    if (!o.bound) continue;
+    hipLaunchKernelGGL(pack_chunk_kernel, dim3(o.nchunks), dim3(256), 0, st, (const TensorDesc*)o.d_tab, (const int2*)o.d_chunks, (const PackDesc*)o.d_pack, h->lp);
+    refresh_images(h, g, st);
   }
   return RECNET_OK;
 }

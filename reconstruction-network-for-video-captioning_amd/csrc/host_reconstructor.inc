@@ -677,7 +677,7 @@ static bool rec_pending_hh_fused(recnet_handle* h, hipStream_t s, int step_off, 
   else { add(0, 2 * R, 0, dG1); add((size_t)2 * R, R, (size_t)3 * R, at_off(h, (void*)dG1, (size_t)3 * R)); }      // GRU: (r, z) in place, n -> packed block 3
   h->gg_site = 3;
   if (!gg_run(h, g, s, &sh)) return false;
-  if (local) { refresh_wst(h, s); refresh_wihh_t(h, s, 2); }      // the streamed-fragment images of the R > 2048 chains follow the two images
+  if (local) { refresh_image(h, WI_WST, s); refresh_image(h, WI_WSTT, s); }      // the streamed-fragment images of the R > 2048 chains follow the two images
   return true;
 }
 static int optimizer_step(recnet_handle* h, int flags, hipStream_t st, int only_group, int deferred, int step_off, unsigned skip_mask) {
@@ -707,7 +707,7 @@ static int optimizer_step(recnet_handle* h, int flags, hipStream_t st, int only_
     hipLaunchKernelGGL(adam_chunk_kernel, dim3(o.nchunks), dim3(256), 0, st, o.d_tab, o.d_chunks, hp, o.d_pnorm, clip,
                        (const int32_t*)(h->ctrl + RN_CTRL_STEP), (const PackDesc*)o.d_pack, h->lp, (const float*)(h->scal + RN_SCAL_POISON),
                        deferred ? (const uint32_t*)(h->ctrl + RN_CTRL_PENDING) : (const uint32_t*)nullptr, step_off, g == 1 ? skip_mask : 0u);
-    if (g == 0) refresh_wcomb_t(h, st);
+    if (g == 0) refresh_images(h, 0, st);
     if (g == 1) rec_images_after_update(h, st, (skip_mask >> RN_REC_T_WHH(h)) & 1u);
   }
   return RECNET_OK;

@@ -10,10 +10,57 @@ struct TensorDesc { float* p; float* g; float* m; float* v; float* vmax; int n; 
 // writes them directly, so the weights are re-packed (bf16) in the same pass that updates them.
 // Rows: only source rows [r0, r0 + nr) are written, to destination row (r - r0) (dst is pre-offset) — the GRU's
 // 3-block weights land in the 4-block packed layout this way.
-// (mode: reserved, 0)
-struct PackDst { void* dst; int ld; int c0; int nc; int r0; int nr; int mode; int pad; };
+// The host projects these from the weight image table (weight_images.hpp: build_pack_tables).
+struct PackDst { void* dst; int ld; int c0; int nc; int r0; int nr; int pad[2]; };
 struct PackDesc { int ndst; int cols; PackDst d[6]; };
 #define RN_CHUNK 8192
+
+// element i of the tensor, value pn, into its packed image(s)
+__device__ __forceinline__ void pack_one(const PackDesc& pk, int lp, int i, float pn) {
+  const int r = i / pk.cols, c = i - r * pk.cols;
+#pragma unroll
+  for (int d = 0; d < 6; ++d)
+    if (d < pk.ndst && c >= pk.d[d].c0 && c < pk.d[d].c0 + pk.d[d].nc && r >= pk.d[d].r0 && r < pk.d[d].r0 + pk.d[d].nr) {
+      const size_t o = (size_t)(r - pk.d[d].r0) * pk.d[d].ld + (c - pk.d[d].c0);
+      if (lp) reinterpret_cast<bf16_t*>(pk.d[d].dst)[o] = (bf16_t)pn; else reinterpret_cast<float*>(pk.d[d].dst)[o] = pn;
+    }
+}
+// every quad of the tensor lies inside one row and inside (or outside) every packed window: all of them on a 4-column grid
+__device__ __forceinline__ bool pack_grid4(const PackDesc& pk) {
+  bool grid4 = (pk.cols & 3) == 0;
+  for (int d = 0; d < 6; ++d)
+    if (d < pk.ndst && ((pk.d[d].c0 | pk.d[d].nc | pk.d[d].ld) & 3)) grid4 = false;
+  return grid4;
+}
+// elements i .. i + 3 (i % 4 == 0): one 8-byte (bf16) or 16-byte store per image on the 4-column grid, element by element off it
+__device__ __forceinline__ void pack_quad(const PackDesc& pk, int lp, bool grid4, int i, const f32x4& n4) {
+  if (!grid4) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) pack_one(pk, lp, i + e, n4[e]);
+    return;
+  }
+  const int r = i / pk.cols, c = i - r * pk.cols;
+#pragma unroll
+  for (int d = 0; d < 6; ++d)
+    if (d < pk.ndst && c >= pk.d[d].c0 && c < pk.d[d].c0 + pk.d[d].nc && r >= pk.d[d].r0 && r < pk.d[d].r0 + pk.d[d].nr) {
+      const size_t o = (size_t)(r - pk.d[d].r0) * pk.d[d].ld + (c - pk.d[d].c0);
+      const bf16x4 hb = {(bf16_t)n4[0], (bf16_t)n4[1], (bf16_t)n4[2], (bf16_t)n4[3]};
+      if (lp) *reinterpret_cast<bf16x4*>(reinterpret_cast<bf16_t*>(pk.d[d].dst) + o) = hb;
+      else *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(pk.d[d].dst) + o) = n4;
+    }
+}
+// The packed images of a group's parameters from the master tensors (recnet_pack_weights): over the optimiser's chunk list,
+// element by element through pack_one (so the stale check holds the Adam kernel's 4-wide stores against these).  Image elements
+// no window maps to (padding, the empty gate block of a GRU) are zero from the workspace's memset and are written by nobody.
+__global__ __launch_bounds__(256) void pack_chunk_kernel(const TensorDesc* __restrict__ tab, const int2* __restrict__ chunks,
+                                                         const PackDesc* __restrict__ pack, int lp) {
+  const int2 ch = chunks[blockIdx.x];
+  const PackDesc pk = pack[ch.x];
+  if (!pk.ndst) return;
+  const TensorDesc td = tab[ch.x];
+  const int end = min(td.n, ch.y + RN_CHUNK);
+  for (int i = ch.y + threadIdx.x; i < end; i += 256) pack_one(pk, lp, i, td.p[i]);
+}
 
 // partial[chunk] = sum over the chunk of p^2 (mode 0) or (g + coef * p / ||p||)^2 (mode 1)
 __global__ __launch_bounds__(256) void sumsq_chunk_kernel(const TensorDesc* __restrict__ tab, const int2* __restrict__ chunks,
@@ -181,19 +228,6 @@ __global__ __launch_bounds__(256) void adam_chunk_kernel(const TensorDesc* __res
   const float cl = clip ? *clip : 1.f;
   PackDesc pk; pk.ndst = 0; pk.cols = 1;
   if (pack) pk = pack[ch.x];
-  // one element: the update and the packed image(s)
-  auto pack_one = [&](int i, float pn) {
-    const int r = i / pk.cols, c = i - r * pk.cols;
-#pragma unroll
-    for (int d = 0; d < 6; ++d)
-      if (d < pk.ndst && c >= pk.d[d].c0 && c < pk.d[d].c0 + pk.d[d].nc &&
-          (pk.d[d].mode || (r >= pk.d[d].r0 && r < pk.d[d].r0 + pk.d[d].nr))) {
-        int dr = r - pk.d[d].r0;
-        if (pk.d[d].mode) { const int gate = r / pk.d[d].nr, u = r - gate * pk.d[d].nr; dr = (u >> 3) * 32 + gate * 8 + (u & 7); }
-        const size_t o = (size_t)dr * pk.d[d].ld + (c - pk.d[d].c0);
-        if (lp) reinterpret_cast<bf16_t*>(pk.d[d].dst)[o] = (bf16_t)pn; else reinterpret_cast<float*>(pk.d[d].dst)[o] = pn;
-      }
-  };
   auto upd = [&](float p, float gr, float& m, float& v, float& vmx) -> float {
     return rn_adam_update(p, gr, m, v, vmx, k, cl, hp, step_size, bc2s);
   };
@@ -204,9 +238,7 @@ __global__ __launch_bounds__(256) void adam_chunk_kernel(const TensorDesc* __res
   int i0 = ch.y;
   if (al) {
     const int nq = (end - ch.y) >> 2;
-    bool grid4 = (pk.cols & 3) == 0;
-    for (int d = 0; d < 6; ++d)
-      if (d < pk.ndst && (((pk.d[d].c0 | pk.d[d].nc | pk.d[d].ld) & 3) || pk.d[d].mode)) grid4 = false;
+    const bool grid4 = pack_grid4(pk);
     for (int q = threadIdx.x; q < nq; q += 256) {
       const int i = ch.y + (q << 2);
       const f32x4 p4 = *reinterpret_cast<const f32x4*>(td.p + i), g4 = *reinterpret_cast<const f32x4*>(td.g + i);
@@ -218,25 +250,7 @@ __global__ __launch_bounds__(256) void adam_chunk_kernel(const TensorDesc* __res
       *reinterpret_cast<f32x4*>(td.m + i) = m4; *reinterpret_cast<f32x4*>(td.v + i) = v4;
       if (hp.amsgrad) *reinterpret_cast<f32x4*>(td.vmax + i) = x4;
       *reinterpret_cast<f32x4*>(td.p + i) = n4;
-      if (pk.ndst) {
-        if (grid4) {
-          const int r = i / pk.cols, c = i - r * pk.cols;
-#pragma unroll
-          for (int d = 0; d < 6; ++d)
-            if (d < pk.ndst && c >= pk.d[d].c0 && c < pk.d[d].c0 + pk.d[d].nc && r >= pk.d[d].r0 && r < pk.d[d].r0 + pk.d[d].nr) {
-              const size_t o = (size_t)(r - pk.d[d].r0) * pk.d[d].ld + (c - pk.d[d].c0);
-              if (lp) {
-                bf16x4 hb; hb[0] = (bf16_t)n4[0]; hb[1] = (bf16_t)n4[1]; hb[2] = (bf16_t)n4[2]; hb[3] = (bf16_t)n4[3];
-                *reinterpret_cast<bf16x4*>(reinterpret_cast<bf16_t*>(pk.d[d].dst) + o) = hb;
-              } else {
-                *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(pk.d[d].dst) + o) = n4;
-              }
-            }
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) pack_one(i + e, n4[e]);
-        }
-      }
+      if (pk.ndst) pack_quad(pk, lp, grid4, i, n4);
     }
     i0 = ch.y + (nq << 2);
   }
@@ -246,6 +260,6 @@ __global__ __launch_bounds__(256) void adam_chunk_kernel(const TensorDesc* __res
     td.m[i] = m; td.v[i] = v;
     if (hp.amsgrad) td.vmax[i] = x;
     td.p[i] = pn;
-    if (pk.ndst) pack_one(i, pn);
+    if (pk.ndst) pack_one(pk, lp, i, pn);
   }
 }

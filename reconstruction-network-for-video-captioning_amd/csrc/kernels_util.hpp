@@ -230,7 +230,7 @@ __global__ void scale_kernel(T* x, size_t n, float s) {
     x[i] = (T)((float)x[i] * s);
 }
 // operand copy: dst[r][c] = (AT)(scale * src[r*ld_src + c]) for c < cols, 0 for cols <= c < ld_dst (the zero
-// padding the DMA-staged GEMM relies on).  Used for enc, the packed weight images and dout.
+// padding the DMA-staged GEMM relies on).  Used for enc, the decoder states and dout.
 template <typename AT>
 __global__ void pack_block_kernel(AT* __restrict__ dst, int ld_dst, const float* __restrict__ src, int ld_src, int rows,
                                   int cols, float scale) {
@@ -247,35 +247,6 @@ __global__ void pack_cols_kernel(AT* __restrict__ dst, int ld_dst, const float* 
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const int r = (int)(i / cols), c = (int)(i % cols);
     dst[(size_t)r * ld_dst + c] = (AT)src[(size_t)r * ld_src + c];
-  }
-}
-// dst[r] = [src1[r, 0:c1) | src2[r, 0:c2) | 0 ...] with leading dimension ld_dst  (concatenated weight image)
-template <typename DT>
-__global__ void pack2_kernel(DT* __restrict__ dst, int ld_dst, const float* __restrict__ src1, int ld1, int c1,
-                             const float* __restrict__ src2, int ld2, int c2, int rows) {
-  const size_t total = (size_t)rows * ld_dst;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int r = (int)(i / ld_dst), c = (int)(i % ld_dst);
-    float v = 0.f;
-    if (c < c1) v = src1[(size_t)r * ld1 + c];
-    else if (c < c1 + c2) v = src2[(size_t)r * ld2 + (c - c1)];
-    dst[i] = (DT)v;
-  }
-}
-// Recurrent weights into the 4-block gate layout: packed row (q * Hd + u) takes master row (map[q] * Hd + u) of
-// src1 (columns [0,c1)) and of src2 (columns [c1, c1+c2)), zeros where map[q] < 0 and in the padding.
-// LSTM: map = {0,1,2,3}.  GRU: W_ih map {0,1,2,-1}, W_hh map {0,1,-1,2}  (see gru_point).
-struct GateMap { int m[4]; };
-template <typename DT>
-__global__ void pack_gates_kernel(DT* __restrict__ dst, int ld_dst, int Hd, const float* __restrict__ src1, int ld1, int c1,
-                                  GateMap map1, const float* __restrict__ src2, int ld2, int c2, GateMap map2) {
-  const size_t total = (size_t)4 * Hd * ld_dst;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int r = (int)(i / ld_dst), c = (int)(i % ld_dst), q = r / Hd, u = r - q * Hd;
-    float v = 0.f;
-    if (c < c1) { if (map1.m[q] >= 0) v = src1[(size_t)(map1.m[q] * Hd + u) * ld1 + c]; }
-    else if (c < c1 + c2) { if (map2.m[q] >= 0) v = src2[(size_t)(map2.m[q] * Hd + u) * ld2 + (c - c1)]; }
-    dst[i] = (DT)v;
   }
 }
 // dst[c][r] = src[r][c]  (32 x 32 tiles through LDS): the K-contiguous image of a weight that a backward chain GEMM

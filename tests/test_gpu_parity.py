@@ -233,6 +233,41 @@ def test_benchmarked_update_path_matches_reference_optimizer(name, mode, prec):
 
 
 @pytest.mark.parametrize("prec", ["f32", "bf16"])
+@pytest.mark.parametrize("cells", [("LSTM", "LSTM"), ("GRU", "GRU")])
+@pytest.mark.parametrize("kind", ["global", "local"])
+def test_packed_images_follow_update_at_ragged_shapes(kind, cells, prec):
+    """The windows of the packed weight images where they can go wrong: the ragged dims of test_fused_step_vs_oracle_ragged_shapes
+    (E = 18 puts the column split of rnn.weight_ih_l0 off the 4-column grid: the element-wise pack stores run; GRU: 3 gate blocks
+    into the 4-block layout; local: [W_ih | W_hh] behind a column offset).  Two eager steps at learning rates of 1e-2: the images
+    equal a fresh pack of the parameters, and — the independent check, the pack and the Adam kernel read one table — the second
+    step's losses are the oracle's losses of the parameters the first step left."""
+    dims = [7, 5, 88, 101, 18, 36, 20, 12]
+    B, F, D, V, E, H, A, RA = dims
+    decP = GU.formula_params(GU.decoder_shapes(V, E, H, A, D, cells[0]), 11)
+    recP = GU.formula_params(GU.rec_shapes(kind, H, D, RA, cells[1]), 12)
+    enc, targets = GU.make_batch(B, F, D, V, [9, 2, 5, 12, 1, 7, 4], 77)
+    C, dec, rec = make_models(dims, kind, prec, decP, recP, cells=cells, decoder_learning_rate=1e-2, reconstructor_learning_rate=1e-2)
+    step = R.TrainStep(dec, rec)
+    encd, tg = enc.cuda(), targets.cuda()
+    T, w = step.prepare(targets.numpy())
+    step(encd, tg, T, w, seed=5)
+    torch.cuda.synchronize()
+    dec1 = {k: dec["model"].state_dict()[k].detach().cpu().clone() for k in decP}
+    rec1 = {k: rec["model"].state_dict()[k].detach().cpu().clone() for k in recP}
+    assert all(float((dec1[k] - decP[k]).abs().max()) > 1e-3 for k in decP), "the first step moved every decoder tensor"
+    assert all(float((rec1[k] - recP[k]).abs().max()) > 1e-3 for k in recP), "the first step moved every reconstructor tensor"
+    sc = step(encd, tg, T, w, seed=6).clone()
+    torch.cuda.synchronize()
+    assert step.engine.chain_status() == 0
+    assert step.engine.images_stale() == 0
+    ref = oracle_grads(dec1, rec1, kind, enc, targets, True, 6, cells=cells)
+    tol = TOL[prec]
+    print("dec_loss %.8f oracle %.8f | rec_loss %.8f oracle %.8f" % (float(sc[2]), ref["dec_loss"], float(sc[5]), ref["rec_loss"]))
+    assert abs(float(sc[2]) - ref["dec_loss"]) <= tol["loss"] * abs(ref["dec_loss"])
+    assert abs(float(sc[5]) - ref["rec_loss"]) <= tol["loss"] * abs(ref["rec_loss"])
+
+
+@pytest.mark.parametrize("prec", ["f32", "bf16"])
 @pytest.mark.parametrize("name", ["tf_half_global", "tf_half_local"])
 def test_teacher_forcing_ratio_below_one_in_the_train_step(name, prec):
     """config.py:71 decoder_teacher_forcing_ratio < 1 (train.py:38,251): TrainStep draws `random.random() <= ratio` per call
