@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define RECNET_ABI_VERSION 7
+#define RECNET_ABI_VERSION 8
 #define RECNET_ATTN_NONE 0
 #define RECNET_ATTN_SOFTMAX 1
 #define RECNET_OK 0
@@ -170,6 +170,22 @@ int recnet_greedy_search(recnet_handle* h, const float* enc, int64_t* tokens_out
  * n_steps_out as above (eval.py:116).  beam_width <= 8. */
 int recnet_beam_search(recnet_handle* h, const float* enc, int32_t beam_width, int64_t* best_out, int32_t* n_steps_out,
                        void* stream);
+/* ---- sampling: one token per row drawn from softmax(logits / temperature) restricted to the top_k largest logits (the
+ * reference has no counterpart: eval.py only has the two deterministic searches).  Gumbel-max on the counter-based hash of the
+ * dropout masks: token = argmax_v (logit_v / temperature - log(-log u_v)), u_v a function of (seed, t, row, v) alone, so a call is
+ * reproducible and a CPU restatement pins it (DESIGN.md "Sampling search").  logits [rows, V] contiguous, read only;
+ * tokens_out [rows] int64; logprobs_out [rows] = log-probability of the token under the distribution sampled from (temperature
+ * and top_k applied).  temperature > 0 and finite; 0 <= top_k <= V, 0 and V = no restriction, ties at the cut admitted lowest
+ * index first, top_k = 1 = arg-max.  The handle supplies the device only: no decoder needs to be bound. */
+int recnet_sample_rows(recnet_handle* h, const float* logits, int32_t rows, int32_t V, float temperature, int32_t top_k,
+                       uint32_t seed, int32_t t, int64_t* tokens_out, float* logprobs_out, void* stream);
+/* ---- sampling search (the reference has no counterpart; the loop is greedy_search's, eval.py:19-33, with the draw above in
+ * place of the arg-max): same start state, eval mode, same stop rule, one device-side loop with no host sync; like the
+ * reference's loop it keeps feeding a caption's own tokens after its <EOS>.  tokens_out [caption_max_len+1][B] int64,
+ * logprobs_out [caption_max_len+1][B] float (row t drawn with step index t), n_steps_out as for recnet_greedy_search: only
+ * rows [0, n_steps) are meaningful, later rows hold what the fixed-length loop went on to draw. */
+int recnet_sample_search(recnet_handle* h, const float* enc, float temperature, int32_t top_k, uint32_t seed,
+                         int64_t* tokens_out, float* logprobs_out, int32_t* n_steps_out, void* stream);
 
 /* ---- forward_decoder, train.py:17-75 (teacher forcing, train.py:38,45).
  * enc [B,F,D]; targets [caption_max_len+1, B] int64 (time-major, <PAD>=0, <EOS>=2);

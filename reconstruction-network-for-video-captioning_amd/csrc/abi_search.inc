@@ -1,4 +1,4 @@
-// C ABI: the decoder's per-step API and the device-side inference search (eval.py:19-120).
+// C ABI: the decoder's per-step API and the device-side inference search (eval.py:19-120), greedy / beam / sampling.
 // Part of api.hip (one translation unit; see the include list there).
 // One decode step on already prepared loop invariants (Uv, P, bias sum): embedding, input projection,
 // h . [W_hh ; attn_W]^T, cell kernel, vocabulary projection.  Rows [0,B) / [B,2B) of Hs_lp are scratch.
@@ -130,6 +130,61 @@ int recnet_greedy_search(recnet_handle* h, const float* enc, int64_t* tokens_out
     if (r) return r;
     int64_t* out_t = tokens_out + (size_t)t * B;
     hipLaunchKernelGGL(argmax_rows_kernel, dim3(B), dim3(256), 0, st, h->sr_logits, V, V, out_t);
+    hipLaunchKernelGGL(search_stop_kernel, dim3(1), dim3(256), 0, st, out_t, B, t, n_steps_out);
+    tok = out_t; cur ^= 1;
+  }
+  hipLaunchKernelGGL(search_finish_kernel, dim3(1), dim3(1), 0, st, n_steps_out, Tm);
+  LAUNCH_OK();
+  return RECNET_OK;
+}
+
+// ---- sampling (the reference has no counterpart; the loop shape is eval.py:19-33)
+static int check_sample(float temperature, int top_k, int V) {
+  if (!(temperature > 0.f) || !std::isfinite(temperature)) return fail(RECNET_EINVAL, "temperature must be positive and finite");
+  if (top_k < 0 || top_k > V) return fail(RECNET_EINVAL, "top_k must be in [0, V]");
+  return RECNET_OK;
+}
+// one draw per row of logits [rows][V]; (B, t) place the rows in the counter space of the draw
+static void launch_sample_rows(const float* logits, int rows, int V, int B, float temperature, int top_k, uint32_t seed, int t,
+                               int64_t* tokens, float* logprobs, hipStream_t st) {
+  SampleArgs a;
+  a.x = logits; a.V = V; a.k = top_k == V ? 0 : top_k; a.B = B; a.t = t;
+  a.temp = temperature; a.key = rn_site_key(seed, RN_SITE_SAMPLE); a.tok = tokens; a.lp = logprobs;
+  if (V <= SR_ROW_LDS_MAX) hipLaunchKernelGGL((sample_rows_kernel<true>), dim3(rows), dim3(256), (size_t)V * 4, st, a);
+  else hipLaunchKernelGGL((sample_rows_kernel<false>), dim3(rows), dim3(256), 0, st, a);
+}
+
+int recnet_sample_rows(recnet_handle* h, const float* logits, int32_t rows, int32_t V, float temperature, int32_t top_k,
+                       uint32_t seed, int32_t t, int64_t* tokens_out, float* logprobs_out, void* stream) {
+  REQUIRE_WS(h);
+  if (!logits || !tokens_out || !logprobs_out) return fail(RECNET_EINVAL, "null argument");
+  if (rows < 1 || V < 1 || t < 0) return fail(RECNET_EINVAL, "rows and V must be positive, t non-negative");
+  int r = check_sample(temperature, top_k, V); if (r) return r;
+  launch_sample_rows(logits, rows, V, rows, temperature, top_k, seed, t, tokens_out, logprobs_out, (hipStream_t)stream);
+  LAUNCH_OK();
+  return RECNET_OK;
+}
+
+int recnet_sample_search(recnet_handle* h, const float* enc, float temperature, int32_t top_k, uint32_t seed,
+                         int64_t* tokens_out, float* logprobs_out, int32_t* n_steps_out, void* stream) {
+  REQUIRE_WS(h);
+  if (!h->dec_bound) return fail(RECNET_ESTATE, "decoder not bound");
+  if (!enc || !tokens_out || !logprobs_out || !n_steps_out) return fail(RECNET_EINVAL, "null argument");
+  int r = check_sample(temperature, top_k, h->V); if (r) return r;
+  hipStream_t st = (hipStream_t)stream;
+  const int B = h->B, H = h->H, V = h->V, Tm = h->Tm;
+  dec_invariants(h, enc, st);
+  hipMemsetAsync(n_steps_out, 0, 4, st);
+  hipMemsetAsync(h->sr_h[0], 0, (size_t)B * H * 4, st);
+  hipMemsetAsync(h->sr_c[0], 0, (size_t)B * H * 4, st);
+  hipLaunchKernelGGL(fill_i64_kernel, dim3(cdiv(B, 256)), dim3(256), 0, st, h->sr_tok[0], (int64_t)1, B);
+  const int64_t* tok = h->sr_tok[0];
+  int cur = 0;
+  for (int t = 0; t < Tm; ++t) {
+    r = dec_step_core(h, tok, h->sr_h[cur], h->sr_c[cur], h->sr_logits, h->sr_h[cur ^ 1], h->sr_c[cur ^ 1], 0, t, st);
+    if (r) return r;
+    int64_t* out_t = tokens_out + (size_t)t * B;
+    launch_sample_rows(h->sr_logits, B, V, B, temperature, top_k, seed, t, out_t, logprobs_out + (size_t)t * B, st);
     hipLaunchKernelGGL(search_stop_kernel, dim3(1), dim3(256), 0, st, out_t, B, t, n_steps_out);
     tok = out_t; cur ^= 1;
   }

@@ -11,7 +11,7 @@
 //   host_common.inc          GEMM wrappers, split-K slabs of the chain sites, column sums, weight packing, invariants
 //   host_decoder.inc         decoder forward chain + loss, backward chain + deferred weight gradients
 //   host_reconstructor.inc   global / local reconstructor forward + backward, optimiser step
-//   abi_search.inc           per-step decoder API, greedy / beam search
+//   abi_search.inc           per-step decoder API, greedy / beam / sampling search
 //   abi_step.inc             sequence-level entry points and the fused train step (stream orchestration)
 //   abi_misc.inc             profiling hooks, bare GEMM entry points
 // Device code: kernels.hpp -> kernels_{util,decoder,reconstructor,search,optim}.hpp, gemm*.hpp (GEMMs),

@@ -36,6 +36,7 @@ static_assert(RN_SCAL_STAMP_END % 2 == 0 && RN_SCAL_RING % 2 == 0 && RN_CTRL_STA
 #define RN_SITE_DEC_EMBED 0u
 #define RN_SITE_DEC_LOGIT 1u
 #define RN_SITE_REC_INPUT 2u
+#define RN_SITE_SAMPLE 3u      // Gumbel noise of the sampling search, tensor [B, V] at step t (kernels_search.hpp: sample_rows_kernel)
 
 __host__ __device__ __forceinline__ uint32_t rn_fmix32(uint32_t x) {
   x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16;

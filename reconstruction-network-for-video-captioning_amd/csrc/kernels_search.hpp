@@ -24,6 +24,116 @@ __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restric
   }
   if (tid == 0) out[row] = si[0];
 }
+// ---- sampling: one token per row drawn from softmax(x / temperature) restricted to the top_k largest logits, by Gumbel-max
+// on the project's counter-based hash (the reference has no counterpart; DESIGN.md "Sampling search" states the definition,
+// tests/sample_ref.py restates it for the CPU).
+#define SR_ROW_LDS_MAX 12288      // floats of a row that are kept in LDS (48 KB); longer rows are re-read from global memory
+// order-preserving key of a float: a < b <=> key(a) < key(b); -0 and +0 share a key, like they compare equal
+__device__ __forceinline__ uint32_t sr_key(float x) {
+  const uint32_t u = __float_as_uint(x == 0.f ? 0.f : x);
+  return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+}
+// inclusive prefix sum over the 256 threads of a block, in thread order; sm: 4 ints of LDS scratch
+__device__ __forceinline__ int block_scan256(int c, int* sm) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int s = c;
+  for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(s, o); if (lane >= o) s += y; }
+  __syncthreads();
+  if (lane == 63) sm[w] = s;
+  __syncthreads();
+  for (int j = 0; j < w; ++j) s += sm[j];
+  return s;
+}
+struct SampleArgs {
+  const float* x; int V, k, B, t;      // logits [rows][V]; k = 0: every entry allowed, else 0 < k < V; B, t: the (t * B + row) of the draw
+  float temp; uint32_t key;            // key = rn_site_key(seed, RN_SITE_SAMPLE)
+  int64_t* tok; float* lp;             // [rows]
+};
+// One workgroup per row.  (1) k > 0: the k-th largest key by a radix select, 8 bits per pass from the top — an LDS histogram of the
+// entries that share the prefix found so far, a scan from the top bin down, one thread owns the bin the k-th entry falls in; entries
+// equal to the cut value are admitted lowest index first (the order of topk_rows_kernel), by a count over contiguous index chunks
+// where they are more than the cut leaves room for.  (2) max of s = x / temp and arg-max of s + g over the allowed entries, lowest
+// index among equals.  (3) sum exp(s - max).  Reads the logits only.
+template <bool RES> __global__ __launch_bounds__(256) void sample_rows_kernel(const SampleArgs p) {
+  extern __shared__ float sr_row[];
+  __shared__ int hist[256]; __shared__ float sv[256]; __shared__ int si[256]; __shared__ int sw[4]; __shared__ float sf[4];
+  __shared__ uint32_t sel[3];
+  const int row = blockIdx.x, tid = threadIdx.x, V = p.V;
+  const float* xg = p.x + (size_t)row * V;
+  if (RES) {
+    for (int v = tid; v < V; v += 256) sr_row[v] = xg[v];
+    __syncthreads();
+  }
+  const float* x = RES ? sr_row : xg;
+  // allowed: key > thr, or key == thr and v < cut
+  uint32_t thr = 0; int cut = V;
+  if (p.k > 0) {
+    uint32_t prefix = 0; int krem = p.k, ceq = 0;
+    for (int shift = 24; shift >= 0; shift -= 8) {
+      hist[tid] = 0;
+      __syncthreads();
+      const uint32_t hi = shift == 24 ? 0u : 0xFFFFFFFFu << (shift + 8);
+      for (int v = tid; v < V; v += 256) {
+        const uint32_t key = sr_key(x[v]);
+        if (((key ^ prefix) & hi) == 0) atomicAdd(&hist[(key >> shift) & 255], 1);
+      }
+      __syncthreads();
+      const int c = hist[255 - tid];                                   // thread order = bins from the top down
+      const int incl = block_scan256(c, sw), excl = incl - c;
+      if (excl < krem && krem <= incl) { sel[0] = 255 - tid; sel[1] = krem - excl; sel[2] = c; }
+      __syncthreads();
+      prefix |= sel[0] << shift; krem = (int)sel[1]; ceq = (int)sel[2];
+    }
+    thr = prefix;
+    if (krem < ceq) {            // more entries equal to the cut value than the cut admits: the krem lowest indices
+      const int C = (V + 255) / 256, v0 = tid * C, v1 = v0 + C < V ? v0 + C : V;
+      int c = 0;
+      for (int v = v0; v < v1; ++v) c += sr_key(x[v]) == thr;
+      const int incl = block_scan256(c, sw), excl = incl - c;
+      if (excl < krem && krem <= incl) {
+        int need = krem - excl;
+        for (int v = v0; v < v1; ++v)
+          if (sr_key(x[v]) == thr && --need == 0) { sel[0] = v + 1; break; }
+      }
+      __syncthreads();
+      cut = (int)sel[0];
+    }
+  }
+  const uint32_t base = ((uint32_t)p.t * (uint32_t)p.B + (uint32_t)row) * (uint32_t)V;
+  float mx = -INFINITY, best = -INFINITY; int bi = 0x7fffffff;
+  for (int v = tid; v < V; v += 256) {
+    const float xv = x[v]; const uint32_t key = sr_key(xv);
+    if (key > thr || (key == thr && v < cut)) {
+      const float s = xv / p.temp;
+      const uint32_t h = rn_fmix32((base + (uint32_t)v) * 0x9E3779B1u + p.key);
+      const float u = ((float)(h >> 9) + 0.5f) * 0x1p-23f;              // exact in fp32, inside (0, 1)
+      const float y = s - logf(-logf(u));
+      mx = fmaxf(mx, s);
+      if (y > best || (y == best && v < bi)) { best = y; bi = v; }
+    }
+  }
+  mx = block_max256(mx, sf);
+  sv[tid] = best; si[tid] = bi;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (tid < w) {
+      const float y = sv[tid + w]; const int j = si[tid + w];
+      if (y > sv[tid] || (y == sv[tid] && j < si[tid])) { sv[tid] = y; si[tid] = j; }
+    }
+    __syncthreads();
+  }
+  float sum = 0.f;
+  for (int v = tid; v < V; v += 256) {
+    const float xv = x[v]; const uint32_t key = sr_key(xv);
+    if (key > thr || (key == thr && v < cut)) sum += rn_exp(xv / p.temp - mx);
+  }
+  sum = block_sum256(sum, sf);
+  if (tid == 0) {
+    const int tok = si[0] < V ? si[0] : 0;                             // (no entry compared: NaN logits)
+    p.tok[row] = tok;
+    p.lp[row] = (x[tok] / p.temp - mx) - logf(sum);
+  }
+}
 // record the step's tokens; the reference stops after the first step whose tokens are all <PAD> (eval.py:30,116)
 __global__ void search_stop_kernel(const int64_t* __restrict__ tokens, int n, int t, int32_t* __restrict__ n_steps) {
   __shared__ int any;

@@ -11,6 +11,7 @@
 //   train_step_fwd_bwd, train_step, optimizer_step      train.py:248-273
 //   decoder_step, reconstructor_step                    Decoder.forward / *Reconstructor.forward (per-step API)
 //   greedy_search, beam_search                          eval.py:19-120
+//   sample_search, sample_rows                          sampling (no counterpart in the reference; loop shape of eval.py:19-33)
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
 #include <torch/library.h>
@@ -188,6 +189,27 @@ std::tuple<at::Tensor, at::Tensor> beam_search(int64_t h, const at::Tensor& enc,
   ok(recnet_beam_search(H(h), enc.data_ptr<float>(), (int32_t)beam_width, best.data_ptr<int64_t>(), n.data_ptr<int32_t>(), stream()), "beam_search");
   return {best, n};
 }
+std::tuple<at::Tensor, at::Tensor, at::Tensor> sample_search(int64_t h, const at::Tensor& enc, double temperature, int64_t top_k, int64_t seed) {
+  chk_enc(h, enc);
+  auto toks = at::zeros({recnet_dim(H(h), RECNET_DIM_TM), enc.size(0)}, enc.options().dtype(at::kLong));
+  auto lps = at::zeros({recnet_dim(H(h), RECNET_DIM_TM), enc.size(0)}, enc.options());
+  auto n = at::zeros({1}, enc.options().dtype(at::kInt));
+  TORCH_CHECK(top_k >= INT32_MIN && top_k <= INT32_MAX, "recnet: top_k out of range");
+  ok(recnet_sample_search(H(h), enc.data_ptr<float>(), (float)temperature, (int32_t)top_k, (uint32_t)seed, toks.data_ptr<int64_t>(),
+                          lps.data_ptr<float>(), n.data_ptr<int32_t>(), stream()), "sample_search");
+  return {toks, lps, n};
+}
+std::tuple<at::Tensor, at::Tensor> sample_rows(int64_t h, const at::Tensor& logits, double temperature, int64_t top_k, int64_t seed, int64_t t) {
+  chk(logits, at::kFloat, "logits");
+  TORCH_CHECK(logits.dim() == 2 && logits.size(0) >= 1 && logits.size(1) >= 1 && logits.size(0) <= INT32_MAX && logits.size(1) <= INT32_MAX,
+              "recnet: logits must be [rows, V], got ", logits.sizes());
+  TORCH_CHECK(top_k >= INT32_MIN && top_k <= INT32_MAX && t >= 0 && t <= INT32_MAX, "recnet: top_k / t out of range");
+  auto toks = at::empty({logits.size(0)}, logits.options().dtype(at::kLong));
+  auto lps = at::empty({logits.size(0)}, logits.options());
+  ok(recnet_sample_rows(H(h), logits.data_ptr<float>(), (int32_t)logits.size(0), (int32_t)logits.size(1), (float)temperature, (int32_t)top_k,
+                        (uint32_t)seed, (int32_t)t, toks.data_ptr<int64_t>(), lps.data_ptr<float>(), stream()), "sample_rows");
+  return {toks, lps};
+}
 
 }  // namespace
 
@@ -206,6 +228,8 @@ TORCH_LIBRARY(recnet, m) {
   m.def("reconstructor_step(int handle, Tensor? input, Tensor hr, Tensor? cr, Tensor? decoder_hiddens, int T, bool train, int seed, int t) -> (Tensor output, Tensor hr, Tensor cr)");
   m.def("greedy_search(int handle, Tensor encoder_outputs) -> (Tensor tokens, Tensor n_steps)");
   m.def("beam_search(int handle, Tensor encoder_outputs, int beam_width) -> (Tensor tokens, Tensor n_steps)");
+  m.def("sample_search(int handle, Tensor encoder_outputs, float temperature, int top_k, int seed) -> (Tensor tokens, Tensor logprobs, Tensor n_steps)");
+  m.def("sample_rows(int handle, Tensor logits, float temperature, int top_k, int seed, int t) -> (Tensor tokens, Tensor logprobs)");
 }
 
 // The handle is an int, so dispatch cannot key on a tensor for every op: ops with tensor arguments are registered for the
@@ -224,6 +248,8 @@ TORCH_LIBRARY_IMPL(recnet, CUDA, m) {
   m.impl("reconstructor_step", reconstructor_step);
   m.impl("greedy_search", greedy_search);
   m.impl("beam_search", beam_search);
+  m.impl("sample_search", sample_search);
+  m.impl("sample_rows", sample_rows);
 }
 TORCH_LIBRARY_IMPL(recnet, CompositeExplicitAutograd, m) {
   m.impl("add_reg_grad", add_reg_grad);

@@ -219,6 +219,34 @@ class Engine:
                    "recnet_beam_search")
         return best, n
 
+    def sample_search(self, enc, temperature=1.0, top_k=0, seed=0):
+        """The loop of greedy_search with a draw from softmax(logits / temperature) over the top_k largest logits in place of
+        the arg-max (recnet_sample_search; the reference has none).  Returns (tokens [Tm, B] int64, logprobs [Tm, B] float32,
+        n_steps int32[1]) device tensors; only rows [:n_steps] are meaningful.  The library checks temperature / top_k."""
+        d = self.dims
+        _chk_tensor(enc, (d["B"], d["F"], d["D"]), torch.float32, "encoder_outputs")
+        Tm = self.hyper["caption_max_len"] + 1
+        toks = torch.zeros(Tm, d["B"], dtype=torch.int64, device=self.device)
+        lps = torch.zeros(Tm, d["B"], dtype=torch.float32, device=self.device)
+        n = torch.zeros(1, dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.recnet_sample_search(self.handle, _ptr(enc), float(temperature), int(top_k), seed & 0xFFFFFFFF,
+                                                 _ptr(toks), _ptr(lps), _ptr(n), _stream()), "recnet_sample_search")
+        return toks, lps, n
+
+    def sample_rows(self, logits, temperature=1.0, top_k=0, seed=0, t=0):
+        """One draw per row of caller-supplied device logits [rows, V] (recnet_sample_rows; no decoder needed).  Returns
+        (tokens [rows] int64, logprobs [rows] float32); `logits` is only read."""
+        if logits.dim() != 2:
+            raise RuntimeError("logits: expected [rows, V], got %s" % (tuple(logits.shape),))
+        rows, V = logits.shape
+        _chk_tensor(logits, (rows, V), torch.float32, "logits")
+        toks = torch.empty(rows, dtype=torch.int64, device=logits.device)
+        lps = torch.empty(rows, dtype=torch.float32, device=logits.device)
+        _lib.check(self.lib.recnet_sample_rows(self.handle, _ptr(logits), int(rows), int(V), float(temperature), int(top_k),
+                                               seed & 0xFFFFFFFF, int(t), _ptr(toks), _ptr(lps), _stream()),
+                   "recnet_sample_rows")
+        return toks, lps
+
     def decoder_step(self, tokens, h_in, c_in, enc, train=False, seed=0, t=0):
         d = self.dims
         B = d["B"]

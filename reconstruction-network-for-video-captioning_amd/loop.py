@@ -20,7 +20,7 @@ from .api import (GraphedStep, build_decoder, build_reconstructor, forward_decod
 from .checkpoint import load_checkpoint, save_checkpoint
 from .dp import DataParallelTrainStep
 from .feed import DeviceFeeder
-from .search import beam_search, greedy_search
+from .search import beam_search, greedy_search, sample_search
 
 
 class Trainer:
@@ -216,8 +216,9 @@ class Trainer:
 @torch.no_grad()
 def evaluate(config, score_batches, decoder, search_method, idx2word, references):
     """score_batches: iterable of (vids, enc [B,F,D]) with B == config.batch_size (the score loader repeats its last
-    sample to fill the batch, dataset/MSVD.py:76-93; "PAD" ids are dropped like eval.py:145).  search_method: "greedy" or
-    ("beam", width).  references: {vid: [caption strings]}.  Returns the score dict of metrics.score_all."""
+    sample to fill the batch, dataset/MSVD.py:76-93; "PAD" ids are dropped like eval.py:145).  search_method: "greedy",
+    ("beam", width) or ("sample", temperature, top_k, seed).  references: {vid: [caption strings]}.  Returns the score dict
+    of metrics.score_all."""
     decoder.eval()
     dev = next(decoder.parameters()).device
     B, H = config.batch_size, decoder.hidden_size
@@ -234,10 +235,15 @@ def evaluate(config, score_batches, decoder, search_method, idx2word, references
             steps = greedy_search(config, decoder, inp, hid, enc)                     # [n_steps][B]
             caps = list(map(list, zip(*steps)))
         else:
-            method, width = search_method
-            if method != "beam":
+            method = search_method[0]
+            if method == "beam":
+                caps = beam_search(config, search_method[1], None, decoder, inp, hid, enc)
+            elif method == "sample":
+                _, temperature, top_k, seed = search_method
+                steps, _ = sample_search(config, decoder, inp, hid, enc, temperature, top_k, seed)
+                caps = list(map(list, zip(*steps)))
+            else:
                 raise NotImplementedError("Unknown search method: {}".format(method))
-            caps = beam_search(config, width, None, decoder, inp, hid, enc)
         for vid, c in zip(vids, caps):
             if vid != "PAD" and vid not in res:
                 res[vid] = [metrics.indices_to_sentence(c, idx2word)]

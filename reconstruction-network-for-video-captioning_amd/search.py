@@ -1,10 +1,13 @@
 """Inference search with the reference's signatures (eval.py:19-33 greedy_search, eval.py:36-120 beam_search),
 run as device-side loops in the HIP library (recnet_greedy_search / recnet_beam_search): no per-sample Python
-list building, no host synchronisation per step — one read-back at the end.
+list building, no host synchronisation per step — one read-back at the end.  sample_search (no counterpart in the
+reference) is greedy_search's loop with a temperature / top-k draw in place of the arg-max (recnet_sample_search).
 
 Differences from the reference that a caller can observe: `input` / `hidden` must be the start state the
 reference's own `evaluate()` builds (<SOS> tokens, zero hidden state, eval.py:131-141) — that is the only
 state the reference ever passes; beam_width <= 8."""
+import math
+
 import torch
 
 from . import _ops
@@ -53,3 +56,37 @@ def beam_search(config, beam_width, vocab, decoder, input, hidden, encoder_outpu
     best, n = _ops.load().beam_search(int(eng.handle.value), encoder_outputs.contiguous(), int(beam_width))
     n = int(n.item())
     return best[:n].t().cpu().tolist()
+
+
+def sample_search(config, decoder, input, hidden, encoder_outputs, temperature=1.0, top_k=0, seed=0):
+    """greedy_search's loop (eval.py:19-33) with one draw per caption and step from softmax(logits / temperature) restricted
+    to the top_k largest logits (0: no restriction; 1: the arg-max) — the reference has no counterpart.  The draw is a pure
+    function of (seed, step, caption, vocabulary index): the same seed gives the same captions.  Returns (tokens, logprobs),
+    both [n_steps][B] lists like greedy_search's; logprobs[t][b] is the log-probability of tokens[t][b] under the
+    distribution it was drawn from.  Like the reference's loop this one goes on after a caption's <EOS> (see
+    sequence_logprob)."""
+    if not (isinstance(temperature, (int, float)) and math.isfinite(temperature) and temperature > 0):
+        raise ValueError("temperature must be a positive finite number (got %r)" % (temperature,))
+    if int(top_k) != top_k or not 0 <= top_k <= decoder.output_size:
+        raise ValueError("top_k must be an integer in [0, %d] (got %r)" % (decoder.output_size, top_k))
+    _check_start(config, input, hidden)
+    eng = _engine(decoder, encoder_outputs)
+    toks, lps, n = _ops.load().sample_search(int(eng.handle.value), encoder_outputs.contiguous(), float(temperature), int(top_k),
+                                             int(seed) & 0xFFFFFFFF)
+    n = int(n.item())
+    return toks[:n].cpu().tolist(), lps[:n].cpu().tolist()
+
+
+def sequence_logprob(tokens, logprobs, eos=2):
+    """Per-caption sum of `logprobs` ([n_steps][B], as sample_search returns them) up to and including the caption's first
+    <EOS>, or over all steps when it has none: the log-probability of the caption as the scorers read it."""
+    B = len(tokens[0]) if tokens else 0
+    out = []
+    for b in range(B):
+        total = 0.0
+        for t in range(len(tokens)):
+            total += logprobs[t][b]
+            if tokens[t][b] == eos:
+                break
+        out.append(total)
+    return out
