@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define RECNET_ABI_VERSION 8
+#define RECNET_ABI_VERSION 9
 #define RECNET_ATTN_NONE 0
 #define RECNET_ATTN_SOFTMAX 1
 #define RECNET_OK 0
@@ -124,6 +124,14 @@ int recnet_create(const recnet_config* cfg, recnet_handle** out);
 void recnet_destroy(recnet_handle* h);
 /* Update the data-parallel placement / learning rates without re-creating (host fields only). */
 int recnet_set_shard(recnet_handle* h, int32_t global_batch_size, int32_t batch_offset);
+/* Replace the Adam hyper-parameters of one model (which: 0 decoder, 1 reconstructor) — what an edit of torch.optim.Adam's
+ * param_groups or a load_state_dict changes: lr, weight decay, betas, eps.  recnet_create takes them from the config
+ * (adam_beta1 / adam_beta2 / adam_eps for both models); this call gives each model its own.  Host fields only: it takes effect
+ * for launches enqueued afterwards, so a captured graph keeps the values it was captured with and has to be captured again.
+ * Whether a model runs AMSGrad is fixed by the config and the state bound to it.  Ranges are torch.optim.Adam's
+ * (lr, weight decay, eps >= 0; 0 <= beta < 1), else RECNET_EINVAL. */
+int recnet_set_optimizer_hyper(recnet_handle* h, int32_t which, double lr, double weight_decay, double beta1, double beta2,
+                               double eps);
 
 /* Bytes of device scratch the caller must provide (activations saved for backward, split-K slabs,
  * packed weights).  Must stay alive and untouched between a forward and its backward. */

@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # RN_LIB_VARIANT=probe: the probe build (in-kernel time stamps); =acqinv: the cross-check build with acquire fences; =fault: fault injection
 _VARIANT = ("_" + os.environ["RN_LIB_VARIANT"] if os.environ.get("RN_LIB_VARIANT") else "")
 LIB_PATH = os.path.join(_HERE, "csrc", "librecnet_hip%s.so" % _VARIANT)
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 REC_NONE, REC_GLOBAL, REC_LOCAL = 0, 1, 2
 PREC_F32, PREC_BF16 = 0, 1
@@ -56,6 +56,7 @@ EXPORTS = {
     "recnet_create": (_i, [C.POINTER(Config), C.POINTER(C.c_void_p)]),
     "recnet_destroy": (None, [C.c_void_p]),
     "recnet_set_shard": (_i, [C.c_void_p, _i, _i]),
+    "recnet_set_optimizer_hyper": (_i, [C.c_void_p, _i, _d, _d, _d, _d, _d]),
     "recnet_workspace_bytes": (C.c_size_t, [C.c_void_p]),
     "recnet_bind_workspace": (_i, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "recnet_bind_decoder": (_i, [C.c_void_p] + [C.POINTER(DecoderTensors)] * 5),
@@ -122,6 +123,7 @@ def check(rc, what=""):
         raise RecNetError("%s failed (code %d): %s" % (what or "recnet call", rc, (msg or b"").decode()))
 
 OPT_REG, OPT_CLIP, OPT_SKIP_DECODER, OPT_SKIP_RECONSTRUCTOR = 1, 2, 4, 8
+DIM_SPLIT_FITS = 10      # RECNET_DIM_SPLIT_FITS of recnet_dim
 EXPORTS["recnet_clip_grad_norm"] = (_i, [C.c_void_p, _i, _f, C.c_void_p, C.c_void_p])
 EXPORTS["recnet_set_step"] = (_i, [C.c_void_p, _i, C.c_void_p])
 EXPORTS["recnet_train_step_fwd_bwd_dev"] = (_i, [C.c_void_p, C.c_void_p, C.c_void_p, _i, C.c_void_p, C.c_uint32,

@@ -101,7 +101,9 @@ def _hyper_from(C, model=None):
               gradient_clip=C.gradient_clip if C.use_gradient_clip else 0.0,
               decoder_lambda_reg=getattr(C, "decoder_lambda_reg", 1e-3),
               reconstructor_lambda_reg=getattr(C, "reconstructor_lambda_reg", 1e-2),
-              lambda_recon=getattr(C, "lambda_recon", 1.0), caption_max_len=C.caption_max_len)
+              lambda_recon=getattr(C, "lambda_recon", 1.0), caption_max_len=C.caption_max_len,
+              adam_beta1=getattr(C, "adam_beta1", 0.9), adam_beta2=getattr(C, "adam_beta2", 0.999),
+              adam_eps=getattr(C, "adam_eps", 1e-8))
     return hy
 
 
@@ -154,19 +156,33 @@ class FusedAdam(torch.optim.Optimizer):
         ms.engines[("opt",)] = eng
         return eng
 
+    def push_hyper(self):
+        """Hands the param group's lr, weight decay, betas and eps to every engine this model is bound to
+        (recnet_set_optimizer_hyper): they may have been edited through param_groups (lr schedules) or replaced by
+        load_state_dict.  Host-side and only when a value changed.  Raises when `amsgrad` no longer is what the state was
+        bound with, and when a value changed while an engine has a live GraphedStep: a captured graph keeps the
+        hyper-parameters it was captured with, so it has to be dropped and captured again after the edit."""
+        g = self.param_groups[0]
+        if bool(g["amsgrad"]) != self._ms.amsgrad:
+            raise ValueError("param_groups[0]['amsgrad'] = %r, but the optimiser state was bound with amsgrad = %r: the "
+                             "variant is fixed when the model is built" % (g["amsgrad"], self._ms.amsgrad))
+        hp = (float(g["lr"]), float(g["weight_decay"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]))
+        for eng in self._ms.engines.values():
+            if eng.opt_hyper[self._which] == hp:
+                continue
+            if len(eng.captured_steps):
+                raise RuntimeError("optimiser hyper-parameters changed (%r -> %r) while a GraphedStep of this engine is alive: "
+                                   "the captured graph holds the old values; drop it and capture again"
+                                   % (eng.opt_hyper[self._which], hp))
+            eng.set_optimizer_hyper(self._which, *hp)
+
     @torch.no_grad()
     def step(self, closure=None):
         if closure is not None:
             raise NotImplementedError("closure is not supported")
         self._ensure_state()
-        g = self.param_groups[0]
         eng = self._engine()
-        # hyper-parameters may have been edited through param_groups (lr schedules)
-        c = eng.cfg
-        if self._which == 0:
-            c.decoder_learning_rate, c.decoder_weight_decay = float(g["lr"]), float(g["weight_decay"])
-        else:
-            c.reconstructor_learning_rate, c.reconstructor_weight_decay = float(g["lr"]), float(g["weight_decay"])
+        self.push_hyper()
         self._ms.step += 1
         skip = _lib.OPT_SKIP_RECONSTRUCTOR if self._which == 0 else _lib.OPT_SKIP_DECODER
         eng.optimizer_step(self._ms.step, skip)
@@ -193,6 +209,9 @@ class FusedAdam(torch.optim.Optimizer):
         ids = state_dict["param_groups"][0]["params"]
         if len(ids) != len(params):
             raise ValueError("optimizer state_dict has %d parameters, the model has %d" % (len(ids), len(params)))
+        if "amsgrad" in state_dict["param_groups"][0] and bool(state_dict["param_groups"][0]["amsgrad"]) != self._ms.amsgrad:
+            raise ValueError("optimizer state_dict was saved with amsgrad = %r, this model was built with amsgrad = %r"
+                             % (state_dict["param_groups"][0]["amsgrad"], self._ms.amsgrad))
         step = None
         for pid, p in zip(ids, params):
             st = saved.get(pid, saved.get(str(pid)))
@@ -240,7 +259,7 @@ def build_decoder(n_vocabs, C=TrainConfig):
     ms = ModelState(model, C.decoder_use_amsgrad)
     hy = _hyper_from(C)
     opt = FusedAdam(ms, 0, lr=C.decoder_learning_rate, weight_decay=C.decoder_weight_decay,
-                    amsgrad=C.decoder_use_amsgrad, hyper=hy)
+                    amsgrad=C.decoder_use_amsgrad, betas=(hy["adam_beta1"], hy["adam_beta2"]), eps=hy["adam_eps"], hyper=hy)
     return {"model": model, "loss": "masked-cross-entropy (fused, train.py:54-68)", "optimizer": opt,
             "lambda_reg": hy["decoder_lambda_reg"], "_state": ms, "_hyper": hy, "_C": C}
 
@@ -266,7 +285,7 @@ def build_reconstructor(C=TrainConfig):
     ms = ModelState(model, C.reconstructor_use_amsgrad)
     hy = _hyper_from(C)
     opt = FusedAdam(ms, 1, lr=C.reconstructor_learning_rate, weight_decay=C.reconstructor_weight_decay,
-                    amsgrad=C.reconstructor_use_amsgrad, hyper=hy)
+                    amsgrad=C.reconstructor_use_amsgrad, betas=(hy["adam_beta1"], hy["adam_beta2"]), eps=hy["adam_eps"], hyper=hy)
     return {"model": model, "loss": "mse (fused, train.py:101,128)", "optimizer": opt,
             "lambda_reg": hy["reconstructor_lambda_reg"], "_state": ms, "_hyper": hy, "_C": C}
 
@@ -483,8 +502,15 @@ class TrainStep:
         else:
             self._free_fwd_bwd(enc, targets, T, step_weight, seed)
 
+    def _push_hyper(self):
+        """param_groups edits (lr schedules, load_state_dict) of the two optimisers reach this step's engine."""
+        self.decoder["optimizer"].push_hyper()
+        if self.reconstructor:
+            self.reconstructor["optimizer"].push_hyper()
+
     def optimizer_step(self):
         ms = self.decoder["_state"]
+        self._push_hyper()
         ms.step += 1
         if self.reconstructor:
             self.reconstructor["_state"].step = ms.step
@@ -499,6 +525,7 @@ class TrainStep:
     def __call__(self, enc, targets, T, step_weight, seed=None):
         ms = self.decoder["_state"]
         seed = self.seed_base + ms.step + 1 if seed is None else seed
+        self._push_hyper()
         ms.step += 1
         if self.reconstructor:
             self.reconstructor["_state"].step = ms.step
@@ -533,6 +560,11 @@ class GraphedStep:
     step count and the dropout seed advance on the device (recnet_train_step_*_dev), so every replay is
     a new training step.
 
+    A captured graph holds the optimiser's hyper-parameters (lr, weight decay, betas, eps) as kernel arguments: the values of
+    the two optimisers' param_groups at construction.  Editing them afterwards cannot reach the replays, so it is refused
+    while a GraphedStep of the engine is alive: the next replay, FusedAdam.step or TrainStep call raises RuntimeError
+    (FusedAdam.push_hyper, a host-side comparison) — drop the GraphedStep, edit, capture again.
+
     One rank: a single graph (fwd + bwd + optimiser).  Data parallel: three graphs with the two gradient
     all-reduces in between,
         graph A (fwd, reconstructor bwd)  ->  all-reduce(reconstructor bucket + decoder out.*, async, RCCL stream)
@@ -554,6 +586,8 @@ class GraphedStep:
             raise ValueError("GraphedStep replays the teacher-forced step; decoder_teacher_forcing_ratio = %g < 1 needs "
                              "TrainStep, which draws per call" % st.teacher_forcing_ratio)
         self.eng = st.engine
+        self._push_hyper = st._push_hyper
+        self._push_hyper()                     # the param groups' values are the ones the capture bakes in
         self.enc, self.targets, self.T, self.w = enc, targets, T, step_weight
         self.ms = st.decoder["_state"]
         self.rs = st.reconstructor["_state"] if st.reconstructor else None
@@ -647,6 +681,7 @@ class GraphedStep:
                 with torch.cuda.graph(g, **mode):
                     eng.optimizer_step_dev(self.flags)
                 self.graphs.append(g)
+        eng.captured_steps.add(self)
 
     def _dp_body(self):
         """The data-parallel step in stream order: part 1 (forward, reconstructor backward) -> early buckets on the wire ->
@@ -705,6 +740,7 @@ class GraphedStep:
             self.rs.model.mark_weights_changed()
 
     def __call__(self):
+        self._push_hyper()                   # host-side: a param-group edit since the capture raises here instead of being replayed over
         if not self.split:
             self.graphs[0].replay()
             self.eng.mark_pending()          # (a replay runs no host code: the handle's lazily refreshed weight images / a deferred update)

@@ -29,6 +29,8 @@ _DEFAULTS = dict(
     reconstructor_use_amsgrad=False, use_gradient_clip=True, gradient_clip=50.0,
     # constants the reference creates inline (train.py:151,188,225)
     decoder_lambda_reg=1e-3, reconstructor_lambda_reg=1e-2, lambda_recon=1.0,
+    # torch.optim.Adam's own defaults, which train.py:149,186 leave alone
+    adam_beta1=0.9, adam_beta2=0.999, adam_eps=1e-8,
     # additions
     precision="bf16",            # "bf16" (bf16 MFMA operands, fp32 accumulate) | "f32" (exact fp32 MFMA)
     decoder_attn_normalize="none",   # "none": the reference (decoder.py:30's softmax is never called) | "softmax": opt-in

@@ -61,6 +61,8 @@ static inline int pad8(int n) { return (n + 7) & ~7; }
 
 struct recnet_handle {
   recnet_config c;
+  // optimiser hyper-parameters per model (0 decoder, 1 reconstructor): from the config at creation, then recnet_set_optimizer_hyper
+  struct OptHyper { double lr, wd, beta1, beta2, eps; } oh[2];
   int B, F, D, E, H, A, V, R, RA, Tm, kind, prec, cml;
   int dgru = 0, rgru = 0; // recurrent cell of the decoder / reconstructor: 0 LSTM, 1 GRU (4-block gate layout, kernels.hpp)
   int lp;                // 1: operand copies / packed weights are bf16 (DMA-staged GEMM); 0: fp32 (exact path)
@@ -426,6 +428,8 @@ int recnet_create(const recnet_config* cfg, recnet_handle** out) {
   auto chain_on = [&](const char* name) { return !has(per_step, name) && !has(per_step, "all"); };
   recnet_handle* h = new recnet_handle();
   h->c = c;
+  h->oh[0] = {c.decoder_learning_rate, c.decoder_weight_decay, c.adam_beta1, c.adam_beta2, c.adam_eps};
+  h->oh[1] = {c.reconstructor_learning_rate, c.reconstructor_weight_decay, c.adam_beta1, c.adam_beta2, c.adam_eps};
   if (h->c.global_batch_size <= 0) h->c.global_batch_size = c.batch_size;
   h->B = c.batch_size; h->F = c.encoder_output_len; h->D = c.encoder_output_size; h->E = c.embedding_size;
   h->H = c.decoder_hidden_size; h->A = c.decoder_attn_size; h->V = c.n_vocabs;
@@ -565,6 +569,15 @@ void recnet_destroy(recnet_handle* h) {
 int recnet_set_shard(recnet_handle* h, int32_t global_batch_size, int32_t batch_offset) {
   if (!h || global_batch_size < h->B || batch_offset < 0) return fail(RECNET_EINVAL, "bad shard");
   h->c.global_batch_size = global_batch_size; h->c.batch_offset = batch_offset;
+  return RECNET_OK;
+}
+
+int recnet_set_optimizer_hyper(recnet_handle* h, int32_t which, double lr, double weight_decay, double beta1, double beta2, double eps) {
+  if (!h || which < 0 || which > 1) return fail(RECNET_EINVAL, "bad model index");
+  // torch.optim.Adam's own checks (adam.py: __init__)
+  if (!(lr >= 0.0) || !(weight_decay >= 0.0) || !(eps >= 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0))
+    return fail(RECNET_EINVAL, "optimiser hyper-parameter out of range (lr, weight decay, eps >= 0; 0 <= beta < 1)");
+  h->oh[which] = {lr, weight_decay, beta1, beta2, eps};
   return RECNET_OK;
 }
 

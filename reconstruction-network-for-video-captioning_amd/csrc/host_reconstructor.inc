@@ -618,10 +618,11 @@ static int bwd_rec(recnet_handle* h, float gscale, float* dhid_out, hipStream_t 
 static AdamHyper adam_hyper(const recnet_handle* h, int g, int flags) {
   const float lam = g == 0 ? h->c.decoder_lambda_reg : h->c.reconstructor_lambda_reg;
   AdamHyper hp;
-  hp.lr = g == 0 ? h->c.decoder_learning_rate : h->c.reconstructor_learning_rate;
-  hp.wd = (float)(g == 0 ? h->c.decoder_weight_decay : h->c.reconstructor_weight_decay);
-  hp.beta1 = h->c.adam_beta1; hp.beta2 = h->c.adam_beta2; hp.eps = (float)h->c.adam_eps;
-  hp.one_m_b1 = (float)(1.0 - h->c.adam_beta1); hp.beta2f = (float)h->c.adam_beta2; hp.one_m_b2 = (float)(1.0 - h->c.adam_beta2);
+  const recnet_handle::OptHyper& oh = h->oh[g];      // (the config's values until recnet_set_optimizer_hyper replaced them)
+  hp.lr = oh.lr;
+  hp.wd = (float)oh.wd;
+  hp.beta1 = oh.beta1; hp.beta2 = oh.beta2; hp.eps = (float)oh.eps;
+  hp.one_m_b1 = (float)(1.0 - oh.beta1); hp.beta2f = (float)oh.beta2; hp.one_m_b2 = (float)(1.0 - oh.beta2);
   hp.amsgrad = g == 0 ? h->c.decoder_use_amsgrad : h->c.reconstructor_use_amsgrad;
   hp.reg_coef = (flags & RECNET_OPT_REG) ? lam * (g == 0 ? 1.0f : h->c.lambda_recon) : 0.f;
   return hp;

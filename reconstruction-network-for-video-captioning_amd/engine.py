@@ -4,6 +4,7 @@ PyTorch is used here for what the task allows it for — device allocations, the
 and (in dp.py) torch.distributed.  Every computation is a call into librecnet_hip.so.
 """
 import ctypes as C
+import weakref
 
 import torch
 
@@ -123,6 +124,10 @@ class Engine:
             self.scalars = torch.zeros(8, dtype=torch.float32, device=self.device)
         self._keep = []
         self.T = None
+        # what the handle steps each model with (lr, weight decay, beta1, beta2, eps): set_optimizer_hyper keeps it current
+        self.opt_hyper = {w: (float(hy[n + "_learning_rate"]), float(hy[n + "_weight_decay"]), float(hy["adam_beta1"]),
+                              float(hy["adam_beta2"]), float(hy["adam_eps"])) for w, n in ((0, "decoder"), (1, "reconstructor"))}
+        self.captured_steps = weakref.WeakSet()      # live api.GraphedStep objects: their graphs hold opt_hyper as kernel arguments
 
     def __del__(self):
         try:
@@ -187,6 +192,13 @@ class Engine:
 
     def set_shard(self, global_batch, batch_offset):
         _lib.check(self.lib.recnet_set_shard(self.handle, global_batch, batch_offset), "recnet_set_shard")
+
+    def set_optimizer_hyper(self, which, lr, weight_decay, beta1, beta2, eps):
+        """Adam hyper-parameters of one model (0 decoder, 1 reconstructor) for the optimiser launches enqueued from now on
+        (recnet_set_optimizer_hyper; host fields only).  A graph captured earlier keeps the values it was captured with."""
+        hp = (float(lr), float(weight_decay), float(beta1), float(beta2), float(eps))
+        _lib.check(self.lib.recnet_set_optimizer_hyper(self.handle, int(which), *hp), "recnet_set_optimizer_hyper")
+        self.opt_hyper[int(which)] = hp
 
     # ------------------------------------------------------------------ hot path
     def pack_weights(self):

@@ -56,6 +56,14 @@ def test_struct_layout_matches_header(lib):
         assert names == [f[0] for f in struct._fields_]
 
 
+def test_named_constants_match_header():
+    """The indices the Python side passes to recnet_dim are the header's, so a renumbering there cannot go unnoticed."""
+    from recnet_amd import _lib
+    hdr = open(HEADER).read()
+    assert int(re.search(r"#define\s+RECNET_DIM_SPLIT_FITS\s+(\d+)", hdr).group(1)) == _lib.DIM_SPLIT_FITS
+    assert int(re.search(r"#define\s+RECNET_ABI_VERSION\s+(\d+)", hdr).group(1)) == _lib.ABI_VERSION
+
+
 def _cfg(**over):
     from recnet_amd import _lib
     c = _lib.Config()
@@ -78,6 +86,15 @@ def test_host_only_entry_points(lib):
     assert 100e6 < nbytes < 8e9          # activations of a B=100, T=31 step: hundreds of MB, far below 288 GB
     assert lib.recnet_set_shard(h, 800, 300) == 0
     assert lib.recnet_set_shard(h, 50, 0) != 0      # global batch smaller than the local one
+    # ABI 9: the optimiser's hyper-parameters of one model after creation (host fields only); torch.optim.Adam's ranges
+    assert _lib.ABI_VERSION >= 9
+    assert lib.recnet_set_optimizer_hyper(h, 0, 1e-3, 1e-2, 0.8, 0.95, 1e-6) == 0
+    assert lib.recnet_set_optimizer_hyper(h, 1, 0.0, 0.0, 0.0, 0.0, 0.0) == 0
+    assert lib.recnet_set_optimizer_hyper(h, 2, 1e-3, 0.0, 0.9, 0.999, 1e-8) == -1      # no such model
+    assert lib.recnet_set_optimizer_hyper(h, 0, 1e-3, 0.0, 1.0, 0.999, 1e-8) == -1      # beta1 = 1
+    assert lib.recnet_set_optimizer_hyper(h, 0, -1e-3, 0.0, 0.9, 0.999, 1e-8) == -1
+    assert lib.recnet_set_optimizer_hyper(h, 0, float("nan"), 0.0, 0.9, 0.999, 1e-8) == -1
+    assert b"hyper-parameter" in lib.recnet_last_error()
     # calling a compute entry point before binding a workspace is a state error, not a crash
     assert lib.recnet_pack_weights(h, None) == -2
     assert b"workspace" in lib.recnet_last_error()

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import recnet_amd as R
+from recnet_amd import _lib
 from tests import golden_util as GU
 from tests.gpu_util import make_models
 
@@ -23,7 +24,7 @@ SHAPES = {"chains": [24, 6, 64, 61, 16, 32, 16, 16], "per_step": [9, 5, 40, 61, 
 def _state(md):
     st = md["_state"].flat()
     out = {"p." + k: v.detach().clone() for k, v in md["model"].state_dict().items()}
-    for name in ("exp_avg", "exp_avg_sq"):
+    for name in ("exp_avg", "exp_avg_sq") + (("max_exp_avg_sq",) if md["_state"].amsgrad else ()):      # (no third set without AMSGrad)
         for k, v in st[name].views.items():
             out[name + "." + k] = v.detach().clone()
     return out
@@ -42,13 +43,31 @@ def _same(a, b, name, exact):
     return torch.allclose(a, b, rtol=2e-4, atol=2e-8)
 
 
-def _run(kind, prec, dims, deferred, lens_sets, order, lr=None):
+# the optimiser settings the reference's defaults never reach: AMSGrad on the reconstructor (the ad_vmax branch of the GEMM
+# epilogue, the split update), a weight decay that matters, other betas
+HYPER = dict(reconstructor_use_amsgrad=True, decoder_weight_decay=1e-2, reconstructor_weight_decay=1e-2, adam_beta1=0.8, adam_beta2=0.95)
+
+
+def _preload_vmax(md, seed):
+    """max_exp_avg_sq of the GEMM-produced recurrent weights spread log-uniformly over 1e-12 .. 1 instead of zero: whatever the
+    scale of exp_avg_sq, some elements keep the stored maximum through every step, some take the fresh value from the first
+    step on and some change sides in between — an update that wrote v in place of max(vmax, v) differs from one that did not."""
+    g = torch.Generator().manual_seed(seed)
+    for k, v in md["_state"].flat()["max_exp_avg_sq"].views.items():
+        if k.startswith("rnn.weight_"):
+            v.copy_((10.0 ** (-12.0 * torch.rand(v.shape, generator=g))).to(v.device))
+
+
+def _run(kind, prec, dims, deferred, lens_sets, order, lr=None, hyper=None, epilogue=False):
     B, F, D, V, E, H, A, RA = dims
     decP = GU.formula_params(GU.decoder_shapes(V, E, H, A, D), 3)
     recP = GU.formula_params(GU.rec_shapes(kind, H, D, RA), 4)
     cfg = {} if lr is None else dict(decoder_learning_rate=lr, reconstructor_learning_rate=lr)
+    cfg.update(hyper or {})
     _, dec, rec = make_models(list(dims), kind, prec, decP, recP, **cfg)
     step = R.DataParallelTrainStep(dec, rec, B, 0, 1, n_frames=F)
+    if hyper and hyper.get("reconstructor_use_amsgrad"):
+        _preload_vmax(rec, 21)
     graphs, losses = [], []
     for i, lens in enumerate(lens_sets):
         enc, targets = GU.make_batch(B, F, D, V, lens, 9 + i)
@@ -60,6 +79,9 @@ def _run(kind, prec, dims, deferred, lens_sets, order, lr=None):
     graphs[0].flush()
     torch.cuda.synchronize()
     assert step.step_impl.engine.chain_status() == 0
+    if epilogue:      # RECNET_DIM_SPLIT_FITS: the split update is applied at this shape, so the GEMM epilogue is what updated W_hh
+        eng = step.step_impl.engine
+        assert eng.lib.recnet_dim(eng.handle, _lib.DIM_SPLIT_FITS) == 1
     import os
     if not os.environ.get("RN_T_SKIP_IMAGES"):
         assert step.step_impl.engine.images_stale() == 0      # the operand images follow the parameters, whichever path updated them
@@ -73,6 +95,21 @@ def _run(kind, prec, dims, deferred, lens_sets, order, lr=None):
 @pytest.mark.parametrize("mode", [True, "recurrent"])      # whole update deferred / only the recurrent weights' (mode 2)
 @pytest.mark.parametrize("lr", [None, 1e-2])
 def test_deferred_update_equals_the_immediate_one_once_flushed(lr, mode, lengths, shape, kind, prec):
+    _deferred_equals_immediate(lr, mode, lengths, shape, kind, prec)
+
+
+@pytest.mark.parametrize("prec", ["bf16", "f32"])
+@pytest.mark.parametrize("mode,kind", [(True, "global"), ("recurrent", "global"), ("recurrent", "local")])
+def test_deferred_update_equals_the_immediate_one_at_other_hyper_parameters(mode, kind, prec):
+    """The hyper-parameter axis of the test above, restricted to shape "chains", full lengths and lr 1e-2 (HYPER: AMSGrad on the
+    reconstructor, weight decay 1e-2, betas 0.8 / 0.95), held to the bars that lr has there; max_exp_avg_sq is compared too.
+    bf16, mode "recurrent": the update of W_hh is the Adam epilogue of its weight-gradient product (csrc/gemm_lds.hpp) with the
+    stored maximum (ad_vmax).  tests/test_gpu_optimizer.py holds the immediate update to a float64 Adam; this holds the
+    epilogue to the immediate update."""
+    _deferred_equals_immediate(1e-2, mode, "full", "chains", kind, prec, HYPER)
+
+
+def _deferred_equals_immediate(lr, mode, lengths, shape, kind, prec, hyper=None):
     """lr None: the reference's learning rates (1e-5 / 1e-6) — the updates are too small to feed rounding differences of the
     atomically summed gradients back into the next step, so GEMM-produced tensors can be held BIT for bit.  lr 1e-2 (at
     the defaults four steps move a weight by less than the tolerances, so a missing update would pass): every step moves every
@@ -97,8 +134,14 @@ def test_deferred_update_equals_the_immediate_one_once_flushed(lr, mode, lengths
     # (mode "recurrent": the in-step half is a different grouped launch than the immediate update's — other split factors,
     # equal to fp32 rounding)
     exact = lengths == "full" and mode is True
-    d0, r0, l0 = _run(kind, prec, dims, False, sets, order, lr)
-    d1, r1, l1 = _run(kind, prec, dims, mode, sets, order, lr)
+    d0, r0, l0 = _run(kind, prec, dims, False, sets, order, lr, hyper)
+    d1, r1, l1 = _run(kind, prec, dims, mode, sets, order, lr, hyper,
+                      epilogue=hyper is not None and prec == "bf16" and mode == "recurrent" and shape == "chains")
+    if hyper and hyper.get("reconstructor_use_amsgrad"):
+        # the stored maximum is the larger operand for some elements of W_hh and the smaller for others, after the last step too
+        v, vmax = r1["exp_avg_sq.rnn.weight_hh_l0"], r1["max_exp_avg_sq.rnn.weight_hh_l0"]
+        kept, fresh = int((vmax > v).sum()), int((vmax == v).sum())
+        assert kept + fresh == v.numel() and kept > v.numel() // 20 and fresh > v.numel() // 20, (kept, fresh, v.numel())
     recP = GU.formula_params(GU.rec_shapes(kind, dims[5], dims[2], dims[7]), 4)
     if lr is None:
         assert np.allclose(l0[:, :7], l1[:, :7], rtol=1e-6 if mode is True else 3e-6, atol=0), (l0[:, 6], l1[:, 6])
@@ -121,7 +164,7 @@ def test_deferred_update_equals_the_immediate_one_once_flushed(lr, mode, lengths
             moved = float((b - v.double()).norm())
             assert moved > 3e-3 * np.sqrt(v.numel()), (k, moved)            # every update happened: a sizeable fraction of lr per element and step
             assert float((a - b).norm()) <= 2e-3 * moved, (k, float((a - b).norm()), moved)
-            for name in ("exp_avg", "exp_avg_sq"):
+            for name in ("exp_avg", "exp_avg_sq") + (("max_exp_avg_sq",) if "max_exp_avg_sq." + k in st1 else ()):
                 a, b = st0[name + "." + k].cpu().double(), st1[name + "." + k].cpu().double()
                 assert float((a - b).norm()) <= 2e-3 * float(b.norm()), (name, k)
     if lengths == "full":      # the same batch four times: the loss falls by far more than the bar above
@@ -184,7 +227,7 @@ def test_split_update_runs_beside_the_decoder_chain_in_the_replayed_graph(kind):
     T, w = step.prepare(targets.numpy())
     run = R.GraphedStep(step, enc.cuda(), targets.cuda(), T, w, warmup=2, defer_reconstructor_update="recurrent")
     eng = step.step_impl.engine
-    assert eng.lib.recnet_dim(eng.handle, 10) == 1, "the split update is applied at the benchmark shapes"
+    assert eng.lib.recnet_dim(eng.handle, _lib.DIM_SPLIT_FITS) == 1, "the split update is applied at the benchmark shapes"
     beside = 0
     for _ in range(6):
         run()

@@ -103,3 +103,51 @@ def test_fused_adam_state_dict_has_torch_adam_layout():
     assert set(sd["state"][0].keys()) == {"step", "exp_avg", "exp_avg_sq", "max_exp_avg_sq"}   # amsgrad (train.py:149)
     assert sd["param_groups"][0]["lr"] == 1e-5 and sd["param_groups"][0]["weight_decay"] == 1e-5
     assert len(sd["state"]) == 11
+
+
+class _StubEngine:
+    """What FusedAdam.push_hyper touches of an Engine (the real one needs a GPU)."""
+
+    def __init__(self, hyper):
+        self.opt_hyper = {0: hyper, 1: hyper}
+        self.captured_steps = set()
+        self.calls = []
+
+    def set_optimizer_hyper(self, which, *hp):
+        self.calls.append((which,) + hp)
+        self.opt_hyper[which] = hp
+
+
+def test_fused_adam_hands_every_hyper_parameter_to_its_engines():
+    """lr, weight decay, betas and eps of the param group reach every engine the model is bound to, only when they changed; a
+    changed `amsgrad` raises (the variant is fixed by the bound state); an edit while a captured step is alive is refused."""
+    C = R.make_config(device="cpu", encoder_output_size=16, reconstructor_hidden_size=16, embedding_size=8,
+                      decoder_hidden_size=8, decoder_attn_size=4, adam_beta1=0.8, adam_eps=1e-6)
+    dec = R.build_decoder(20, C)
+    opt, g = dec["optimizer"], dec["optimizer"].param_groups[0]
+    assert g["betas"] == (0.8, 0.999) and g["eps"] == 1e-6 and dec["_hyper"]["adam_beta1"] == 0.8      # the config's values arrive
+    first = (1e-5, 1e-5, 0.8, 0.999, 1e-6)
+    a, b = _StubEngine(first), _StubEngine(first)
+    dec["_state"].engines.update({("x",): a, ("y",): b})
+    opt.push_hyper()
+    assert a.calls == [] and b.calls == []                   # nothing changed: nothing is sent
+    g["lr"], g["weight_decay"], g["betas"], g["eps"] = 3e-4, 1e-2, (0.7, 0.9), 1e-5
+    opt.push_hyper()
+    assert a.calls == [(0, 3e-4, 1e-2, 0.7, 0.9, 1e-5)] and b.calls == a.calls
+    b.captured_steps.add(object())
+    opt.push_hyper()                                          # unchanged values: a live captured step is no obstacle
+    g["lr"] = 1e-3
+    with pytest.raises(RuntimeError, match="capture again"):
+        opt.push_hyper()
+    assert b.opt_hyper[0][0] == 3e-4
+    b.captured_steps.clear()
+    opt.push_hyper()
+    assert b.opt_hyper[0][0] == 1e-3
+    g["amsgrad"] = False
+    with pytest.raises(ValueError, match="amsgrad"):
+        opt.push_hyper()
+    g["amsgrad"] = True
+    sd = opt.state_dict()
+    sd["param_groups"][0]["amsgrad"] = False
+    with pytest.raises(ValueError, match="amsgrad"):
+        opt.load_state_dict(sd)
