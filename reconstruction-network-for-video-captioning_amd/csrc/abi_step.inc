@@ -171,15 +171,18 @@ static void hoist_rec_parts(recnet_handle* h, hipStream_t sn) {
   z.p[z.cnt] = h->bsum4r; z.n[z.cnt] = (size_t)4 * h->R; ++z.cnt;
   hipLaunchKernelGGL(zero_list_kernel, dim3(64), dim3(256), 0, sn, z);
 }
-static void hoist_side_work(recnet_handle* h, hipStream_t st) {
+// fork_recorded: the caller (dec_fwd_chain) recorded the fork events EV_HOIST_FORK / EV_S3_FORK itself, in front of its chain launch.
+// Returns what the pending reconstructor update returned.
+static int hoist_side_work(recnet_handle* h, const HoistWork& w, hipStream_t st, bool fork_recorded) {
   RN_RANGE("recnet: hoisted side work (parameter norms, zeroing, frame mean)");
   const bool split_upd = h->ss.defer_now && h->defer_rec == 2;
+  int r = RECNET_OK;
   if (h->ss.defer_now) {
     // forked HERE, i.e. after the decoder prologue has been enqueued: forked at the start of the step the replayed graph
     // ran the whole update in front of the prologue (the prologue's first kernel started 0.5 ms late)
-    if (h->ss.hoist_fork_recorded) hipStreamWaitEvent(h->s3, h->ev[EV_S3_FORK], 0); else fork_to(h, EV_S3_FORK, st, h->s3);
+    if (fork_recorded) hipStreamWaitEvent(h->s3, h->ev[EV_S3_FORK], 0); else fork_to(h, EV_S3_FORK, st, h->s3);
     if (h->persist_dec) wait_chain(h, 0, h->s3);      // the pending products start once the decoder chain is resident (wait_chain_kernel)
-    h->ss.defer_err = rec_pending_update(h, h->s3, -1, h->defer_flags);
+    r = rec_pending_update(h, h->s3, -1, h->defer_flags);
     // mode 2: only W_hh changes here — its norm (the regulariser's value) follows the update; the gate bias and the zeroing do not
     // depend on it and stay with the ordinary hoisted work below, so that the input-side product of the reconstructor's forward
     // (which needs the bias sum) does not wait for this branch: only the recurrent chain does (fwd_rec_global)
@@ -191,16 +194,15 @@ static void hoist_side_work(recnet_handle* h, hipStream_t st) {
   if (h->ss.img_defer_now && !h->ss.defer_now) {
     // deferred image refresh (api.hip: img_defer_now): the transposes / fragment packs the previous fused step left out, on the third
     // stream beside the decoder's chain; EV_PENDING_DONE = done (the reconstructor's chains wait for it, fwd_rec_*: rec_wait_pending)
-    if (h->ss.hoist_fork_recorded) hipStreamWaitEvent(h->s3, h->ev[EV_S3_FORK], 0); else fork_to(h, EV_S3_FORK, st, h->s3);
+    if (fork_recorded) hipStreamWaitEvent(h->s3, h->ev[EV_S3_FORK], 0); else fork_to(h, EV_S3_FORK, st, h->s3);
     if (h->persist_dec) wait_chain(h, 0, h->s3);
     refresh_images(h, 1, h->s3);
     hipEventRecord(h->ev[EV_PENDING_DONE], h->s3);
   }
   const bool rec = h->kind != RECNET_REC_NONE && !h->ss.defer_now;
   hipStream_t sd = h->s2;
-  hipStream_t sn = h->ss.hoist_par ? sd : st;
-  h->ss.hoist_pending = 0;
-  if (sn != st) { if (h->ss.hoist_fork_recorded) hipStreamWaitEvent(sd, h->ev[EV_HOIST_FORK], 0); else fork_to(h, EV_HOIST_FORK, st, sd); }
+  hipStream_t sn = w.par ? sd : st;
+  if (sn != st) { if (fork_recorded) hipStreamWaitEvent(sd, h->ev[EV_HOIST_FORK], 0); else fork_to(h, EV_HOIST_FORK, st, sd); }
   if (sn != st && h->persist_dec) wait_chain(h, 0, sn);      // nothing of this branch before the decoder chain is resident
   param_norms(h, 0, h->scal + RN_SCAL_DEC_REG, sn);
   if (rec) { param_norms(h, 1, h->scal + RN_SCAL_REC_REG, sn); gate_bias(h->rP.rnn_bias_ih_l0, h->rP.rnn_bias_hh_l0, h->bsum_r, h->R, h->rgru, sn); }
@@ -215,42 +217,37 @@ static void hoist_side_work(recnet_handle* h, hipStream_t st) {
     h->ss.prezeroed = 1;
   }
   if (h->kind == RECNET_REC_GLOBAL) {
-    hipLaunchKernelGGL(mean_over_f_kernel, dim3(ew_blocks((size_t)h->B * h->D)), dim3(256), 0, sn, h->ss.hoist_enc, h->B, h->F, h->D, h->encmean);
+    hipLaunchKernelGGL(mean_over_f_kernel, dim3(ew_blocks((size_t)h->B * h->D)), dim3(256), 0, sn, w.enc, h->B, h->F, h->D, h->encmean);
     h->ss.encmean_hoisted = 1;
   }
   if (sn != st) hipEventRecord(h->ev[EV_HOIST_DONE], sd);
+  return r;
 }
 
 // What only needs the decoder's forward pass: vocabulary projection + CE + output-layer gradients (+ the attended
 // features for the deferred dW_ih), on the side stream when there is one.
-static void side_after_decoder_fwd(recnet_handle* h, hipStream_t st) {
+static int side_after_decoder_fwd(recnet_handle* h, const SideWork& w, hipStream_t st, bool fork_recorded) {
   hipStream_t sd = h->overlap ? h->s2 : st;
   const bool par = sd != st;
-  h->ss.side_pending = 0;
-  // (side_fork_recorded: the caller recorded the fork event EV_SIDE_FORK itself, IN FRONT of a chain launch it then enqueued — the side
+  // (fork_recorded: the caller — fwd_rec_global — recorded the fork event EV_SIDE_FORK itself, IN FRONT of a chain launch it then enqueued — the side
   // work is enqueued behind that launch on the host but depends only on what preceded it)
   if (par) {
-    if (h->ss.side_fork_recorded) {
+    if (fork_recorded) {
       hipStreamWaitEvent(sd, h->ev[EV_SIDE_FORK], 0);
       // the fork point lies in front of the reconstructor's forward chain, which may still be waiting for something else (mode 2
       // of the deferred update: W_hh's pending update) when this branch becomes runnable: hold it until the chain is resident
       if (h->kind == RECNET_REC_GLOBAL && h->persist_rec) wait_chain(h, 2, sd);
     } else fork_to(h, EV_SIDE_FORK, st, sd);
-    h->ss.side_fork_recorded = 0; h->ss.gws_cur = h->gws2;
   }
   h->ss.join_pending = par; h->ss.join_recorded = 0; h->ss.side_tail_open = 0;
-  // (beside the reconstructor's chains when there is a side stream: a persistent chain holds ~3/4 of the CUs)
-  if (par && h->kind != RECNET_REC_NONE) h->ss.gg_slots = 2 * (h->ncu > 192 ? h->ncu - 192 : 32);
-  int r = dec_fwd_loss(h, h->ss.side_targets, h->ss.side_T, h->ss.side_stepw, 1, sd);
+  int r = dec_fwd_loss(h, w.targets, w.T, w.stepw, 1, sd);
   // (measured and rejected, round 4: the output layer's own gradients and the attended features beside the BPTT chain instead of
   // here, with the split reconstructor update — the products the BPTT waits for come 17 us earlier, but that window is full
   // and the tail grows by 67 us: C2 1.773 against 1.724 ms)
-  if (!r) r = dec_bwd_out(h, 1.0f, sd);
-  h->ss.gg_slots = 0;
-  if (!r && par && h->ss.side_phase != 2) { dec_ctx_rows(h, h->ss.side_enc, 0, h->ss.side_T, sd); h->ss.ctx_done = 1; }   // off the tail
+  if (!r) r = dec_bwd_out(h, 1.0f, sd, 3, w.phase == 0);
+  if (!r && par && w.phase != 2) { dec_ctx_rows(h, w.enc, 0, w.T, sd); h->ss.ctx_done = 1; }   // off the tail
   if (h->ss.side_tail_open) hipEventRecord(h->ev[EV_SIDE_TAIL], sd);      // (dec_bwd_out recorded the join the BPTT waits for in front of this branch's rest)
-  h->ss.gws_cur = h->gws;
-  h->ss.side_err = r;
+  return r;
 }
 
 // The whole forward + backward.  The four dependent chains (decoder fwd, reconstructor fwd, reconstructor bwd,
@@ -269,6 +266,10 @@ static int fwd_bwd_impl(recnet_handle* h, const float* enc, const int64_t* targe
   const bool par = sd != st;
   int r;
   bool s3_join = false;
+  // total = dec_loss + lambda_recon * rec_loss, and the reconstructor's loss scalars in front of it: scalars only the export at the
+  // step's end reads — on the side stream behind the BPTT's fork when there is one (one launch less between the reconstructor's
+  // backward and the decoder's BPTT)
+  const bool total_late = rec && phase == 0 && par;
   const float* dh = rec ? h->dHsrec : nullptr;
   h->ss.early_opt_done = 0;
   if (phase != 2) h->free_fwd = 0;                 // the fused step is teacher-forced
@@ -304,18 +305,13 @@ static int fwd_bwd_impl(recnet_handle* h, const float* enc, const int64_t* targe
     // Work that does not depend on the batch's forward pass (hoist_side_work below) goes to the side stream.  It is forked
     // from inside dec_fwd_chain, after the decoder's prologue has been enqueued: forked at the very start of the step it
     // ran before the prologue instead of beside it (80 us on the critical path in the kernel trace).
-    h->ss.hoist_pending = 1; h->ss.hoist_enc = enc; h->ss.hoist_par = par ? 1 : 0;
-    h->ss.norms_hoisted = 1;
-    r = dec_fwd_chain(h, enc, targets, T, 1, st);
-    if (h->ss.hoist_pending) hoist_side_work(h, st);
-    if (!r && h->ss.defer_err) { r = h->ss.defer_err; h->ss.defer_err = 0; }
-    if (r) { h->ss.norms_hoisted = 0; return r; }
-    h->ss.side_targets = targets; h->ss.side_stepw = stepw; h->ss.side_enc = enc; h->ss.side_T = T; h->ss.side_phase = phase; h->ss.side_err = 0;
-    h->ss.side_pending = 1;
+    const HoistWork hoist = {par ? 1 : 0, enc};
+    r = dec_fwd_chain(h, enc, targets, T, 1, st, nullptr, &hoist); if (r) return r;
+    const SideWork side = {targets, stepw, enc, T, phase};
     // global reconstructor: the side work is forked from inside fwd_rec_global, behind the batched input GEMM (so that
     // GEMM does not share the chip with the vocabulary projection; the persistent chain that follows leaves CUs free)
-    if (!(par && h->kind == RECNET_REC_GLOBAL)) side_after_decoder_fwd(h, st);
-    if (h->ss.side_err) { h->ss.norms_hoisted = 0; return h->ss.side_err; }
+    const bool side_in_rec = par && h->kind == RECNET_REC_GLOBAL;
+    if (!side_in_rec) { r = side_after_decoder_fwd(h, side, st, false); if (r) return r; }
     if (rec) {
       // bsum_r and the reconstructor's norm.  (Joining the hoisted branch through the pending-update branch instead — one
       // cross-stream edge in front of the reconstructor's chain instead of two, with the reconstructor's gate bias formed by
@@ -325,32 +321,18 @@ static int fwd_bwd_impl(recnet_handle* h, const float* enc, const int64_t* targe
       if (defer && h->defer_rec != 2) hipStreamWaitEvent(st, h->ev[EV_PENDING_DONE], 0);          // ... and the updated parameters (deferred update)
       else if (defer) h->ss.rec_wait_pending = 1;                  // (mode 2: only the recurrent chain waits, see fwd_rec_global)
       if (h->ss.img_defer_now) h->ss.rec_wait_pending = 1;            // (deferred image refresh: the chains wait for the third stream's EV_PENDING_DONE)
-      h->ss.rec_loss_defer = (phase == 0 && par) ? 1 : 0;      // (the same condition as total_late below: the loss scalars go where the total goes)
-      r = fwd_rec(h, enc, T, 1, st);
-      h->ss.rec_loss_defer = 0;
-      h->ss.norms_hoisted = 0;
-      if (h->ss.side_pending) side_after_decoder_fwd(h, st);
-      if (!r) r = h->ss.side_err;
-      if (r) return r;
+      r = fwd_rec(h, enc, T, 1, st, /*norms_hoisted*/ true, /*loss_late*/ total_late, side_in_rec ? &side : nullptr); if (r) return r;      // (the loss scalars go where the total goes)
       // (measured and rejected in the fused step: the deferred gradients forked right behind the chain share the chip with the
       // d hiddens products the BPTT waits for, C2 2.06 -> 2.10 ms, C5 5.04 -> 5.44 ms)
       h->ss.deferred_done = 0;
       // phase 1 (data parallel, graph A): there is no decoder BPTT in this graph to hide the deferred products behind; forked
       // here they at least run beside the d hiddens products that follow the chain instead of after them
-      h->ss.deferred_early = (par && !defer && phase == 1) ? 1 : 0;
-      h->ss.deferred_early_flags = early_opt >= 0 ? early_opt : -1;
-      r = bwd_rec_chain(h, h->c.lambda_recon, h->dHsrec, st);
-      h->ss.deferred_early = 0;
-      if (r) return r;
+      r = bwd_rec_chain(h, h->c.lambda_recon, h->dHsrec, st, par && !defer && phase == 1, early_opt >= 0 ? early_opt : -1); if (r) return r;
       if (h->ss.join_pending) {                         // the decoder BPTT needs dHs_out; RN_SCAL_DEC_LOSS is final
         if (h->ss.join_recorded) hipStreamWaitEvent(st, h->ev[EV_SIDE_JOIN], 0); else join_from(h, EV_SIDE_JOIN, st, sd);
         h->ss.join_pending = 0; h->ss.join_recorded = 0;
       }
-      // total = dec_loss + lambda_recon * rec_loss: a scalar only the export at the step's end reads — on the side stream behind
-      // the fork below when there is one (one launch less between the reconstructor's backward and the decoder's BPTT)
-      bool total_late = phase == 0 && par;
-      if (!total_late) { if (h->ss.rec_loss_late) rec_loss_scalars(h, st); hipLaunchKernelGGL(axpb_kernel, dim3(1), dim3(1), 0, st, h->scal + RN_SCAL_DEC_LOSS, h->scal + RN_SCAL_REC_LOSS, h->c.lambda_recon, h->scal + RN_SCAL_TOTAL); }
-      h->ss.total_late = total_late ? 1 : 0;
+      if (!total_late) hipLaunchKernelGGL(axpb_kernel, dim3(1), dim3(1), 0, st, h->scal + RN_SCAL_DEC_LOSS, h->scal + RN_SCAL_REC_LOSS, h->c.lambda_recon, h->scal + RN_SCAL_TOTAL);
       if (phase == 1) {
         // (dp_overlap: the caller makes the stream of its early all-reduce wait for the side stream itself — recnet_join_side —
         // so that this stream can go on with the decoder's BPTT while the reconstructor's weight gradients are still being formed)
@@ -362,21 +344,18 @@ static int fwd_bwd_impl(recnet_handle* h, const float* enc, const int64_t* targe
       if (h->ss.join_recorded) hipStreamWaitEvent(st, h->ev[EV_SIDE_JOIN], 0); else join_from(h, EV_SIDE_JOIN, st, sd);      // dHs_out of the vocabulary projection
       h->ss.join_pending = 0; h->ss.join_recorded = 0;
     }
-    h->ss.norms_hoisted = 0;
     if (phase == 1) return RECNET_OK;
   }
   // (measured without effect: the BPTT chain enqueued in front of this fork, C2 1.906 / 1.906 ms, C3 2.32 / 2.32 ms)
   if (par) fork_to(h, EV_BPTT_FORK, st, sd);
-  if (h->ss.total_late) {      // (see above; sd is ordered behind the reconstructor's chains by the fork, and joined at the step's end)
-    if (h->ss.rec_loss_late) rec_loss_scalars(h, sd);
+  if (total_late) {      // (see above; sd is ordered behind the reconstructor's chains by the fork, and joined at the step's end)
+    rec_loss_scalars(h, sd);
     hipLaunchKernelGGL(axpb_kernel, dim3(1), dim3(1), 0, sd, h->scal + RN_SCAL_DEC_LOSS, h->scal + RN_SCAL_REC_LOSS, h->c.lambda_recon, h->scal + RN_SCAL_TOTAL);
-    h->ss.total_late = 0;
   }
   if (defer) {
     // this step's update stays pending: only what its deferred products could not read later is done now — the product
     // with the decoder's hidden states (local) and the zeroing of the gate gradients of the steps that did not run (global:
     // the deferred products always cover caption_max_len + 1 steps)
-    h->ss.gws_cur = h->gws2;
     if (h->defer_rec == 2) {
       // mode 2: everything but the recurrent weights is updated NOW, beside the decoder's BPTT chain (input-side and output-layer
       // products, bias sums, their Adam step); d W_hh = dG^T . h_{t-1} — 60 % of the reconstructor's weight-gradient work — and
@@ -387,7 +366,6 @@ static int fwd_bwd_impl(recnet_handle* h, const float* enc, const int64_t* targe
     } else {
       r = bwd_rec_deferred(h, sd, 1);
     }
-    h->ss.gws_cur = h->gws;
     if (r) { h->ss.defer_now = 0; return r; }
     if (h->kind == RECNET_REC_GLOBAL && T < h->Tm)
       hipMemsetAsync(at_off(h, h->dGr, (size_t)T * h->B * h->ld4R), 0, (size_t)(h->Tm - T) * h->B * h->ld4R * (h->lp ? 2 : 4), sd);
@@ -395,10 +373,8 @@ static int fwd_bwd_impl(recnet_handle* h, const float* enc, const int64_t* targe
     h->maybe_pending = 1; h->ss.early_opt_done = 1; h->ss.deferred_done = 1;
   }
   if (phase == 0 && rec && !h->ss.deferred_done) {
-    if (par) h->ss.gws_cur = h->gws2;
     if (par && h->persist_dec_bwd) wait_chain(h, 1, sd);      // (the BPTT chain is launched on `st` below; this branch waits for its residency)
     r = bwd_rec_deferred(h, sd, 0); if (r) return r;
-    h->ss.gws_cur = h->gws;
     if (early_opt >= 0 && par) {
       // The reconstructor's Adam step + re-transpose on a third stream behind its deferred products, so that the side stream is free for its half of the decoder's deferred gradients the moment the BPTT chain ends (the update
       // streams 0.5 GB and holds the side stream for ~130 us past the end of the chain).  Measured and rejected (round 3):

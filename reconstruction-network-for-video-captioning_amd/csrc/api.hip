@@ -127,9 +127,8 @@ struct recnet_handle {
   int64_t* in_tok = nullptr;   // [Tm][B] tokens fed by the last free-running forward (its backward scatters the embedding gradient by them)
   int free_fwd = 0;
   size_t gws_floats, slab_floats;
-  float* gws2 = nullptr;   // the side stream's split-K slabs (ss.gws_cur: the ones gemm() uses now)
+  float* gws2 = nullptr;   // the side stream's split-K slabs (gws3: the third stream's; host_common.inc: gemm_lane)
   unsigned* gcnt = nullptr;      // tile counters of the grouped launches' in-launch split-K sums: one block of RN_GCNT_WORDS per slab workspace
-  int gg_site = 0;               // the next grouped launch stamps its start / end into this slot (1..8) of the group stamps
   // environment switches, read ONCE per handle in recnet_create (round 6: no getenv on any enqueue path; a test that flips one creates
   // a new handle).  Each selects between two tested forms of one piece of the schedule, never the arithmetic (tests/test_gpu_knobs.py,
   // tests/test_gpu_parity.py: _chain_variants).
@@ -148,7 +147,7 @@ struct recnet_handle {
   int prof_on = 0; std::vector<hipEvent_t> prof_ev; size_t prof_used = 0;
 };
 // the schedule state back to "between two steps"
-static void sched_reset(recnet_handle* h) { h->ss = StepSched{}; h->ss.gws_cur = h->gws; }
+static void sched_reset(recnet_handle* h) { h->ss = StepSched{}; }
 
 // leading dimensions of the operand buffers and the k-step counts of the R > 2048 chains (recnet_create, before the image table)
 static void set_dims(recnet_handle* h) {

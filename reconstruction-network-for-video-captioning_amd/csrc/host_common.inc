@@ -65,24 +65,32 @@ struct RnRange {
 // last-arriving slice (no reduction launch).  bf16 path only; the exact-fp32 path runs the members one by one.
 struct GemmGroup { int a_col, b_col, n; RnGemmDesc d[GG_MAX]; };
 static GemmGroup gg_begin(int a_col, int b_col) { GemmGroup g; g.a_col = a_col; g.b_col = b_col; g.n = 0; return g; }
-// h->ss.gg_slots: workgroup slots the next launches can expect (0: the whole chip) — set by the call sites that run beside a chain
-// kernel or beside another grouped launch (launch.hpp: rn_launch_gemm_group)
+// What a product's launch needs beyond its operands.  slots: workgroup slots it can expect (0: the whole chip) — for a launch beside
+// a chain kernel or beside another grouped launch (launch.hpp: rn_launch_gemm_group).  sum_in_launch: gemm() runs its product as a
+// group of one, whose K slices are summed inside the launch.  site (1..8, 0 = none): gg_run's launch stamps its start / end into
+// this slot of the handle's group stamps.
+struct GemmOpts { int slots = 0, sum_in_launch = 0, site = 0; };
+static GemmOpts stamp_site(int site) { GemmOpts o; o.site = site; return o; }
 static void gemm(recnet_handle* h, const void* A, int a_col, int lda, const void* Bm, int b_col, int ldb, float* C, int ldc,
-                 const float* bias, int M, int N, int K, float alpha, int acc, hipStream_t st);
+                 const float* bias, int M, int N, int K, float alpha, int acc, hipStream_t st, GemmOpts o = GemmOpts());
 static void gemm_to_at(recnet_handle* h, const void* A, int a_col, int lda, const void* Bm, int b_col, int ldb, void* C,
                        int ldc, int M, int N, int K, hipStream_t st);
-// the tile counters that go with the split-K slabs in use (one block per slab workspace: launches on different streams never share)
-static unsigned* gg_counters(recnet_handle* h) {
-  return h->gcnt + (h->ss.gws_cur == h->gws2 ? RN_GCNT_WORDS : (h->ss.gws_cur == h->gws3 ? 2 * RN_GCNT_WORDS : 0));
+// The split-K slabs and the tile counters (one block of RN_GCNT_WORDS per slab workspace) a product uses follow from the stream it is
+// enqueued on: the handle's side streams have their own, so that launches on different streams never share.  (Only a side stream
+// that exists is compared: a null s2 / s3 is not the caller's null stream.)
+struct GemmLane { float* ws; unsigned* cnt; };
+static GemmLane gemm_lane(const recnet_handle* h, hipStream_t st) {
+  if (h->s3 && st == h->s3) return {h->gws3, h->gcnt + 2 * RN_GCNT_WORDS};
+  if (h->s2 && st == h->s2) return {h->gws2, h->gcnt + RN_GCNT_WORDS};
+  return {h->gws, h->gcnt};
 }
 // adam != null: members with ad_p set apply their Adam update in the epilogue (returns false if the launch did not qualify —
 // nothing was enqueued then, and the caller runs the plain products and the optimiser kernel instead)
-static bool gg_run(recnet_handle* h, GemmGroup& g, hipStream_t st, const AdamShared* adam = nullptr) {
-  if (g.n == 0) { h->gg_site = 0; return true; }
-  // h->gg_site (1..8, 0 = none): this launch stamps its start / end into slot gg_site of the handle's group stamps
-  unsigned long long* stamp = h->gg_site > 0 ? reinterpret_cast<unsigned long long*>(h->gbar + CS_WS_GROUP_STAMPS) + 2 * (h->gg_site - 1) : nullptr;
-  h->gg_site = 0;
-  if (h->lp && h->sw.gemm_group && !rn_launch_gemm_group(g.a_col, g.b_col, g.d, g.n, h->ss.gws_cur, h->gws_floats, gg_counters(h), RN_GCNT_WORDS, st, h->ss.gg_slots, adam, stamp)) { g.n = 0; return true; }
+static bool gg_run(recnet_handle* h, GemmGroup& g, hipStream_t st, GemmOpts o = GemmOpts(), const AdamShared* adam = nullptr) {
+  if (g.n == 0) return true;
+  unsigned long long* stamp = o.site > 0 ? reinterpret_cast<unsigned long long*>(h->gbar + CS_WS_GROUP_STAMPS) + 2 * (o.site - 1) : nullptr;
+  const GemmLane ln = gemm_lane(h, st);
+  if (h->lp && h->sw.gemm_group && !rn_launch_gemm_group(g.a_col, g.b_col, g.d, g.n, ln.ws, h->gws_floats, ln.cnt, RN_GCNT_WORDS, st, o.slots, adam, stamp)) { g.n = 0; return true; }
   if (adam) { g.n = 0; return false; }
   for (int i = 0; i < g.n; ++i) {
     const RnGemmDesc& e = g.d[i];
@@ -102,16 +110,17 @@ static void gg_add(recnet_handle* h, GemmGroup& g, const void* A, int lda, const
 }
 // batched GEMM on operand buffers (AT) with automatic split-K; fp32 output
 static void gemm(recnet_handle* h, const void* A, int a_col, int lda, const void* Bm, int b_col, int ldb, float* C, int ldc,
-                 const float* bias, int M, int N, int K, float alpha, int acc, hipStream_t st) {
-  if (h->lp && h->ss.gemm_single_group) {      // a group of one: same kernel, split products summed inside the launch
+                 const float* bias, int M, int N, int K, float alpha, int acc, hipStream_t st, GemmOpts o) {
+  const GemmLane ln = gemm_lane(h, st);
+  if (h->lp && o.sum_in_launch) {      // a group of one: same kernel, split products summed inside the launch
     RnGemmDesc e;
     e.A = A; e.lda = lda; e.B = Bm; e.ldb = ldb; e.C = C; e.ldc = ldc; e.bias = bias; e.M = M; e.N = N; e.K = K; e.alpha = alpha;
     e.accumulate = acc; e.c_bf16 = 0; e.c2 = nullptr; e.ldc2 = 0; e.ad_p = nullptr;
-    if (h->sw.gemm_group && !rn_launch_gemm_group(a_col, b_col, &e, 1, h->ss.gws_cur, h->gws_floats, gg_counters(h), RN_GCNT_WORDS, st, h->ss.gg_slots)) return;
+    if (h->sw.gemm_group && !rn_launch_gemm_group(a_col, b_col, &e, 1, ln.ws, h->gws_floats, ln.cnt, RN_GCNT_WORDS, st, o.slots)) return;
   }
   int s = rn_pick_splitk(h->prec, M, N, K, 16, 0);
   while (s > 1 && (size_t)s * M * N > h->gws_floats) s >>= 1;
-  rn_launch_gemm(h->prec, A, h->lp, a_col, lda, Bm, h->lp, b_col, ldb, C, ldc, bias, M, N, K, alpha, acc, s, h->ss.gws_cur, 1, st);
+  rn_launch_gemm(h->prec, A, h->lp, a_col, lda, Bm, h->lp, b_col, ldb, C, ldc, bias, M, N, K, alpha, acc, s, ln.ws, 1, st);
 }
 // same, output written as an operand buffer (AT) — direct epilogue only
 static void gemm_to_at(recnet_handle* h, const void* A, int a_col, int lda, const void* Bm, int b_col, int ldb, void* C,
@@ -236,8 +245,12 @@ static void wait_chain(recnet_handle* h, int k, hipStream_t st) {
   const unsigned long long* stamps = reinterpret_cast<const unsigned long long*>(h->gbar + CS_WS_STAMPS);
   hipLaunchKernelGGL(wait_chain_kernel, dim3(1), dim3(64), 0, st, reinterpret_cast<const unsigned long long*>(h->ctrl + RN_CTRL_STAMP_START), stamps + 2 * k, 30000u);
 }
-static void hoist_side_work(recnet_handle* h, hipStream_t st);   // abi_step.inc
-static void side_after_decoder_fwd(recnet_handle* h, hipStream_t st);   // abi_step.inc
+// The two pieces of the fused step that a sequence may enqueue on fwd_bwd_impl's behalf, where the captured order wants them
+// (abi_step.inc).  The callee that is handed one enqueues it and returns its error behind its own; null: nothing to enqueue.
+struct HoistWork { int par; const float* enc; };      // hoist_side_work: on the side stream?; the features (frame mean)
+struct SideWork { const int64_t* targets; const float* stepw; const float* enc; int T, phase; };      // side_after_decoder_fwd
+static int hoist_side_work(recnet_handle* h, const HoistWork& w, hipStream_t st, bool fork_recorded);
+static int side_after_decoder_fwd(recnet_handle* h, const SideWork& w, hipStream_t st, bool fork_recorded);
 // ---- the images DERIVED from the packed weights (weight_images.hpp): shapes, sources and existence come from the handle's table.
 // A transposed image = (its source image)^T, K contiguous (source rows beyond its extent read as zero -> the padding of the
 // transposed rows); src_cols > 0: only the first src_cols columns of the source.  A fragment image: one 16-byte fragment per thread.

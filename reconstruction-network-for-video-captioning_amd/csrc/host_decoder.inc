@@ -5,15 +5,16 @@
 // free_tokens != nullptr: free-running decoding (train.py:46-51) — the input of step t+1 is the argmax of step t's
 // (dropped-out) logits, written to free_tokens [T][B]; the per-step embedding / input projection / vocabulary projection
 // then sit inside the chain.  Forward only.
+// hoist != nullptr (fused step): the step's hoisted work is forked from here and forms the parameter norms (hoist_side_work).
 static int dec_fwd_chain(recnet_handle* h, const float* enc, const int64_t* targets, int T, int train, hipStream_t st,
-                         int64_t* free_tokens = nullptr) {
+                         int64_t* free_tokens = nullptr, const HoistWork* hoist = nullptr) {
   RN_RANGE("recnet: decoder forward chain (decoder.py:45-70 x T)");
   const int B = h->B, F = h->F, E = h->E, H = h->H, A = h->A, V = h->V;
   h->ss.mp_done = 0;
-  if (!h->ss.norms_hoisted) param_norms(h, 0, h->scal + RN_SCAL_DEC_REG, st);
+  if (!hoist) param_norms(h, 0, h->scal + RN_SCAL_DEC_REG, st);
   // The input part of the gates (embeddings -> Xe) does not depend on the features: in the fused step it runs on the side
   // stream beside the feature products Uv / P (EV_XE_FORK joins it in front of the chain)
-  const bool fork_xe = !free_tokens && h->overlap && h->s2 && h->ss.hoist_pending && h->ss.hoist_par;
+  const bool fork_xe = !free_tokens && h->overlap && h->s2 && hoist && hoist->par;
   // bf16 path, round 4: the three products of the prologue — Xe, Uv, P — are ONE grouped launch (774 tiles in one hardware
   // queue instead of launches of 400, 22 and 352 workgroups): only the embedding gather runs beside the feature cast
   const bool pro_group = fork_xe && h->lp;
@@ -33,15 +34,12 @@ static int dec_fwd_chain(recnet_handle* h, const float* enc, const int64_t* targ
     gg_add(h, g, h->emb_lp, h->ldE, h->We_w, h->ldE, h->Xe, 4 * H, h->bsum_d, T * B, 4 * H, E, 1.f, 0, st);
     gg_add(h, g, h->enc_lp, h->ldD, h->U_w, h->ldD, h->Uv, A, nullptr, B * F, A, h->D, 1.f, 0, st);
     gg_add(h, g, h->enc_lp, h->ldD, h->Wc_w, h->ldD, (float*)h->P, h->ld4H, nullptr, B * F, 4 * H, h->D, 1.f, 0, st, 1);
-    h->gg_site = 1;
-    gg_run(h, g, st);
+    gg_run(h, g, st, stamp_site(1));
   } else if (fork_xe) {
     fork_to(h, EV_XE_FORK, st, h->s2);
-    h->ss.gws_cur = h->gws2;
     gate_bias(h->dP.rnn_bias_ih_l0, h->dP.rnn_bias_hh_l0, h->bsum_d, H, h->dgru, h->s2);   // Xe's bias
     embed_fwd(h, targets, nullptr, T * B, train, 0, h->s2);
     gemm(h, h->emb_lp, 0, h->ldE, h->We_w, 0, h->ldE, h->Xe, 4 * H, h->bsum_d, T * B, 4 * H, E, 1.f, 0, h->s2);
-    h->ss.gws_cur = h->gws;
     hipEventRecord(h->ev[EV_XE_JOIN], h->s2);
   }
   if (!pro_group) dec_invariants(h, enc, st, !fork_xe);   // (Uv on the side stream as well: measured +10 us, the two products share the chip anyway)
@@ -61,9 +59,10 @@ static int dec_fwd_chain(recnet_handle* h, const float* enc, const int64_t* targ
   // captured in this order the chain stays on the prologue's hardware queue (the first-captured successor of a graph node does)
   // instead of paying a cross-queue hand-over of ~20 us on the critical path; the branches wait for the chain's residency anyway
   // (wait_chain_kernel)
-  const bool hoist_late = h->ss.hoist_pending && h->persist_dec && !free_tokens && (h->ld4H & 7) == 0 && h->overlap && h->s2;
-  if (hoist_late) { hipEventRecord(h->ev[EV_HOIST_FORK], st); hipEventRecord(h->ev[EV_S3_FORK], st); h->ss.hoist_fork_recorded = 1; }
-  else if (h->ss.hoist_pending) hoist_side_work(h, st);     // forked here: beside the chain, behind the prologue (fwd_bwd_impl)
+  const bool hoist_late = hoist && h->persist_dec && !free_tokens && (h->ld4H & 7) == 0 && h->overlap && h->s2;
+  int hoist_r = RECNET_OK;
+  if (hoist_late) { hipEventRecord(h->ev[EV_HOIST_FORK], st); hipEventRecord(h->ev[EV_S3_FORK], st); }
+  else if (hoist) hoist_r = hoist_side_work(h, *hoist, st, false);     // forked here: beside the chain, behind the prologue (fwd_bwd_impl)
   if (h->persist_dec && !free_tokens && (h->ld4H & 7) == 0) {
    hipEvent_t pe = prof_bracket_begin(h, RN_SITE_DEC_CHAIN_FWD, st);
    // batches above RC_PAN_ROWS captions: one launch per row group of h->bgrp captions (csrc/api.hip) — a group is an
@@ -105,10 +104,9 @@ static int dec_fwd_chain(recnet_handle* h, const float* enc, const int64_t* targ
     }
    }
     if (pe) hipEventRecord(pe, st);
-    if (hoist_late && h->ss.hoist_pending) hoist_side_work(h, st);
-    h->ss.hoist_fork_recorded = 0;
+    if (hoist_late) hoist_r = hoist_side_work(h, *hoist, st, true);
     h->T_last = T; h->train_last = train;
-    return RECNET_OK;
+    return hoist_r;
   }
   DecCellArgs a;
   a.B = B; a.F = F; a.H = H; a.A = A;
@@ -148,7 +146,7 @@ static int dec_fwd_chain(recnet_handle* h, const float* enc, const int64_t* targ
     }
   }
   h->T_last = T; h->train_last = train;
-  return RECNET_OK;
+  return hoist_r;
 }
 // vocabulary projection + loss for all steps (decoder.py:68-69, train.py:54-68); independent of the reconstructor
 static int dec_fwd_loss(recnet_handle* h, const int64_t* targets, int T, const float* stepw, int train, hipStream_t st,
@@ -178,7 +176,8 @@ static int fwd_decoder(recnet_handle* h, const float* enc, const int64_t* target
 // ---------------------------------------------------------------------------------------------- decoder backward
 // output layer: dHs_out = dlogits . W_o, dW_o, db_o — needs only the decoder forward
 // part: bit 0 = d hiddens (what the BPTT chain needs), bit 1 = the layer's own gradients dW_o, db_o (needed by the optimiser only)
-static int dec_bwd_out(recnet_handle* h, float gscale, hipStream_t st, int part = 3) {
+// early_join: the caller is the whole fused step's side branch (side_after_decoder_fwd, phase 0), whose join the BPTT waits for
+static int dec_bwd_out(recnet_handle* h, float gscale, hipStream_t st, int part = 3, bool early_join = false) {
   RN_RANGE("recnet: output layer backward");
   const int B = h->B, H = h->H, V = h->V, T = h->T_last, TB = T * B;
   if (gscale != 1.0f && (part & 1)) {
@@ -191,7 +190,7 @@ static int dec_bwd_out(recnet_handle* h, float gscale, hipStream_t st, int part 
   // it) — the output layer's own gradients and the attended features that follow run beside the BPTT chain, whose 129 workgroups
   // leave half the chip idle and which nothing else shares in this configuration (EV_SIDE_TAIL covers them for the step's tail).  With a
   // reconstructor the same was measured in round 4 and is off: there the BPTT waits for the reconstructor's d-hiddens product.
-  if ((part & 1) && h->kind == RECNET_REC_NONE && h->ss.join_pending && !h->ss.join_recorded && st == h->s2 && h->ss.side_phase == 0) {
+  if ((part & 1) && h->kind == RECNET_REC_NONE && h->ss.join_pending && !h->ss.join_recorded && st == h->s2 && early_join) {
     hipEventRecord(h->ev[EV_SIDE_JOIN], st); h->ss.join_recorded = 1; h->ss.side_tail_open = 1;
   }
   if (!(part & 2)) return RECNET_OK;
@@ -302,9 +301,8 @@ static int dec_bwd_deferred_rows(recnet_handle* h, const float* enc, const int64
     void* ctx = at_off(h, h->ctx_lp, r0 * h->ldD);
     gemm(h, dG, 1, ldWS, ctx, 1, h->ldD, h->dGd.rnn_weight_ih_l0 + E, E + D, nullptr, GH, D, nrow, 1.f, acc, st);
   }
-  // the rest touches other gradient tensors: on a second stream (with the second split-K workspace) when the caller has one
-  float* const gws_keep = h->ss.gws_cur;
-  if (st2 && st2 != st) { st = st2; h->ss.gws_cur = h->gws2; }
+  // the rest touches other gradient tensors: on a second stream when the caller has one
+  if (st2 && st2 != st) st = st2;
   // dWh_t = sum of its RN_FCH frame-chunk partials (operand of dW_attn and source of d attn_b)
   {
     const size_t n = (size_t)nrow * h->ldA;
@@ -323,7 +321,6 @@ static int dec_bwd_deferred_rows(recnet_handle* h, const float* enc, const int64
     hipMemsetAsync(h->dGd.rnn_weight_hh_l0, 0, (size_t)GH * H * 4, st);
     hipMemsetAsync(h->dGd.attn_W_weight, 0, (size_t)A * H * 4, st);
   }
-  h->ss.gws_cur = gws_keep;
   return RECNET_OK;
 }
 // what needs the whole chain: bias gradients (column sums over all rows), d attn_U (dUv is complete after step 0), d attn_w
@@ -376,19 +373,15 @@ static int dec_bwd_deferred_grouped(recnet_handle* h, const float* enc, const in
     hipMemsetAsync(h->dGd.attn_W_weight, 0, (size_t)A * H * 4, st);
   }
   gg_add(h, g, h->dUv_lp, h->ldA, h->enc_lp, h->ldD, h->dGd.attn_U_weight, D, nullptr, A, D, B * F, 1.f, 0, st);
-  h->gg_site = 4;
-  gg_run(h, g, st);
+  gg_run(h, g, st, stamp_site(4));
   // ---- beside it: embedding branch + column sums.  With three streams the embedding branch (d emb product + two scatter kernels: the
   // longest thing beside the grouped launch) takes the THIRD one, which is idle when the BPTT ends — the second still runs the
   // reconstructor's in-step optimiser for ~20 us then —, and the short column sums queue behind that
   hipStream_t sb = three ? st3 : (two ? st2 : st);
-  float* const gws_keep = h->ss.gws_cur;
-  if (three) h->ss.gws_cur = h->gws3; else if (two) h->ss.gws_cur = h->gws2;
-  if (two) h->ss.gg_slots = h->ncu > 0 ? h->ncu / 2 : 128;      // (beside the grouped launch above)
-  h->ss.gemm_single_group = 1;      // (K slices summed inside the launch: no reduction launch in front of the embedding scatter)
-  gemm(h, dG, 0, ldWS, h->We_w, 1, h->ldE, h->demb, E, nullptr, TB, E, 4 * H, 1.f, 0, sb);
-  h->ss.gemm_single_group = 0;
-  h->ss.gg_slots = 0;
+  GemmOpts eo;
+  eo.sum_in_launch = 1;      // (no reduction launch in front of the embedding scatter)
+  if (two) eo.slots = h->ncu > 0 ? h->ncu / 2 : 128;      // (beside the grouped launch above)
+  gemm(h, dG, 0, ldWS, h->We_w, 1, h->ldE, h->demb, E, nullptr, TB, E, 4 * H, 1.f, 0, sb, eo);
   if (!h->ss.prezeroed) hipMemsetAsync(h->dGd.embedding_weight, 0, (size_t)V * E * 4, sb);
   hipLaunchKernelGGL(embed_bwd_kernel, dim3(TB), dim3(128), 0, sb, h->dGd.embedding_weight, targets, h->demb, B, E, V,
                      h->c.embedding_scale, mkdrop(h, RN_SITE_DEC_EMBED, h->c.embedding_dropout, train), 0,
@@ -401,21 +394,13 @@ static int dec_bwd_deferred_grouped(recnet_handle* h, const float* enc, const in
   colsum_t<float>(h->dwacc, RN_FCH * B, A, A, h->dGd.attn_w_weight, sc, h->ss.prezeroed);
   colsum_at(h, dWh, TB, A, ld_dwh, h->dGd.attn_b, sc, h->ss.prezeroed);
   if (three) join_from(h, EV_TAIL3_JOIN, st, st3);
-  h->ss.gws_cur = gws_keep;
   return RECNET_OK;
 }
 static int dec_bwd_deferred(recnet_handle* h, const float* enc, const int64_t* targets, hipStream_t st, hipStream_t st2 = nullptr, hipStream_t st3 = nullptr) {
   RN_RANGE("recnet: decoder deferred weight gradients");
   if (h->lp) return dec_bwd_deferred_grouped(h, enc, targets, st, st2, st3);
   int r = dec_bwd_deferred_rows(h, enc, targets, 0, h->T_last, 0, st, st2); if (r) return r;
-  if (st2 && st2 != st) {
-    float* const keep = h->ss.gws_cur;
-    h->ss.gws_cur = h->gws2;
-    r = dec_bwd_deferred_tail(h, st2);
-    h->ss.gws_cur = keep;
-    return r;
-  }
-  return dec_bwd_deferred_tail(h, st);
+  return dec_bwd_deferred_tail(h, (st2 && st2 != st) ? st2 : st);
 }
 static int bwd_decoder(recnet_handle* h, const float* enc, const int64_t* targets, const float* dhid, float gscale,
                        hipStream_t st) {

@@ -46,9 +46,11 @@ static void mse_and_dout(recnet_handle* h, float* out, const float* ref, int Sn,
   else hipLaunchKernelGGL(mse_vec_kernel<float>, dim3(nb), dim3(256), 0, st, out, ref, Sn, rows_b, R, bstride, sstride, gcoef, h->msep,
                           lp ? (float*)h->dout_lp : (float*)nullptr, h->c.lambda_recon);
 }
-static int fwd_rec_global(recnet_handle* h, const float* enc, int T, int train, hipStream_t st) {
+// norms_hoisted: the parameter norms and the gate bias come from hoist_side_work.  side != nullptr: the fused step's side work
+// is forked from here, behind the batched input product.
+static int fwd_rec_global(recnet_handle* h, const float* enc, int T, int train, hipStream_t st, bool norms_hoisted, const SideWork* side) {
   const int B = h->B, F = h->F, D = h->D, H = h->H, R = h->R;
-  if (!h->ss.norms_hoisted) {
+  if (!norms_hoisted) {
     param_norms(h, 1, h->scal + RN_SCAL_REC_REG, st);
     gate_bias(h->rP.rnn_bias_ih_l0, h->rP.rnn_bias_hh_l0, h->bsum_r, R, h->rgru, st);
   }
@@ -69,9 +71,10 @@ static int fwd_rec_global(recnet_handle* h, const float* enc, int T, int train, 
   // it — so that the chain's workgroups, which need whole CUs, are dispatched before the projection's workgroups start filling
   // every CU partly (C2: 1.926 -> 1.913 ms)
   // (one-graph step only: in the data-parallel three-graph form it costs 0.17 ms — 2.31 against 2.14 ms at one rank)
-  const bool side_late = h->ss.in_fused && h->ss.side_pending && h->overlap && h->s2 && h->persist_rec;
-  if (side_late) { hipEventRecord(h->ev[EV_SIDE_FORK], st); h->ss.side_fork_recorded = 1; }
-  else if (h->ss.side_pending) side_after_decoder_fwd(h, st);       // see fwd_bwd_impl
+  const bool side_late = h->ss.in_fused && side && h->overlap && h->s2 && h->persist_rec;
+  int side_r = RECNET_OK;
+  if (side_late) hipEventRecord(h->ev[EV_SIDE_FORK], st);
+  else if (side) side_r = side_after_decoder_fwd(h, *side, st, false);       // see fwd_bwd_impl
   if (h->ss.rec_wait_pending) { hipStreamWaitEvent(st, h->ev[EV_PENDING_DONE], 0); h->ss.rec_wait_pending = 0; }      // W_hh's pending update (mode 2)
   // batches above RC_PAN_ROWS captions run the chain once per row group (h->bgrp rows each, csrc/api.hip): a group is an
   // independent batch for the chain — same weights, its own rows of every [T][B][.] tensor (row stride Bs = B)
@@ -126,7 +129,7 @@ static int fwd_rec_global(recnet_handle* h, const float* enc, int T, int train, 
       else rc_launch(h, RN_SITE_REC_CHAIN_FWD, (rec_chain_kernel<16, 2, 7, 2>), g, sm, st, a);
     }
   }
-  if (side_late && h->ss.side_pending) side_after_decoder_fwd(h, st);
+  if (side_late) side_r = side_after_decoder_fwd(h, *side, st, true);
   for (int t = 0; t < T && !h->persist_rec; ++t) {
     int S = 0;
     if (t > 0) S = gemm_slabs(h, RN_TAG_REC_FWD, at_off(h, h->Hr_lp, (size_t)(t - 1) * B * h->ldR), h->ldR, h->Whh_w, 0, h->ldR, B, 4 * R, R, st);
@@ -142,7 +145,7 @@ static int fwd_rec_global(recnet_handle* h, const float* enc, int T, int train, 
     h->ss.encmean_hoisted = 0;
     h->dout_scale = h->c.lambda_recon; h->ss.dout_ready = 1;
     h->mse_nb = (R / 16) * 2; h->mse_scale = (float)(1.0 / (cnt * T));
-    return RECNET_OK;
+    return side_r;
   }
   gemm(h, h->hrmean_lp, 0, h->ldR, h->Wor_w, 0, h->ldR, h->outm, R, h->rP.out_bias, B, R, R, 1.f, 0, st);
   if (!h->ss.encmean_hoisted) hipLaunchKernelGGL(mean_over_f_kernel, dim3(ew_blocks((size_t)B * D)), dim3(256), 0, st, enc, B, F, D, h->encmean);
@@ -150,7 +153,7 @@ static int fwd_rec_global(recnet_handle* h, const float* enc, int T, int train, 
   const int nb = 256;
   mse_and_dout(h, h->outm, h->encmean, 1, B, R, (size_t)R, (size_t)0, (float)(2.0 / (cnt * T)), nb, st);
   h->mse_nb = nb; h->mse_scale = (float)(1.0 / (cnt * T));
-  return RECNET_OK;
+  return side_r;
 }
 
 static void lstm_bwd(recnet_handle* h, int Hd, int S, int slab_ld, int slab_col0, const float* dh_direct, int dhd_ld,
@@ -176,25 +179,22 @@ static bool rec_pending_hh_fused(recnet_handle* h, hipStream_t s, int step_off, 
 // (the gate gradients), not the batched d hiddens products behind it: forked to the side stream right after the chain launch
 // they get a head start of ~130 us over forking them in front of the decoder's BPTT, which is what the side stream was
 // still busy with when the BPTT ended.  The join the BPTT needs (vocabulary-projection side work) is recorded first.
-static int rec_deferred_fork(recnet_handle* h, hipStream_t st) {
-  if (!h->ss.deferred_early) return RECNET_OK;
-  h->ss.deferred_early = 0;
+// Called by the backward chains for a caller that asked for it (bwd_rec_chain: fork_deferred); opt_flags >= 0: the optimiser step too.
+static int rec_deferred_fork(recnet_handle* h, hipStream_t st, int opt_flags) {
   hipStream_t sd = h->s2;
   if (h->ss.join_pending) { hipEventRecord(h->ev[EV_SIDE_JOIN], sd); h->ss.join_recorded = 1; }
   fork_to(h, EV_REC_DW_FORK, st, sd);
-  h->ss.gws_cur = h->gws2;
-  int r = bwd_rec_deferred(h, sd, 0);
-  h->ss.gws_cur = h->gws;
-  if (r) return r;
+  int r = bwd_rec_deferred(h, sd, 0); if (r) return r;
   h->ss.deferred_done = 1;
-  if (h->ss.deferred_early_flags >= 0) {
-    r = optimizer_step(h, h->ss.deferred_early_flags, sd, 1); if (r) return r;
+  if (opt_flags >= 0) {
+    r = optimizer_step(h, opt_flags, sd, 1); if (r) return r;
     h->ss.early_opt_done = 1;
   }
   return RECNET_OK;
 }
 
-static int bwd_rec_global(recnet_handle* h, float gscale, float* dhid_out, hipStream_t st) {
+// fork_deferred: the deferred weight gradients are forked to the side stream right behind the chain (rec_deferred_fork)
+static int bwd_rec_global(recnet_handle* h, float gscale, float* dhid_out, hipStream_t st, bool fork_deferred, int opt_flags) {
   const int B = h->B, H = h->H, R = h->R, T = h->T_last, TB = T * B, ld4R = h->ld4R;
   const int train = h->train_last;
   // dout (operand copy) = gscale * d loss / d out_mean
@@ -237,16 +237,16 @@ static int bwd_rec_global(recnet_handle* h, float gscale, float* dhid_out, hipSt
              t > 0 ? (h->rgru ? h->Hr : h->Cr) + (size_t)(t - 1) * B * R : nullptr, h->dcr_carry, t == T - 1, at_off(h, h->dGr, (size_t)t * B * ld4R), ld4R, st);
     if (t > 0) S = gemm_slabs(h, RN_TAG_REC_BWD, at_off(h, h->dGr, (size_t)t * B * ld4R), ld4R, h->Whh_w, 1, h->ldR, B, R, 4 * R, st);
   }
-  { const int rr = rec_deferred_fork(h, st); if (rr) return rr; }
+  if (fork_deferred) { const int rr = rec_deferred_fork(h, st, opt_flags); if (rr) return rr; }
   // input-side gradients, batched: ONE product over both halves of W_ih (the h_t half and the pooled-states half), then one
   // kernel that folds the pooled half through its dropout masks and the 1 / T^2 pooling back onto every step
   // (Leaving the K slices of this product in their slabs for global_dhid_kernel to add up — one launch less in front of the
   // decoder's BPTT — was measured in round 4: no change, 1.699 against 1.683 ms within the box's spread; not kept.)
   // (a group of one: the K slices are summed inside the launch by the last-arriving slice — the separate reduction kernel was 17 us of the
   //  gap in front of the decoder's BPTT, where the side stream's weight-gradient products still run)
-  h->ss.gemm_single_group = 1;
-  gemm(h, h->dGr, 0, ld4R, h->Wih_f, 1, h->ld2H, h->dmpd, 2 * H, nullptr, TB, 2 * H, 4 * R, 1.f, 0, st);
-  h->ss.gemm_single_group = 0;
+  GemmOpts go;
+  go.sum_in_launch = 1;
+  gemm(h, h->dGr, 0, ld4R, h->Wih_f, 1, h->ld2H, h->dmpd, 2 * H, nullptr, TB, 2 * H, 4 * R, 1.f, 0, st, go);
   hipLaunchKernelGGL(global_dhid_kernel, dim3((unsigned)(((size_t)B * H + 63) / 64)), dim3(256), 0, st, h->dmpd, dhid_out, T, B, H,
                      (float)h->cml / ((float)T * (float)T), mkdrop(h, RN_SITE_REC_INPUT, h->c.reconstructor_decoder_dropout, train));
   return RECNET_OK;
@@ -272,23 +272,22 @@ static int bwd_rec_global_deferred(recnet_handle* h, hipStream_t st, int which =
   } else {
     hipMemsetAsync(h->rG.rnn_weight_hh_l0, 0, (size_t)GR * R * 4, st);
   }
-  if (!(which & 2)) { h->gg_site = 3; gg_run(h, g, st); return RECNET_OK; }
+  if (!(which & 2)) { gg_run(h, g, st, stamp_site(3)); return RECNET_OK; }
   gg_add(h, g, h->dGr, ld4R, h->Xcat_g, h->ld2H, h->rG.rnn_weight_ih_l0, 2 * H, nullptr, GR, 2 * H, TB, 1.f, 0, st);   // d W_ih = dG^T . [h_t ; drop(mp)]
   gg_add(h, g, h->dout_lp, h->ldR, h->hrmean_lp, h->ldR, h->rG.out_weight, R, nullptr, R, R, B, 1.f, 0, st);            // d W_o = dout^T . mean_t hr_t
   // the column sums first: in the fused step this stream runs beside the decoder's BPTT chain, whose whole-CU workgroups must
   // be resident before the grouped launch's ~1000 workgroups start filling every CU (they were 480 instead of 325 us otherwise)
   colsum_at(h, h->dout_lp, B, R, h->ldR, h->rG.out_bias, st, h->ss.prezeroed);
   gate_bias_grad(h, h->dGr, TB, R, ld4R, h->rG.rnn_bias_ih_l0, h->rG.rnn_bias_hh_l0, h->rgru, st);
-  h->gg_site = 2;
-  gg_run(h, g, st);
+  gg_run(h, g, st, stamp_site(2));
   return RECNET_OK;
 }
 
 // ---------------------------------------------------------------------------------------------- local reconstructor
-static int fwd_rec_local(recnet_handle* h, const float* enc, int T, int train, hipStream_t st) {
+static int fwd_rec_local(recnet_handle* h, const float* enc, int T, int train, hipStream_t st, bool norms_hoisted) {
   const int B = h->B, F = h->F, D = h->D, H = h->H, R = h->R, RA = h->RA, ldHR = h->ldHR;
   const size_t esz = h->lp ? 2 : 4;
-  if (!h->ss.norms_hoisted) {
+  if (!norms_hoisted) {
     param_norms(h, 1, h->scal + RN_SCAL_REC_REG, st);
     gate_bias(h->rP.rnn_bias_ih_l0, h->rP.rnn_bias_hh_l0, h->bsum_r, R, h->rgru, st);
   }
@@ -377,7 +376,7 @@ static int fwd_rec_local(recnet_handle* h, const float* enc, int T, int train, h
   return RECNET_OK;
 }
 
-static int bwd_rec_local(recnet_handle* h, float gscale, float* dhid_out, hipStream_t st) {
+static int bwd_rec_local(recnet_handle* h, float gscale, float* dhid_out, hipStream_t st, bool fork_deferred, int opt_flags) {
   const int B = h->B, F = h->F, H = h->H, R = h->R, RA = h->RA, T = h->T_last, TB = T * B, FB = F * B;
   const int train = h->train_last, ld4R = h->ld4R, ldHR = h->ldHR;
   // (the output layer's own gradients do not feed the chain: bwd_rec_local_deferred)
@@ -497,7 +496,7 @@ static int bwd_rec_local(recnet_handle* h, float gscale, float* dhid_out, hipStr
         S2 = gemm_slabs(h, RN_TAG_REC_ATT_BWD, at_off(h, h->dWhr, (size_t)s * B * h->ldRA4), h->ldRA4, h->Wr4_w, 1, h->ldR, B, R, RN_TCH * RA, st, h->slab2);
     }
   }
-  { const int rr = rec_deferred_fork(h, st); if (rr) return rr; }
+  if (fork_deferred) { const int rr = rec_deferred_fork(h, st, opt_flags); if (rr) return rr; }
   gemm(h, h->dUd_lp, 0, h->ldRA, h->Ur_w, 1, h->ldH, dhid_out, H, nullptr, TB, H, RA, 1.f, 1, st);
   return RECNET_OK;
 }
@@ -521,8 +520,7 @@ static int bwd_rec_local_deferred(recnet_handle* h, hipStream_t st, int part = 0
         gg_add(h, g, at_off(h, (void*)dG1, (size_t)3 * R), ld4R, h->Hr_lp, h->ldR, h->rG.rnn_weight_hh_l0 + (size_t)2 * R * R, R, nullptr, R, R, nr, 1.f, 0, st);
       }
     } else if (hh) hipMemsetAsync(h->rG.rnn_weight_hh_l0, 0, (size_t)GR * R * 4, st);
-    h->gg_site = 3;
-    gg_run(h, g, st);
+    gg_run(h, g, st, stamp_site(3));
     return RECNET_OK;
   }
   gg_add(h, g, h->dout_lp, h->ldR, h->Hr_lp, h->ldR, h->rG.out_weight, R, nullptr, R, R, FB, 1.f, 0, st);              // d W_o = dout^T . hr
@@ -550,8 +548,7 @@ static int bwd_rec_local_deferred(recnet_handle* h, hipStream_t st, int part = 0
   colsum_at(h, h->dWhrs, FB, RA, h->ldRA, h->rG.attn_b, st);
   colsum_t<float>(h->dwacc_r, RN_TCH * B, RA, RA, h->rG.attn_w_weight, st);
   gate_bias_grad(h, h->dGr, FB, R, ld4R, h->rG.rnn_bias_ih_l0, h->rG.rnn_bias_hh_l0, h->rgru, st);
-  h->gg_site = 2;
-  gg_run(h, g, st);      // (behind the column sums: see bwd_rec_global_deferred)
+  gg_run(h, g, st, stamp_site(2));      // (behind the column sums: see bwd_rec_global_deferred)
   return RECNET_OK;
 }
 
@@ -560,23 +557,25 @@ static void rec_loss_scalars(recnet_handle* h, hipStream_t st) {
   if (h->ss.rec_norm_late) { hipStreamWaitEvent(st, h->ev[EV_WHH_NORM], 0); h->ss.rec_norm_late = 0; }
   hipLaunchKernelGGL(rec_loss_finalize_kernel, dim3(1), dim3(256), 0, st, h->msep, h->mse_nb, h->mse_scale, h->scal,
                      h->c.reconstructor_lambda_reg, h->c.lambda_recon);
-  h->ss.rec_loss_late = 0;
 }
-static int fwd_rec(recnet_handle* h, const float* enc, int T, int train, hipStream_t st) {
+// loss_late: the caller launches rec_loss_scalars itself (fused step: on the side stream behind the BPTT's fork, not between the
+// two chains).  norms_hoisted, side: see fwd_rec_global (the local form takes no side work).
+static int fwd_rec(recnet_handle* h, const float* enc, int T, int train, hipStream_t st, bool norms_hoisted = false, bool loss_late = false,
+                   const SideWork* side = nullptr) {
   RN_RANGE("recnet: reconstructor forward (train.py:78-131)");
-  int r = h->kind == RECNET_REC_GLOBAL ? fwd_rec_global(h, enc, T, train, st) : fwd_rec_local(h, enc, T, train, st);
+  int r = h->kind == RECNET_REC_GLOBAL ? fwd_rec_global(h, enc, T, train, st, norms_hoisted, side) : fwd_rec_local(h, enc, T, train, st, norms_hoisted);
   if (r) return r;
   // rec_loss = mse + lambda_reg * reg ; total = dec_loss + lambda_recon * rec_loss
   // (launching it on the fused step's side stream behind the BPTT's fork, like the total-loss scalar, was measured: no change)
-  if (h->ss.rec_loss_defer) h->ss.rec_loss_late = 1;      // fused step: launched on the side stream behind the BPTT's fork (rec_loss_scalars), not between the two chains
-  else rec_loss_scalars(h, st);
+  if (!loss_late) rec_loss_scalars(h, st);
   h->T_last = T; h->train_last = train; h->fwd_rec_done = 1;
   return RECNET_OK;
 }
 // chain part (ends with d loss / d hiddens, which the decoder backward needs) and the deferred weight gradients
-static int bwd_rec_chain(recnet_handle* h, float gscale, float* dhid_out, hipStream_t st) {
+static int bwd_rec_chain(recnet_handle* h, float gscale, float* dhid_out, hipStream_t st, bool fork_deferred = false, int opt_flags = -1) {
   RN_RANGE("recnet: reconstructor backward chain");
-  return h->kind == RECNET_REC_GLOBAL ? bwd_rec_global(h, gscale, dhid_out, st) : bwd_rec_local(h, gscale, dhid_out, st);
+  return h->kind == RECNET_REC_GLOBAL ? bwd_rec_global(h, gscale, dhid_out, st, fork_deferred, opt_flags)
+                                      : bwd_rec_local(h, gscale, dhid_out, st, fork_deferred, opt_flags);
 }
 static int bwd_rec_deferred(recnet_handle* h, hipStream_t st, int part, int which) {
   RN_RANGE("recnet: reconstructor deferred weight gradients");
@@ -588,13 +587,11 @@ static int bwd_rec_deferred(recnet_handle* h, hipStream_t st, int part, int whic
 // Adam kernel reads the device's pending word (RN_CTRL_PENDING) and does nothing when no step left one; the products then ran on
 // stale operands into gradient buffers nobody reads.  step_off = -1 when the step counter was already advanced.
 static int rec_pending_update(recnet_handle* h, hipStream_t s, int step_off, int flags) {
-  float* const keep = h->ss.gws_cur;
-  if (s == h->s3) h->ss.gws_cur = h->gws3;
   const int pz = h->ss.prezeroed; h->ss.prezeroed = 0;          // the column sums' atomic targets: colsum_at zeroes them itself
   const bool split = h->defer_rec == 2;      // only the recurrent weights were left pending (mode 2)
   if (split && rec_pending_hh_fused(h, s, step_off, flags)) {
     // product + Adam update + both operand images of W_hh in one launch (W_o^T was refreshed inside the step that updated W_o)
-    h->ss.prezeroed = pz; h->ss.gws_cur = keep;
+    h->ss.prezeroed = pz;
     hipLaunchKernelGGL(set_u32_kernel, dim3(1), dim3(1), 0, s, h->ctrl + RN_CTRL_PENDING, 0u);
     return RECNET_OK;
   }
@@ -605,7 +602,6 @@ static int rec_pending_update(recnet_handle* h, hipStream_t s, int step_off, int
   const int fused = h->ss.in_fused; h->ss.in_fused = 0;
   if (!r) r = optimizer_step(h, flags, s, 1, 1, step_off, split ? ~(1u << RN_REC_T_WHH(h)) : 0u);
   h->ss.in_fused = fused;
-  h->ss.gws_cur = keep;
   if (r) return r;
   hipLaunchKernelGGL(set_u32_kernel, dim3(1), dim3(1), 0, s, h->ctrl + RN_CTRL_PENDING, 0u);
   return RECNET_OK;
@@ -676,8 +672,7 @@ static bool rec_pending_hh_fused(recnet_handle* h, hipStream_t s, int step_off, 
   };
   if (!h->rgru) add(0, 4 * R, 0, dG1);
   else { add(0, 2 * R, 0, dG1); add((size_t)2 * R, R, (size_t)3 * R, at_off(h, (void*)dG1, (size_t)3 * R)); }      // GRU: (r, z) in place, n -> packed block 3
-  h->gg_site = 3;
-  if (!gg_run(h, g, s, &sh)) return false;
+  if (!gg_run(h, g, s, stamp_site(3), &sh)) return false;
   if (local) { refresh_image(h, WI_WST, s); refresh_image(h, WI_WSTT, s); }      // the streamed-fragment images of the R > 2048 chains follow the two images
   return true;
 }

@@ -36,32 +36,20 @@ enum RnEvent {
 };
 
 // The default member initialisers are the state between two steps (sched_reset, api.hip).  What persists across steps by design —
-// maybe_pending, images_maybe_stale, defer_rec, defer_flags, split_ok, fwd_*_done, T_last, free_fwd, gg_site — stays in the handle.
+// maybe_pending, images_maybe_stale, defer_rec, defer_flags, split_ok, fwd_*_done, T_last, free_fwd — stays in the handle.  What one
+// function hands to the next as an argument or a result is one: the GEMM options and lane (host_common.inc: GemmOpts, gemm_lane), the
+// hoisted and side work of the fused step (HoistWork, SideWork), the parameters of dec_fwd_chain / fwd_rec / bwd_rec_chain / dec_bwd_out.
 struct StepSched {
-  // ---- within one entry-point call: written and consumed while one C-ABI call enqueues
-  // side_after_decoder_fwd's arguments.  Set: fwd_bwd_impl behind the decoder's forward chain.  Read: side_after_decoder_fwd, called
-  // from there or from inside fwd_rec_global (which tests side_pending); side_phase also by dec_bwd_out.
-  int side_pending = 0, side_T = 0, side_phase = 0, side_err = 0;
-  const int64_t* side_targets = nullptr; const float* side_stepw = nullptr; const float* side_enc = nullptr;
-  // hoist_side_work's arguments.  Set: fwd_bwd_impl in front of dec_fwd_chain.  Read: dec_fwd_chain (where to fork it), hoist_side_work.
-  int hoist_pending = 0, hoist_par = 0; const float* hoist_enc = nullptr;
-  int hoist_fork_recorded = 0;   // dec_fwd_chain recorded the fork events of hoist_side_work itself, in front of the chain launch.  Set / cleared: dec_fwd_chain.  Read: hoist_side_work
-  int side_fork_recorded = 0;    // ... and fwd_rec_global that of side_after_decoder_fwd (EV_SIDE_FORK).  Set: fwd_rec_global.  Read / cleared: side_after_decoder_fwd
-  int norms_hoisted = 0;         // parameter norms and the reconstructor's gate bias come from hoist_side_work.  Set / cleared: fwd_bwd_impl.  Read: dec_fwd_chain, fwd_rec_*
-  int encmean_hoisted = 0;       // ... and the frame mean of the features.  Set: hoist_side_work, fwd_rec_global.  Read / cleared: fwd_rec_global
+  // ---- within one entry-point call: ambient flags, written and consumed while one C-ABI call enqueues.  Each is either set by a callee
+  // for a later sibling of its caller, or describes the whole call and is read at several depths below the function that sets it
+  int encmean_hoisted = 0;       // the frame mean of the features is formed already.  Set: hoist_side_work, fwd_rec_global.  Read / cleared: fwd_rec_global
   int join_pending = 0;          // the side branch of side_after_decoder_fwd is not joined yet.  Set: side_after_decoder_fwd.  Read / cleared: fwd_bwd_impl; read: rec_deferred_fork, dec_bwd_out
   int join_recorded = 0;         // EV_SIDE_JOIN was recorded early.  Set: rec_deferred_fork, dec_bwd_out.  Read / cleared: fwd_bwd_impl
   int side_tail_open = 0;        // decoder-only: dec_bwd_out recorded the BPTT's join in front of the rest of the side branch (EV_SIDE_TAIL covers the rest).  Set: dec_bwd_out.  Read: side_after_decoder_fwd; cleared: dec_bwd_deferred
-  int total_late = 0;            // the total-loss scalar is formed on the side stream behind the BPTT's fork.  Set / read / cleared: fwd_bwd_impl
-  int rec_loss_defer = 0;        // fused step: the reconstructor's loss scalars are formed beside the BPTT (rec_loss_scalars) instead of between its two chains.  Set / cleared: fwd_bwd_impl.  Read: fwd_rec
-  int rec_loss_late = 0;         // ... and they are still to be launched.  Set: fwd_rec.  Read: fwd_bwd_impl; cleared: rec_loss_scalars
   int rec_norm_late = 0;         // mode 2: the norm of the pending-updated W_hh is joined in front of the loss scalars (EV_WHH_NORM), not in front of the chain.  Set: hoist_side_work.  Read / cleared: rec_loss_scalars
   int rec_wait_pending = 0;      // the reconstructor's recurrent chain waits for EV_PENDING_DONE (W_hh's pending update in mode 2, the deferred image refresh).  Set: fwd_bwd_impl.  Read / cleared: fwd_rec_global, fwd_rec_local
-  // rec_deferred_fork (host_reconstructor.inc).  Set: fwd_bwd_impl around bwd_rec_chain.  Read: rec_deferred_fork.  deferred_done: set there
-  // and by the deferring branch of fwd_bwd_impl, read / cleared by fwd_bwd_impl.
-  int deferred_early = 0, deferred_early_flags = -1, deferred_done = 0;
+  int deferred_done = 0;         // the reconstructor's deferred gradients are enqueued already.  Set: rec_deferred_fork, the deferring branch of fwd_bwd_impl.  Read / cleared: fwd_bwd_impl
   int defer_now = 0;             // this step leaves its reconstructor update pending and completes the one before it on s3.  Set: fwd_bwd_impl.  Read: hoist_side_work; cleared: fwd_bwd
-  int defer_err = 0;             // ... and what rec_pending_update returned there.  Set: hoist_side_work.  Read / cleared: fwd_bwd_impl
   // Deferred refresh of the reconstructor's DERIVED weight images (opt-in with the deferred-update modes, applies where the split update
   // does not — 28 x 3584, row groups): the fused step skips the transposes / fragment packs behind its reconstructor Adam step (183 us at
   // the end of the step at 28 x 3584) and runs them at the start of the NEXT fused step, on the third stream beside the decoder's forward
@@ -70,9 +58,6 @@ struct StepSched {
   int img_defer_now = 0;         // Set: fwd_bwd_impl.  Read: hoist_side_work, rec_images_after_update; cleared: fused_step
   int s3_late = 0;               // the third stream's reconstructor update is joined behind the decoder's optimiser step.  Set: fwd_bwd_impl.  Read / cleared: fused_step, step_fail_cleanup
   int in_fused = 0;              // the call is the one-graph fused step (its first kernel writes the step-start stamp).  Set / cleared: fused_step.  Read: wait_chain, fwd_rec_global, fwd_bwd_impl
-  int gg_slots = 0;              // workgroup slots the next grouped launches can expect (0 = whole chip): see host_common.inc.  Set / cleared around their products: side_after_decoder_fwd, dec_bwd_deferred.  Read: gg_run, gemm
-  int gemm_single_group = 0;     // set around a single product whose K slices are to be summed inside its launch (host_decoder.inc: the embedding branch).  Read: gemm
-  float* gws_cur = nullptr;      // the split-K slabs gemm() uses now: h->gws between steps (sched_reset), gws2 / gws3 around work enqueued on s2 / s3 by whoever enqueues it.  Read: gemm, gg_run, gg_counters
 
   // ---- carried between the calls of one step: part 1 to part 2, forward to backward, a chain to its consumer
   int dp_overlap = 0;            // part 1 of the data-parallel step leaves the side stream's weight-gradient products unjoined.  Set: recnet_set_dp_overlap.  Read: fwd_bwd_impl (part 1)
