@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define RECNET_ABI_VERSION 9
+#define RECNET_ABI_VERSION 10
 #define RECNET_ATTN_NONE 0
 #define RECNET_ATTN_SOFTMAX 1
 #define RECNET_OK 0
@@ -194,6 +194,25 @@ int recnet_sample_rows(recnet_handle* h, const float* logits, int32_t rows, int3
  * rows [0, n_steps) are meaningful, later rows hold what the fixed-length loop went on to draw. */
 int recnet_sample_search(recnet_handle* h, const float* enc, float temperature, int32_t top_k, uint32_t seed,
                          int64_t* tokens_out, float* logprobs_out, int32_t* n_steps_out, void* stream);
+
+/* ---- scoring: how probable is a GIVEN token / caption under the model (the reference has no counterpart).
+ * recnet_logprob_rows: logprobs_out[r] = s_k - logsumexp_v s_v with s_v = logits[r, v] / temperature and k = tokens[r] (the maximum
+ * is subtracted before the exponentials); a token outside [0, V) gives -inf and is never used as an index.  logits [rows, V]
+ * contiguous, read only; tokens [rows] int64; temperature > 0 and finite.  The handle supplies the device only, as for
+ * recnet_sample_rows. */
+int recnet_logprob_rows(recnet_handle* h, const float* logits, const int64_t* tokens, int32_t rows, int32_t V, float temperature,
+                        float* logprobs_out, void* stream);
+/* recnet_score_captions: the teacher-forced loop of train.py:25,45 in eval mode (no dropout) over tokens [T][B] int64, time-major,
+ * 1 <= T <= caption_max_len + 1: step 0 is fed <SOS> and the zero state, step t > 0 is fed tokens[t - 1].
+ * logprobs_out [T][B] = log-probability of tokens[t][b] under softmax(logits_t / temperature), every row, unmasked;
+ * caption_logprob_out [B] = sum of rows 0 .. e_b in ascending t, e_b = the first t with tokens[t][b] == <EOS> (2) or T - 1 when
+ * there is none (later rows never enter the sum); length_out [B] int32 = e_b + 1.  enc == NULL reuses the invariants of the previous
+ * call / of recnet_decoder_prepare, like recnet_decoder_step.  PRECONDITION: every token lies in [0, V) (the embedding gather
+ * indexes by them; the Python layer checks).  One stream-ordered sequence, no host synchronisation.  The call overwrites the saved
+ * state of a decoder forward (hidden states, gate activations, logits): a following recnet_backward_decoder /
+ * recnet_forward_reconstructor(hiddens = NULL) is refused with their state error until the next forward. */
+int recnet_score_captions(recnet_handle* h, const float* enc, const int64_t* tokens, int32_t T, float temperature,
+                          float* logprobs_out, float* caption_logprob_out, int32_t* length_out, void* stream);
 
 /* ---- forward_decoder, train.py:17-75 (teacher forcing, train.py:38,45).
  * enc [B,F,D]; targets [caption_max_len+1, B] int64 (time-major, <PAD>=0, <EOS>=2);

@@ -9,6 +9,7 @@ Host-side mirror of the reference interface for the hot path:
   train.py:248-273 (the step body)           -> api.TrainStep (single stream, hipGraph-capturable)
   eval.py greedy_search / beam_search        -> search.* (device-side loops)
   (no counterpart) temperature / top-k draws -> search.sample_search, search.sequence_logprob
+  (no counterpart) scoring given captions    -> search.score_captions, search.best_of_n, loop.perplexity
 All compute goes through csrc/librecnet_hip.so (C ABI: include/recnet_hip.h).
 """
 from .config import TrainConfig, make_config  # noqa: F401
@@ -17,6 +18,7 @@ from .api import (build_decoder, build_reconstructor, forward_decoder, forward_g
                   forward_local_reconstructor, clip_grad_norm_, TrainStep, GraphedStep, FusedAdam, decode_len,
                   step_weights)
 from .dp import DataParallelTrainStep, shard_bounds  # noqa: F401
-from .search import greedy_search, beam_search, sample_search, sequence_logprob  # noqa: F401
-from .loop import Trainer, evaluate  # noqa: F401
+from .search import (greedy_search, beam_search, sample_search, sequence_logprob, score_captions, best_of_n,  # noqa: F401
+                     pick_best_of_n)
+from .loop import Trainer, evaluate, perplexity  # noqa: F401
 from .checkpoint import save_checkpoint, load_checkpoint, read_checkpoint  # noqa: F401

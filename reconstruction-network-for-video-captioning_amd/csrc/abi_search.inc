@@ -1,4 +1,5 @@
-// C ABI: the decoder's per-step API and the device-side inference search (eval.py:19-120), greedy / beam / sampling.
+// C ABI: the decoder's per-step API, the device-side inference search (eval.py:19-120), greedy / beam / sampling, and the scoring of
+// given captions.
 // Part of api.hip (one translation unit; see the include list there).
 // One decode step on already prepared loop invariants (Uv, P, bias sum): embedding, input projection,
 // h . [W_hh ; attn_W]^T, cell kernel, vocabulary projection.  Rows [0,B) / [B,2B) of Hs_lp are scratch.
@@ -189,6 +190,50 @@ int recnet_sample_search(recnet_handle* h, const float* enc, float temperature, 
     tok = out_t; cur ^= 1;
   }
   hipLaunchKernelGGL(search_finish_kernel, dim3(1), dim3(1), 0, st, n_steps_out, Tm);
+  LAUNCH_OK();
+  return RECNET_OK;
+}
+
+// ---- scoring given captions (the reference has no counterpart; the loop is train.py:25,45 in eval mode)
+static void launch_logprob_rows(const float* logits, const int64_t* tokens, int rows, int V, float temperature, float* logprobs,
+                                hipStream_t st) {
+  LogprobArgs a;
+  a.x = logits; a.V = V; a.temp = temperature; a.tok = tokens; a.lp = logprobs;
+  if (V <= LP_NV * 256) hipLaunchKernelGGL((logprob_rows_kernel<true>), dim3(rows), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((logprob_rows_kernel<false>), dim3(rows), dim3(256), 0, st, a);
+}
+
+int recnet_logprob_rows(recnet_handle* h, const float* logits, const int64_t* tokens, int32_t rows, int32_t V, float temperature,
+                        float* logprobs_out, void* stream) {
+  REQUIRE_WS(h);
+  if (!logits || !tokens || !logprobs_out) return fail(RECNET_EINVAL, "null argument");
+  if (rows < 1 || V < 1) return fail(RECNET_EINVAL, "rows and V must be positive");
+  int r = check_sample(temperature, 0, V); if (r) return r;
+  launch_logprob_rows(logits, tokens, rows, V, temperature, logprobs_out, (hipStream_t)stream);
+  LAUNCH_OK();
+  return RECNET_OK;
+}
+
+// The teacher-forced forward in eval mode (the persistent chain where the handle runs it, the per-step kernels otherwise), the
+// batched vocabulary product into h->logits, the row kernel, the per-caption sums.  Hs / acts / logits no longer hold a training
+// forward afterwards: a backward call is refused until the next forward.
+int recnet_score_captions(recnet_handle* h, const float* enc, const int64_t* tokens, int32_t T, float temperature,
+                          float* logprobs_out, float* caption_logprob_out, int32_t* length_out, void* stream) {
+  REQUIRE_WS(h);
+  FLUSH_PENDING(h, stream);      // (a pending reconstructor update reads the operands of the step it belongs to: Hs_lp is overwritten here)
+  if (!h->dec_bound) return fail(RECNET_ESTATE, "decoder not bound");
+  if (check_T(h, T)) return fail(RECNET_EINVAL, "T out of range");
+  if (!tokens || !logprobs_out || !caption_logprob_out || !length_out) return fail(RECNET_EINVAL, "null argument");
+  int r = check_sample(temperature, 0, h->V); if (r) return r;
+  hipStream_t st = (hipStream_t)stream;
+  const int B = h->B, H = h->H, V = h->V;
+  // step 0 is fed <SOS>, step t > 0 tokens[t - 1] (embed_fwd_kernel's teacher-forcing rule); enc == NULL: the invariants of the
+  // previous call / of recnet_decoder_prepare
+  r = dec_fwd_chain(h, enc, tokens, T, 0, st, nullptr, nullptr, DFC_NO_REG_NORM | (enc ? 0 : DFC_REUSE_INVARIANTS)); if (r) return r;
+  h->fwd_dec_done = h->fwd_rec_done = 0; h->ss.mp_done = 0; h->ss.xcat_done = 0;
+  gemm(h, h->Hs_lp, 0, h->ldH, h->Wo_w, 0, h->ldH, h->logits, V, h->dP.out_bias, T * B, V, H, 1.f, 0, st);
+  launch_logprob_rows(h->logits, tokens, T * B, V, temperature, logprobs_out, st);
+  hipLaunchKernelGGL(caption_logprob_kernel, dim3(cdiv(B, 256)), dim3(256), 0, st, logprobs_out, tokens, T, B, caption_logprob_out, length_out);
   LAUNCH_OK();
   return RECNET_OK;
 }

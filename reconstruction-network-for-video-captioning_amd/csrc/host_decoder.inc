@@ -6,12 +6,15 @@
 // (dropped-out) logits, written to free_tokens [T][B]; the per-step embedding / input projection / vocabulary projection
 // then sit inside the chain.  Forward only.
 // hoist != nullptr (fused step): the step's hoisted work is forked from here and forms the parameter norms (hoist_side_work).
+// flags (recnet_score_captions): DFC_REUSE_INVARIANTS — Uv / P / the gate bias are what the previous call left (enc is not read);
+// DFC_NO_REG_NORM — the regulariser's parameter norms are not formed (a pass that has no loss).
+enum { DFC_REUSE_INVARIANTS = 1, DFC_NO_REG_NORM = 2 };
 static int dec_fwd_chain(recnet_handle* h, const float* enc, const int64_t* targets, int T, int train, hipStream_t st,
-                         int64_t* free_tokens = nullptr, const HoistWork* hoist = nullptr) {
+                         int64_t* free_tokens = nullptr, const HoistWork* hoist = nullptr, unsigned flags = 0) {
   RN_RANGE("recnet: decoder forward chain (decoder.py:45-70 x T)");
   const int B = h->B, F = h->F, E = h->E, H = h->H, A = h->A, V = h->V;
   h->ss.mp_done = 0;
-  if (!hoist) param_norms(h, 0, h->scal + RN_SCAL_DEC_REG, st);
+  if (!hoist && !(flags & DFC_NO_REG_NORM)) param_norms(h, 0, h->scal + RN_SCAL_DEC_REG, st);
   // The input part of the gates (embeddings -> Xe) does not depend on the features: in the fused step it runs on the side
   // stream beside the feature products Uv / P (EV_XE_FORK joins it in front of the chain)
   const bool fork_xe = !free_tokens && h->overlap && h->s2 && hoist && hoist->par;
@@ -42,7 +45,7 @@ static int dec_fwd_chain(recnet_handle* h, const float* enc, const int64_t* targ
     gemm(h, h->emb_lp, 0, h->ldE, h->We_w, 0, h->ldE, h->Xe, 4 * H, h->bsum_d, T * B, 4 * H, E, 1.f, 0, h->s2);
     hipEventRecord(h->ev[EV_XE_JOIN], h->s2);
   }
-  if (!pro_group) dec_invariants(h, enc, st, !fork_xe);   // (Uv on the side stream as well: measured +10 us, the two products share the chip anyway)
+  if (!pro_group && !(flags & DFC_REUSE_INVARIANTS)) dec_invariants(h, enc, st, !fork_xe);   // (Uv on the side stream as well: measured +10 us, the two products share the chip anyway)
   if (pro_group) {
   } else if (fork_xe) {
     hipStreamWaitEvent(st, h->ev[EV_XE_JOIN], 0);

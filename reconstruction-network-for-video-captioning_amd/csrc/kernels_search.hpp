@@ -1,4 +1,4 @@
-// RecNet gfx950 kernels: device-side greedy / beam search.
+// RecNet gfx950 kernels: device-side greedy / beam / sampling search, scoring of given captions.
 // Included through kernels.hpp.
 #pragma once
 // =============================================================================================
@@ -133,6 +133,56 @@ template <bool RES> __global__ __launch_bounds__(256) void sample_rows_kernel(co
     p.tok[row] = tok;
     p.lp[row] = (x[tok] / p.temp - mx) - logf(sum);
   }
+}
+// ---- scoring: the log-probability of a GIVEN token per row (the reference has no counterpart; DESIGN.md section 9 states the
+// definitions, tests/score_ref.py restates them for the CPU)
+//   lp[row] = s_k - logsumexp_v s_v ,  s_v = x[row, v] / temp ,  k = tok[row] ;  k outside [0, V): lp = -inf, k is never an index
+struct LogprobArgs {
+  const float* x; int V;               // logits [rows][V], read only
+  float temp;
+  const int64_t* tok; float* lp;       // [rows]
+};
+#define LP_NV 20                       // floats of a row per thread that stay in registers (rows up to 5120, like ce_kernel)
+// One workgroup per row, the shape of ce_kernel.  RES: the row is loaded once and stays in registers; else it is read from global
+// memory twice (max, then sum).  The maximum is subtracted before the exponentials; same formulas as sample_rows_kernel's
+// log-probability (s = x / temp, __expf, logf), so that the two agree on a token the sampler drew.
+template <bool RES> __global__ __launch_bounds__(256) void logprob_rows_kernel(const LogprobArgs p) {
+  __shared__ float sf[4];
+  const int row = blockIdx.x, tid = threadIdx.x, V = p.V;
+  const float* x = p.x + (size_t)row * V;
+  const long k = p.tok[row];
+  const bool in_range = k >= 0 && k < V;
+  float mx = -INFINITY, sum = 0.f;
+  if (RES) {
+    float s[LP_NV];
+#pragma unroll
+    for (int i = 0; i < LP_NV; ++i) { const int v = tid + 256 * i; s[i] = v < V ? x[v] / p.temp : -INFINITY; }
+#pragma unroll
+    for (int i = 0; i < LP_NV; ++i) mx = fmaxf(mx, s[i]);
+    mx = block_max256(mx, sf);
+#pragma unroll
+    for (int i = 0; i < LP_NV; ++i) sum += tid + 256 * i < V ? rn_exp(s[i] - mx) : 0.f;
+  } else {
+    for (int v = tid; v < V; v += 256) mx = fmaxf(mx, x[v] / p.temp);
+    mx = block_max256(mx, sf);
+    for (int v = tid; v < V; v += 256) sum += rn_exp(x[v] / p.temp - mx);
+  }
+  sum = block_sum256(sum, sf);
+  if (tid == 0) p.lp[row] = in_range ? (x[k] / p.temp - mx) - logf(sum) : -INFINITY;
+}
+// Per-caption reduction over lp [T][B] / tokens [T][B]: e_b = the first t with tokens[t][b] == <EOS> (2), else T - 1;
+// len[b] = e_b + 1; sum[b] = lp[0][b] + ... + lp[e_b][b] in ascending t (one thread per caption, no atomics: two calls give the same
+// bits).  Rows behind e_b are not read into the sum (they may hold -inf).  The rule of search.sequence_logprob.
+__global__ __launch_bounds__(256) void caption_logprob_kernel(const float* __restrict__ lp, const int64_t* __restrict__ tokens, int T,
+                                                              int B, float* __restrict__ sum_out, int32_t* __restrict__ len_out) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  float s = 0.f; int e = T - 1;
+  for (int t = 0; t < T; ++t) {
+    s += lp[(size_t)t * B + b];
+    if (tokens[(size_t)t * B + b] == 2) { e = t; break; }
+  }
+  sum_out[b] = s; len_out[b] = e + 1;
 }
 // record the step's tokens; the reference stops after the first step whose tokens are all <PAD> (eval.py:30,116)
 __global__ void search_stop_kernel(const int64_t* __restrict__ tokens, int n, int t, int32_t* __restrict__ n_steps) {

@@ -12,6 +12,7 @@
 //   decoder_step, reconstructor_step                    Decoder.forward / *Reconstructor.forward (per-step API)
 //   greedy_search, beam_search                          eval.py:19-120
 //   sample_search, sample_rows                          sampling (no counterpart in the reference; loop shape of eval.py:19-33)
+//   score_captions                                      teacher-forced log-probabilities of given captions (train.py:25,45, eval mode)
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
 #include <torch/library.h>
@@ -210,6 +211,22 @@ std::tuple<at::Tensor, at::Tensor> sample_rows(int64_t h, const at::Tensor& logi
                         (uint32_t)seed, (int32_t)t, toks.data_ptr<int64_t>(), lps.data_ptr<float>(), stream()), "sample_rows");
   return {toks, lps};
 }
+// tokens [T, B] with every entry in [0, V): the caller's duty (search.score_captions checks it)
+std::tuple<at::Tensor, at::Tensor, at::Tensor> score_captions(int64_t h, const c10::optional<at::Tensor>& enc, const at::Tensor& tokens,
+                                                              double temperature) {
+  if (enc.has_value() && enc->defined()) chk_enc(h, *enc);
+  chk(tokens, at::kLong, "tokens");
+  TORCH_CHECK(tokens.dim() == 2 && tokens.size(1) == dim(h, RECNET_DIM_B), "recnet: tokens has sizes ", tokens.sizes(), ", the engine expects [T, ",
+              dim(h, RECNET_DIM_B), "]");
+  const int64_t T = tokens.size(0), B = tokens.size(1);
+  TORCH_CHECK(T <= INT32_MAX, "recnet: T out of range");
+  auto lps = at::zeros({T, B}, tokens.options().dtype(at::kFloat));
+  auto cap = at::zeros({B}, tokens.options().dtype(at::kFloat));
+  auto len = at::zeros({B}, tokens.options().dtype(at::kInt));
+  ok(recnet_score_captions(H(h), fptr(enc, "encoder_outputs"), tokens.data_ptr<int64_t>(), (int32_t)T, (float)temperature,
+                           lps.data_ptr<float>(), cap.data_ptr<float>(), len.data_ptr<int32_t>(), stream()), "score_captions");
+  return {lps, cap, len};
+}
 
 }  // namespace
 
@@ -230,6 +247,7 @@ TORCH_LIBRARY(recnet, m) {
   m.def("beam_search(int handle, Tensor encoder_outputs, int beam_width) -> (Tensor tokens, Tensor n_steps)");
   m.def("sample_search(int handle, Tensor encoder_outputs, float temperature, int top_k, int seed) -> (Tensor tokens, Tensor logprobs, Tensor n_steps)");
   m.def("sample_rows(int handle, Tensor logits, float temperature, int top_k, int seed, int t) -> (Tensor tokens, Tensor logprobs)");
+  m.def("score_captions(int handle, Tensor? encoder_outputs, Tensor tokens, float temperature) -> (Tensor logprobs, Tensor caption_logprob, Tensor lengths)");
 }
 
 // The handle is an int, so dispatch cannot key on a tensor for every op: ops with tensor arguments are registered for the
@@ -250,6 +268,7 @@ TORCH_LIBRARY_IMPL(recnet, CUDA, m) {
   m.impl("beam_search", beam_search);
   m.impl("sample_search", sample_search);
   m.impl("sample_rows", sample_rows);
+  m.impl("score_captions", score_captions);
 }
 TORCH_LIBRARY_IMPL(recnet, CompositeExplicitAutograd, m) {
   m.impl("add_reg_grad", add_reg_grad);

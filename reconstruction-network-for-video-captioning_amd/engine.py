@@ -259,6 +259,39 @@ class Engine:
                    "recnet_sample_rows")
         return toks, lps
 
+    def logprob_rows(self, logits, tokens, temperature=1.0):
+        """Log-probability of tokens[r] under softmax(logits[r] / temperature) for caller-supplied device logits [rows, V]
+        (recnet_logprob_rows; no decoder needed).  tokens [rows] int64; one outside [0, V) gives -inf.  Returns logprobs [rows]
+        float32; `logits` is only read."""
+        if logits.dim() != 2:
+            raise RuntimeError("logits: expected [rows, V], got %s" % (tuple(logits.shape),))
+        rows, V = logits.shape
+        _chk_tensor(logits, (rows, V), torch.float32, "logits")
+        _chk_tensor(tokens, (rows,), torch.int64, "tokens")
+        lps = torch.empty(rows, dtype=torch.float32, device=logits.device)
+        _lib.check(self.lib.recnet_logprob_rows(self.handle, _ptr(logits), _ptr(tokens), int(rows), int(V), float(temperature),
+                                                _ptr(lps), _stream()), "recnet_logprob_rows")
+        return lps
+
+    def score_captions(self, enc, tokens, temperature=1.0):
+        """Teacher-forced log-probabilities of given captions, eval mode (recnet_score_captions).  tokens [T, B] int64 with every
+        entry in [0, V) (the caller's duty: search.score_captions checks); enc None reuses the invariants of the previous call.
+        Returns (logprobs [T, B] float32, caption_logprob [B] float32, lengths [B] int32) device tensors.  The library checks T
+        and temperature."""
+        d = self.dims
+        if enc is not None:
+            _chk_tensor(enc, (d["B"], d["F"], d["D"]), torch.float32, "encoder_outputs")
+        if tokens.dim() != 2:
+            raise RuntimeError("tokens: expected [T, B], got %s" % (tuple(tokens.shape),))
+        T = tokens.shape[0]
+        _chk_tensor(tokens, (T, d["B"]), torch.int64, "tokens")
+        lps = torch.zeros(T, d["B"], dtype=torch.float32, device=self.device)
+        cap = torch.zeros(d["B"], dtype=torch.float32, device=self.device)
+        ln = torch.zeros(d["B"], dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.recnet_score_captions(self.handle, _ptr(enc), _ptr(tokens), int(T), float(temperature), _ptr(lps),
+                                                  _ptr(cap), _ptr(ln), _stream()), "recnet_score_captions")
+        return lps, cap, ln
+
     def decoder_step(self, tokens, h_in, c_in, enc, train=False, seed=0, t=0):
         d = self.dims
         B = d["B"]

@@ -20,7 +20,7 @@ from .api import (GraphedStep, build_decoder, build_reconstructor, forward_decod
 from .checkpoint import load_checkpoint, save_checkpoint
 from .dp import DataParallelTrainStep
 from .feed import DeviceFeeder
-from .search import beam_search, greedy_search, sample_search
+from .search import _caption_tensor, _score, beam_search, best_of_n, greedy_search, sample_search
 
 
 class Trainer:
@@ -217,7 +217,8 @@ class Trainer:
 def evaluate(config, score_batches, decoder, search_method, idx2word, references):
     """score_batches: iterable of (vids, enc [B,F,D]) with B == config.batch_size (the score loader repeats its last
     sample to fill the batch, dataset/MSVD.py:76-93; "PAD" ids are dropped like eval.py:145).  search_method: "greedy",
-    ("beam", width) or ("sample", temperature, top_k, seed).  references: {vid: [caption strings]}.  Returns the score dict
+    ("beam", width), ("sample", temperature, top_k, seed) or ("best_of", n, temperature, top_k, seed) (search.best_of_n: the
+    best of n sampled candidates by the model's length-normalised log-probability).  references: {vid: [caption strings]}.  Returns the score dict
     of metrics.score_all."""
     decoder.eval()
     dev = next(decoder.parameters()).device
@@ -242,6 +243,9 @@ def evaluate(config, score_batches, decoder, search_method, idx2word, references
                 _, temperature, top_k, seed = search_method
                 steps, _ = sample_search(config, decoder, inp, hid, enc, temperature, top_k, seed)
                 caps = list(map(list, zip(*steps)))
+            elif method == "best_of":
+                _, n, temperature, top_k, seed = search_method
+                caps = best_of_n(config, decoder, inp, hid, enc, n, temperature, top_k, seed)[0]
             else:
                 raise NotImplementedError("Unknown search method: {}".format(method))
         for vid, c in zip(vids, caps):
@@ -249,3 +253,21 @@ def evaluate(config, score_batches, decoder, search_method, idx2word, references
                 res[vid] = [metrics.indices_to_sentence(c, idx2word)]
     gts = {v: references[v] for v in res}
     return metrics.score_all(gts, res)
+
+
+@torch.no_grad()
+def perplexity(config, decoder, batches):
+    """Teacher-forced per-token perplexity (the reference's validation pass, train.py:310-372, is free-running only):
+    exp(-sum caption_logprob / sum length) over all captions of `batches`, (enc [B,F,D], targets [31,B]) pairs as in
+    Trainer.validate; a caption counts up to and including its <EOS> (search.score_captions)."""
+    decoder.eval()
+    dev = next(decoder.parameters()).device
+    total = torch.zeros(1, dtype=torch.float64, device=dev)
+    count = torch.zeros(1, dtype=torch.int64, device=dev)
+    for enc, targets in batches:
+        enc = torch.as_tensor(enc, dtype=torch.float32).to(dev)
+        targets = torch.as_tensor(targets).long().to(dev)
+        _, cap, ln = _score(decoder, enc, _caption_tensor(config, decoder, enc.shape[0], targets), 1.0, False)
+        total += cap.double().sum()
+        count += ln.sum()
+    return float(torch.exp(-total / count).item())
