@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define RECNET_ABI_VERSION 10
+#define RECNET_ABI_VERSION 11
 #define RECNET_ATTN_NONE 0
 #define RECNET_ATTN_SOFTMAX 1
 #define RECNET_OK 0
@@ -214,6 +214,28 @@ int recnet_logprob_rows(recnet_handle* h, const float* logits, const int64_t* to
 int recnet_score_captions(recnet_handle* h, const float* enc, const int64_t* tokens, int32_t T, float temperature,
                           float* logprobs_out, float* caption_logprob_out, int32_t* length_out, void* stream);
 
+/* ---- reconstruction error of GIVEN captions (the reference has no counterpart: it only ever forms the batch mean, as a training
+ * loss).  How well does the reconstructor recover this video's features from the decoder states of this
+ * caption?  Both reconstructors are separable per caption (models/global_reconstructor.py:30-46, models/local_reconstructor.py:37-55);
+ * in eval mode (no dropout), for hidden states [T,1,B,H] and features enc [B,F,D]:
+ *   global: recon[b, :] = mean_t out_t[b, :]  (train.py:96-98);   err[b] = (1 / R) sum_r (recon[b, r] - mean_f enc[b, f, r])^2 / T  (train.py:99-102)
+ *   local:  recon[b, f, :] = out_f[b, :]      (train.py:125-127); err[b] = (1 / (F D)) sum_{f, d} (recon[b, f, d] - enc[b, f, d])^2  (train.py:128)
+ * so mean_b err[b] is the reference's MSE term (rec_mse) at the same hidden states; the normaliser never involves the batch
+ * (global_batch_size / batch_offset play no part).  Exactly one of tokens / hiddens is non-NULL: tokens [T][B] int64 = the
+ * teacher-forced decoder forward in eval mode exactly as recnet_score_captions runs it (step 0 fed <SOS>; the same PRECONDITION:
+ * every token in [0, V)), the reconstructor then runs on the states it leaves; hiddens [T,1,B,H] = states handed in, as
+ * recnet_forward_reconstructor takes them.  1 <= T <= caption_max_len + 1; the global error depends on T, so errors of one video
+ * are comparable only at a common T.  err_out [B]; recon_out NULL or the reconstruction itself, global [B,R], local [B,F,D].  One
+ * fixed summation order per caption and no atomics: two calls on the same inputs return the same bits.  One stream-ordered
+ * sequence, no host synchronisation, no allocation; a pending deferred update is completed first.  The call runs the
+ * reconstructor's forward without its regulariser norms, loss epilogues and loss scalars (no recnet_scalars are written) and leaves
+ * the handle between two steps: a following recnet_backward_reconstructor / recnet_backward_decoder /
+ * recnet_forward_reconstructor(hiddens = NULL) is refused with their state error until the next forward.  RECNET_ESTATE: no
+ * reconstructor (or, with tokens, no decoder) bound; RECNET_EINVAL: both or neither of tokens / hiddens, NULL enc / err_out, T out
+ * of range. */
+int recnet_reconstruction_error(recnet_handle* h, const float* enc, const int64_t* tokens, const float* hiddens, int32_t T,
+                                float* err_out, float* recon_out, void* stream);
+
 /* ---- forward_decoder, train.py:17-75 (teacher forcing, train.py:38,45).
  * enc [B,F,D]; targets [caption_max_len+1, B] int64 (time-major, <PAD>=0, <EOS>=2);
  * T = number of steps the reference's loop would run (train.py:66), computed by the caller from the
@@ -342,6 +364,7 @@ int recnet_abort_step(recnet_handle* h);
 #define RECNET_SITE_REC_CHAIN_BWD 8   /* ... and the whole backward chain                                              */
 #define RECNET_SITE_DEC_CHAIN_FWD 9   /* decoder, bf16, teacher-forced: the whole forward chain as one persistent launch */
 #define RECNET_SITE_DEC_CHAIN_BWD 10  /* ... and the whole BPTT chain                                                    */
+#define RECNET_SITE_RECON_ERR 11      /* recnet_reconstruction_error: the row kernel (and the sum of its parts) alone          */
 int recnet_profile_begin(recnet_handle* h, int32_t site);
 int recnet_profile_end(recnet_handle* h, int32_t* n_launches, double* total_ms);
 /* Same read-out without leaving profiling mode.  Brackets are taken around EAGER launches only: on a capturing stream the

@@ -10,6 +10,7 @@ Host-side mirror of the reference interface for the hot path:
   eval.py greedy_search / beam_search        -> search.* (device-side loops)
   (no counterpart) temperature / top-k draws -> search.sample_search, search.sequence_logprob
   (no counterpart) scoring given captions    -> search.score_captions, search.best_of_n, loop.perplexity
+  (no counterpart) reconstruction error      -> search.reconstruction_errors, search.canonical_captions
 All compute goes through csrc/librecnet_hip.so (C ABI: include/recnet_hip.h).
 """
 from .config import TrainConfig, make_config  # noqa: F401
@@ -19,6 +20,6 @@ from .api import (build_decoder, build_reconstructor, forward_decoder, forward_g
                   step_weights)
 from .dp import DataParallelTrainStep, shard_bounds  # noqa: F401
 from .search import (greedy_search, beam_search, sample_search, sequence_logprob, score_captions, best_of_n,  # noqa: F401
-                     pick_best_of_n)
+                     pick_best_of_n, canonical_captions, reconstruction_errors)
 from .loop import Trainer, evaluate, perplexity  # noqa: F401
 from .checkpoint import save_checkpoint, load_checkpoint, read_checkpoint  # noqa: F401

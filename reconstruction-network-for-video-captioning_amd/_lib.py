@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # RN_LIB_VARIANT=probe: the probe build (in-kernel time stamps); =acqinv: the cross-check build with acquire fences; =fault: fault injection
 _VARIANT = ("_" + os.environ["RN_LIB_VARIANT"] if os.environ.get("RN_LIB_VARIANT") else "")
 LIB_PATH = os.path.join(_HERE, "csrc", "librecnet_hip%s.so" % _VARIANT)
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 REC_NONE, REC_GLOBAL, REC_LOCAL = 0, 1, 2
 PREC_F32, PREC_BF16 = 0, 1
@@ -157,6 +157,7 @@ EXPORTS["recnet_sample_rows"] = (_i, [C.c_void_p, C.c_void_p, _i, _i, _f, _i, C.
 EXPORTS["recnet_sample_search"] = (_i, [C.c_void_p, C.c_void_p, _f, _i, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
 EXPORTS["recnet_logprob_rows"] = (_i, [C.c_void_p, C.c_void_p, C.c_void_p, _i, _i, _f, C.c_void_p, C.c_void_p])
 EXPORTS["recnet_score_captions"] = (_i, [C.c_void_p, C.c_void_p, C.c_void_p, _i, _f, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
+EXPORTS["recnet_reconstruction_error"] = (_i, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _i, C.c_void_p, C.c_void_p, C.c_void_p])
 EXPORTS["recnet_reconstructor_step"] = (_i, [C.c_void_p] * 5 + [_i] + [C.c_void_p] * 3 + [_i, C.c_uint32, _i, C.c_void_p])
 EXPORTS["recnet_chain_status"] = (_i, [C.c_void_p, C.POINTER(_i), C.c_void_p])
 EXPORTS["recnet_chain_reset"] = (_i, [C.c_void_p, _i, C.c_void_p])

@@ -10,7 +10,8 @@ from . import _lib
 OPS_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "librecnet_torch_ops.so")
 OP_NAMES = ("forward_decoder", "forward_decoder_free", "backward_decoder", "forward_reconstructor", "backward_reconstructor",
             "add_reg_grad", "train_step_fwd_bwd", "train_step", "optimizer_step", "clip_grad_norm", "decoder_step",
-            "reconstructor_step", "greedy_search", "beam_search", "sample_search", "sample_rows", "score_captions")
+            "reconstructor_step", "greedy_search", "beam_search", "sample_search", "sample_rows", "score_captions",
+            "reconstruction_error")
 _loaded = False
 
 

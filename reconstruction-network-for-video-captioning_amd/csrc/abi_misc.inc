@@ -1,7 +1,7 @@
 // C ABI: launch-site profiling hooks and the bare GEMM entry points.
 // Part of api.hip (one translation unit; see the include list there).
 int recnet_profile_begin(recnet_handle* h, int32_t site) {
-  if (!h || site < 1 || site > 10) return fail(RECNET_EINVAL, "bad profile site");
+  if (!h || site < 1 || site > 11) return fail(RECNET_EINVAL, "bad profile site");
   h->prof_on = site; h->prof_used = 0;
   return RECNET_OK;
 }

@@ -1,5 +1,5 @@
-// C ABI: the decoder's per-step API, the device-side inference search (eval.py:19-120), greedy / beam / sampling, and the scoring of
-// given captions.
+// C ABI: the decoder's per-step API, the device-side inference search (eval.py:19-120), greedy / beam / sampling, the scoring of
+// given captions and their per-caption reconstruction error (train.py:96-102 / :125-128 in eval mode).
 // Part of api.hip (one translation unit; see the include list there).
 // One decode step on already prepared loop invariants (Uv, P, bias sum): embedding, input projection,
 // h . [W_hh ; attn_W]^T, cell kernel, vocabulary projection.  Rows [0,B) / [B,2B) of Hs_lp are scratch.
@@ -234,6 +234,69 @@ int recnet_score_captions(recnet_handle* h, const float* enc, const int64_t* tok
   gemm(h, h->Hs_lp, 0, h->ldH, h->Wo_w, 0, h->ldH, h->logits, V, h->dP.out_bias, T * B, V, H, 1.f, 0, st);
   launch_logprob_rows(h->logits, tokens, T * B, V, temperature, logprobs_out, st);
   hipLaunchKernelGGL(caption_logprob_kernel, dim3(cdiv(B, 256)), dim3(256), 0, st, logprobs_out, tokens, T, B, caption_logprob_out, length_out);
+  LAUNCH_OK();
+  return RECNET_OK;
+}
+
+// ---- reconstruction error of given captions (the reference has no counterpart: train.py:99-102 / :128 only form the batch mean)
+// The row kernel over the reconstruction the outputs-only forward left in h->outm / h->outl.  Grid: the caption's items cut into NP
+// parts so that B * NP workgroups cover the chip about twice (B = 100 on 256 CUs: 6 parts of a global caption and 6 of a local one), a part never
+// below one wave's worth of items; the partial sums [B][NP] go through h->rowloss (NP <= caption_max_len + 1 keeps them inside it;
+// the decoder forward that owns it is invalidated by the call anyway).
+static void launch_recon_err(recnet_handle* h, const float* enc, int T, float* err_out, float* recon_out, hipStream_t st) {
+  const int B = h->B, F = h->F, R = h->R;
+  const bool local = h->kind == RECNET_REC_LOCAL;
+  ReconErrArgs a;
+  a.out = local ? h->outl : h->outm; a.enc = enc; a.recon = recon_out; a.B = B; a.F = F; a.R = R;
+  a.scale = local ? (float)(1.0 / ((double)F * R)) : (float)(1.0 / ((double)R * T));
+  const bool vec = (R & 3) == 0 && (((uintptr_t)a.out) & 15) == 0 && (((uintptr_t)enc) & 15) == 0 && (((uintptr_t)recon_out) & 15) == 0;
+  const long n = (long)(local ? F : 1) * (vec ? R >> 2 : R);
+  const int want = cdiv(2L * (h->ncu > 0 ? h->ncu : 256), B), most = cdiv(n, 64);
+  int NP = want < most ? want : most;
+  if (NP > h->Tm) NP = h->Tm;
+  if (NP < 1) NP = 1;
+  a.NP = NP; a.dst = NP == 1 ? err_out : h->rowloss;
+  const dim3 g(B, NP);
+  hipEvent_t pe = prof_bracket_begin(h, RN_SITE_RECON_ERR, st);
+  if (local) {
+    if (vec) hipLaunchKernelGGL((recon_err_kernel<true, 4>), g, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((recon_err_kernel<true, 1>), g, dim3(256), 0, st, a);
+  } else {
+    if (vec) hipLaunchKernelGGL((recon_err_kernel<false, 4>), g, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((recon_err_kernel<false, 1>), g, dim3(256), 0, st, a);
+  }
+  if (NP > 1) hipLaunchKernelGGL(recon_err_finalize_kernel, dim3(cdiv(B, 256)), dim3(256), 0, st, (const float*)h->rowloss, NP, B, a.scale, err_out);
+  if (pe) hipEventRecord(pe, st);
+}
+
+// The decoder's teacher-forced forward in eval mode as recnet_score_captions runs it (tokens), or hidden states handed in as
+// recnet_forward_reconstructor takes them (hiddens); then the reconstructor's forward in eval mode with outputs only (fwd_rec:
+// the same chains, row groups and per-step fall-backs as recnet_forward_reconstructor(train = 0), without norms, loss epilogues and
+// loss scalars), then the row kernel.  The handle is left between two steps: no saved forward a backward could follow.
+int recnet_reconstruction_error(recnet_handle* h, const float* enc, const int64_t* tokens, const float* hiddens, int32_t T,
+                                float* err_out, float* recon_out, void* stream) {
+  REQUIRE_WS(h);
+  FLUSH_PENDING(h, stream);
+  if (h->kind == RECNET_REC_NONE || !h->rec_bound) return fail(RECNET_ESTATE, "reconstructor not bound");
+  if (!enc || !err_out) return fail(RECNET_EINVAL, "null argument");
+  if ((tokens != nullptr) == (hiddens != nullptr)) return fail(RECNET_EINVAL, "exactly one of tokens / hiddens must be given");
+  if (check_T(h, T)) return fail(RECNET_EINVAL, "T out of range");
+  if (tokens && !h->dec_bound) return fail(RECNET_ESTATE, "decoder not bound");
+  hipStream_t st = (hipStream_t)stream;
+  int r;
+  if (tokens) {
+    r = dec_fwd_chain(h, enc, tokens, T, 0, st, nullptr, nullptr, DFC_NO_REG_NORM); if (r) return r;
+  } else {   // hidden states handed in by the caller: refresh the fp32 image and its operand copy
+    copyf(hiddens, h->Hs, (size_t)T * h->B * h->H, st);
+    pack_block(h, h->Hs_lp, h->ldH, hiddens, h->H, T * h->B, h->H, 1.f, st);
+    h->ss.mp_done = 0;
+  }
+  h->fwd_dec_done = h->fwd_rec_done = 0;
+  h->ss.xcat_done = 0;          // (as recnet_forward_reconstructor: the operand is formed here, in eval mode)
+  r = fwd_rec(h, enc, T, 0, st, false, false, nullptr, /*outputs_only*/ true); if (r) return r;
+  launch_recon_err(h, enc, T, err_out, recon_out, st);
+  h->fwd_dec_done = h->fwd_rec_done = 0;
+  h->ss.mp_done = 0; h->ss.xcat_done = 0; h->ss.dout_ready = 0; h->ss.dhr_done = 0; h->ss.encmean_hoisted = 0;
   LAUNCH_OK();
   return RECNET_OK;
 }

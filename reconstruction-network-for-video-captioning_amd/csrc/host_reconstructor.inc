@@ -48,10 +48,13 @@ static void mse_and_dout(recnet_handle* h, float* out, const float* ref, int Sn,
 }
 // norms_hoisted: the parameter norms and the gate bias come from hoist_side_work.  side != nullptr: the fused step's side work
 // is forked from here, behind the batched input product.
-static int fwd_rec_global(recnet_handle* h, const float* enc, int T, int train, hipStream_t st, bool norms_hoisted, const SideWork* side) {
+// outputs_only (recnet_reconstruction_error): no regulariser norms, no loss epilogue, no MSE pass — h->outm is left holding the
+// reconstruction mean_t out_t itself instead of d loss / d out, and h->scal is not written.
+static int fwd_rec_global(recnet_handle* h, const float* enc, int T, int train, hipStream_t st, bool norms_hoisted, const SideWork* side,
+                          bool outputs_only = false) {
   const int B = h->B, F = h->F, D = h->D, H = h->H, R = h->R;
   if (!norms_hoisted) {
-    param_norms(h, 1, h->scal + RN_SCAL_REC_REG, st);
+    if (!outputs_only) param_norms(h, 1, h->scal + RN_SCAL_REC_REG, st);
     gate_bias(h->rP.rnn_bias_ih_l0, h->rP.rnn_bias_hh_l0, h->bsum_r, R, h->rgru, st);
   }
   // mean-pooled decoder states, rescaled by caption_max_len / T (global_reconstructor.py:33-37): (cml / T^2) sum_t h_t
@@ -101,7 +104,7 @@ static int fwd_rec_global(recnet_handle* h, const float* enc, int T, int train, 
       // rec_epi 1: output layer + MSE + d out as an epilogue of the chain (rec_chain.hpp) instead of a split-K GEMM, its
       // reduction and the MSE kernel between the two chains (C2: 1.837 -> 1.815 ms)
       const int f_epi = h->sw.rec_epi;
-      if (f_epi && a.master && h->lp && h->ldR == R && nb == B && h->hm_pan) {
+      if (f_epi && !outputs_only && a.master && h->lp && h->ldR == R && nb == B && h->hm_pan) {
         if (!h->ss.encmean_hoisted) hipLaunchKernelGGL(mean_over_f_kernel, dim3(ew_blocks((size_t)B * D)), dim3(256), 0, st, enc, B, F, D, h->encmean);
         h->ss.encmean_hoisted = 1;
         const double cnt = (double)h->c.global_batch_size * R;
@@ -148,6 +151,7 @@ static int fwd_rec_global(recnet_handle* h, const float* enc, int T, int train, 
     return side_r;
   }
   gemm(h, h->hrmean_lp, 0, h->ldR, h->Wor_w, 0, h->ldR, h->outm, R, h->rP.out_bias, B, R, R, 1.f, 0, st);
+  if (outputs_only) { h->ss.dout_ready = 0; return side_r; }
   if (!h->ss.encmean_hoisted) hipLaunchKernelGGL(mean_over_f_kernel, dim3(ew_blocks((size_t)B * D)), dim3(256), 0, st, enc, B, F, D, h->encmean);
   h->ss.encmean_hoisted = 0;
   const int nb = 256;
@@ -284,11 +288,12 @@ static int bwd_rec_global_deferred(recnet_handle* h, hipStream_t st, int which =
 }
 
 // ---------------------------------------------------------------------------------------------- local reconstructor
-static int fwd_rec_local(recnet_handle* h, const float* enc, int T, int train, hipStream_t st, bool norms_hoisted) {
+// outputs_only: see fwd_rec_global — h->outl [F][B][R] is left holding the reconstruction out_f itself.
+static int fwd_rec_local(recnet_handle* h, const float* enc, int T, int train, hipStream_t st, bool norms_hoisted, bool outputs_only = false) {
   const int B = h->B, F = h->F, D = h->D, H = h->H, R = h->R, RA = h->RA, ldHR = h->ldHR;
   const size_t esz = h->lp ? 2 : 4;
   if (!norms_hoisted) {
-    param_norms(h, 1, h->scal + RN_SCAL_REC_REG, st);
+    if (!outputs_only) param_norms(h, 1, h->scal + RN_SCAL_REC_REG, st);
     gate_bias(h->rP.rnn_bias_ih_l0, h->rP.rnn_bias_hh_l0, h->bsum_r, R, h->rgru, st);
   }
   // Ud = hiddens . U_r^T   (local_reconstructor.py:42, hoisted)
@@ -361,7 +366,7 @@ static int fwd_rec_local(recnet_handle* h, const float* enc, int T, int train, h
   // `out` in between); the partial sums are per output tile
   const int tiles = ((F * B + 127) / 128) * ((R + 127) / 128);      // (128 x 128 output tiles: gemm_lds.hpp)
   const int f_me = h->sw.mse_epi;
-  if (f_me && h->lp && h->ldR == R && (R & 3) == 0 && (D & 3) == 0 && tiles <= 1024 && (((uintptr_t)enc) & 15) == 0 && (((uintptr_t)h->outl) & 15) == 0) {
+  if (f_me && !outputs_only && h->lp && h->ldR == R && (R & 3) == 0 && (D & 3) == 0 && tiles <= 1024 && (((uintptr_t)enc) & 15) == 0 && (((uintptr_t)h->outl) & 15) == 0) {
     RnMse m; m.ref = enc; m.part = h->msep; m.bstride = (size_t)F * D; m.sstride = (size_t)D; m.B = B; m.gcoef = (float)(2.0 / cnt); m.lp = h->c.lambda_recon;
     rn_launch_gemm(h->prec, h->Hr_lp, 1, 0, h->ldR, h->Wor_w, 1, 0, h->ldR, h->outl, R, h->rP.out_bias, F * B, R, R, 1.f, 0, 1, nullptr, 0, st, 0, 0,
                    h->dout_lp, h->ldR, &m);
@@ -370,6 +375,7 @@ static int fwd_rec_local(recnet_handle* h, const float* enc, int T, int train, h
     return RECNET_OK;
   }
   gemm(h, h->Hr_lp, 0, h->ldR, h->Wor_w, 0, h->ldR, h->outl, R, h->rP.out_bias, F * B, R, R, 1.f, 0, st);
+  if (outputs_only) { h->ss.dout_ready = 0; return RECNET_OK; }
   const int nb = 512;
   mse_and_dout(h, h->outl, enc, F, B, R, (size_t)F * D, (size_t)D, (float)(2.0 / cnt), nb, st);
   h->mse_nb = nb; h->mse_scale = (float)(1.0 / cnt);
@@ -559,12 +565,15 @@ static void rec_loss_scalars(recnet_handle* h, hipStream_t st) {
                      h->c.reconstructor_lambda_reg, h->c.lambda_recon);
 }
 // loss_late: the caller launches rec_loss_scalars itself (fused step: on the side stream behind the BPTT's fork, not between the
-// two chains).  norms_hoisted, side: see fwd_rec_global (the local form takes no side work).
+// two chains).  norms_hoisted, side: see fwd_rec_global (the local form takes no side work).  outputs_only: the reconstruction
+// itself stays in h->outm / h->outl, no loss is formed, and the pass is not one a backward may follow.
 static int fwd_rec(recnet_handle* h, const float* enc, int T, int train, hipStream_t st, bool norms_hoisted = false, bool loss_late = false,
-                   const SideWork* side = nullptr) {
+                   const SideWork* side = nullptr, bool outputs_only = false) {
   RN_RANGE("recnet: reconstructor forward (train.py:78-131)");
-  int r = h->kind == RECNET_REC_GLOBAL ? fwd_rec_global(h, enc, T, train, st, norms_hoisted, side) : fwd_rec_local(h, enc, T, train, st, norms_hoisted);
+  int r = h->kind == RECNET_REC_GLOBAL ? fwd_rec_global(h, enc, T, train, st, norms_hoisted, side, outputs_only)
+                                       : fwd_rec_local(h, enc, T, train, st, norms_hoisted, outputs_only);
   if (r) return r;
+  if (outputs_only) { h->T_last = T; h->train_last = train; h->fwd_rec_done = 0; return RECNET_OK; }
   // rec_loss = mse + lambda_reg * reg ; total = dec_loss + lambda_recon * rec_loss
   // (launching it on the fused step's side stream behind the BPTT's fork, like the total-loss scalar, was measured: no change)
   if (!loss_late) rec_loss_scalars(h, st);

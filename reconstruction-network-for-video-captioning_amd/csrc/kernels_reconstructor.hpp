@@ -1,4 +1,5 @@
-// RecNet gfx950 kernels: reconstructors: element-wise LSTM / GRU step, global helpers, MSE, local attention forward / backward.
+// RecNet gfx950 kernels: reconstructors: element-wise LSTM / GRU step, global helpers, MSE, the per-caption reconstruction error
+// (train.py:96-102 / :125-128 in eval mode), local attention forward / backward.
 // Included through kernels.hpp.
 #pragma once
 // =============================================================================================
@@ -311,6 +312,79 @@ __global__ __launch_bounds__(256) void mse_vec_kernel(float* __restrict__ out, c
   }
   acc = block_sum256(acc, sm);
   if (threadIdx.x == 0) partial[blockIdx.x] = acc;
+}
+
+// ---- reconstruction error of given captions (inference; the reference only forms the batch mean: DESIGN.md section 10).  Both
+// reconstructors are separable per caption (models/global_reconstructor.py:30-46, models/local_reconstructor.py:37-55); in eval mode
+//   global (train.py:96-102):  recon[b, :] = mean_t out_t[b, :] = out[b, :]          err[b] = (1 / R) sum_r (recon[b, r] - mean_f enc[b, f, r])^2 / T
+//   local  (train.py:125-128): recon[b, f, :] = out_f[b, :] = out[f * B + b, :]      err[b] = (1 / (F D)) sum_{f, d} (recon[b, f, d] - enc[b, f, d])^2
+// so mean_b err[b] is the reference's MSE term.  `out` holds the reconstruction itself (fwd_rec_*: outputs_only), [B][R] resp. [F][B][R];
+// enc [B][F][D] with D == R; the frame mean of the global form is taken here, frames in ascending order, then / F (mean_over_f_kernel's
+// arithmetic).  recon (may be null) receives the reconstruction in the public layout, [B][R] resp. [B][F][D]: the local form's
+// transposition is this kernel's store.
+// grid (B, NP): the caption's items (VW floats each; global R / VW, local F * R / VW) are cut into NP contiguous parts, one workgroup
+// each.  One fixed summation order per caption — a lane's items in ascending order, wave_sum, the four waves in order, then the parts in
+// ascending order (recon_err_finalize_kernel) — and no atomics: two calls on the same inputs return the same bits.
+// NP == 1: dst = err, scaled here; else dst = the partial sums [B][NP].
+struct ReconErrArgs {
+  const float* out; const float* enc; float* recon; float* dst;
+  int B, F, R, NP;
+  float scale;
+};
+template <bool LOCAL, int VW>
+__global__ __launch_bounds__(256) void recon_err_kernel(const ReconErrArgs p) {
+  static_assert(VW == 1 || VW == 4, "scalar or 16-byte form");
+  __shared__ float sm[4];
+  const int b = blockIdx.x, part = blockIdx.y;
+  const int R = p.R, F = p.F, Rq = R / VW;
+  const int n = LOCAL ? F * Rq : Rq;
+  const int per = (n + p.NP - 1) / p.NP;
+  const int i0 = part * per, i1 = min(n, i0 + per);
+  const float* __restrict__ encb = p.enc + (size_t)b * F * R;
+  const float fF = (float)F;
+  float acc = 0.f;
+  for (int i = i0 + (int)threadIdx.x; i < i1; i += 256) {
+    const int f = LOCAL ? i / Rq : 0, r = (LOCAL ? i - f * Rq : i) * VW;
+    const size_t o = LOCAL ? ((size_t)f * p.B + b) * R + r : (size_t)b * R + r;             // `out` row (f, b) resp. b
+    const size_t q = LOCAL ? ((size_t)b * F + f) * R + r : o;                                // public layout
+    if (VW == 4) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(p.out + o);
+      f32x4 e;
+      if (LOCAL) {
+        e = *reinterpret_cast<const f32x4*>(encb + (size_t)f * R + r);
+      } else {
+        f32x4 s = {0.f, 0.f, 0.f, 0.f};
+        for (int g = 0; g < F; ++g) s += *reinterpret_cast<const f32x4*>(encb + (size_t)g * R + r);
+        e[0] = s[0] / fF; e[1] = s[1] / fF; e[2] = s[2] / fF; e[3] = s[3] / fF;
+      }
+      const f32x4 d = v - e;
+      acc += (d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]);
+      if (p.recon) *reinterpret_cast<f32x4*>(p.recon + q) = v;
+    } else {
+      const float v = p.out[o];
+      float e;
+      if (LOCAL) {
+        e = encb[(size_t)f * R + r];
+      } else {
+        float s = 0.f;
+        for (int g = 0; g < F; ++g) s += encb[(size_t)g * R + r];
+        e = s / fF;
+      }
+      const float d = v - e;
+      acc += d * d;
+      if (p.recon) p.recon[q] = v;
+    }
+  }
+  acc = block_sum256(acc, sm);
+  if (threadIdx.x == 0) p.dst[(size_t)b * p.NP + part] = p.NP == 1 ? acc * p.scale : acc;
+}
+// err[b] = scale * sum_p part[b][p], parts in ascending order
+__global__ void recon_err_finalize_kernel(const float* __restrict__ part, int NP, int B, float scale, float* __restrict__ err) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  float s = 0.f;
+  for (int k = 0; k < NP; ++k) s += part[(size_t)b * NP + k];
+  err[b] = s * scale;
 }
 
 // =============================================================================================

@@ -18,6 +18,7 @@
 #define RN_SITE_REC_CHAIN_BWD 8
 #define RN_SITE_DEC_CHAIN_FWD 9
 #define RN_SITE_DEC_CHAIN_BWD 10
+#define RN_SITE_RECON_ERR 11
 
 // ---- gemm.hip
 int rn_gemm_bk(int prec);

@@ -13,6 +13,7 @@
 //   greedy_search, beam_search                          eval.py:19-120
 //   sample_search, sample_rows                          sampling (no counterpart in the reference; loop shape of eval.py:19-33)
 //   score_captions                                      teacher-forced log-probabilities of given captions (train.py:25,45, eval mode)
+//   reconstruction_error                                per-caption reconstruction error and the reconstruction (train.py:96-102 / :125-128, eval mode)
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
 #include <torch/library.h>
@@ -227,6 +228,36 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> score_captions(int64_t h, const c
                            lps.data_ptr<float>(), cap.data_ptr<float>(), len.data_ptr<int32_t>(), stream()), "score_captions");
   return {lps, cap, len};
 }
+// Exactly one of tokens [T, B] (every entry in [0, V): the caller's duty, search.reconstruction_errors checks it) and hiddens
+// [T, 1, B, H].  recon: global [B, R], local [B, F, D]; an empty tensor when it is not asked for.
+std::tuple<at::Tensor, at::Tensor> reconstruction_error(int64_t h, const at::Tensor& enc, const c10::optional<at::Tensor>& tokens,
+                                                        const c10::optional<at::Tensor>& hiddens, bool want_recon) {
+  chk_enc(h, enc);
+  const bool has_t = tokens.has_value() && tokens->defined(), has_h = hiddens.has_value() && hiddens->defined();
+  TORCH_CHECK(has_t != has_h, "recnet: exactly one of tokens / hiddens must be given");
+  const int64_t B = dim(h, RECNET_DIM_B), Hd = dim(h, RECNET_DIM_H), R = dim(h, RECNET_DIM_R);
+  TORCH_CHECK(R > 0, "recnet: the engine was created without a reconstructor");
+  int64_t T = 0;
+  if (has_t) {
+    chk(*tokens, at::kLong, "tokens");
+    TORCH_CHECK(tokens->dim() == 2 && tokens->size(1) == B, "recnet: tokens has sizes ", tokens->sizes(), ", the engine expects [T, ", B, "]");
+    T = tokens->size(0);
+  } else {
+    chk(*hiddens, at::kFloat, "decoder_hiddens");
+    TORCH_CHECK(hiddens->dim() == 4 && hiddens->size(1) == 1 && hiddens->size(2) == B && hiddens->size(3) == Hd,
+                "recnet: decoder_hiddens has sizes ", hiddens->sizes(), ", the engine expects [T, 1, ", B, ", ", Hd, "]");
+    T = hiddens->size(0);
+  }
+  chk_T(h, T);
+  auto err = at::zeros({B}, enc.options());
+  const bool local = dim(h, RECNET_DIM_RA) > 0;      // recnet_create: a local reconstructor needs RA > 0, every other kind holds RA = 0
+  at::Tensor recon = !want_recon ? at::empty({0}, enc.options())
+                                 : (local ? at::zeros({B, dim(h, RECNET_DIM_F), dim(h, RECNET_DIM_D)}, enc.options()) : at::zeros({B, R}, enc.options()));
+  ok(recnet_reconstruction_error(H(h), enc.data_ptr<float>(), has_t ? tokens->data_ptr<int64_t>() : nullptr,
+                                 has_h ? hiddens->data_ptr<float>() : nullptr, (int32_t)T, err.data_ptr<float>(),
+                                 want_recon ? recon.data_ptr<float>() : nullptr, stream()), "reconstruction_error");
+  return {err, recon};
+}
 
 }  // namespace
 
@@ -248,6 +279,7 @@ TORCH_LIBRARY(recnet, m) {
   m.def("sample_search(int handle, Tensor encoder_outputs, float temperature, int top_k, int seed) -> (Tensor tokens, Tensor logprobs, Tensor n_steps)");
   m.def("sample_rows(int handle, Tensor logits, float temperature, int top_k, int seed, int t) -> (Tensor tokens, Tensor logprobs)");
   m.def("score_captions(int handle, Tensor? encoder_outputs, Tensor tokens, float temperature) -> (Tensor logprobs, Tensor caption_logprob, Tensor lengths)");
+  m.def("reconstruction_error(int handle, Tensor encoder_outputs, Tensor? tokens, Tensor? decoder_hiddens, bool want_recon) -> (Tensor err, Tensor recon)");
 }
 
 // The handle is an int, so dispatch cannot key on a tensor for every op: ops with tensor arguments are registered for the
@@ -269,6 +301,7 @@ TORCH_LIBRARY_IMPL(recnet, CUDA, m) {
   m.impl("sample_search", sample_search);
   m.impl("sample_rows", sample_rows);
   m.impl("score_captions", score_captions);
+  m.impl("reconstruction_error", reconstruction_error);
 }
 TORCH_LIBRARY_IMPL(recnet, CompositeExplicitAutograd, m) {
   m.impl("add_reg_grad", add_reg_grad);

@@ -292,6 +292,37 @@ class Engine:
                                                   _ptr(cap), _ptr(ln), _stream()), "recnet_score_captions")
         return lps, cap, ln
 
+    def reconstruction_error(self, enc, tokens=None, hiddens=None, want_recon=False):
+        """Per-caption reconstruction error in eval mode (recnet_reconstruction_error): how well the reconstructor recovers
+        enc [B, F, D] from the decoder states of the given captions.  Exactly one of tokens [T, B] int64 (every entry in [0, V):
+        the caller's duty, search.reconstruction_errors checks; the teacher-forced decoder forward of score_captions runs first)
+        and hiddens [T, 1, B, H] (states handed in).  Returns (err [B] float32, recon) device tensors; recon is None unless
+        want_recon, else the reconstruction itself, global [B, R] = mean_t out_t, local [B, F, D].  mean(err) is the rec_mse of
+        forward_reconstructor(train=False) at the same states.  The library checks T and the bound models."""
+        d = self.dims
+        B = d["B"]
+        _chk_tensor(enc, (B, d["F"], d["D"]), torch.float32, "encoder_outputs")
+        if (tokens is None) == (hiddens is None):
+            raise RuntimeError("exactly one of tokens / hiddens must be given")
+        if tokens is not None:
+            if tokens.dim() != 2:
+                raise RuntimeError("tokens: expected [T, B], got %s" % (tuple(tokens.shape),))
+            T = tokens.shape[0]
+            _chk_tensor(tokens, (T, B), torch.int64, "tokens")
+        else:
+            if hiddens.dim() != 4:
+                raise RuntimeError("decoder_hiddens: expected [T, 1, B, H], got %s" % (tuple(hiddens.shape),))
+            T = hiddens.shape[0]
+            _chk_tensor(hiddens, (T, 1, B, d["H"]), torch.float32, "decoder_hiddens")
+        err = torch.zeros(B, dtype=torch.float32, device=self.device)
+        recon = None
+        if want_recon:
+            shape = (B, d["F"], d["D"]) if self.kind == "local" else (B, d.get("R", d["D"]))
+            recon = torch.zeros(shape, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.recnet_reconstruction_error(self.handle, _ptr(enc), _ptr(tokens), _ptr(hiddens), int(T), _ptr(err),
+                                                        _ptr(recon), _stream()), "recnet_reconstruction_error")
+        return err, recon
+
     def decoder_step(self, tokens, h_in, c_in, enc, train=False, seed=0, t=0):
         d = self.dims
         B = d["B"]
@@ -538,7 +569,7 @@ class Engine:
     # ---- live measurement of one recurrent-step GEMM site with HIP events on its own stream
     def profile_site(self, site, fn, iters=3):
         """Runs fn() `iters` times with hipEvents around every launch of `site` (1 dec fwd, 2 dec bwd, 3 rec
-        fwd, 4 rec bwd, 5 local-attention, 7-10 the chain kernels); returns (launches, average ms per launch).  fn() launches
+        fwd, 4 rec bwd, 5 local-attention, 7-10 the chain kernels, 11 the reconstruction-error kernel); returns (launches, average ms per launch).  fn() launches
         EAGERLY: on a capturing stream no bracket is taken (csrc/host_common.inc: prof_take)."""
         _lib.check(self.lib.recnet_profile_begin(self.handle, int(site)), "recnet_profile_begin")
         for _ in range(iters):

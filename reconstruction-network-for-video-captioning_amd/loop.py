@@ -214,12 +214,13 @@ class Trainer:
 
 # ---------------------------------------------------------------------- scoring, eval.py:123-169
 @torch.no_grad()
-def evaluate(config, score_batches, decoder, search_method, idx2word, references):
+def evaluate(config, score_batches, decoder, search_method, idx2word, references, reconstructor=None):
     """score_batches: iterable of (vids, enc [B,F,D]) with B == config.batch_size (the score loader repeats its last
     sample to fill the batch, dataset/MSVD.py:76-93; "PAD" ids are dropped like eval.py:145).  search_method: "greedy",
     ("beam", width), ("sample", temperature, top_k, seed) or ("best_of", n, temperature, top_k, seed) (search.best_of_n: the
-    best of n sampled candidates by the model's length-normalised log-probability).  references: {vid: [caption strings]}.  Returns the score dict
-    of metrics.score_all."""
+    best of n sampled candidates by the model's length-normalised log-probability) or ("best_of_recon", n, temperature, top_k,
+    seed, recon_weight) (the same with recon_weight times the reconstruction error of `reconstructor` subtracted from the score).
+    references: {vid: [caption strings]}.  Returns the score dict of metrics.score_all."""
     decoder.eval()
     dev = next(decoder.parameters()).device
     B, H = config.batch_size, decoder.hidden_size
@@ -246,6 +247,12 @@ def evaluate(config, score_batches, decoder, search_method, idx2word, references
             elif method == "best_of":
                 _, n, temperature, top_k, seed = search_method
                 caps = best_of_n(config, decoder, inp, hid, enc, n, temperature, top_k, seed)[0]
+            elif method == "best_of_recon":
+                _, n, temperature, top_k, seed, recon_weight = search_method
+                if reconstructor is None:
+                    raise ValueError('the "best_of_recon" method needs a reconstructor')
+                reconstructor.eval()
+                caps = best_of_n(config, decoder, inp, hid, enc, n, temperature, top_k, seed, reconstructor, recon_weight)[0]
             else:
                 raise NotImplementedError("Unknown search method: {}".format(method))
         for vid, c in zip(vids, caps):

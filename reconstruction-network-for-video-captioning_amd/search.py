@@ -3,12 +3,15 @@ run as device-side loops in the HIP library (recnet_greedy_search / recnet_beam_
 list building, no host synchronisation per step — one read-back at the end.  sample_search (no counterpart in the
 reference) is greedy_search's loop with a temperature / top-k draw in place of the arg-max (recnet_sample_search).
 score_captions answers the opposite question — how probable are these captions under the model — with the teacher-forced
-forward in eval mode (recnet_score_captions); best_of_n ranks sampled candidates by it.
+forward in eval mode (recnet_score_captions); best_of_n ranks sampled candidates by it.  reconstruction_errors asks the
+question the model was built around — how well does the reconstructor recover a video's features from the decoder states of
+a caption (recnet_reconstruction_error) — and best_of_n can rank by that as well.
 
 Differences from the reference that a caller can observe: `input` / `hidden` must be the start state the
 reference's own `evaluate()` builds (<SOS> tokens, zero hidden state, eval.py:131-141) — that is the only
 state the reference ever passes; beam_width <= 8."""
 import math
+import numbers
 
 import torch
 
@@ -153,39 +156,145 @@ def score_captions(config, decoder, encoder_outputs, captions, temperature=1.0, 
     return lps.cpu().tolist(), cap.cpu().tolist(), ln.cpu().tolist()
 
 
-def pick_best_of_n(caption_logprobs, lengths):
-    """The selection rule of best_of_n on host tables [n][B]: for each caption the candidate k with the largest
-    caption_logprobs[k][b] / lengths[k][b], the lowest k among equals.  Returns (chosen k [B], normalised score [B])."""
+def canonical_captions(captions, T=None, eos=2, pad=0):
+    """Captions as the model saw them in training, where targets are padded: every token behind a caption's first <EOS>
+    becomes <PAD>, and <PAD> rows are appended up to T steps (T None: no rows are added).  captions: a [T0, B] LongTensor or a
+    [T0][B] list of lists (search loops go on feeding a caption its own tokens after its <EOS>: sample_search).  A pure tensor
+    function: a device tensor stays on its device and nothing is read back.  Returns a [max(T0, T), B] LongTensor."""
+    cap = captions if isinstance(captions, torch.Tensor) else torch.tensor([list(r) for r in captions], dtype=torch.long)
+    if cap.dim() != 2 or cap.dtype != torch.long:
+        raise ValueError("captions must be a [T, B] LongTensor (got %s %s)" % (cap.dtype, tuple(cap.shape)))
+    T0, B = cap.shape
+    if T is not None and (int(T) != T or T < T0):
+        raise ValueError("T must be an integer >= the %d steps of the captions (got %r)" % (T0, T))
+    is_eos = (cap == eos).long()
+    behind = (is_eos.cumsum(0) - is_eos) > 0                 # strictly behind the caption's first <EOS>
+    out = cap.masked_fill(behind, pad)
+    if T is not None and T > T0:
+        out = torch.cat([out, out.new_full((int(T) - T0, B), pad)], dim=0)
+    return out
+
+
+def _rec_engine(config, decoder, reconstructor, encoder_outputs):
+    """An engine with decoder AND reconstructor bound, cached on the decoder like _engine's, keyed by the reconstructor's kind
+    as well; the packed weight images are refreshed on every call (see _engine)."""
+    B, F = encoder_outputs.shape[0], encoder_outputs.shape[1]
+    key = ("rec", reconstructor.kind, B, F, encoder_outputs.device, int(config.caption_max_len))   # (Tm and the cml / T^2 rescale are baked in)
+    hit = decoder._step_engines.get(key)
+    if hit is None or hit[1] is not reconstructor:
+        dims = decoder.dims(B, F)
+        dims.update(R=reconstructor.hidden_size, RA=getattr(reconstructor, "attn_size", 0), rec_cell=reconstructor.model_name)
+        hy = decoder.hyper()
+        hy.update(reconstructor_decoder_dropout=reconstructor.decoder_dropout_p, caption_max_len=config.caption_max_len)
+        eng = Engine(dims, reconstructor.kind, decoder.precision, hy, device=encoder_outputs.device)
+        eng.bind_decoder({k: v.data for k, v in decoder.named_tensors().items()})
+        eng.bind_reconstructor({k: v.data for k, v in reconstructor.named_tensors().items()})
+        hit = decoder._step_engines[key] = (eng, reconstructor)
+    eng = hit[0]
+    eng.pack_weights()
+    return eng
+
+
+def _check_reconstructor(config, decoder, reconstructor, encoder_outputs):
+    if getattr(reconstructor, "kind", None) not in ("global", "local"):
+        raise ValueError("reconstructor must be a GlobalReconstructor or a LocalReconstructor (got %r)" % (type(reconstructor).__name__,))
+    if encoder_outputs.dim() != 3:
+        raise ValueError("encoder_outputs must be [B, F, D] (got %s)" % (tuple(encoder_outputs.shape),))
+    if reconstructor.decoder_hidden_size != decoder.hidden_size:
+        raise ValueError("the reconstructor reads decoder states of size %d, the decoder's are %d"
+                         % (reconstructor.decoder_hidden_size, decoder.hidden_size))
+    if reconstructor.hidden_size != encoder_outputs.shape[2] or decoder.encoder_size != encoder_outputs.shape[2]:
+        raise ValueError("encoder_outputs have %d features per frame, the decoder expects %d and the reconstructor rebuilds %d"
+                         % (encoder_outputs.shape[2], decoder.encoder_size, reconstructor.hidden_size))
+    if reconstructor.kind == "global" and reconstructor.caption_max_len != config.caption_max_len:
+        raise ValueError("the global reconstructor was built for caption_max_len %d, the config says %d"
+                         % (reconstructor.caption_max_len, config.caption_max_len))
+    if reconstructor.precision != decoder.precision:
+        raise ValueError("decoder (%s) and reconstructor (%s) must share one precision" % (decoder.precision, reconstructor.precision))
+
+
+def _rec_errors(config, decoder, reconstructor, encoder_outputs, tokens, want_recon=False):
+    """Device tensors (err [B], recon or an empty tensor) of checked, canonical tokens [T, B]."""
+    eng = _rec_engine(config, decoder, reconstructor, encoder_outputs)
+    return _ops.load().reconstruction_error(int(eng.handle.value), encoder_outputs.contiguous(),
+                                            tokens.to(encoder_outputs.device).contiguous(), None, bool(want_recon))
+
+
+def reconstruction_errors(config, decoder, reconstructor, encoder_outputs, captions, T=None, want_recon=False):
+    """How well does the reconstructor recover each video's features from the decoder states of its caption
+    (recnet_reconstruction_error): the teacher-forced decoder forward of score_captions in eval mode, the reconstructor's
+    forward in eval mode on the states it leaves, and per caption the mean squared error the reference only ever averages over
+    the batch (train.py:99-102 global, divided by T; train.py:128 local) — the mean of the returned values is the reference's
+    MSE term.  captions as for score_captions; they are canonicalised first (canonical_captions: <PAD> behind the first <EOS>,
+    <PAD> rows up to T).  The global error depends on T: compare errors of one video only at a common T.  Returns err [B] as a
+    list, or (err, reconstruction) with want_recon: a device tensor, global [B, R] = mean_t out_t, local [B, F, D].
+    Arguments are checked before anything is launched."""
+    _check_reconstructor(config, decoder, reconstructor, encoder_outputs)
+    tokens = _caption_tensor(config, decoder, encoder_outputs.shape[0], captions)
+    if T is not None and (int(T) != T or not tokens.shape[0] <= T <= config.caption_max_len + 1):
+        raise ValueError("T must be an integer between the %d steps of the captions and caption_max_len + 1 = %d (got %r)"
+                         % (tokens.shape[0], config.caption_max_len + 1, T))
+    err, recon = _rec_errors(config, decoder, reconstructor, encoder_outputs, canonical_captions(tokens, T), want_recon)
+    return (err.cpu().tolist(), recon) if want_recon else err.cpu().tolist()
+
+
+def pick_best_of_n(caption_logprobs, lengths, rec_errors=None, recon_weight=0.0):
+    """The selection rule of best_of_n on host tables [n][B]: for each caption the candidate k with the largest score
+    caption_logprobs[k][b] / lengths[k][b] - recon_weight * rec_errors[k][b], the lowest k among equals (rec_errors None: the
+    first term alone).  Returns (chosen k [B], score [B])."""
     n = len(caption_logprobs)
     B = len(caption_logprobs[0]) if n else 0
+
+    def score(k, b):
+        s = caption_logprobs[k][b] / lengths[k][b]
+        return s if rec_errors is None else s - recon_weight * rec_errors[k][b]
     ks, scores = [], []
     for b in range(B):
-        best_k, best = 0, caption_logprobs[0][b] / lengths[0][b]
+        best_k, best = 0, score(0, b)
         for k in range(1, n):
-            s = caption_logprobs[k][b] / lengths[k][b]
+            s = score(k, b)
             if s > best:
                 best_k, best = k, s
         ks.append(best_k); scores.append(best)
     return ks, scores
 
 
-def best_of_n(config, decoder, input, hidden, encoder_outputs, n, temperature=1.0, top_k=0, seed=0):
+def best_of_n(config, decoder, input, hidden, encoder_outputs, n, temperature=1.0, top_k=0, seed=0, reconstructor=None,
+              recon_weight=0.0):
     """n sampled candidates per video, ranked by the model's own length-normalised log-probability.  Candidate k is
     sample_search's rollout with seed (seed + k) & 0xFFFFFFFF; every candidate set is scored by score_captions at temperature
     1 (the sampler's own log-probabilities are under the tempered / cut distribution), the invariants of the features computed
     once and reused for k >= 1; per video the candidate with the largest caption_logprob / length wins, the lowest k among
-    equals.  Returns (captions: [B] token lists cut after their <EOS>, chosen k [B], normalised score [B])."""
+    equals.  With a reconstructor and recon_weight != 0 the score is caption_logprob / length - recon_weight * rec_error
+    (pick_best_of_n): all n candidate sets are canonicalised to the common T* = the longest rollout (the global error depends
+    on T, so the candidates of one video must share it) and passed to the reconstruction error; the n x B errors are read back
+    once.  That costs one more decoder chain pass per candidate set — the reconstruction error runs its own teacher-forced
+    forward instead of reusing the scorer's states — which keeps the log-probability half bit for bit what it is without a
+    reconstructor.  Returns (captions: [B] token lists cut after their <EOS>, chosen k [B], score [B])."""
     if int(n) != n or n < 1:
         raise ValueError("n must be a positive integer (got %r)" % (n,))
+    use_rec = reconstructor is not None and recon_weight != 0
+    if reconstructor is None and recon_weight != 0:
+        raise ValueError("recon_weight = %r needs a reconstructor" % (recon_weight,))
+    if use_rec:
+        if not (isinstance(recon_weight, numbers.Real) and math.isfinite(recon_weight)):   # (numpy scalars are numbers.Real too)
+            raise ValueError("recon_weight must be a finite number (got %r)" % (recon_weight,))
+        recon_weight = float(recon_weight)
+        _check_reconstructor(config, decoder, reconstructor, encoder_outputs)
     cands = [sample_search(config, decoder, input, hidden, encoder_outputs, temperature, top_k, (seed + k) & 0xFFFFFFFF)[0]
              for k in range(int(n))]
-    caps, lens = [], []
+    caps, lens, checked = [], [], []
     for k, toks in enumerate(cands):
         tokens = _caption_tensor(config, decoder, encoder_outputs.shape[0], toks)
         _, cap, ln = _score(decoder, encoder_outputs, tokens, 1.0, k > 0)
-        caps.append(cap); lens.append(ln)
+        caps.append(cap); lens.append(ln); checked.append(tokens)
     caps = torch.stack(caps).cpu().tolist()          # one read-back each for the n x B sums and lengths
     lens = torch.stack(lens).cpu().tolist()
-    ks, scores = pick_best_of_n(caps, lens)
+    errs = None
+    if use_rec:
+        t_star = max(tokens.shape[0] for tokens in checked)
+        errs = [_rec_errors(config, decoder, reconstructor, encoder_outputs, canonical_captions(tokens, t_star))[0] for tokens in checked]
+        errs = torch.stack(errs).cpu().tolist()
+    ks, scores = pick_best_of_n(caps, lens, errs, recon_weight if use_rec else 0.0)
     out = [[cands[k][t][b] for t in range(lens[k][b])] for b, k in enumerate(ks)]
     return out, ks, scores
