@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define RECNET_ABI_VERSION 11
+#define RECNET_ABI_VERSION 12
 #define RECNET_ATTN_NONE 0
 #define RECNET_ATTN_SOFTMAX 1
 #define RECNET_OK 0
@@ -235,6 +235,31 @@ int recnet_score_captions(recnet_handle* h, const float* enc, const int64_t* tok
  * of range. */
 int recnet_reconstruction_error(recnet_handle* h, const float* enc, const int64_t* tokens, const float* hiddens, int32_t T,
                                 float* err_out, float* recon_out, void* stream);
+
+/* ---- N-best beam search on log-probabilities (the reference has no counterpart: recnet_beam_search above restates eval.py:36-120,
+ * whose log(sigmoid) scores compare with nothing else here; DESIGN.md section 11 states the definitions).
+ * recnet_beam_select_rows: one selection step on caller-supplied device arrays.  logits [nb][rows][V] contiguous, read only;
+ * cum [nb][rows]; finished [nb][rows] int32.  A live hypothesis i of row r offers cum[i][r] + log_softmax(logits[i][r])[v] for every
+ * v (the maximum is subtracted before the exponentials; the formulas of recnet_logprob_rows at temperature 1, bit for bit); a
+ * finished one (finished != 0) offers v = <PAD> (0) at cum[i][r] and -inf at every other v.  vals_out / idx_out [rows][beam_width]:
+ * the beam_width largest of the nb * V candidates in descending order, idx = i * V + v, the lowest idx first among equal values.
+ * 1 <= nb <= 8, 1 <= beam_width <= min(8, V).  One launch, no score array, no atomics: two calls give the same bits.  The handle
+ * supplies the device only, as for recnet_sample_rows. */
+int recnet_beam_select_rows(recnet_handle* h, const float* logits, const float* cum, const int32_t* finished, int32_t nb,
+                            int32_t rows, int32_t V, int32_t beam_width, float* vals_out, int32_t* idx_out, void* stream);
+/* recnet_beam_search_nbest: start from <SOS>, the zero state and one hypothesis with cum = 0; at every step the selection above
+ * over the hypotheses of a caption (1 at step 0, then beam_width), all of them advanced by ONE batched decode step; only <EOS> (2)
+ * finishes a hypothesis, len = position of its <EOS> + 1, or the number of steps run when it has none.  n_steps_out (device int32)
+ * = the first step after which every hypothesis of every caption is finished, + 1, else caption_max_len + 1; the device loop has a
+ * fixed trip count and carries the hypotheses over unchanged with <PAD> appended.  Final rank per caption: score = cum /
+ * len^length_alpha descending, lowest beam index among equals (length_alpha = 0: the raw sum).  tokens_out
+ * [beam_width][caption_max_len+1][B] int64, rank-major: each rank is a time-major caption tensor with <PAD> behind <EOS>, which
+ * recnet_score_captions / recnet_reconstruction_error take as it is (rows >= n_steps are <PAD>); cum_out / score_out
+ * [beam_width][B] float, len_out [beam_width][B] int32.  RECNET_EINVAL before any launch: beam_width outside [1, min(8, V)],
+ * length_alpha negative or not finite, a NULL pointer; RECNET_ESTATE: decoder not bound.  Like the other searches the call
+ * overwrites the decoder's loop invariants and clears the saved forward. */
+int recnet_beam_search_nbest(recnet_handle* h, const float* enc, int32_t beam_width, float length_alpha, int64_t* tokens_out,
+                             float* cum_out, int32_t* len_out, float* score_out, int32_t* n_steps_out, void* stream);
 
 /* ---- forward_decoder, train.py:17-75 (teacher forcing, train.py:38,45).
  * enc [B,F,D]; targets [caption_max_len+1, B] int64 (time-major, <PAD>=0, <EOS>=2);

@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # RN_LIB_VARIANT=probe: the probe build (in-kernel time stamps); =acqinv: the cross-check build with acquire fences; =fault: fault injection
 _VARIANT = ("_" + os.environ["RN_LIB_VARIANT"] if os.environ.get("RN_LIB_VARIANT") else "")
 LIB_PATH = os.path.join(_HERE, "csrc", "librecnet_hip%s.so" % _VARIANT)
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 REC_NONE, REC_GLOBAL, REC_LOCAL = 0, 1, 2
 PREC_F32, PREC_BF16 = 0, 1
@@ -155,6 +155,8 @@ EXPORTS["recnet_greedy_search"] = (_i, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_
 EXPORTS["recnet_beam_search"] = (_i, [C.c_void_p, C.c_void_p, _i, C.c_void_p, C.c_void_p, C.c_void_p])
 EXPORTS["recnet_sample_rows"] = (_i, [C.c_void_p, C.c_void_p, _i, _i, _f, _i, C.c_uint32, _i, C.c_void_p, C.c_void_p, C.c_void_p])
 EXPORTS["recnet_sample_search"] = (_i, [C.c_void_p, C.c_void_p, _f, _i, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
+EXPORTS["recnet_beam_select_rows"] = (_i, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _i, _i, _i, _i, C.c_void_p, C.c_void_p, C.c_void_p])
+EXPORTS["recnet_beam_search_nbest"] = (_i, [C.c_void_p, C.c_void_p, _i, _f] + [C.c_void_p] * 6)
 EXPORTS["recnet_logprob_rows"] = (_i, [C.c_void_p, C.c_void_p, C.c_void_p, _i, _i, _f, C.c_void_p, C.c_void_p])
 EXPORTS["recnet_score_captions"] = (_i, [C.c_void_p, C.c_void_p, C.c_void_p, _i, _f, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
 EXPORTS["recnet_reconstruction_error"] = (_i, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _i, C.c_void_p, C.c_void_p, C.c_void_p])

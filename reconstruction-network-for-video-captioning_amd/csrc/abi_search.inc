@@ -16,9 +16,9 @@ static int dec_step_core(recnet_handle* h, const int64_t* tokens, const float* h
   DecCellArgs a;
   a.t = t; a.B = B; a.F = F; a.H = H; a.A = A; a.S = S; a.slab = h_in ? h->slab : nullptr;
   a.Xe = h->Xe; a.P = h->P; a.ldp = h->ld4H; a.Uv = h->Uv; a.ab = h->dP.attn_b; a.w = h->dP.attn_w_weight;
-  a.gru = h->dgru; a.c_prev = h->dgru ? h_in : c_in; a.h_out = h_out; a.c_out = c_out; a.acts = nullptr; a.Wh_out = nullptr; a.att_out = nullptr; a.softmax = h->c.decoder_attn_normalize == RECNET_ATTN_SOFTMAX;
+  a.gru = h->dgru; a.c_prev = h->dgru ? h_in : c_in; a.h_out = h_out; a.c_out = c_out; a.acts = nullptr; a.Wh_out = nullptr; a.att_out = nullptr; a.softmax = h->c.decoder_attn_normalize == RECNET_ATTN_SOFTMAX; a.nc = 0;
   a.h_lp = at_off(h, h->Hs_lp, (size_t)B * h->ldH); a.ld_hlp = h->ldH;
-  launch_dec_cell(h, a, st);
+  launch_dec_cell(h, a, B, st);
   gemm(h, at_off(h, h->Hs_lp, (size_t)B * h->ldH), 0, h->ldH, h->Wo_w, 0, h->ldH, logits, V, h->dP.out_bias, B, V, H, 1.f, 0, st);
   if (train && h->c.decoder_out_dropout > 0.f)
     hipLaunchKernelGGL(logits_drop_kernel, dim3(ew_blocks((size_t)B * V)), dim3(256), 0, st, logits, B, V,
@@ -345,3 +345,96 @@ int recnet_beam_search(recnet_handle* h, const float* enc, int32_t beam_width, i
   return RECNET_OK;
 }
 
+
+// ---- N-best beam search on log-probabilities (the reference has no counterpart; DESIGN.md section 11)
+static int check_beam(int beam_width, int V, float length_alpha) {
+  if (beam_width < 1 || beam_width > 8 || beam_width > V) return fail(RECNET_EINVAL, "beam_width must be in [1, min(8, V)]");
+  if (!std::isfinite(length_alpha) || length_alpha < 0.f) return fail(RECNET_EINVAL, "length_alpha must be finite and >= 0");
+  return RECNET_OK;
+}
+static void launch_beam_select(const float* logits, const float* cum, const int32_t* fin, int nb, int rows, int V, int bw, float* vals,
+                               int32_t* idx, hipStream_t st) {
+  BeamSelArgs a;
+  a.x = logits; a.cum = cum; a.fin = fin; a.nb = nb; a.rows = rows; a.V = V; a.vals = vals; a.idx = idx;
+  switch (bw) {
+#define RN_BSEL(W) case W: hipLaunchKernelGGL((beam_select_kernel<W>), dim3(rows), dim3(256), 0, st, a); break;
+    RN_BSEL(1) RN_BSEL(2) RN_BSEL(3) RN_BSEL(4) RN_BSEL(5) RN_BSEL(6) RN_BSEL(7) RN_BSEL(8)
+#undef RN_BSEL
+  }
+}
+
+int recnet_beam_select_rows(recnet_handle* h, const float* logits, const float* cum, const int32_t* finished, int32_t nb,
+                            int32_t rows, int32_t V, int32_t beam_width, float* vals_out, int32_t* idx_out, void* stream) {
+  REQUIRE_WS(h);
+  if (!logits || !cum || !finished || !vals_out || !idx_out) return fail(RECNET_EINVAL, "null argument");
+  if (rows < 1 || V < 1 || nb < 1 || nb > 8) return fail(RECNET_EINVAL, "rows and V must be positive, nb in [1, 8]");
+  if ((long)nb * V > 0x7fffffffL) return fail(RECNET_EINVAL, "nb * V must fit an int32 index");
+  int r = check_beam(beam_width, V, 0.f); if (r) return r;
+  launch_beam_select(logits, cum, finished, nb, rows, V, beam_width, vals_out, idx_out, (hipStream_t)stream);
+  LAUNCH_OK();
+  return RECNET_OK;
+}
+
+// One decode step for rows = nb * B rows ordered [beam][caption] (dec_step_core's sequence, each launch once for all beams): the
+// embedding, the input product, h . [W_hh ; attn_W]^T, the cell kernel (Uv / P per caption: DecCellArgs::nc) and the vocabulary
+// product, on the search block's own operand rows (bs_*).
+static void beam_step_all(recnet_handle* h, int nb, const int64_t* tokens, const float* h_in, const float* c_in, float* logits,
+                          float* h_out, float* c_out, int t, hipStream_t st) {
+  const int B = h->B, F = h->F, E = h->E, H = h->H, A = h->A, V = h->V, rows = nb * B;
+  const DropDesc dd = mkdrop(h, RN_SITE_DEC_EMBED, h->c.embedding_dropout, 0);
+  // (the kernel's B places a row in (t, b) for the dropout mask and picks tokens[row % B]: eval mode, one step of `rows` tokens)
+  if (h->lp) hipLaunchKernelGGL(embed_fwd_kernel<bf16_t>, dim3(rows), dim3(128), 0, st, h->dP.embedding_weight, (const int64_t*)nullptr, tokens, (bf16_t*)h->bs_emb, h->ldE, rows, E, V, h->c.embedding_scale, dd, t);
+  else hipLaunchKernelGGL(embed_fwd_kernel<float>, dim3(rows), dim3(128), 0, st, h->dP.embedding_weight, (const int64_t*)nullptr, tokens, (float*)h->bs_emb, h->ldE, rows, E, V, h->c.embedding_scale, dd, t);
+  gemm(h, h->bs_emb, 0, h->ldE, h->We_w, 0, h->ldE, h->bs_Xe, 4 * H, h->bsum_d, rows, 4 * H, E, 1.f, 0, st);
+  pack_block(h, h->bs_hlp, h->ldH, h_in, H, rows, H, 1.f, st);
+  const int S = gemm_slabs(h, RN_TAG_DEC_FWD, h->bs_hlp, h->ldH, h->Wcomb, 0, h->ldH, rows, 4 * H + A, H, st);
+  void* h_lp = at_off(h, h->bs_hlp, (size_t)8 * B * h->ldH);
+  DecCellArgs a;
+  a.t = t; a.B = rows; a.F = F; a.H = H; a.A = A; a.S = S; a.slab = h->slab; a.nc = B;
+  a.Xe = h->bs_Xe; a.P = h->P; a.ldp = h->ld4H; a.Uv = h->Uv; a.ab = h->dP.attn_b; a.w = h->dP.attn_w_weight;
+  a.gru = h->dgru; a.c_prev = h->dgru ? h_in : c_in; a.h_out = h_out; a.c_out = c_out; a.acts = nullptr; a.Wh_out = nullptr; a.att_out = nullptr; a.softmax = h->c.decoder_attn_normalize == RECNET_ATTN_SOFTMAX;
+  a.h_lp = h_lp; a.ld_hlp = h->ldH;
+  launch_dec_cell(h, a, rows, st);
+  gemm(h, h_lp, 0, h->ldH, h->Wo_w, 0, h->ldH, logits, V, h->dP.out_bias, rows, V, H, 1.f, 0, st);
+}
+
+int recnet_beam_search_nbest(recnet_handle* h, const float* enc, int32_t beam_width, float length_alpha, int64_t* tokens_out,
+                             float* cum_out, int32_t* len_out, float* score_out, int32_t* n_steps_out, void* stream) {
+  REQUIRE_WS(h);
+  if (!h->dec_bound) return fail(RECNET_ESTATE, "decoder not bound");
+  if (!enc || !tokens_out || !cum_out || !len_out || !score_out || !n_steps_out) return fail(RECNET_EINVAL, "null argument");
+  int r = check_beam(beam_width, h->V, length_alpha); if (r) return r;
+  hipStream_t st = (hipStream_t)stream;
+  const int B = h->B, H = h->H, V = h->V, Tm = h->Tm, bw = beam_width;
+  dec_invariants(h, enc, st);
+  h->fwd_dec_done = 0;
+  hipMemsetAsync(n_steps_out, 0, 4, st);
+  // one initial hypothesis per caption: <SOS>, zero state, cum = 0, not finished
+  hipMemsetAsync(h->sr_h[0], 0, (size_t)B * H * 4, st);
+  hipMemsetAsync(h->sr_c[0], 0, (size_t)B * H * 4, st);
+  hipMemsetAsync(h->sr_cum[0], 0, (size_t)B * 4, st);
+  hipMemsetAsync(h->sr_hist[0], 0, (size_t)B * Tm * 8, st);
+  hipMemsetAsync(h->sr_eos[0], 0, (size_t)B * 4, st);          // fin = 0
+  hipLaunchKernelGGL(fill_i64_kernel, dim3(cdiv(B, 256)), dim3(256), 0, st, h->sr_tok[0], (int64_t)1, B);
+  int cur = 0, nb = 1;
+  for (int t = 0; t < Tm; ++t) {
+    beam_step_all(h, nb, h->sr_tok[cur], h->sr_h[cur], h->sr_c[cur], h->sr_scores, h->sr_hn, h->sr_cn, t, st);
+    launch_beam_select(h->sr_scores, h->sr_cum[cur], h->sr_eos[cur], nb, B, V, bw, h->sr_vals, h->sr_idx, st);
+    BeamNUpdArgs u;
+    u.B = B; u.H = H; u.V = V; u.Tm = Tm; u.bw = bw; u.t = t;
+    u.vals = h->sr_vals; u.idx = h->sr_idx; u.h_next = h->sr_hn; u.c_next = h->dgru ? nullptr : h->sr_cn;
+    u.fin_old = h->sr_eos[cur]; u.hist_old = h->sr_hist[cur];
+    u.h_new = h->sr_h[cur ^ 1]; u.c_new = h->sr_c[cur ^ 1]; u.cum_new = h->sr_cum[cur ^ 1];
+    u.fin_new = h->sr_eos[cur ^ 1]; u.hist_new = h->sr_hist[cur ^ 1]; u.tok_new = h->sr_tok[cur ^ 1];
+    hipLaunchKernelGGL(beam_nbest_update_kernel, dim3(bw, B), dim3(128), 0, st, u);
+    hipLaunchKernelGGL(beam_nbest_stop_kernel, dim3(1), dim3(256), 0, st, h->sr_eos[cur ^ 1], bw * B, t, n_steps_out);
+    cur ^= 1; nb = bw;
+  }
+  hipLaunchKernelGGL(search_finish_kernel, dim3(1), dim3(1), 0, st, n_steps_out, Tm);
+  hipLaunchKernelGGL(beam_nbest_rank_kernel, dim3(cdiv(B, 256)), dim3(256), 0, st, h->sr_cum[cur], h->sr_eos[cur], n_steps_out, B, bw,
+                     length_alpha, cum_out, len_out, score_out, h->bs_order);
+  hipLaunchKernelGGL(beam_nbest_gather_kernel, dim3(cdiv(bw * Tm * B, 256)), dim3(256), 0, st, h->sr_hist[cur], h->bs_order, tokens_out,
+                     B, Tm, bw);
+  LAUNCH_OK();
+  return RECNET_OK;
+}

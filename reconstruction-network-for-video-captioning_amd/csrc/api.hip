@@ -124,6 +124,7 @@ struct recnet_handle {
   // inference search scratch (beam width <= 8)
   float *sr_logits, *sr_scores, *sr_h[2], *sr_c[2], *sr_hn, *sr_cn, *sr_cum[2], *sr_vals;
   int64_t *sr_tok[2], *sr_hist[2]; int32_t *sr_eos[2], *sr_idx;
+  void *bs_emb = nullptr, *bs_hlp = nullptr; float* bs_Xe = nullptr; int32_t* bs_order = nullptr;   // recnet_beam_search_nbest
   int64_t* in_tok = nullptr;   // [Tm][B] tokens fed by the last free-running forward (its backward scatters the embedding gradient by them)
   int free_fwd = 0;
   size_t gws_floats, slab_floats;
@@ -304,6 +305,9 @@ static size_t carve(recnet_handle* h, char* base) {
     }
     h->in_tok = (int64_t*)take(2 * Tm * B);
     h->sr_hn = take(W * B * H); h->sr_cn = take(W * B * H); h->sr_vals = take(W * B); h->sr_idx = (int32_t*)take(W * B);
+    // the batched step of the N-best beam search (all W beams of a step in one pass): embeddings, input products, operand rows of
+    // the incoming ([0, W B)) and outgoing ([W B, 2 W B)) hidden states; its own rows, so that the search works for any Tm >= 1
+    h->bs_emb = takev(W * B * ldE); h->bs_Xe = take(W * B * 4 * H); h->bs_hlp = takev(2 * W * B * ldH); h->bs_order = (int32_t*)take(W * B);
   }
   if (h->kind != RECNET_REC_NONE) {
     h->bsum_r = take(4 * R);

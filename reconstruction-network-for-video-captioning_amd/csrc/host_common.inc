@@ -300,15 +300,19 @@ static int pack_weights(recnet_handle* h, hipStream_t st) {
   return RECNET_OK;
 }
 
-static void launch_dec_cell(recnet_handle* h, const DecCellArgs& a, hipStream_t st) {
+// rows: the captions of the batch, or [beam][caption] rows over args.nc captions (DecCellArgs).  The row count is taken from here
+// alone: the kernels' B (the slab stride) is set to it, whatever the caller left in args.B.
+static void launch_dec_cell(recnet_handle* h, const DecCellArgs& args, int rows, hipStream_t st) {
+  DecCellArgs a = args;
+  a.B = rows;
   if (h->lp && (h->H & 7) == 0 && h->F <= 32 && h->A <= 128 && (h->ld4H & 7) == 0) {
     const size_t smv = (size_t)(h->A + ((h->F + 3) & ~3) + 4 * 512 + 16) * 4;
-    hipLaunchKernelGGL(dec_cell_vec_kernel<bf16_t>, dim3(h->B, cdiv(h->H, 512)), dim3(256), smv, st, a);
+    hipLaunchKernelGGL(dec_cell_vec_kernel<bf16_t>, dim3(rows, cdiv(h->H, 512)), dim3(256), smv, st, a);
     return;
   }
   // units per workgroup: 256 (1024 threads) when H allows, so a caption is covered by H/256 workgroups
   int uc = h->H >= 256 ? 256 : (h->H >= 128 ? 128 : 64);
-  dim3 grid(h->B, cdiv(h->H, uc));
+  dim3 grid(rows, cdiv(h->H, uc));
   const size_t sm = (size_t)(h->A + h->F + 4 * uc + 16) * 4;
   LAUNCH_AT(h, dec_cell_kernel, grid, dim3(4 * uc), sm, st, a);
 }

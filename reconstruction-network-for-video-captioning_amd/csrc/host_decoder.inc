@@ -114,7 +114,7 @@ static int dec_fwd_chain(recnet_handle* h, const float* enc, const int64_t* targ
   DecCellArgs a;
   a.B = B; a.F = F; a.H = H; a.A = A;
   a.P = h->P; a.ldp = h->ld4H; a.Uv = h->Uv; a.ab = h->dP.attn_b; a.w = h->dP.attn_w_weight;
-  a.ld_hlp = h->ldH; a.gru = h->dgru;
+  a.ld_hlp = h->ldH; a.gru = h->dgru; a.nc = 0;
   const float* prev_state = h->dgru ? h->Hs : h->Cs;   // what the pointwise part carries: h_{t-1} (GRU) / c_{t-1}
   for (int t = 0; t < T; ++t) {
     if (free_tokens) {
@@ -134,7 +134,7 @@ static int dec_fwd_chain(recnet_handle* h, const float* enc, const int64_t* targ
     a.h_lp = at_off(h, h->Hs_lp, (size_t)t * B * h->ldH);
     a.acts = h->acts + (size_t)t * B * 4 * H;
     a.Wh_out = h->Wh + (size_t)t * B * A; a.att_out = h->att + (size_t)t * B * F; a.softmax = h->c.decoder_attn_normalize == RECNET_ATTN_SOFTMAX;
-    launch_dec_cell(h, a, st);
+    launch_dec_cell(h, a, B, st);
     if (free_tokens) {   // logits_t, then argmax of what Decoder.forward returns (the dropped-out logits, decoder.py:68-69)
       float* lg = h->logits + (size_t)t * B * V;
       gemm(h, at_off(h, h->Hs_lp, (size_t)t * B * h->ldH), 0, h->ldH, h->Wo_w, 0, h->ldH, lg, V, h->dP.out_bias, B, V, H, 1.f, 0, st);

@@ -31,6 +31,8 @@ struct DecCellArgs {
   float* Wh_out;          // [B][A] or nullptr
   float* att_out;         // [B][F] or nullptr
   int softmax;            // 1: softmax over the frames of the energies (attn_softmax_lds)
+  int nc;                 // 0: rows are captions.  > 0: rows are [beam][caption] over nc captions (B = the row count): row b reads
+                          // the per-caption operands Uv / P of caption b % nc (the batched step of the N-best beam search)
 };
 
 template <typename AT>
@@ -41,6 +43,7 @@ __global__ __launch_bounds__(1024) void dec_cell_kernel(const DecCellArgs p) {
   float* spre = sa + p.F;       // [4 * UC]
   const int NT = blockDim.x, UC = NT >> 2, NW = NT >> 6;
   const int b = blockIdx.x, u0 = blockIdx.y * UC, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int bc = p.nc ? b % p.nc : b;         // the caption whose Uv / P this row reads
   const int H = p.H, A = p.A, F = p.F, W4 = 4 * H, WS = 4 * H + A;
   const size_t zs = (size_t)p.B * WS;
   // ---- every global load of the kernel is issued up front (the kernel is one link of a dependent chain and
@@ -53,7 +56,7 @@ __global__ __launch_bounds__(1024) void dec_cell_kernel(const DecCellArgs p) {
   const AT* pp = nullptr;
   if (u < H) {
     const int col = g * H + u;
-    pp = reinterpret_cast<const AT*>(p.P) + (size_t)b * F * p.ldp + col;
+    pp = reinterpret_cast<const AT*>(p.P) + (size_t)bc * F * p.ldp + col;
 #pragma unroll
     for (int f = 0; f < 32; ++f) if (f < F) pv[f] = (float)pp[(size_t)f * p.ldp];
     pre = p.Xe[(size_t)b * W4 + col];
@@ -71,7 +74,7 @@ __global__ __launch_bounds__(1024) void dec_cell_kernel(const DecCellArgs p) {
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const int k = lane + 64 * j;
-        uvr[i][j] = (f < F && k < A) ? p.Uv[((size_t)b * F + f) * A + k] : 0.f;
+        uvr[i][j] = (f < F && k < A) ? p.Uv[((size_t)bc * F + f) * A + k] : 0.f;
       }
     }
   }
@@ -100,7 +103,7 @@ __global__ __launch_bounds__(1024) void dec_cell_kernel(const DecCellArgs p) {
     }
   } else {
     for (int f = wave; f < F; f += NW) {
-      const float* uv = p.Uv + ((size_t)b * F + f) * A;
+      const float* uv = p.Uv + ((size_t)bc * F + f) * A;
       float s = 0.f;
       for (int k = lane; k < A; k += 64) s += p.w[k] * rn_tanh(swh[k] + uv[k] + p.ab[k]);
       s = wave_sum(s);
@@ -156,6 +159,7 @@ __global__ __launch_bounds__(256) void dec_cell_vec_kernel(const DecCellArgs p) 
   float* sa = swh + p.A;        // [F] (+ pad to 16 B)
   float* spre = sa + ((p.F + 3) & ~3);   // [4][512]
   const int b = blockIdx.x, u0 = blockIdx.y * 512, tid = threadIdx.x, lane = tid & 63, g = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int bc = p.nc ? b % p.nc : b;         // the caption whose Uv / P this row reads
   const int H = p.H, A = p.A, F = p.F, W4 = 4 * H, WS = 4 * H + A;
   const size_t zs = (size_t)p.B * WS;
   const int u = u0 + lane * 8;
@@ -170,7 +174,7 @@ __global__ __launch_bounds__(256) void dec_cell_vec_kernel(const DecCellArgs p) 
   for (int z = 0; z < 4; ++z) { sl[z][0] = x0; sl[z][1] = x0; }
   const int S4 = p.slab ? (p.S < 4 ? p.S : 4) : 0;
   if (live) {
-    const AT* pp = reinterpret_cast<const AT*>(p.P) + (size_t)b * F * p.ldp + col;
+    const AT* pp = reinterpret_cast<const AT*>(p.P) + (size_t)bc * F * p.ldp + col;
 #pragma unroll
     for (int f = 0; f < 32; ++f) { if (f < F) pv[f].load(pp + (size_t)f * p.ldp); else pv[f].zero(); }
     x0 = *reinterpret_cast<const f32x4*>(p.Xe + (size_t)b * W4 + col);
@@ -193,7 +197,7 @@ __global__ __launch_bounds__(256) void dec_cell_vec_kernel(const DecCellArgs p) 
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int k = lane + 64 * j;
-      uvr[i][j] = (f < F && k < A) ? p.Uv[((size_t)b * F + f) * A + k] : 0.f;
+      uvr[i][j] = (f < F && k < A) ? p.Uv[((size_t)bc * F + f) * A + k] : 0.f;
     }
   }
   // attention vectors, c_{t-1} of the pointwise phase, and this thread's column of the attention pre-activation W h

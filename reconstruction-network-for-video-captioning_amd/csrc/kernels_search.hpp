@@ -273,3 +273,157 @@ __global__ void beam_best_kernel(const int64_t* __restrict__ hist, int64_t* __re
   best[i] = hist[(size_t)b * Tm + t];
 }
 
+// =============================================================================================
+// N-best beam search on log-probabilities (the reference has no counterpart; DESIGN.md section 11 states the definitions,
+// tests/beam_ref.py restates them for the CPU).  recnet_beam_search above stays the reference's search.
+// =============================================================================================
+// A candidate (value y, flat index j) as one 64-bit word that orders like the selection: the larger value first, the lower index
+// among equal values (the order of topk_rows_kernel); -0 and +0, and all -inf, share a value key.  0 is below every candidate.
+__device__ __forceinline__ unsigned long long bs_pack(float y, int j) {
+  return ((unsigned long long)sr_key(y) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)j);
+}
+__device__ __forceinline__ float bs_value(unsigned long long c) {
+  const uint32_t k = (uint32_t)(c >> 32);
+  return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu));
+}
+__device__ __forceinline__ int bs_index(unsigned long long c) { return (int)(0xFFFFFFFFu - (uint32_t)c); }
+struct BeamSelArgs {
+  const float* x;                      // logits [nb][rows][V], read only
+  const float* cum;                    // [nb][rows]
+  const int32_t* fin;                  // [nb][rows], != 0: the hypothesis is finished
+  int nb, rows, V;
+  float* vals; int32_t* idx;           // [rows][BW], descending; idx = i * V + v
+};
+// One workgroup per caption.  (1) Per hypothesis the maximum and sum exp(x - max) of its row, the formulas and summation order of
+// logprob_rows_kernel at temperature 1, so that the two agree on a token to the bit.  (2) Every thread walks its strided share of
+// the nb * V candidates cum_i + ((x_v - max_i) - log sum_i) in ascending flat index and keeps its best BW in registers (the insertion
+// is a fully unrolled compare-exchange chain: no runtime-indexed register array, nothing in scratch).  A finished hypothesis offers
+// <PAD> (0) at cum_i and -inf elsewhere: only its first BW + 1 entries can be selected, the others are not visited.  (3) BW block
+// arg-max rounds over the list heads; the thread that owned the winner shifts its list.  Value and index travel as one 64-bit word
+// (bs_pack): one integer compare orders two candidates.  No score array, one pass over the logits for all winners, no atomics: two
+// calls give the same bits.
+template <int BW> __global__ __launch_bounds__(256) void beam_select_kernel(const BeamSelArgs p) {
+  __shared__ float sf[4]; __shared__ float s_mx[8], s_ls[8]; __shared__ unsigned long long wc[2][4];
+  const int r = blockIdx.x, tid = threadIdx.x, V = p.V, nb = p.nb;
+  for (int i = 0; i < nb; ++i) {
+    if (p.fin[i * p.rows + r]) continue;                               // (uniform over the workgroup)
+    const float* x = p.x + ((size_t)i * p.rows + r) * V;
+    float mx = -INFINITY, sum = 0.f;
+    for (int v = tid; v < V; v += 256) mx = fmaxf(mx, x[v]);
+    mx = block_max256(mx, sf);
+    for (int v = tid; v < V; v += 256) sum += rn_exp(x[v] - mx);
+    sum = block_sum256(sum, sf);
+    if (tid == 0) { s_mx[i] = mx; s_ls[i] = logf(sum); }
+  }
+  __syncthreads();
+  unsigned long long lc[BW];
+#pragma unroll
+  for (int k = 0; k < BW; ++k) lc[k] = 0ull;
+  for (int i = 0; i < nb; ++i) {
+    const float c = p.cum[i * p.rows + r];
+    const bool fin = p.fin[i * p.rows + r] != 0;
+    const float* x = p.x + ((size_t)i * p.rows + r) * V;
+    const float mx = fin ? 0.f : s_mx[i], ls = fin ? 0.f : s_ls[i];
+    const int n = fin ? (V < BW + 1 ? V : BW + 1) : V;
+    for (int v = tid; v < n; v += 256) {
+      const float y = fin ? (v == 0 ? c : -INFINITY) : c + ((x[v] - mx) - ls);
+      unsigned long long e = bs_pack(y, i * V + v);
+      if (e > lc[BW - 1]) {
+#pragma unroll
+        for (int k = 0; k < BW; ++k)
+          if (e > lc[k]) { const unsigned long long d = lc[k]; lc[k] = e; e = d; }
+      }
+    }
+  }
+  const int lane = tid & 63, wave = tid >> 6;
+  for (int k = 0; k < BW; ++k) {
+    unsigned long long e = lc[0];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const unsigned long long d = __shfl_xor(e, o);
+      e = d > e ? d : e;
+    }
+    if (lane == 0) wc[k & 1][wave] = e;
+    __syncthreads();
+    e = wc[k & 1][0];
+#pragma unroll
+    for (int w = 1; w < 4; ++w) e = wc[k & 1][w] > e ? wc[k & 1][w] : e;
+    if (e != 0ull && lc[0] == e) {           // (candidates are distinct: their indices are)
+#pragma unroll
+      for (int q = 0; q + 1 < BW; ++q) lc[q] = lc[q + 1];
+      lc[BW - 1] = 0ull;
+    }
+    if (tid == 0) {                           // (e == 0: fewer than BW candidates compared, NaN-free inputs never get here)
+      p.vals[(size_t)r * BW + k] = e ? bs_value(e) : -INFINITY; p.idx[(size_t)r * BW + k] = e ? bs_index(e) : 0;
+    }
+  }
+}
+// regather the hypotheses of the N-best search: new beam k of caption b continues old beam src = idx / V with token idx % V.
+// fin = position of the hypothesis's <EOS> + 1 (its length), 0 while it has none; only <EOS> (2) finishes a hypothesis.
+struct BeamNUpdArgs {
+  int B, H, V, Tm, bw, t;
+  const float* vals; const int32_t* idx;                 // [B][bw]
+  const float* h_next; const float* c_next;              // [nb_old][B][H] states after this step (c_next unused by a GRU)
+  const int32_t* fin_old; const int64_t* hist_old;       // [nb_old][B], [nb_old][B][Tm]
+  float* h_new; float* c_new; float* cum_new; int32_t* fin_new; int64_t* hist_new; int64_t* tok_new;
+};
+__global__ __launch_bounds__(128) void beam_nbest_update_kernel(const BeamNUpdArgs p) {
+  const int k = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+  const int flat = p.idx[b * p.bw + k];
+  const int src = flat / p.V, tok = flat % p.V;
+  const size_t so = ((size_t)src * p.B + b), dn = ((size_t)k * p.B + b);
+  for (int j = tid; j < p.H; j += 128) {
+    p.h_new[dn * p.H + j] = p.h_next[so * p.H + j];
+    if (p.c_next) p.c_new[dn * p.H + j] = p.c_next[so * p.H + j];
+  }
+  for (int j = tid; j < p.Tm; j += 128) p.hist_new[dn * p.Tm + j] = j < p.t ? p.hist_old[so * p.Tm + j] : (j == p.t ? (int64_t)tok : 0);
+  if (tid == 0) {
+    const int f = p.fin_old[so];
+    p.cum_new[dn] = p.vals[b * p.bw + k];
+    p.fin_new[dn] = f ? f : (tok == 2 ? p.t + 1 : 0);
+    p.tok_new[dn] = tok;
+  }
+}
+// the search stops after the first step at which every hypothesis of every caption is finished
+__global__ void beam_nbest_stop_kernel(const int32_t* __restrict__ fin, int n, int t, int32_t* __restrict__ n_steps) {
+  __shared__ int live;
+  if (threadIdx.x == 0) live = 0;
+  __syncthreads();
+  int a = 0;
+  for (int i = threadIdx.x; i < n; i += blockDim.x) a |= (fin[i] == 0);
+  if (a) atomicOr(&live, 1);
+  __syncthreads();
+  if (threadIdx.x == 0 && !live && *n_steps == 0) *n_steps = t + 1;
+}
+// final ranking, one thread per caption: len = fin, or n_steps without an <EOS>; score = cum / len^alpha (alpha = 0: cum);
+// descending score, lowest beam index among equals.  order[r][b] = the beam that takes rank r.
+__global__ __launch_bounds__(256) void beam_nbest_rank_kernel(const float* __restrict__ cum, const int32_t* __restrict__ fin,
+                                                              const int32_t* __restrict__ n_steps, int B, int bw, float alpha,
+                                                              float* __restrict__ cum_out, int32_t* __restrict__ len_out,
+                                                              float* __restrict__ score_out, int32_t* __restrict__ order) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  const int ns = *n_steps;
+  unsigned taken = 0;
+  for (int r = 0; r < bw; ++r) {
+    float best = 0.f; int bi = -1;
+    for (int i = 0; i < bw; ++i) {
+      if (taken >> i & 1) continue;
+      const int f = fin[i * B + b], len = f ? f : ns;
+      const float c = cum[i * B + b];
+      const float s = alpha == 0.f ? c : c / (float)pow((double)len, (double)alpha);
+      if (bi < 0 || s > best) { best = s; bi = i; }
+    }
+    taken |= 1u << bi;
+    const int f = fin[bi * B + b];
+    cum_out[r * B + b] = cum[bi * B + b]; len_out[r * B + b] = f ? f : ns; score_out[r * B + b] = best; order[r * B + b] = bi;
+  }
+}
+// tokens[r][t][b] = hist[order[r][b]][b][t]
+__global__ void beam_nbest_gather_kernel(const int64_t* __restrict__ hist, const int32_t* __restrict__ order, int64_t* __restrict__ tokens,
+                                         int B, int Tm, int bw) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= bw * Tm * B) return;
+  const int b = i % B, t = (i / B) % Tm, r = i / (B * Tm);
+  tokens[i] = hist[((size_t)order[r * B + b] * B + b) * Tm + t];
+}

@@ -11,6 +11,7 @@
 //   train_step_fwd_bwd, train_step, optimizer_step      train.py:248-273
 //   decoder_step, reconstructor_step                    Decoder.forward / *Reconstructor.forward (per-step API)
 //   greedy_search, beam_search                          eval.py:19-120
+//   beam_search_nbest, beam_select_rows                 N-best beam search on log-probabilities (no counterpart)
 //   sample_search, sample_rows                          sampling (no counterpart in the reference; loop shape of eval.py:19-33)
 //   score_captions                                      teacher-forced log-probabilities of given captions (train.py:25,45, eval mode)
 //   reconstruction_error                                per-caption reconstruction error and the reconstruction (train.py:96-102 / :125-128, eval mode)
@@ -212,6 +213,37 @@ std::tuple<at::Tensor, at::Tensor> sample_rows(int64_t h, const at::Tensor& logi
                         (uint32_t)seed, (int32_t)t, toks.data_ptr<int64_t>(), lps.data_ptr<float>(), stream()), "sample_rows");
   return {toks, lps};
 }
+// logits [nb, rows, V], cum [nb, rows] float, finished [nb, rows] int32 -> vals [rows, beam_width], idx [rows, beam_width] int32
+std::tuple<at::Tensor, at::Tensor> beam_select_rows(int64_t h, const at::Tensor& logits, const at::Tensor& cum, const at::Tensor& finished,
+                                                    int64_t beam_width) {
+  chk(logits, at::kFloat, "logits"); chk(cum, at::kFloat, "cum"); chk(finished, at::kInt, "finished");
+  TORCH_CHECK(logits.dim() == 3 && logits.size(0) >= 1 && logits.size(1) >= 1 && logits.size(2) >= 1 && logits.size(1) <= INT32_MAX &&
+              logits.size(2) <= INT32_MAX && logits.size(0) <= 8, "recnet: logits must be [nb <= 8, rows, V], got ", logits.sizes());
+  shape(cum, {logits.size(0), logits.size(1)}, "cum"); shape(finished, {logits.size(0), logits.size(1)}, "finished");
+  TORCH_CHECK(beam_width >= 1 && beam_width <= 8 && beam_width <= logits.size(2), "recnet: beam_width must be in [1, min(8, V)], got ", beam_width);
+  auto vals = at::empty({logits.size(1), beam_width}, logits.options());
+  auto idx = at::empty({logits.size(1), beam_width}, logits.options().dtype(at::kInt));
+  ok(recnet_beam_select_rows(H(h), logits.data_ptr<float>(), cum.data_ptr<float>(), finished.data_ptr<int32_t>(), (int32_t)logits.size(0),
+                             (int32_t)logits.size(1), (int32_t)logits.size(2), (int32_t)beam_width, vals.data_ptr<float>(),
+                             idx.data_ptr<int32_t>(), stream()), "beam_select_rows");
+  return {vals, idx};
+}
+// tokens [beam_width, Tm, B] rank-major, cum / score [beam_width, B] float, len [beam_width, B] int32, n_steps [1] int32
+// (the width is checked here before the outputs are allocated and zeroed; length_alpha by the library, behind those fills)
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> beam_search_nbest(int64_t h, const at::Tensor& enc, int64_t beam_width,
+                                                                                         double length_alpha) {
+  chk_enc(h, enc);
+  TORCH_CHECK(beam_width >= 1 && beam_width <= 8 && beam_width <= dim(h, RECNET_DIM_V), "recnet: beam_width must be in [1, min(8, V)], got ", beam_width);
+  const int64_t B = enc.size(0);
+  auto toks = at::zeros({beam_width, recnet_dim(H(h), RECNET_DIM_TM), B}, enc.options().dtype(at::kLong));
+  auto cum = at::zeros({beam_width, B}, enc.options()), score = at::zeros({beam_width, B}, enc.options());
+  auto len = at::zeros({beam_width, B}, enc.options().dtype(at::kInt));
+  auto n = at::zeros({1}, enc.options().dtype(at::kInt));
+  ok(recnet_beam_search_nbest(H(h), enc.data_ptr<float>(), (int32_t)beam_width, (float)length_alpha, toks.data_ptr<int64_t>(),
+                              cum.data_ptr<float>(), len.data_ptr<int32_t>(), score.data_ptr<float>(), n.data_ptr<int32_t>(), stream()),
+     "beam_search_nbest");
+  return {toks, cum, len, score, n};
+}
 // tokens [T, B] with every entry in [0, V): the caller's duty (search.score_captions checks it)
 std::tuple<at::Tensor, at::Tensor, at::Tensor> score_captions(int64_t h, const c10::optional<at::Tensor>& enc, const at::Tensor& tokens,
                                                               double temperature) {
@@ -278,6 +310,8 @@ TORCH_LIBRARY(recnet, m) {
   m.def("beam_search(int handle, Tensor encoder_outputs, int beam_width) -> (Tensor tokens, Tensor n_steps)");
   m.def("sample_search(int handle, Tensor encoder_outputs, float temperature, int top_k, int seed) -> (Tensor tokens, Tensor logprobs, Tensor n_steps)");
   m.def("sample_rows(int handle, Tensor logits, float temperature, int top_k, int seed, int t) -> (Tensor tokens, Tensor logprobs)");
+  m.def("beam_select_rows(int handle, Tensor logits, Tensor cum, Tensor finished, int beam_width) -> (Tensor vals, Tensor idx)");
+  m.def("beam_search_nbest(int handle, Tensor encoder_outputs, int beam_width, float length_alpha) -> (Tensor tokens, Tensor cum, Tensor lengths, Tensor score, Tensor n_steps)");
   m.def("score_captions(int handle, Tensor? encoder_outputs, Tensor tokens, float temperature) -> (Tensor logprobs, Tensor caption_logprob, Tensor lengths)");
   m.def("reconstruction_error(int handle, Tensor encoder_outputs, Tensor? tokens, Tensor? decoder_hiddens, bool want_recon) -> (Tensor err, Tensor recon)");
 }
@@ -300,6 +334,8 @@ TORCH_LIBRARY_IMPL(recnet, CUDA, m) {
   m.impl("beam_search", beam_search);
   m.impl("sample_search", sample_search);
   m.impl("sample_rows", sample_rows);
+  m.impl("beam_select_rows", beam_select_rows);
+  m.impl("beam_search_nbest", beam_search_nbest);
   m.impl("score_captions", score_captions);
   m.impl("reconstruction_error", reconstruction_error);
 }

@@ -231,6 +231,44 @@ class Engine:
                    "recnet_beam_search")
         return best, n
 
+    def beam_search_nbest(self, enc, beam_width, length_alpha=0.0):
+        """N-best beam search on log-probabilities (recnet_beam_search_nbest; the reference has none).
+        Returns device tensors (tokens [bw, Tm, B] int64 rank-major, each rank canonical: <PAD> behind <EOS>; cum [bw, B]
+        float32; len [bw, B] int32; score [bw, B] float32 = cum / len^length_alpha; n_steps int32[1]).  The library checks
+        beam_width in [1, min(8, V)] and length_alpha finite and >= 0 before any launch of its own; the output tensors are
+        allocated and zeroed here first (for a width outside [1, 8] with one rank), so a refused call has still run those fills:
+        search.beam_search_nbest checks its arguments before anything at all."""
+        d = self.dims
+        _chk_tensor(enc, (d["B"], d["F"], d["D"]), torch.float32, "encoder_outputs")
+        Tm, B, bw = self.hyper["caption_max_len"] + 1, d["B"], (int(beam_width) if 1 <= int(beam_width) <= 8 else 1)
+        toks = torch.zeros(bw, Tm, B, dtype=torch.int64, device=self.device)
+        cum = torch.zeros(bw, B, dtype=torch.float32, device=self.device)
+        ln = torch.zeros(bw, B, dtype=torch.int32, device=self.device)
+        score = torch.zeros(bw, B, dtype=torch.float32, device=self.device)
+        n = torch.zeros(1, dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.recnet_beam_search_nbest(self.handle, _ptr(enc), int(beam_width), float(length_alpha), _ptr(toks),
+                                                     _ptr(cum), _ptr(ln), _ptr(score), _ptr(n), _stream()),
+                   "recnet_beam_search_nbest")
+        return toks, cum, ln, score, n
+
+    def beam_select_rows(self, logits, cum, finished, beam_width):
+        """One selection step of the N-best beam search on caller-supplied device arrays (recnet_beam_select_rows; no decoder
+        needed): logits [nb, rows, V] float32 (only read), cum [nb, rows] float32, finished [nb, rows] int32.  Returns
+        (vals [rows, bw] float32, idx [rows, bw] int32): the bw largest of cum_i + log_softmax(logits_i)[v] (a finished
+        hypothesis offers <PAD> at cum_i alone) in descending order, idx = i * V + v, the lowest idx first among equals."""
+        if logits.dim() != 3:
+            raise RuntimeError("logits: expected [nb, rows, V], got %s" % (tuple(logits.shape),))
+        nb, rows, V = logits.shape
+        _chk_tensor(logits, (nb, rows, V), torch.float32, "logits")
+        _chk_tensor(cum, (nb, rows), torch.float32, "cum")
+        _chk_tensor(finished, (nb, rows), torch.int32, "finished")
+        bw = max(int(beam_width), 1)
+        vals = torch.empty(rows, bw, dtype=torch.float32, device=logits.device)
+        idx = torch.empty(rows, bw, dtype=torch.int32, device=logits.device)
+        _lib.check(self.lib.recnet_beam_select_rows(self.handle, _ptr(logits), _ptr(cum), _ptr(finished), int(nb), int(rows), int(V),
+                                                    int(beam_width), _ptr(vals), _ptr(idx), _stream()), "recnet_beam_select_rows")
+        return vals, idx
+
     def sample_search(self, enc, temperature=1.0, top_k=0, seed=0):
         """The loop of greedy_search with a draw from softmax(logits / temperature) over the top_k largest logits in place of
         the arg-max (recnet_sample_search; the reference has none).  Returns (tokens [Tm, B] int64, logprobs [Tm, B] float32,

@@ -20,7 +20,8 @@ from .api import (GraphedStep, build_decoder, build_reconstructor, forward_decod
 from .checkpoint import load_checkpoint, save_checkpoint
 from .dp import DataParallelTrainStep
 from .feed import DeviceFeeder
-from .search import _caption_tensor, _score, beam_search, best_of_n, greedy_search, sample_search
+from .search import (_caption_tensor, _score, beam_search, beam_search_nbest, best_of_beam, best_of_n, greedy_search,
+                     sample_search)
 
 
 class Trainer:
@@ -219,7 +220,10 @@ def evaluate(config, score_batches, decoder, search_method, idx2word, references
     sample to fill the batch, dataset/MSVD.py:76-93; "PAD" ids are dropped like eval.py:145).  search_method: "greedy",
     ("beam", width), ("sample", temperature, top_k, seed) or ("best_of", n, temperature, top_k, seed) (search.best_of_n: the
     best of n sampled candidates by the model's length-normalised log-probability) or ("best_of_recon", n, temperature, top_k,
-    seed, recon_weight) (the same with recon_weight times the reconstruction error of `reconstructor` subtracted from the score).
+    seed, recon_weight) (the same with recon_weight times the reconstruction error of `reconstructor` subtracted from the score),
+    ("beam_nbest", width, length_alpha) (search.beam_search_nbest: the first-ranked hypothesis of the beam search on
+    log-probabilities) or ("beam_recon", width, length_alpha, recon_weight) (search.best_of_beam: its hypotheses reranked with the
+    reconstruction error of `reconstructor`).
     references: {vid: [caption strings]}.  Returns the score dict of metrics.score_all."""
     decoder.eval()
     dev = next(decoder.parameters()).device
@@ -253,6 +257,15 @@ def evaluate(config, score_batches, decoder, search_method, idx2word, references
                     raise ValueError('the "best_of_recon" method needs a reconstructor')
                 reconstructor.eval()
                 caps = best_of_n(config, decoder, inp, hid, enc, n, temperature, top_k, seed, reconstructor, recon_weight)[0]
+            elif method == "beam_nbest":
+                _, width, length_alpha = search_method
+                caps = [hyps[0][0] for hyps in beam_search_nbest(config, decoder, inp, hid, enc, width, length_alpha)]
+            elif method == "beam_recon":
+                _, width, length_alpha, recon_weight = search_method
+                if reconstructor is None:
+                    raise ValueError('the "beam_recon" method needs a reconstructor')
+                reconstructor.eval()
+                caps = best_of_beam(config, decoder, inp, hid, enc, width, length_alpha, reconstructor, recon_weight)[0]
             else:
                 raise NotImplementedError("Unknown search method: {}".format(method))
         for vid, c in zip(vids, caps):

@@ -5,7 +5,9 @@ reference) is greedy_search's loop with a temperature / top-k draw in place of t
 score_captions answers the opposite question — how probable are these captions under the model — with the teacher-forced
 forward in eval mode (recnet_score_captions); best_of_n ranks sampled candidates by it.  reconstruction_errors asks the
 question the model was built around — how well does the reconstructor recover a video's features from the decoder states of
-a caption (recnet_reconstruction_error) — and best_of_n can rank by that as well.
+a caption (recnet_reconstruction_error) — and best_of_n can rank by that as well.  beam_search_nbest is a second beam search,
+standard in its scoring (sums of log-softmax, recnet_beam_search_nbest): it returns all beam_width hypotheses with scores that
+compare with score_captions / sequence_logprob, and best_of_beam reranks them by the reconstructor.
 
 Differences from the reference that a caller can observe: `input` / `hidden` must be the start state the
 reference's own `evaluate()` builds (<SOS> tokens, zero hidden state, eval.py:131-141) — that is the only
@@ -297,4 +299,79 @@ def best_of_n(config, decoder, input, hidden, encoder_outputs, n, temperature=1.
         errs = torch.stack(errs).cpu().tolist()
     ks, scores = pick_best_of_n(caps, lens, errs, recon_weight if use_rec else 0.0)
     out = [[cands[k][t][b] for t in range(lens[k][b])] for b, k in enumerate(ks)]
+    return out, ks, scores
+
+
+def _nbest_engine(config, decoder, encoder_outputs):
+    """_engine with the caption length of `config` (Tm is baked into the handle), cached under its own key."""
+    B, F = encoder_outputs.shape[0], encoder_outputs.shape[1]
+    key = ("nbest", B, F, encoder_outputs.device, int(config.caption_max_len))
+    eng = decoder._step_engines.get(key)
+    if eng is None:
+        hy = decoder.hyper()
+        hy.update(caption_max_len=int(config.caption_max_len))
+        eng = Engine(decoder.dims(B, F), None, decoder.precision, hy, device=encoder_outputs.device)
+        eng.bind_decoder({k: v.data for k, v in decoder.named_tensors().items()})
+        decoder._step_engines[key] = eng
+    eng.pack_weights()           # (see _engine)
+    return eng
+
+
+def _check_beam(decoder, beam_width, length_alpha):
+    if int(beam_width) != beam_width or not 1 <= beam_width <= min(8, decoder.output_size):
+        raise ValueError("beam_width must be an integer in [1, %d] (got %r)" % (min(8, decoder.output_size), beam_width))
+    if not (isinstance(length_alpha, numbers.Real) and math.isfinite(length_alpha) and length_alpha >= 0):
+        raise ValueError("length_alpha must be a finite number >= 0 (got %r)" % (length_alpha,))
+
+
+def _beam_nbest(config, decoder, input, hidden, encoder_outputs, beam_width, length_alpha):
+    """Device tensors (tokens [bw, n_steps, B], cum [bw, B], len [bw, B], score [bw, B]) of the checked search."""
+    _check_beam(decoder, beam_width, length_alpha)
+    _check_start(config, input, hidden)
+    eng = _nbest_engine(config, decoder, encoder_outputs)
+    toks, cum, ln, score, n = _ops.load().beam_search_nbest(int(eng.handle.value), encoder_outputs.contiguous(), int(beam_width),
+                                                            float(length_alpha))
+    return toks[:, :int(n.item())], cum, ln, score
+
+
+def beam_search_nbest(config, decoder, input, hidden, encoder_outputs, beam_width, length_alpha=0.0):
+    """Beam search on the model's own log-probabilities (the reference has no counterpart: its beam_search scores by
+    log(sigmoid(logit))).  A hypothesis' value is the sum of log_softmax(logits_t)[token_t] over its steps — what score_captions
+    and sequence_logprob return for it; a hypothesis with <EOS> is finished and carried with <PAD>; at every step the beam_width
+    best continuations of all hypotheses of a caption are kept, the lowest (beam, token) among equals; the search ends when every
+    hypothesis is finished or after caption_max_len + 1 steps.  The final order is by cum / length^length_alpha (0: the raw
+    sum).  All beams of a step run as one batched decode step on the device (recnet_beam_search_nbest).  Returns, per caption, a
+    list of beam_width tuples (tokens cut after <EOS>, cum, length, score) in rank order.  Arguments are checked before anything
+    is launched."""
+    toks, cum, ln, score = _beam_nbest(config, decoder, input, hidden, encoder_outputs, beam_width, length_alpha)
+    toks, cum, ln, score = toks.cpu().tolist(), cum.cpu().tolist(), ln.cpu().tolist(), score.cpu().tolist()
+    B = encoder_outputs.shape[0]
+    return [[([toks[r][t][b] for t in range(ln[r][b])], cum[r][b], ln[r][b], score[r][b]) for r in range(int(beam_width))]
+            for b in range(B)]
+
+
+def best_of_beam(config, decoder, input, hidden, encoder_outputs, beam_width, length_alpha=0.0, reconstructor=None,
+                 recon_weight=0.0):
+    """The beam_width hypotheses of beam_search_nbest, reranked like best_of_n's candidates: per video the rank k with the largest
+    cum / length - recon_weight * rec_error (pick_best_of_n, the lowest k among equals; without a reconstructor or with
+    recon_weight = 0 the first term alone).  Every rank of the search is a canonical [n_steps, B] caption set already, so it goes to
+    the reconstruction error as it is, all ranks at the common T = n_steps (the global error depends on T).  Returns what
+    best_of_n returns: (captions: [B] token lists cut after their <EOS>, chosen k [B], score [B])."""
+    use_rec = reconstructor is not None and recon_weight != 0
+    if reconstructor is None and recon_weight != 0:
+        raise ValueError("recon_weight = %r needs a reconstructor" % (recon_weight,))
+    if use_rec:
+        if not (isinstance(recon_weight, numbers.Real) and math.isfinite(recon_weight)):
+            raise ValueError("recon_weight must be a finite number (got %r)" % (recon_weight,))
+        recon_weight = float(recon_weight)
+        _check_reconstructor(config, decoder, reconstructor, encoder_outputs)
+    toks, cum, ln, _ = _beam_nbest(config, decoder, input, hidden, encoder_outputs, beam_width, length_alpha)
+    errs = None
+    if use_rec:
+        errs = torch.stack([_rec_errors(config, decoder, reconstructor, encoder_outputs, toks[r])[0]
+                            for r in range(int(beam_width))]).cpu().tolist()
+    lens = ln.cpu().tolist()
+    ks, scores = pick_best_of_n(cum.cpu().tolist(), lens, errs, recon_weight if use_rec else 0.0)
+    toks = toks.cpu().tolist()
+    out = [[toks[k][t][b] for t in range(lens[k][b])] for b, k in enumerate(ks)]
     return out, ks, scores

@@ -1,0 +1,76 @@
+"""Times the two beam searches and the greedy search on one handle: recnet_beam_search (the reference's
+search: one decode step per beam, a score array, one arg-max pass per winner) against recnet_beam_search_nbest (all beams in one
+batched step, the fused selection) at each width, greedy_search beside width 1, and the selection kernel alone at nb = 8 on
+random logits, at the benchmark's decoder shape, bf16.  HIP events around `reps` back-to-back calls after `warmup` calls of each;
+the calls are alternated over `rounds` rounds so that drift hits them alike; the median and the spread over rounds are printed as
+one JSON line.  The selection kernel reads each logit three times (maximum, sum of exponentials, candidates): `select_bytes_read`
+counts all three passes, `select_bytes_unique` the array once.
+
+    python tools/beam_time.py [--B 100 --F 28 --D 1536 --V 4188 --widths 1,5,8 --reps 10 --warmup 3 --rounds 5]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    for k, v in (("B", 100), ("F", 28), ("D", 1536), ("E", 468), ("H", 512), ("A", 128), ("V", 4188), ("reps", 10), ("warmup", 3),
+                 ("rounds", 5)):
+        ap.add_argument("--" + k, type=int, default=v)
+    ap.add_argument("--widths", default="1,5,8")
+    ap.add_argument("--length_alpha", type=float, default=0.7)
+    ap.add_argument("--precision", default="bf16")
+    a = ap.parse_args()
+    widths = [int(w) for w in a.widths.split(",")]
+    import recnet_amd as R
+    from recnet_amd.engine import Engine
+    if not torch.cuda.is_available():
+        raise SystemExit("beam_time.py needs a GPU: a CPU run says nothing about these times")
+    torch.manual_seed(0)
+    dec = R.Decoder("LSTM", 1, a.D, a.E, 1, a.H, a.A, a.V, 0.5, 0.5, 0.5, precision=a.precision).cuda().eval()
+    eng = Engine(dec.dims(a.B, a.F), None, a.precision, dec.hyper(), device="cuda")
+    eng.bind_decoder({k: v.data for k, v in dec.named_tensors().items()})
+    eng.pack_weights()
+    enc = torch.randn(a.B, a.F, a.D, device="cuda")
+    nb = 8
+    logits = torch.randn(nb, a.B, a.V, device="cuda") * 2.0
+    cum = -torch.rand(nb, a.B, device="cuda") * 6.0
+    fin = torch.zeros(nb, a.B, dtype=torch.int32, device="cuda")
+    calls = {"greedy_search": lambda: eng.greedy_search(enc)}
+    for w in widths:
+        calls["beam_search_w%d" % w] = lambda w=w: eng.beam_search(enc, w)
+        calls["beam_search_nbest_w%d" % w] = lambda w=w: eng.beam_search_nbest(enc, w, a.length_alpha)
+        calls["beam_select_rows_nb8_w%d" % w] = lambda w=w: eng.beam_select_rows(logits, cum, fin, w)
+    for fn in calls.values():
+        for _ in range(a.warmup):
+            fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in calls}
+    for _ in range(a.rounds):
+        for k, fn in calls.items():
+            reps = a.reps * (20 if k.startswith("beam_select") else 1)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(reps):
+                fn()
+            e1.record()
+            e1.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / reps)
+    assert eng.chain_status() == 0
+    out = {"shape": {k: getattr(a, k) for k in ("B", "F", "D", "E", "H", "A", "V")}, "T": eng.hyper["caption_max_len"] + 1,
+           "precision": a.precision, "length_alpha": a.length_alpha, "reps": a.reps, "rounds": a.rounds,
+           "select_bytes_unique": nb * a.B * a.V * 4, "select_bytes_read": 3 * nb * a.B * a.V * 4}
+    for k, v in ms.items():
+        out[k + "_ms"] = {"median": statistics.median(v), "min": min(v), "max": max(v)}
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
