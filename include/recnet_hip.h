@@ -20,6 +20,8 @@
 extern "C" {
 #endif
 
+/* 12 still: recnet_beam_select_rows_constrained / recnet_beam_search_nbest_constrained were added without changing any existing
+ * entry.  A library built before them is still caught: a binding that resolves every declared symbol fails on the first one missing. */
 #define RECNET_ABI_VERSION 12
 #define RECNET_ATTN_NONE 0
 #define RECNET_ATTN_SOFTMAX 1
@@ -260,6 +262,32 @@ int recnet_beam_select_rows(recnet_handle* h, const float* logits, const float* 
  * overwrites the decoder's loop invariants and clears the saved forward. */
 int recnet_beam_search_nbest(recnet_handle* h, const float* enc, int32_t beam_width, float length_alpha, int64_t* tokens_out,
                              float* cum_out, int32_t* len_out, float* score_out, int32_t* n_steps_out, void* stream);
+
+/* ---- Constrained N-best beam search (no counterpart in the reference).  Three controls on what a LIVE
+ * hypothesis offers at step t, given its generated history w_0 .. w_{t-1} (<SOS> is not part of it).  Token v is not offered if
+ *   v is one of the n_banned ids of `banned`;  or  v = <EOS> (2) and t < min_length;  or  no_repeat_ngram = n >= 1, t >= n - 1 and
+ *   (w_{t-n+1} .. w_{t-1}, v) already occurs in the history as an n-gram (n = 1: every token of the history).
+ * Tokens compare as ids (<PAD> emitted by a live hypothesis is a token like any other).  Finished hypotheses are untouched: <PAD>
+ * at cum and nothing else.  There is no renormalisation: an offered candidate keeps cum + log_softmax(logits)[v] over all V
+ * entries, so cum remains the model's log-probability of the hypothesis and recnet_score_captions reproduces it as before.
+ * Ranges: 0 <= no_repeat_ngram, min_length <= caption_max_len (0 = off), 0 <= n_banned <= 16, the ids distinct, in [0, V) and
+ * not <EOS>.  `banned` is a HOST pointer, read during the call (the ids travel as kernel arguments: no device array, no copy, the
+ * call stays capturable); it may be NULL when n_banned = 0.  With any constraint on, the call is refused unless every live
+ * hypothesis is left at least beam_width offered tokens: beam_width + n_banned + caption_max_len + 1 <= V for the search,
+ * beam_width + n_banned + t + 1 <= V for the kernel alone; -inf is then never selected from a live hypothesis.  With all three off
+ * both entries launch the kernels of the unconstrained entries above and return the same bits.
+ * recnet_beam_select_rows_constrained: recnet_beam_select_rows plus hist [nb][rows][Tm] int64 (device; entries [0, t) are read; may
+ * be NULL when no_repeat_ngram = 0) and the step 0 <= t < Tm.  recnet_beam_search_nbest_constrained: recnet_beam_search_nbest with
+ * the constrained selection at every step; recnet_beam_search_nbest is this entry with the constraints off.  RECNET_EINVAL before
+ * any launch for everything above. */
+int recnet_beam_select_rows_constrained(recnet_handle* h, const float* logits, const float* cum, const int32_t* finished,
+                                        const int64_t* hist, int32_t nb, int32_t rows, int32_t V, int32_t Tm, int32_t t,
+                                        int32_t beam_width, int32_t no_repeat_ngram, int32_t min_length, const int32_t* banned,
+                                        int32_t n_banned, float* vals_out, int32_t* idx_out, void* stream);
+int recnet_beam_search_nbest_constrained(recnet_handle* h, const float* enc, int32_t beam_width, float length_alpha,
+                                         int32_t no_repeat_ngram, int32_t min_length, const int32_t* banned, int32_t n_banned,
+                                         int64_t* tokens_out, float* cum_out, int32_t* len_out, float* score_out, int32_t* n_steps_out,
+                                         void* stream);
 
 /* ---- forward_decoder, train.py:17-75 (teacher forcing, train.py:38,45).
  * enc [B,F,D]; targets [caption_max_len+1, B] int64 (time-major, <PAD>=0, <EOS>=2);

@@ -11,7 +11,8 @@ OPS_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "lib
 OP_NAMES = ("forward_decoder", "forward_decoder_free", "backward_decoder", "forward_reconstructor", "backward_reconstructor",
             "add_reg_grad", "train_step_fwd_bwd", "train_step", "optimizer_step", "clip_grad_norm", "decoder_step",
             "reconstructor_step", "greedy_search", "beam_search", "sample_search", "sample_rows", "score_captions",
-            "reconstruction_error", "beam_search_nbest", "beam_select_rows")
+            "reconstruction_error", "beam_search_nbest", "beam_select_rows", "beam_search_nbest_constrained",
+            "beam_select_rows_constrained")
 _loaded = False
 
 

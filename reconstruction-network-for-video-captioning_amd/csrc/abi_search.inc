@@ -352,25 +352,86 @@ static int check_beam(int beam_width, int V, float length_alpha) {
   if (!std::isfinite(length_alpha) || length_alpha < 0.f) return fail(RECNET_EINVAL, "length_alpha must be finite and >= 0");
   return RECNET_OK;
 }
+// the constraints of the constrained form (DESIGN.md section 12), checked: all off = the unconstrained kernel is launched
+struct BeamBans {
+  int ngram = 0, min_len = 0, n_banned = 0;
+  int32_t banned[16] = {};
+  bool on() const { return ngram > 0 || min_len > 0 || n_banned > 0; }
+};
+// ranges (Tm = caption_max_len + 1), distinct ids in [0, V) without <EOS>, and room for beam_width offered tokens on every live
+// hypothesis: it bans at most n_banned + t_max + 1 tokens (t_max: the last step the call runs)
+static int check_beam_bans(int no_repeat_ngram, int min_length, const int32_t* banned, int n_banned, int beam_width, int V, int Tm,
+                           int t_max, BeamBans* out) {
+  if (no_repeat_ngram < 0 || no_repeat_ngram > Tm - 1) return fail(RECNET_EINVAL, "no_repeat_ngram must be in [0, caption_max_len]");
+  if (min_length < 0 || min_length > Tm - 1) return fail(RECNET_EINVAL, "min_length must be in [0, caption_max_len]");
+  if (n_banned < 0 || n_banned > 16) return fail(RECNET_EINVAL, "n_banned must be in [0, 16]");
+  if (n_banned > 0 && !banned) return fail(RECNET_EINVAL, "null argument");
+  out->ngram = no_repeat_ngram; out->min_len = min_length; out->n_banned = n_banned;
+  for (int k = 0; k < n_banned; ++k) {
+    if (banned[k] < 0 || banned[k] >= V) return fail(RECNET_EINVAL, "banned tokens must be in [0, V)");
+    if (banned[k] == 2) return fail(RECNET_EINVAL, "<EOS> cannot be banned");
+    for (int j = 0; j < k; ++j)
+      if (banned[j] == banned[k]) return fail(RECNET_EINVAL, "banned tokens must be distinct");
+    out->banned[k] = banned[k];
+  }
+  if (out->on() && (long)beam_width + n_banned + t_max + 1 > (long)V)
+    return fail(RECNET_EINVAL, "the vocabulary is too small for these constraints: beam_width + n_banned + steps + 1 must not exceed V");
+  if (out->on() && (size_t)(8 + 8 * bs_ban_stride(t_max)) * 4 > 48 * 1024) return fail(RECNET_EINVAL, "caption_max_len too large for the ban lists");
+  return RECNET_OK;
+}
+// bans == nullptr or all off: the unconstrained instantiation; else the constrained one on hist [nb][rows][Tm] at step t
 static void launch_beam_select(const float* logits, const float* cum, const int32_t* fin, int nb, int rows, int V, int bw, float* vals,
-                               int32_t* idx, hipStream_t st) {
-  BeamSelArgs a;
+                               int32_t* idx, hipStream_t st, const BeamBans* bans = nullptr, const int64_t* hist = nullptr, int Tm = 0,
+                               int t = 0) {
+  BeamSelCArgs a;
   a.x = logits; a.cum = cum; a.fin = fin; a.nb = nb; a.rows = rows; a.V = V; a.vals = vals; a.idx = idx;
+  if (!bans || !bans->on()) {
+    const BeamSelArgs& u = a;
+    switch (bw) {
+#define RN_BSEL(W) case W: hipLaunchKernelGGL((beam_select_kernel<W>), dim3(rows), dim3(256), 0, st, u); break;
+      RN_BSEL(1) RN_BSEL(2) RN_BSEL(3) RN_BSEL(4) RN_BSEL(5) RN_BSEL(6) RN_BSEL(7) RN_BSEL(8)
+#undef RN_BSEL
+    }
+    return;
+  }
+  a.hist = hist; a.Tm = Tm; a.t = t; a.ngram = bans->ngram; a.min_len = bans->min_len; a.n_banned = bans->n_banned;
+  for (int k = 0; k < 16; ++k) a.banned[k] = bans->banned[k];
+  const size_t sm = (size_t)(8 + nb * bs_ban_stride(t)) * 4;
   switch (bw) {
-#define RN_BSEL(W) case W: hipLaunchKernelGGL((beam_select_kernel<W>), dim3(rows), dim3(256), 0, st, a); break;
+#define RN_BSEL(W) case W: hipLaunchKernelGGL((beam_select_kernel<W, true>), dim3(rows), dim3(256), sm, st, a); break;
     RN_BSEL(1) RN_BSEL(2) RN_BSEL(3) RN_BSEL(4) RN_BSEL(5) RN_BSEL(6) RN_BSEL(7) RN_BSEL(8)
 #undef RN_BSEL
   }
 }
 
-int recnet_beam_select_rows(recnet_handle* h, const float* logits, const float* cum, const int32_t* finished, int32_t nb,
-                            int32_t rows, int32_t V, int32_t beam_width, float* vals_out, int32_t* idx_out, void* stream) {
-  REQUIRE_WS(h);
+static int check_select_rows(const float* logits, const float* cum, const int32_t* finished, int nb, int rows, int V, int beam_width,
+                             const float* vals_out, const int32_t* idx_out) {
   if (!logits || !cum || !finished || !vals_out || !idx_out) return fail(RECNET_EINVAL, "null argument");
   if (rows < 1 || V < 1 || nb < 1 || nb > 8) return fail(RECNET_EINVAL, "rows and V must be positive, nb in [1, 8]");
   if ((long)nb * V > 0x7fffffffL) return fail(RECNET_EINVAL, "nb * V must fit an int32 index");
-  int r = check_beam(beam_width, V, 0.f); if (r) return r;
+  return check_beam(beam_width, V, 0.f);
+}
+
+int recnet_beam_select_rows(recnet_handle* h, const float* logits, const float* cum, const int32_t* finished, int32_t nb,
+                            int32_t rows, int32_t V, int32_t beam_width, float* vals_out, int32_t* idx_out, void* stream) {
+  REQUIRE_WS(h);
+  int r = check_select_rows(logits, cum, finished, nb, rows, V, beam_width, vals_out, idx_out); if (r) return r;
   launch_beam_select(logits, cum, finished, nb, rows, V, beam_width, vals_out, idx_out, (hipStream_t)stream);
+  LAUNCH_OK();
+  return RECNET_OK;
+}
+
+int recnet_beam_select_rows_constrained(recnet_handle* h, const float* logits, const float* cum, const int32_t* finished,
+                                        const int64_t* hist, int32_t nb, int32_t rows, int32_t V, int32_t Tm, int32_t t,
+                                        int32_t beam_width, int32_t no_repeat_ngram, int32_t min_length, const int32_t* banned,
+                                        int32_t n_banned, float* vals_out, int32_t* idx_out, void* stream) {
+  REQUIRE_WS(h);
+  int r = check_select_rows(logits, cum, finished, nb, rows, V, beam_width, vals_out, idx_out); if (r) return r;
+  if (Tm < 1 || t < 0 || t >= Tm) return fail(RECNET_EINVAL, "Tm must be positive and t in [0, Tm)");
+  BeamBans bans;
+  r = check_beam_bans(no_repeat_ngram, min_length, banned, n_banned, beam_width, V, Tm, t, &bans); if (r) return r;
+  if (no_repeat_ngram > 0 && !hist) return fail(RECNET_EINVAL, "null argument");
+  launch_beam_select(logits, cum, finished, nb, rows, V, beam_width, vals_out, idx_out, (hipStream_t)stream, &bans, hist, Tm, t);
   LAUNCH_OK();
   return RECNET_OK;
 }
@@ -398,12 +459,16 @@ static void beam_step_all(recnet_handle* h, int nb, const int64_t* tokens, const
   gemm(h, h_lp, 0, h->ldH, h->Wo_w, 0, h->ldH, logits, V, h->dP.out_bias, rows, V, H, 1.f, 0, st);
 }
 
-int recnet_beam_search_nbest(recnet_handle* h, const float* enc, int32_t beam_width, float length_alpha, int64_t* tokens_out,
-                             float* cum_out, int32_t* len_out, float* score_out, int32_t* n_steps_out, void* stream) {
+int recnet_beam_search_nbest_constrained(recnet_handle* h, const float* enc, int32_t beam_width, float length_alpha,
+                                         int32_t no_repeat_ngram, int32_t min_length, const int32_t* banned, int32_t n_banned,
+                                         int64_t* tokens_out, float* cum_out, int32_t* len_out, float* score_out, int32_t* n_steps_out,
+                                         void* stream) {
   REQUIRE_WS(h);
   if (!h->dec_bound) return fail(RECNET_ESTATE, "decoder not bound");
   if (!enc || !tokens_out || !cum_out || !len_out || !score_out || !n_steps_out) return fail(RECNET_EINVAL, "null argument");
   int r = check_beam(beam_width, h->V, length_alpha); if (r) return r;
+  BeamBans bans;
+  r = check_beam_bans(no_repeat_ngram, min_length, banned, n_banned, beam_width, h->V, h->Tm, h->Tm - 1, &bans); if (r) return r;
   hipStream_t st = (hipStream_t)stream;
   const int B = h->B, H = h->H, V = h->V, Tm = h->Tm, bw = beam_width;
   dec_invariants(h, enc, st);
@@ -419,7 +484,7 @@ int recnet_beam_search_nbest(recnet_handle* h, const float* enc, int32_t beam_wi
   int cur = 0, nb = 1;
   for (int t = 0; t < Tm; ++t) {
     beam_step_all(h, nb, h->sr_tok[cur], h->sr_h[cur], h->sr_c[cur], h->sr_scores, h->sr_hn, h->sr_cn, t, st);
-    launch_beam_select(h->sr_scores, h->sr_cum[cur], h->sr_eos[cur], nb, B, V, bw, h->sr_vals, h->sr_idx, st);
+    launch_beam_select(h->sr_scores, h->sr_cum[cur], h->sr_eos[cur], nb, B, V, bw, h->sr_vals, h->sr_idx, st, &bans, h->sr_hist[cur], Tm, t);
     BeamNUpdArgs u;
     u.B = B; u.H = H; u.V = V; u.Tm = Tm; u.bw = bw; u.t = t;
     u.vals = h->sr_vals; u.idx = h->sr_idx; u.h_next = h->sr_hn; u.c_next = h->dgru ? nullptr : h->sr_cn;
@@ -437,4 +502,10 @@ int recnet_beam_search_nbest(recnet_handle* h, const float* enc, int32_t beam_wi
                      B, Tm, bw);
   LAUNCH_OK();
   return RECNET_OK;
+}
+
+int recnet_beam_search_nbest(recnet_handle* h, const float* enc, int32_t beam_width, float length_alpha, int64_t* tokens_out,
+                             float* cum_out, int32_t* len_out, float* score_out, int32_t* n_steps_out, void* stream) {
+  return recnet_beam_search_nbest_constrained(h, enc, beam_width, length_alpha, 0, 0, nullptr, 0, tokens_out, cum_out, len_out, score_out,
+                                              n_steps_out, stream);
 }

@@ -294,6 +294,18 @@ struct BeamSelArgs {
   int nb, rows, V;
   float* vals; int32_t* idx;           // [rows][BW], descending; idx = i * V + v
 };
+// The constrained form (tests/beam_constrained_ref.py restates it): a live hypothesis with the generated history
+// w_0 .. w_{t-1} (its hist row) does not offer token v when v is one of the static bans, when v = <EOS> and t < min_len, or when
+// ngram = n >= 1 and appending v would repeat an n-gram of the history.  Finished hypotheses are untouched.
+struct BeamSelCArgs : BeamSelArgs {
+  const int64_t* hist;                 // [nb][rows][Tm], entries [0, t) are read (may be null when ngram = 0)
+  int Tm, t, ngram, min_len, n_banned; // 0 <= t < Tm; ngram, min_len in [0, Tm); n_banned in [0, 16]
+  int32_t banned[16];                  // distinct ids in [0, V), none of them <EOS>
+};
+template <bool CONSTRAINED> struct BeamSelArgsOf { typedef BeamSelArgs type; };
+template <> struct BeamSelArgsOf<true> { typedef BeamSelCArgs type; };
+// dynamic LDS of the constrained form: 8 list lengths, then per hypothesis a ban list of at most t + 17 ids
+__host__ __device__ __forceinline__ int bs_ban_stride(int t) { return t + 17; }
 // One workgroup per caption.  (1) Per hypothesis the maximum and sum exp(x - max) of its row, the formulas and summation order of
 // logprob_rows_kernel at temperature 1, so that the two agree on a token to the bit.  (2) Every thread walks its strided share of
 // the nb * V candidates cum_i + ((x_v - max_i) - log sum_i) in ascending flat index and keeps its best BW in registers (the insertion
@@ -302,9 +314,52 @@ struct BeamSelArgs {
 // arg-max rounds over the list heads; the thread that owned the winner shifts its list.  Value and index travel as one 64-bit word
 // (bs_pack): one integer compare orders two candidates.  No score array, one pass over the logits for all winners, no atomics: two
 // calls give the same bits.
-template <int BW> __global__ __launch_bounds__(256) void beam_select_kernel(const BeamSelArgs p) {
+// CONSTRAINED: (0) one wave per live hypothesis writes its ban list into LDS, 64 entries at a time: lane j < t - n + 1 compares the
+// n - 1 tokens at j with the last n - 1 and bans hist[j + n - 1] on a match; the static bans and the conditional <EOS> follow; a
+// ballot packs the entries that hold an id, in lane order (duplicates stay, they are harmless).  The barrier that ends (1) publishes
+// the lists.  In (2) a thread only ever meets the tokens v = tid (mod 256), so once per hypothesis it reads the list and keeps the
+// one banned id of its own residue in a register (`many`: it has two or more, then the list is scanned); the test sits behind the
+// compare that guards an insertion, so the common path keeps its one compare and the walk reads no LDS (scanning the list there
+// instead costs 50-90 %: a wave takes the branch whenever one of its 64 lanes inserts).  A banned candidate
+// enters no thread's list and (3) is unchanged.  The values of the offered candidates are those of the unconstrained form, bit for
+// bit: (1) still runs over all V entries (no renormalisation).
+template <int BW, bool CONSTRAINED = false> __global__ __launch_bounds__(256)
+void beam_select_kernel(const typename BeamSelArgsOf<CONSTRAINED>::type p) {
   __shared__ float sf[4]; __shared__ float s_mx[8], s_ls[8]; __shared__ unsigned long long wc[2][4];
+  extern __shared__ __attribute__((aligned(16))) int bs_ban[];
   const int r = blockIdx.x, tid = threadIdx.x, V = p.V, nb = p.nb;
+  int S = 0;
+  if constexpr (CONSTRAINED) {
+    S = bs_ban_stride(p.t);
+    const int ln = tid & 63, t = p.t, n = p.ngram;
+    const int ng = n >= 1 && t >= n - 1 ? t - n + 1 : 0;
+    const int used = ng + p.n_banned + (t < p.min_len ? 1 : 0);                 // <= t + 17
+    for (int i = tid >> 6; i < nb; i += 4) {
+      const bool live = p.fin[i * p.rows + r] == 0;
+      int cnt = 0;
+      for (int c = 0; c < used; c += 64) {                                      // (uniform over the wave)
+        const int j = c + ln;
+        int id = -1;
+        if (live && j < ng) {                                                   // (ng > 0 only with ngram >= 1: hist is not null)
+          const int64_t* hs = p.hist + ((size_t)i * p.rows + r) * p.Tm;
+          bool same = true;
+          for (int k = 0; k + 1 < n; ++k) same &= hs[j + k] == hs[t - n + 1 + k];
+          const int64_t w = hs[j + n - 1];
+          if (same && w >= 0 && w < V) id = (int)w;
+        } else if (live && j < used) {
+          const int s = j - ng;
+          id = 2;                                                               // behind the static bans: <EOS> while t < min_len
+#pragma unroll
+          for (int k = 0; k < 16; ++k)
+            if (s == k && k < p.n_banned) id = p.banned[k];
+        }
+        const unsigned long long m = __ballot(id >= 0);
+        if (id >= 0) bs_ban[8 + i * S + cnt + __popcll(m & ((1ull << ln) - 1ull))] = id;
+        cnt += __popcll(m);
+      }
+      if (ln == 0) bs_ban[i] = cnt;
+    }
+  }
   for (int i = 0; i < nb; ++i) {
     if (p.fin[i * p.rows + r]) continue;                               // (uniform over the workgroup)
     const float* x = p.x + ((size_t)i * p.rows + r) * V;
@@ -325,13 +380,30 @@ template <int BW> __global__ __launch_bounds__(256) void beam_select_kernel(cons
     const float* x = p.x + ((size_t)i * p.rows + r) * V;
     const float mx = fin ? 0.f : s_mx[i], ls = fin ? 0.f : s_ls[i];
     const int n = fin ? (V < BW + 1 ? V : BW + 1) : V;
+    const int nban = CONSTRAINED ? bs_ban[i] : 0;                      // (0 for a finished hypothesis)
+    const int* ban = bs_ban + 8 + i * S;
+    int mine = -1; bool many = false;                                  // the banned id this thread can meet: v = tid (mod 256)
+    if constexpr (CONSTRAINED) {
+      for (int j = 0; j < nban; ++j) {
+        const int id = ban[j];
+        if ((id & 255) == tid) { many |= mine >= 0 && mine != id; mine = id; }
+      }
+    }
     for (int v = tid; v < n; v += 256) {
       const float y = fin ? (v == 0 ? c : -INFINITY) : c + ((x[v] - mx) - ls);
       unsigned long long e = bs_pack(y, i * V + v);
       if (e > lc[BW - 1]) {
+        bool offered = true;
+        if constexpr (CONSTRAINED) {
+          offered = v != mine;
+          if (many)                                                    // (two banned ids 256 apart or more: rare)
+            for (int j = 0; j < nban; ++j) offered &= ban[j] != v;
+        }
+        if (offered) {
 #pragma unroll
-        for (int k = 0; k < BW; ++k)
-          if (e > lc[k]) { const unsigned long long d = lc[k]; lc[k] = e; e = d; }
+          for (int k = 0; k < BW; ++k)
+            if (e > lc[k]) { const unsigned long long d = lc[k]; lc[k] = e; e = d; }
+        }
       }
     }
   }

@@ -12,6 +12,7 @@
 //   decoder_step, reconstructor_step                    Decoder.forward / *Reconstructor.forward (per-step API)
 //   greedy_search, beam_search                          eval.py:19-120
 //   beam_search_nbest, beam_select_rows                 N-best beam search on log-probabilities (no counterpart)
+//   beam_search_nbest_constrained, beam_select_rows_constrained   the same with no-repeat n-grams, a minimum length, banned ids (section 12)
 //   sample_search, sample_rows                          sampling (no counterpart in the reference; loop shape of eval.py:19-33)
 //   score_captions                                      teacher-forced log-probabilities of given captions (train.py:25,45, eval mode)
 //   reconstruction_error                                per-caption reconstruction error and the reconstruction (train.py:96-102 / :125-128, eval mode)
@@ -244,6 +245,68 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> beam_sear
      "beam_search_nbest");
   return {toks, cum, len, score, n};
 }
+// ---- the constrained forms: the ids of `banned` travel to the library as a host array
+static std::vector<int32_t> ban_ids(at::IntArrayRef banned) {
+  TORCH_CHECK(banned.size() <= 16, "recnet: at most 16 banned tokens, got ", banned.size());
+  std::vector<int32_t> ids;
+  for (const int64_t v : banned) {
+    TORCH_CHECK(v >= 0 && v <= INT32_MAX, "recnet: banned token out of range: ", v);
+    ids.push_back((int32_t)v);
+  }
+  return ids;
+}
+static void chk_constraints(int64_t no_repeat_ngram, int64_t min_length) {
+  TORCH_CHECK(no_repeat_ngram >= 0 && no_repeat_ngram <= INT32_MAX && min_length >= 0 && min_length <= INT32_MAX,
+              "recnet: no_repeat_ngram / min_length out of range");
+}
+// beam_select_rows plus hist [nb, rows, Tm] int64 (undefined: allowed when no_repeat_ngram = 0) and the step t
+std::tuple<at::Tensor, at::Tensor> beam_select_rows_constrained(int64_t h, const at::Tensor& logits, const at::Tensor& cum,
+                                                                const at::Tensor& finished, const c10::optional<at::Tensor>& hist, int64_t t,
+                                                                int64_t beam_width, int64_t no_repeat_ngram, int64_t min_length,
+                                                                at::IntArrayRef banned) {
+  chk(logits, at::kFloat, "logits"); chk(cum, at::kFloat, "cum"); chk(finished, at::kInt, "finished");
+  TORCH_CHECK(logits.dim() == 3 && logits.size(0) >= 1 && logits.size(1) >= 1 && logits.size(2) >= 1 && logits.size(1) <= INT32_MAX &&
+              logits.size(2) <= INT32_MAX && logits.size(0) <= 8, "recnet: logits must be [nb <= 8, rows, V], got ", logits.sizes());
+  shape(cum, {logits.size(0), logits.size(1)}, "cum"); shape(finished, {logits.size(0), logits.size(1)}, "finished");
+  TORCH_CHECK(beam_width >= 1 && beam_width <= 8 && beam_width <= logits.size(2), "recnet: beam_width must be in [1, min(8, V)], got ", beam_width);
+  TORCH_CHECK(t >= 0 && t < INT32_MAX, "recnet: t out of range");
+  chk_constraints(no_repeat_ngram, min_length);
+  const auto ids = ban_ids(banned);
+  int64_t Tm = INT32_MAX;            // (no hist: only min_length / the static bans can be on, and they read no history)
+  const int64_t* hp = nullptr;
+  if (hist.has_value() && hist->defined()) {
+    chk(*hist, at::kLong, "hist");
+    TORCH_CHECK(hist->dim() == 3 && hist->size(0) == logits.size(0) && hist->size(1) == logits.size(1) && hist->size(2) >= 1 &&
+                hist->size(2) <= INT32_MAX, "recnet: hist must be [nb, rows, Tm], got ", hist->sizes());
+    Tm = hist->size(2); hp = hist->data_ptr<int64_t>();
+  }
+  auto vals = at::empty({logits.size(1), beam_width}, logits.options());
+  auto idx = at::empty({logits.size(1), beam_width}, logits.options().dtype(at::kInt));
+  ok(recnet_beam_select_rows_constrained(H(h), logits.data_ptr<float>(), cum.data_ptr<float>(), finished.data_ptr<int32_t>(), hp,
+                                         (int32_t)logits.size(0), (int32_t)logits.size(1), (int32_t)logits.size(2), (int32_t)Tm, (int32_t)t,
+                                         (int32_t)beam_width, (int32_t)no_repeat_ngram, (int32_t)min_length, ids.data(), (int32_t)ids.size(),
+                                         vals.data_ptr<float>(), idx.data_ptr<int32_t>(), stream()), "beam_select_rows_constrained");
+  return {vals, idx};
+}
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> beam_search_nbest_constrained(int64_t h, const at::Tensor& enc,
+                                                                                                     int64_t beam_width, double length_alpha,
+                                                                                                     int64_t no_repeat_ngram, int64_t min_length,
+                                                                                                     at::IntArrayRef banned) {
+  chk_enc(h, enc);
+  TORCH_CHECK(beam_width >= 1 && beam_width <= 8 && beam_width <= dim(h, RECNET_DIM_V), "recnet: beam_width must be in [1, min(8, V)], got ", beam_width);
+  chk_constraints(no_repeat_ngram, min_length);
+  const auto ids = ban_ids(banned);
+  const int64_t B = enc.size(0);
+  auto toks = at::zeros({beam_width, recnet_dim(H(h), RECNET_DIM_TM), B}, enc.options().dtype(at::kLong));
+  auto cum = at::zeros({beam_width, B}, enc.options()), score = at::zeros({beam_width, B}, enc.options());
+  auto len = at::zeros({beam_width, B}, enc.options().dtype(at::kInt));
+  auto n = at::zeros({1}, enc.options().dtype(at::kInt));
+  ok(recnet_beam_search_nbest_constrained(H(h), enc.data_ptr<float>(), (int32_t)beam_width, (float)length_alpha, (int32_t)no_repeat_ngram,
+                                          (int32_t)min_length, ids.data(), (int32_t)ids.size(), toks.data_ptr<int64_t>(), cum.data_ptr<float>(),
+                                          len.data_ptr<int32_t>(), score.data_ptr<float>(), n.data_ptr<int32_t>(), stream()),
+     "beam_search_nbest_constrained");
+  return {toks, cum, len, score, n};
+}
 // tokens [T, B] with every entry in [0, V): the caller's duty (search.score_captions checks it)
 std::tuple<at::Tensor, at::Tensor, at::Tensor> score_captions(int64_t h, const c10::optional<at::Tensor>& enc, const at::Tensor& tokens,
                                                               double temperature) {
@@ -312,6 +375,8 @@ TORCH_LIBRARY(recnet, m) {
   m.def("sample_rows(int handle, Tensor logits, float temperature, int top_k, int seed, int t) -> (Tensor tokens, Tensor logprobs)");
   m.def("beam_select_rows(int handle, Tensor logits, Tensor cum, Tensor finished, int beam_width) -> (Tensor vals, Tensor idx)");
   m.def("beam_search_nbest(int handle, Tensor encoder_outputs, int beam_width, float length_alpha) -> (Tensor tokens, Tensor cum, Tensor lengths, Tensor score, Tensor n_steps)");
+  m.def("beam_select_rows_constrained(int handle, Tensor logits, Tensor cum, Tensor finished, Tensor? hist, int t, int beam_width, int no_repeat_ngram, int min_length, int[] banned) -> (Tensor vals, Tensor idx)");
+  m.def("beam_search_nbest_constrained(int handle, Tensor encoder_outputs, int beam_width, float length_alpha, int no_repeat_ngram, int min_length, int[] banned) -> (Tensor tokens, Tensor cum, Tensor lengths, Tensor score, Tensor n_steps)");
   m.def("score_captions(int handle, Tensor? encoder_outputs, Tensor tokens, float temperature) -> (Tensor logprobs, Tensor caption_logprob, Tensor lengths)");
   m.def("reconstruction_error(int handle, Tensor encoder_outputs, Tensor? tokens, Tensor? decoder_hiddens, bool want_recon) -> (Tensor err, Tensor recon)");
 }
@@ -336,6 +401,8 @@ TORCH_LIBRARY_IMPL(recnet, CUDA, m) {
   m.impl("sample_rows", sample_rows);
   m.impl("beam_select_rows", beam_select_rows);
   m.impl("beam_search_nbest", beam_search_nbest);
+  m.impl("beam_select_rows_constrained", beam_select_rows_constrained);
+  m.impl("beam_search_nbest_constrained", beam_search_nbest_constrained);
   m.impl("score_captions", score_captions);
   m.impl("reconstruction_error", reconstruction_error);
 }

@@ -231,8 +231,20 @@ class Engine:
                    "recnet_beam_search")
         return best, n
 
-    def beam_search_nbest(self, enc, beam_width, length_alpha=0.0):
+    @staticmethod
+    def _ban_array(banned_tokens):
+        """The ids as the int32 host array the constrained entries read during the call (None when there are none)."""
+        ids = [int(v) for v in banned_tokens]
+        if any(not -2 ** 31 <= v < 2 ** 31 for v in ids):
+            raise RuntimeError("banned_tokens: ids must fit an int32 (got %r)" % (ids,))
+        return ((C.c_int32 * len(ids))(*ids) if ids else None), len(ids)
+
+    def beam_search_nbest(self, enc, beam_width, length_alpha=0.0, no_repeat_ngram=0, min_length=0, banned_tokens=()):
         """N-best beam search on log-probabilities (recnet_beam_search_nbest; the reference has none).
+        no_repeat_ngram / min_length / banned_tokens (all off by default, and then the call is
+        recnet_beam_search_nbest's as before): no n-gram twice in a hypothesis, no <EOS> before min_length tokens, ids that are never
+        emitted; any of them on: recnet_beam_search_nbest_constrained, which checks their ranges and that the vocabulary leaves
+        every live hypothesis beam_width offered tokens.
         Returns device tensors (tokens [bw, Tm, B] int64 rank-major, each rank canonical: <PAD> behind <EOS>; cum [bw, B]
         float32; len [bw, B] int32; score [bw, B] float32 = cum / len^length_alpha; n_steps int32[1]).  The library checks
         beam_width in [1, min(8, V)] and length_alpha finite and >= 0 before any launch of its own; the output tensors are
@@ -246,16 +258,27 @@ class Engine:
         ln = torch.zeros(bw, B, dtype=torch.int32, device=self.device)
         score = torch.zeros(bw, B, dtype=torch.float32, device=self.device)
         n = torch.zeros(1, dtype=torch.int32, device=self.device)
-        _lib.check(self.lib.recnet_beam_search_nbest(self.handle, _ptr(enc), int(beam_width), float(length_alpha), _ptr(toks),
-                                                     _ptr(cum), _ptr(ln), _ptr(score), _ptr(n), _stream()),
-                   "recnet_beam_search_nbest")
+        if no_repeat_ngram == 0 and min_length == 0 and len(banned_tokens) == 0:
+            _lib.check(self.lib.recnet_beam_search_nbest(self.handle, _ptr(enc), int(beam_width), float(length_alpha), _ptr(toks),
+                                                         _ptr(cum), _ptr(ln), _ptr(score), _ptr(n), _stream()),
+                       "recnet_beam_search_nbest")
+        else:
+            ban, n_ban = self._ban_array(banned_tokens)
+            _lib.check(self.lib.recnet_beam_search_nbest_constrained(self.handle, _ptr(enc), int(beam_width), float(length_alpha),
+                                                                     int(no_repeat_ngram), int(min_length), ban, n_ban, _ptr(toks),
+                                                                     _ptr(cum), _ptr(ln), _ptr(score), _ptr(n), _stream()),
+                       "recnet_beam_search_nbest_constrained")
         return toks, cum, ln, score, n
 
-    def beam_select_rows(self, logits, cum, finished, beam_width):
+    def beam_select_rows(self, logits, cum, finished, beam_width, hist=None, t=None, no_repeat_ngram=0, min_length=0,
+                         banned_tokens=()):
         """One selection step of the N-best beam search on caller-supplied device arrays (recnet_beam_select_rows; no decoder
         needed): logits [nb, rows, V] float32 (only read), cum [nb, rows] float32, finished [nb, rows] int32.  Returns
         (vals [rows, bw] float32, idx [rows, bw] int32): the bw largest of cum_i + log_softmax(logits_i)[v] (a finished
-        hypothesis offers <PAD> at cum_i alone) in descending order, idx = i * V + v, the lowest idx first among equals."""
+        hypothesis offers <PAD> at cum_i alone) in descending order, idx = i * V + v, the lowest idx first among equals.
+        With t given (the step, and hist [nb, rows, Tm] int64: the tokens generated so far in entries [0, t); needed for
+        no_repeat_ngram only) the call is recnet_beam_select_rows_constrained's: what a live hypothesis does not offer is
+        DESIGN.md section 12's."""
         if logits.dim() != 3:
             raise RuntimeError("logits: expected [nb, rows, V], got %s" % (tuple(logits.shape),))
         nb, rows, V = logits.shape
@@ -265,8 +288,23 @@ class Engine:
         bw = max(int(beam_width), 1)
         vals = torch.empty(rows, bw, dtype=torch.float32, device=logits.device)
         idx = torch.empty(rows, bw, dtype=torch.int32, device=logits.device)
-        _lib.check(self.lib.recnet_beam_select_rows(self.handle, _ptr(logits), _ptr(cum), _ptr(finished), int(nb), int(rows), int(V),
-                                                    int(beam_width), _ptr(vals), _ptr(idx), _stream()), "recnet_beam_select_rows")
+        if t is None:
+            if hist is not None or no_repeat_ngram != 0 or min_length != 0 or len(banned_tokens) != 0:
+                raise RuntimeError("the constrained selection needs the step t")
+            _lib.check(self.lib.recnet_beam_select_rows(self.handle, _ptr(logits), _ptr(cum), _ptr(finished), int(nb), int(rows), int(V),
+                                                        int(beam_width), _ptr(vals), _ptr(idx), _stream()), "recnet_beam_select_rows")
+            return vals, idx
+        Tm = 0x7FFFFFFF              # (no hist: only min_length / the static bans can be on, and they read no history)
+        if hist is not None:
+            if hist.dim() != 3:
+                raise RuntimeError("hist: expected [nb, rows, Tm], got %s" % (tuple(hist.shape),))
+            Tm = hist.shape[2]
+            _chk_tensor(hist, (nb, rows, Tm), torch.int64, "hist")
+        ban, n_ban = self._ban_array(banned_tokens)
+        _lib.check(self.lib.recnet_beam_select_rows_constrained(self.handle, _ptr(logits), _ptr(cum), _ptr(finished), _ptr(hist), int(nb),
+                                                                int(rows), int(V), int(Tm), int(t), int(beam_width), int(no_repeat_ngram),
+                                                                int(min_length), ban, n_ban, _ptr(vals), _ptr(idx), _stream()),
+                   "recnet_beam_select_rows_constrained")
         return vals, idx
 
     def sample_search(self, enc, temperature=1.0, top_k=0, seed=0):

@@ -214,6 +214,22 @@ class Trainer:
 
 
 # ---------------------------------------------------------------------- scoring, eval.py:123-169
+_CONSTRAINT_KEYS = ("no_repeat_ngram", "min_length", "banned_tokens")
+
+
+def _split_constraints(search_method, n):
+    """(the first n fields of a beam method tuple, its optional trailing dict of constraints); anything else is refused."""
+    search_method = tuple(search_method)
+    if len(search_method) == n:
+        return search_method, {}
+    if len(search_method) != n + 1 or not isinstance(search_method[n], dict):
+        raise ValueError("the %r method takes %d fields and an optional dict of constraints (got %r)" % (search_method[0], n, search_method))
+    unknown = sorted(set(search_method[n]) - set(_CONSTRAINT_KEYS))
+    if unknown:
+        raise ValueError("unknown constraint %s: the keys are %s" % (", ".join(map(repr, unknown)), ", ".join(_CONSTRAINT_KEYS)))
+    return search_method[:n], dict(search_method[n])
+
+
 @torch.no_grad()
 def evaluate(config, score_batches, decoder, search_method, idx2word, references, reconstructor=None):
     """score_batches: iterable of (vids, enc [B,F,D]) with B == config.batch_size (the score loader repeats its last
@@ -223,7 +239,9 @@ def evaluate(config, score_batches, decoder, search_method, idx2word, references
     seed, recon_weight) (the same with recon_weight times the reconstruction error of `reconstructor` subtracted from the score),
     ("beam_nbest", width, length_alpha) (search.beam_search_nbest: the first-ranked hypothesis of the beam search on
     log-probabilities) or ("beam_recon", width, length_alpha, recon_weight) (search.best_of_beam: its hypotheses reranked with the
-    reconstruction error of `reconstructor`).
+    reconstruction error of `reconstructor`).  The two beam forms take an optional trailing dict with the keys no_repeat_ngram,
+    min_length and banned_tokens (the constraints of search.beam_search_nbest): ("beam_nbest", width, length_alpha, {...}),
+    ("beam_recon", width, length_alpha, recon_weight, {...}).
     references: {vid: [caption strings]}.  Returns the score dict of metrics.score_all."""
     decoder.eval()
     dev = next(decoder.parameters()).device
@@ -258,14 +276,14 @@ def evaluate(config, score_batches, decoder, search_method, idx2word, references
                 reconstructor.eval()
                 caps = best_of_n(config, decoder, inp, hid, enc, n, temperature, top_k, seed, reconstructor, recon_weight)[0]
             elif method == "beam_nbest":
-                _, width, length_alpha = search_method
-                caps = [hyps[0][0] for hyps in beam_search_nbest(config, decoder, inp, hid, enc, width, length_alpha)]
+                (_, width, length_alpha), constraints = _split_constraints(search_method, 3)     # (search_method itself stays: it is parsed again for the next batch)
+                caps = [hyps[0][0] for hyps in beam_search_nbest(config, decoder, inp, hid, enc, width, length_alpha, **constraints)]
             elif method == "beam_recon":
-                _, width, length_alpha, recon_weight = search_method
+                (_, width, length_alpha, recon_weight), constraints = _split_constraints(search_method, 4)
                 if reconstructor is None:
                     raise ValueError('the "beam_recon" method needs a reconstructor')
                 reconstructor.eval()
-                caps = best_of_beam(config, decoder, inp, hid, enc, width, length_alpha, reconstructor, recon_weight)[0]
+                caps = best_of_beam(config, decoder, inp, hid, enc, width, length_alpha, reconstructor, recon_weight, **constraints)[0]
             else:
                 raise NotImplementedError("Unknown search method: {}".format(method))
         for vid, c in zip(vids, caps):

@@ -324,17 +324,51 @@ def _check_beam(decoder, beam_width, length_alpha):
         raise ValueError("length_alpha must be a finite number >= 0 (got %r)" % (length_alpha,))
 
 
-def _beam_nbest(config, decoder, input, hidden, encoder_outputs, beam_width, length_alpha):
+def _check_constraints(config, decoder, beam_width, no_repeat_ngram, min_length, banned_tokens):
+    """The checks of the constrained search; returns the banned ids as a list of ints."""
+    cml, V = int(config.caption_max_len), decoder.output_size
+    for name, v in (("no_repeat_ngram", no_repeat_ngram), ("min_length", min_length)):
+        if not isinstance(v, numbers.Real) or int(v) != v or not 0 <= v <= cml:
+            raise ValueError("%s must be an integer in [0, caption_max_len = %d] (got %r)" % (name, cml, v))
+    try:
+        ids = list(banned_tokens)
+    except TypeError:
+        raise ValueError("banned_tokens must be a sequence of token ids (got %r)" % (banned_tokens,))
+    if len(ids) > 16:
+        raise ValueError("at most 16 tokens can be banned (got %d)" % len(ids))
+    for v in ids:
+        if not isinstance(v, numbers.Real) or int(v) != v or not 0 <= v < V:
+            raise ValueError("banned_tokens must be token ids in [0, %d) (got %r)" % (V, v))
+        if v == 2:
+            raise ValueError("<EOS> (2) cannot be banned: no hypothesis could finish")
+    ids = [int(v) for v in ids]
+    if len(set(ids)) != len(ids):
+        raise ValueError("banned_tokens must be distinct (got %r)" % (ids,))
+    if (no_repeat_ngram or min_length or ids) and beam_width + len(ids) + cml + 1 > V:
+        raise ValueError("the vocabulary (%d) is too small for these constraints: beam_width + banned tokens + caption_max_len + 1 = %d "
+                         "must not exceed it" % (V, beam_width + len(ids) + cml + 1))
+    return ids
+
+
+def _beam_nbest(config, decoder, input, hidden, encoder_outputs, beam_width, length_alpha, no_repeat_ngram=0, min_length=0,
+                banned_tokens=()):
     """Device tensors (tokens [bw, n_steps, B], cum [bw, B], len [bw, B], score [bw, B]) of the checked search."""
     _check_beam(decoder, beam_width, length_alpha)
+    ids = _check_constraints(config, decoder, beam_width, no_repeat_ngram, min_length, banned_tokens)
     _check_start(config, input, hidden)
     eng = _nbest_engine(config, decoder, encoder_outputs)
-    toks, cum, ln, score, n = _ops.load().beam_search_nbest(int(eng.handle.value), encoder_outputs.contiguous(), int(beam_width),
-                                                            float(length_alpha))
+    if no_repeat_ngram or min_length or ids:
+        toks, cum, ln, score, n = _ops.load().beam_search_nbest_constrained(int(eng.handle.value), encoder_outputs.contiguous(),
+                                                                            int(beam_width), float(length_alpha), int(no_repeat_ngram),
+                                                                            int(min_length), ids)
+    else:
+        toks, cum, ln, score, n = _ops.load().beam_search_nbest(int(eng.handle.value), encoder_outputs.contiguous(), int(beam_width),
+                                                                float(length_alpha))
     return toks[:, :int(n.item())], cum, ln, score
 
 
-def beam_search_nbest(config, decoder, input, hidden, encoder_outputs, beam_width, length_alpha=0.0):
+def beam_search_nbest(config, decoder, input, hidden, encoder_outputs, beam_width, length_alpha=0.0, no_repeat_ngram=0, min_length=0,
+                      banned_tokens=()):
     """Beam search on the model's own log-probabilities (the reference has no counterpart: its beam_search scores by
     log(sigmoid(logit))).  A hypothesis' value is the sum of log_softmax(logits_t)[token_t] over its steps — what score_captions
     and sequence_logprob return for it; a hypothesis with <EOS> is finished and carried with <PAD>; at every step the beam_width
@@ -342,8 +376,14 @@ def beam_search_nbest(config, decoder, input, hidden, encoder_outputs, beam_widt
     hypothesis is finished or after caption_max_len + 1 steps.  The final order is by cum / length^length_alpha (0: the raw
     sum).  All beams of a step run as one batched decode step on the device (recnet_beam_search_nbest).  Returns, per caption, a
     list of beam_width tuples (tokens cut after <EOS>, cum, length, score) in rank order.  Arguments are checked before anything
-    is launched."""
-    toks, cum, ln, score = _beam_nbest(config, decoder, input, hidden, encoder_outputs, beam_width, length_alpha)
+    is launched.
+    Three controls on what a hypothesis may emit, all off by default (recnet_beam_search_nbest_constrained):
+    no_repeat_ngram = n > 0: no n-gram occurs twice in a hypothesis; min_length = m: no <EOS> before m tokens; banned_tokens: at
+    most 16 ids that are never emitted (not <EOS>).  They remove candidates inside the selection, so the beam keeps its width; the
+    values are not renormalised: cum is still the model's log-probability of the hypothesis, the one score_captions returns.  They
+    need beam_width + len(banned_tokens) + caption_max_len + 1 <= V."""
+    toks, cum, ln, score = _beam_nbest(config, decoder, input, hidden, encoder_outputs, beam_width, length_alpha, no_repeat_ngram,
+                                       min_length, banned_tokens)
     toks, cum, ln, score = toks.cpu().tolist(), cum.cpu().tolist(), ln.cpu().tolist(), score.cpu().tolist()
     B = encoder_outputs.shape[0]
     return [[([toks[r][t][b] for t in range(ln[r][b])], cum[r][b], ln[r][b], score[r][b]) for r in range(int(beam_width))]
@@ -351,12 +391,13 @@ def beam_search_nbest(config, decoder, input, hidden, encoder_outputs, beam_widt
 
 
 def best_of_beam(config, decoder, input, hidden, encoder_outputs, beam_width, length_alpha=0.0, reconstructor=None,
-                 recon_weight=0.0):
+                 recon_weight=0.0, no_repeat_ngram=0, min_length=0, banned_tokens=()):
     """The beam_width hypotheses of beam_search_nbest, reranked like best_of_n's candidates: per video the rank k with the largest
     cum / length - recon_weight * rec_error (pick_best_of_n, the lowest k among equals; without a reconstructor or with
     recon_weight = 0 the first term alone).  Every rank of the search is a canonical [n_steps, B] caption set already, so it goes to
-    the reconstruction error as it is, all ranks at the common T = n_steps (the global error depends on T).  Returns what
-    best_of_n returns: (captions: [B] token lists cut after their <EOS>, chosen k [B], score [B])."""
+    the reconstruction error as it is, all ranks at the common T = n_steps (the global error depends on T).  no_repeat_ngram /
+    min_length / banned_tokens are beam_search_nbest's.  Returns what best_of_n returns: (captions: [B] token lists cut after
+    their <EOS>, chosen k [B], score [B])."""
     use_rec = reconstructor is not None and recon_weight != 0
     if reconstructor is None and recon_weight != 0:
         raise ValueError("recon_weight = %r needs a reconstructor" % (recon_weight,))
@@ -365,7 +406,8 @@ def best_of_beam(config, decoder, input, hidden, encoder_outputs, beam_width, le
             raise ValueError("recon_weight must be a finite number (got %r)" % (recon_weight,))
         recon_weight = float(recon_weight)
         _check_reconstructor(config, decoder, reconstructor, encoder_outputs)
-    toks, cum, ln, _ = _beam_nbest(config, decoder, input, hidden, encoder_outputs, beam_width, length_alpha)
+    toks, cum, ln, _ = _beam_nbest(config, decoder, input, hidden, encoder_outputs, beam_width, length_alpha, no_repeat_ngram,
+                                   min_length, banned_tokens)
     errs = None
     if use_rec:
         errs = torch.stack([_rec_errors(config, decoder, reconstructor, encoder_outputs, toks[r])[0]

@@ -4,7 +4,9 @@ batched step, the fused selection) at each width, greedy_search beside width 1, 
 random logits, at the benchmark's decoder shape, bf16.  HIP events around `reps` back-to-back calls after `warmup` calls of each;
 the calls are alternated over `rounds` rounds so that drift hits them alike; the median and the spread over rounds are printed as
 one JSON line.  The selection kernel reads each logit three times (maximum, sum of exponentials, candidates): `select_bytes_read`
-counts all three passes, `select_bytes_unique` the array once.
+counts all three passes, `select_bytes_unique` the array once.  The `_constrained` rows are the same calls
+with no_repeat_ngram = 2, min_length = 3 and two banned ids, the kernel alone at the last step (t = T - 1) on random histories over
+a 4-letter alphabet: read them against the unconstrained rows of the same run.
 
     python tools/beam_time.py [--B 100 --F 28 --D 1536 --V 4188 --widths 1,5,8 --reps 10 --warmup 3 --rounds 5]
 """
@@ -22,7 +24,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 def main():
     ap = argparse.ArgumentParser()
     for k, v in (("B", 100), ("F", 28), ("D", 1536), ("E", 468), ("H", 512), ("A", 128), ("V", 4188), ("reps", 10), ("warmup", 3),
-                 ("rounds", 5)):
+                 ("rounds", 5), ("constrained", 1)):
         ap.add_argument("--" + k, type=int, default=v)
     ap.add_argument("--widths", default="1,5,8")
     ap.add_argument("--length_alpha", type=float, default=0.7)
@@ -43,11 +45,19 @@ def main():
     logits = torch.randn(nb, a.B, a.V, device="cuda") * 2.0
     cum = -torch.rand(nb, a.B, device="cuda") * 6.0
     fin = torch.zeros(nb, a.B, dtype=torch.int32, device="cuda")
+    Tm = eng.hyper["caption_max_len"] + 1
+    hist = torch.randint(3, 7, (nb, a.B, Tm), device="cuda")
+    con = dict(no_repeat_ngram=2, min_length=3, banned_tokens=(5, 9))
     calls = {"greedy_search": lambda: eng.greedy_search(enc)}
     for w in widths:
         calls["beam_search_w%d" % w] = lambda w=w: eng.beam_search(enc, w)
         calls["beam_search_nbest_w%d" % w] = lambda w=w: eng.beam_search_nbest(enc, w, a.length_alpha)
+        if not a.constrained:            # (--constrained 0: the call set of section 11, for a like-for-like run against an older commit)
+            calls["beam_select_rows_nb8_w%d" % w] = lambda w=w: eng.beam_select_rows(logits, cum, fin, w)
+            continue
+        calls["beam_search_nbest_constrained_w%d" % w] = lambda w=w: eng.beam_search_nbest(enc, w, a.length_alpha, **con)
         calls["beam_select_rows_nb8_w%d" % w] = lambda w=w: eng.beam_select_rows(logits, cum, fin, w)
+        calls["beam_select_rows_constrained_nb8_w%d" % w] = lambda w=w: eng.beam_select_rows(logits, cum, fin, w, hist=hist, t=Tm - 1, **con)
     for fn in calls.values():
         for _ in range(a.warmup):
             fn()
@@ -64,7 +74,7 @@ def main():
             e1.synchronize()
             ms[k].append(e0.elapsed_time(e1) / reps)
     assert eng.chain_status() == 0
-    out = {"shape": {k: getattr(a, k) for k in ("B", "F", "D", "E", "H", "A", "V")}, "T": eng.hyper["caption_max_len"] + 1,
+    out = {"shape": {k: getattr(a, k) for k in ("B", "F", "D", "E", "H", "A", "V")}, "T": Tm, "constraints": {k: list(v) if isinstance(v, tuple) else v for k, v in con.items()},
            "precision": a.precision, "length_alpha": a.length_alpha, "reps": a.reps, "rounds": a.rounds,
            "select_bytes_unique": nb * a.B * a.V * 4, "select_bytes_read": 3 * nb * a.B * a.V * 4}
     for k, v in ms.items():
