@@ -1,30 +1,38 @@
 // C ABI: the decoder's per-step API, the device-side inference search (eval.py:19-120), greedy / beam / sampling, the scoring of
 // given captions and their per-caption reconstruction error (train.py:96-102 / :125-128 in eval mode).
 // Part of api.hip (one translation unit; see the include list there).
-// One decode step on already prepared loop invariants (Uv, P, bias sum): embedding, input projection,
-// h . [W_hh ; attn_W]^T, cell kernel, vocabulary projection.  Rows [0,B) / [B,2B) of Hs_lp are scratch.
-static int dec_step_core(recnet_handle* h, const int64_t* tokens, const float* h_in, const float* c_in, float* logits,
-                         float* h_out, float* c_out, int train, int t, hipStream_t st) {
-  const int B = h->B, F = h->F, E = h->E, H = h->H, A = h->A, V = h->V;
-  embed_fwd(h, nullptr, tokens, B, train, t, st);
-  gemm(h, h->emb_lp, 0, h->ldE, h->We_w, 0, h->ldE, h->Xe, 4 * H, h->bsum_d, B, 4 * H, E, 1.f, 0, st);
+// The operand rows a decode step works on: the embedding rows, their input product, the operand copy of the incoming hidden
+// states and of the outgoing ones (the vocabulary product reads those).
+struct DecStepRows { void* emb; float* Xe; void* h_lp_in; void* h_lp_out; };
+// B rows on the training operand buffers: rows [0,B) / [B,2B) of Hs_lp are scratch
+static DecStepRows dec_rows_batch(recnet_handle* h) { return {h->emb_lp, h->Xe, h->Hs_lp, at_off(h, h->Hs_lp, (size_t)h->B * h->ldH)}; }
+// up to 8 * B rows ordered [beam][caption] on the N-best search's own operand rows
+static DecStepRows dec_rows_beams(recnet_handle* h) { return {h->bs_emb, h->bs_Xe, h->bs_hlp, at_off(h, h->bs_hlp, (size_t)8 * h->B * h->ldH)}; }
+// One decode step of `rows` rows on already prepared loop invariants (Uv, P, bias sum): embedding, input projection,
+// h . [W_hh ; attn_W]^T, cell kernel, vocabulary projection, each launch once for all rows.  nc = 0: one row per caption; nc = B:
+// [beam][caption] rows that share the captions' Uv / P (DecCellArgs::nc).  h_in null: the zero state, no recurrent product.
+static void dec_step(recnet_handle* h, int rows, int nc, const DecStepRows& r, const int64_t* tokens, const float* h_in,
+                     const float* c_in, float* logits, float* h_out, float* c_out, int train, int t, hipStream_t st) {
+  const int F = h->F, E = h->E, H = h->H, A = h->A, V = h->V;
+  // (the kernel's B places a row in (t, b) for the dropout mask and picks tokens[row % B]: one step of `rows` tokens)
+  embed_fwd(h, nullptr, tokens, r.emb, rows, rows, train, t, st);
+  gemm(h, r.emb, 0, h->ldE, h->We_w, 0, h->ldE, r.Xe, 4 * H, h->bsum_d, rows, 4 * H, E, 1.f, 0, st);
   int S = 0;
   if (h_in) {   // operand copy of the incoming hidden state, then h . [W_hh ; attn_W]^T
-    pack_block(h, h->Hs_lp, h->ldH, h_in, H, B, H, 1.f, st);
-    S = gemm_slabs(h, RN_TAG_DEC_FWD, h->Hs_lp, h->ldH, h->Wcomb, 0, h->ldH, B, 4 * H + A, H, st);
+    pack_block(h, r.h_lp_in, h->ldH, h_in, H, rows, H, 1.f, st);
+    S = gemm_slabs(h, RN_TAG_DEC_FWD, r.h_lp_in, h->ldH, h->Wcomb, 0, h->ldH, rows, 4 * H + A, H, st);
   }
   DecCellArgs a;
-  a.t = t; a.B = B; a.F = F; a.H = H; a.A = A; a.S = S; a.slab = h_in ? h->slab : nullptr;
-  a.Xe = h->Xe; a.P = h->P; a.ldp = h->ld4H; a.Uv = h->Uv; a.ab = h->dP.attn_b; a.w = h->dP.attn_w_weight;
-  a.gru = h->dgru; a.c_prev = h->dgru ? h_in : c_in; a.h_out = h_out; a.c_out = c_out; a.acts = nullptr; a.Wh_out = nullptr; a.att_out = nullptr; a.softmax = h->c.decoder_attn_normalize == RECNET_ATTN_SOFTMAX; a.nc = 0;
-  a.h_lp = at_off(h, h->Hs_lp, (size_t)B * h->ldH); a.ld_hlp = h->ldH;
-  launch_dec_cell(h, a, B, st);
-  gemm(h, at_off(h, h->Hs_lp, (size_t)B * h->ldH), 0, h->ldH, h->Wo_w, 0, h->ldH, logits, V, h->dP.out_bias, B, V, H, 1.f, 0, st);
+  a.t = t; a.B = rows; a.F = F; a.H = H; a.A = A; a.S = S; a.slab = h_in ? h->slab : nullptr; a.nc = nc;
+  a.Xe = r.Xe; a.P = h->P; a.ldp = h->ld4H; a.Uv = h->Uv; a.ab = h->dP.attn_b; a.w = h->dP.attn_w_weight;
+  a.gru = h->dgru; a.c_prev = h->dgru ? h_in : c_in; a.h_out = h_out; a.c_out = c_out; a.acts = nullptr; a.Wh_out = nullptr; a.att_out = nullptr; a.softmax = h->c.decoder_attn_normalize == RECNET_ATTN_SOFTMAX;
+  a.h_lp = r.h_lp_out; a.ld_hlp = h->ldH;
+  launch_dec_cell(h, a, rows, st);
+  gemm(h, r.h_lp_out, 0, h->ldH, h->Wo_w, 0, h->ldH, logits, V, h->dP.out_bias, rows, V, H, 1.f, 0, st);
   if (train && h->c.decoder_out_dropout > 0.f)
-    hipLaunchKernelGGL(logits_drop_kernel, dim3(ew_blocks((size_t)B * V)), dim3(256), 0, st, logits, B, V,
+    hipLaunchKernelGGL(logits_drop_kernel, dim3(ew_blocks((size_t)rows * V)), dim3(256), 0, st, logits, rows, V,
                        mkdrop(h, RN_SITE_DEC_LOGIT, h->c.decoder_out_dropout, train), t);
   h->fwd_dec_done = 0;
-  return RECNET_OK;
 }
 
 int recnet_decoder_prepare(recnet_handle* h, const float* enc, void* stream) {
@@ -46,7 +54,7 @@ int recnet_decoder_step(recnet_handle* h, const int64_t* tokens, const float* h_
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(set_u32_kernel, dim3(1), dim3(1), 0, st, h->ctrl, seed);
   if (enc) dec_invariants(h, enc, st);   // enc == NULL: reuse what recnet_decoder_prepare / the last call computed
-  int r = dec_step_core(h, tokens, h_in, c_in, logits, h_out, c_out, train, t, st); if (r) return r;
+  dec_step(h, h->B, 0, dec_rows_batch(h), tokens, h_in, c_in, logits, h_out, c_out, train, t, st);
   LAUNCH_OK();
   return RECNET_OK;
 }
@@ -112,29 +120,58 @@ int recnet_reconstructor_step(recnet_handle* h, const float* input, const float*
   return RECNET_OK;
 }
 
-int recnet_greedy_search(recnet_handle* h, const float* enc, int64_t* tokens_out, int32_t* n_steps_out, void* stream) {
+// ---- the skeleton of the device-side searches: every entry opens with search_check, its own argument checks follow, then
+// search_begin, its loop of Tm steps (a fixed trip count, no host synchronisation) and search_end
+static int search_check(const recnet_handle* h, bool args_given) {
   REQUIRE_WS(h);
   if (!h->dec_bound) return fail(RECNET_ESTATE, "decoder not bound");
-  if (!enc || !tokens_out || !n_steps_out) return fail(RECNET_EINVAL, "null argument");
-  hipStream_t st = (hipStream_t)stream;
-  const int B = h->B, H = h->H, V = h->V, Tm = h->Tm;
+  if (!args_given) return fail(RECNET_EINVAL, "null argument");
+  return RECNET_OK;
+}
+// The invariants, n_steps = 0 and one initial hypothesis per caption in slot 0 of the sr_* pairs: <SOS> = 1 (eval.py:131), the zero
+// state; beam_eos_fill >= 0 (the two beam searches): also log-prob 0, an empty history and the <EOS> words filled with that byte
+// (eval.py:37-42: 0xFF = -1, no <EOS> yet; the N-best search: 0, not finished).
+static void search_begin(recnet_handle* h, const float* enc, int32_t* n_steps_out, int beam_eos_fill, hipStream_t st) {
+  const int B = h->B, H = h->H, Tm = h->Tm;
   dec_invariants(h, enc, st);
   hipMemsetAsync(n_steps_out, 0, 4, st);
   hipMemsetAsync(h->sr_h[0], 0, (size_t)B * H * 4, st);
   hipMemsetAsync(h->sr_c[0], 0, (size_t)B * H * 4, st);
-  // <SOS> = 1 for every caption (eval.py:131)
+  if (beam_eos_fill >= 0) {
+    hipMemsetAsync(h->sr_cum[0], 0, (size_t)B * 4, st);
+    hipMemsetAsync(h->sr_hist[0], 0, (size_t)B * Tm * 8, st);
+    hipMemsetAsync(h->sr_eos[0], beam_eos_fill, (size_t)B * 4, st);
+  }
   hipLaunchKernelGGL(fill_i64_kernel, dim3(cdiv(B, 256)), dim3(256), 0, st, h->sr_tok[0], (int64_t)1, B);
+}
+// a search that never stopped ran all Tm steps
+static void search_end(recnet_handle* h, int32_t* n_steps_out, hipStream_t st) {
+  hipLaunchKernelGGL(search_finish_kernel, dim3(1), dim3(1), 0, st, n_steps_out, h->Tm);
+}
+// One hypothesis per caption (eval.py:19-33): pick(t, out_t) launches what turns h->sr_logits [B][V] into the step's tokens out_t [B]
+static void search_one_per_caption(recnet_handle* h, const float* enc, int64_t* tokens_out, int32_t* n_steps_out, hipStream_t st,
+                                   const std::function<void(int, int64_t*)>& pick) {
+  const int B = h->B;
+  search_begin(h, enc, n_steps_out, -1, st);
+  const DecStepRows rows = dec_rows_batch(h);
   const int64_t* tok = h->sr_tok[0];
   int cur = 0;
-  for (int t = 0; t < Tm; ++t) {
-    int r = dec_step_core(h, tok, h->sr_h[cur], h->sr_c[cur], h->sr_logits, h->sr_h[cur ^ 1], h->sr_c[cur ^ 1], 0, t, st);
-    if (r) return r;
+  for (int t = 0; t < h->Tm; ++t) {
+    dec_step(h, B, 0, rows, tok, h->sr_h[cur], h->sr_c[cur], h->sr_logits, h->sr_h[cur ^ 1], h->sr_c[cur ^ 1], 0, t, st);
     int64_t* out_t = tokens_out + (size_t)t * B;
-    hipLaunchKernelGGL(argmax_rows_kernel, dim3(B), dim3(256), 0, st, h->sr_logits, V, V, out_t);
-    hipLaunchKernelGGL(search_stop_kernel, dim3(1), dim3(256), 0, st, out_t, B, t, n_steps_out);
+    pick(t, out_t);
+    hipLaunchKernelGGL(search_stop_kernel, dim3(1), dim3(256), 0, st, out_t, (const int32_t*)nullptr, B, t, n_steps_out);
     tok = out_t; cur ^= 1;
   }
-  hipLaunchKernelGGL(search_finish_kernel, dim3(1), dim3(1), 0, st, n_steps_out, Tm);
+  search_end(h, n_steps_out, st);
+}
+
+int recnet_greedy_search(recnet_handle* h, const float* enc, int64_t* tokens_out, int32_t* n_steps_out, void* stream) {
+  int r = search_check(h, enc && tokens_out && n_steps_out); if (r) return r;
+  hipStream_t st = (hipStream_t)stream;
+  search_one_per_caption(h, enc, tokens_out, n_steps_out, st, [&](int, int64_t* out_t) {
+    hipLaunchKernelGGL(argmax_rows_kernel, dim3(h->B), dim3(256), 0, st, h->sr_logits, h->V, h->V, out_t);
+  });
   LAUNCH_OK();
   return RECNET_OK;
 }
@@ -168,28 +205,12 @@ int recnet_sample_rows(recnet_handle* h, const float* logits, int32_t rows, int3
 
 int recnet_sample_search(recnet_handle* h, const float* enc, float temperature, int32_t top_k, uint32_t seed,
                          int64_t* tokens_out, float* logprobs_out, int32_t* n_steps_out, void* stream) {
-  REQUIRE_WS(h);
-  if (!h->dec_bound) return fail(RECNET_ESTATE, "decoder not bound");
-  if (!enc || !tokens_out || !logprobs_out || !n_steps_out) return fail(RECNET_EINVAL, "null argument");
-  int r = check_sample(temperature, top_k, h->V); if (r) return r;
+  int r = search_check(h, enc && tokens_out && logprobs_out && n_steps_out); if (r) return r;
+  r = check_sample(temperature, top_k, h->V); if (r) return r;
   hipStream_t st = (hipStream_t)stream;
-  const int B = h->B, H = h->H, V = h->V, Tm = h->Tm;
-  dec_invariants(h, enc, st);
-  hipMemsetAsync(n_steps_out, 0, 4, st);
-  hipMemsetAsync(h->sr_h[0], 0, (size_t)B * H * 4, st);
-  hipMemsetAsync(h->sr_c[0], 0, (size_t)B * H * 4, st);
-  hipLaunchKernelGGL(fill_i64_kernel, dim3(cdiv(B, 256)), dim3(256), 0, st, h->sr_tok[0], (int64_t)1, B);
-  const int64_t* tok = h->sr_tok[0];
-  int cur = 0;
-  for (int t = 0; t < Tm; ++t) {
-    r = dec_step_core(h, tok, h->sr_h[cur], h->sr_c[cur], h->sr_logits, h->sr_h[cur ^ 1], h->sr_c[cur ^ 1], 0, t, st);
-    if (r) return r;
-    int64_t* out_t = tokens_out + (size_t)t * B;
-    launch_sample_rows(h->sr_logits, B, V, B, temperature, top_k, seed, t, out_t, logprobs_out + (size_t)t * B, st);
-    hipLaunchKernelGGL(search_stop_kernel, dim3(1), dim3(256), 0, st, out_t, B, t, n_steps_out);
-    tok = out_t; cur ^= 1;
-  }
-  hipLaunchKernelGGL(search_finish_kernel, dim3(1), dim3(1), 0, st, n_steps_out, Tm);
+  search_one_per_caption(h, enc, tokens_out, n_steps_out, st, [&](int t, int64_t* out_t) {
+    launch_sample_rows(h->sr_logits, h->B, h->V, h->B, temperature, top_k, seed, t, out_t, logprobs_out + (size_t)t * h->B, st);
+  });
   LAUNCH_OK();
   return RECNET_OK;
 }
@@ -301,50 +322,44 @@ int recnet_reconstruction_error(recnet_handle* h, const float* enc, const int64_
   return RECNET_OK;
 }
 
+// the regather of both beam searches on the sr_* pairs: slot `cur` and the step's states sr_hn / sr_cn into slot cur ^ 1
+static BeamUpdArgs beam_update_args(recnet_handle* h, int bw, int t, int cur, const int32_t* n_steps) {
+  BeamUpdArgs u;
+  u.B = h->B; u.H = h->H; u.V = h->V; u.Tm = h->Tm; u.bw = bw; u.t = t;
+  u.vals = h->sr_vals; u.idx = h->sr_idx; u.h_next = h->sr_hn; u.c_next = h->dgru ? nullptr : h->sr_cn;
+  u.eos_old = h->sr_eos[cur]; u.hist_old = h->sr_hist[cur];
+  u.h_new = h->sr_h[cur ^ 1]; u.c_new = h->sr_c[cur ^ 1]; u.cum_new = h->sr_cum[cur ^ 1];
+  u.eos_new = h->sr_eos[cur ^ 1]; u.hist_new = h->sr_hist[cur ^ 1]; u.tok_new = h->sr_tok[cur ^ 1];
+  u.n_steps = n_steps;
+  return u;
+}
+
 int recnet_beam_search(recnet_handle* h, const float* enc, int32_t beam_width, int64_t* best_out, int32_t* n_steps_out,
                        void* stream) {
-  REQUIRE_WS(h);
-  if (!h->dec_bound) return fail(RECNET_ESTATE, "decoder not bound");
-  if (!enc || !best_out || !n_steps_out) return fail(RECNET_EINVAL, "null argument");
+  int r = search_check(h, enc && best_out && n_steps_out); if (r) return r;
   if (beam_width < 1 || beam_width > 8) return fail(RECNET_EINVAL, "beam_width must be in [1, 8]");
   hipStream_t st = (hipStream_t)stream;
   const int B = h->B, H = h->H, V = h->V, Tm = h->Tm, bw = beam_width;
-  dec_invariants(h, enc, st);
-  hipMemsetAsync(n_steps_out, 0, 4, st);
-  // one initial hypothesis per caption: <SOS>, zero state, log-prob 0, no <EOS> (eval.py:37-42)
-  hipMemsetAsync(h->sr_h[0], 0, (size_t)B * H * 4, st);
-  hipMemsetAsync(h->sr_c[0], 0, (size_t)B * H * 4, st);
-  hipMemsetAsync(h->sr_cum[0], 0, (size_t)B * 4, st);
-  hipMemsetAsync(h->sr_hist[0], 0, (size_t)B * Tm * 8, st);
-  hipMemsetAsync(h->sr_eos[0], 0xFF, (size_t)B * 4, st);       // -1
-  hipLaunchKernelGGL(fill_i64_kernel, dim3(cdiv(B, 256)), dim3(256), 0, st, h->sr_tok[0], (int64_t)1, B);
+  search_begin(h, enc, n_steps_out, 0xFF, st);
+  const DecStepRows rows = dec_rows_batch(h);
   int cur = 0, nb = 1;
   for (int t = 0; t < Tm; ++t) {
-    for (int i = 0; i < nb; ++i) {
-      int r = dec_step_core(h, h->sr_tok[cur] + (size_t)i * B, h->sr_h[cur] + (size_t)i * B * H, h->sr_c[cur] + (size_t)i * B * H,
-                            h->sr_logits, h->sr_hn + (size_t)i * B * H, h->sr_cn + (size_t)i * B * H, 0, t, st);
-      if (r) return r;
+    for (int i = 0; i < nb; ++i) {   // the reference's search: one decode step of B rows per beam
+      dec_step(h, B, 0, rows, h->sr_tok[cur] + (size_t)i * B, h->sr_h[cur] + (size_t)i * B * H, h->sr_c[cur] + (size_t)i * B * H,
+               h->sr_logits, h->sr_hn + (size_t)i * B * H, h->sr_cn + (size_t)i * B * H, 0, t, st);
       hipLaunchKernelGGL(beam_score_kernel, dim3(B), dim3(256), 0, st, h->sr_logits, h->sr_cum[cur], h->sr_eos[cur], h->sr_scores,
                          B, V, nb, i, t);
     }
     hipLaunchKernelGGL(topk_rows_kernel, dim3(B), dim3(256), 0, st, h->sr_scores, nb * V, bw, h->sr_vals, h->sr_idx);
-    BeamUpdArgs u;
-    u.B = B; u.H = H; u.V = V; u.Tm = Tm; u.bw = bw; u.t = t;
-    u.vals = h->sr_vals; u.idx = h->sr_idx; u.h_next = h->sr_hn; u.c_next = h->sr_cn;
-    u.last_eos_old = h->sr_eos[cur]; u.hist_old = h->sr_hist[cur];
-    u.h_new = h->sr_h[cur ^ 1]; u.c_new = h->sr_c[cur ^ 1]; u.cum_new = h->sr_cum[cur ^ 1];
-    u.last_eos_new = h->sr_eos[cur ^ 1]; u.hist_new = h->sr_hist[cur ^ 1]; u.tok_new = h->sr_tok[cur ^ 1];
-    u.n_steps = n_steps_out;
-    hipLaunchKernelGGL(beam_update_kernel, dim3(bw, B), dim3(128), 0, st, u);
-    hipLaunchKernelGGL(search_stop_kernel, dim3(1), dim3(256), 0, st, h->sr_tok[cur ^ 1], bw * B, t, n_steps_out);
+    hipLaunchKernelGGL(beam_update_kernel<false>, dim3(bw, B), dim3(128), 0, st, beam_update_args(h, bw, t, cur, n_steps_out));
+    hipLaunchKernelGGL(search_stop_kernel, dim3(1), dim3(256), 0, st, h->sr_tok[cur ^ 1], (const int32_t*)nullptr, bw * B, t, n_steps_out);
     cur ^= 1; nb = bw;
   }
-  hipLaunchKernelGGL(search_finish_kernel, dim3(1), dim3(1), 0, st, n_steps_out, Tm);
-  hipLaunchKernelGGL(beam_best_kernel, dim3(cdiv(B * Tm, 256)), dim3(256), 0, st, h->sr_hist[cur], best_out, B, Tm);
+  search_end(h, n_steps_out, st);
+  hipLaunchKernelGGL(beam_gather_kernel, dim3(cdiv(B * Tm, 256)), dim3(256), 0, st, h->sr_hist[cur], (const int32_t*)nullptr, best_out, B, Tm, 1);
   LAUNCH_OK();
   return RECNET_OK;
 }
-
 
 // ---- N-best beam search on log-probabilities (the reference has no counterpart; DESIGN.md section 11)
 static int check_beam(int beam_width, int V, float length_alpha) {
@@ -436,69 +451,30 @@ int recnet_beam_select_rows_constrained(recnet_handle* h, const float* logits, c
   return RECNET_OK;
 }
 
-// One decode step for rows = nb * B rows ordered [beam][caption] (dec_step_core's sequence, each launch once for all beams): the
-// embedding, the input product, h . [W_hh ; attn_W]^T, the cell kernel (Uv / P per caption: DecCellArgs::nc) and the vocabulary
-// product, on the search block's own operand rows (bs_*).
-static void beam_step_all(recnet_handle* h, int nb, const int64_t* tokens, const float* h_in, const float* c_in, float* logits,
-                          float* h_out, float* c_out, int t, hipStream_t st) {
-  const int B = h->B, F = h->F, E = h->E, H = h->H, A = h->A, V = h->V, rows = nb * B;
-  const DropDesc dd = mkdrop(h, RN_SITE_DEC_EMBED, h->c.embedding_dropout, 0);
-  // (the kernel's B places a row in (t, b) for the dropout mask and picks tokens[row % B]: eval mode, one step of `rows` tokens)
-  if (h->lp) hipLaunchKernelGGL(embed_fwd_kernel<bf16_t>, dim3(rows), dim3(128), 0, st, h->dP.embedding_weight, (const int64_t*)nullptr, tokens, (bf16_t*)h->bs_emb, h->ldE, rows, E, V, h->c.embedding_scale, dd, t);
-  else hipLaunchKernelGGL(embed_fwd_kernel<float>, dim3(rows), dim3(128), 0, st, h->dP.embedding_weight, (const int64_t*)nullptr, tokens, (float*)h->bs_emb, h->ldE, rows, E, V, h->c.embedding_scale, dd, t);
-  gemm(h, h->bs_emb, 0, h->ldE, h->We_w, 0, h->ldE, h->bs_Xe, 4 * H, h->bsum_d, rows, 4 * H, E, 1.f, 0, st);
-  pack_block(h, h->bs_hlp, h->ldH, h_in, H, rows, H, 1.f, st);
-  const int S = gemm_slabs(h, RN_TAG_DEC_FWD, h->bs_hlp, h->ldH, h->Wcomb, 0, h->ldH, rows, 4 * H + A, H, st);
-  void* h_lp = at_off(h, h->bs_hlp, (size_t)8 * B * h->ldH);
-  DecCellArgs a;
-  a.t = t; a.B = rows; a.F = F; a.H = H; a.A = A; a.S = S; a.slab = h->slab; a.nc = B;
-  a.Xe = h->bs_Xe; a.P = h->P; a.ldp = h->ld4H; a.Uv = h->Uv; a.ab = h->dP.attn_b; a.w = h->dP.attn_w_weight;
-  a.gru = h->dgru; a.c_prev = h->dgru ? h_in : c_in; a.h_out = h_out; a.c_out = c_out; a.acts = nullptr; a.Wh_out = nullptr; a.att_out = nullptr; a.softmax = h->c.decoder_attn_normalize == RECNET_ATTN_SOFTMAX;
-  a.h_lp = h_lp; a.ld_hlp = h->ldH;
-  launch_dec_cell(h, a, rows, st);
-  gemm(h, h_lp, 0, h->ldH, h->Wo_w, 0, h->ldH, logits, V, h->dP.out_bias, rows, V, H, 1.f, 0, st);
-}
-
 int recnet_beam_search_nbest_constrained(recnet_handle* h, const float* enc, int32_t beam_width, float length_alpha,
                                          int32_t no_repeat_ngram, int32_t min_length, const int32_t* banned, int32_t n_banned,
                                          int64_t* tokens_out, float* cum_out, int32_t* len_out, float* score_out, int32_t* n_steps_out,
                                          void* stream) {
-  REQUIRE_WS(h);
-  if (!h->dec_bound) return fail(RECNET_ESTATE, "decoder not bound");
-  if (!enc || !tokens_out || !cum_out || !len_out || !score_out || !n_steps_out) return fail(RECNET_EINVAL, "null argument");
-  int r = check_beam(beam_width, h->V, length_alpha); if (r) return r;
+  int r = search_check(h, enc && tokens_out && cum_out && len_out && score_out && n_steps_out); if (r) return r;
+  r = check_beam(beam_width, h->V, length_alpha); if (r) return r;
   BeamBans bans;
   r = check_beam_bans(no_repeat_ngram, min_length, banned, n_banned, beam_width, h->V, h->Tm, h->Tm - 1, &bans); if (r) return r;
   hipStream_t st = (hipStream_t)stream;
-  const int B = h->B, H = h->H, V = h->V, Tm = h->Tm, bw = beam_width;
-  dec_invariants(h, enc, st);
-  h->fwd_dec_done = 0;
-  hipMemsetAsync(n_steps_out, 0, 4, st);
-  // one initial hypothesis per caption: <SOS>, zero state, cum = 0, not finished
-  hipMemsetAsync(h->sr_h[0], 0, (size_t)B * H * 4, st);
-  hipMemsetAsync(h->sr_c[0], 0, (size_t)B * H * 4, st);
-  hipMemsetAsync(h->sr_cum[0], 0, (size_t)B * 4, st);
-  hipMemsetAsync(h->sr_hist[0], 0, (size_t)B * Tm * 8, st);
-  hipMemsetAsync(h->sr_eos[0], 0, (size_t)B * 4, st);          // fin = 0
-  hipLaunchKernelGGL(fill_i64_kernel, dim3(cdiv(B, 256)), dim3(256), 0, st, h->sr_tok[0], (int64_t)1, B);
+  const int B = h->B, V = h->V, Tm = h->Tm, bw = beam_width;
+  search_begin(h, enc, n_steps_out, 0, st);
+  const DecStepRows rows = dec_rows_beams(h);
   int cur = 0, nb = 1;
-  for (int t = 0; t < Tm; ++t) {
-    beam_step_all(h, nb, h->sr_tok[cur], h->sr_h[cur], h->sr_c[cur], h->sr_scores, h->sr_hn, h->sr_cn, t, st);
+  for (int t = 0; t < Tm; ++t) {   // all nb * B hypotheses in one decode step, the captions' Uv / P shared by their beams
+    dec_step(h, nb * B, B, rows, h->sr_tok[cur], h->sr_h[cur], h->sr_c[cur], h->sr_scores, h->sr_hn, h->sr_cn, 0, t, st);
     launch_beam_select(h->sr_scores, h->sr_cum[cur], h->sr_eos[cur], nb, B, V, bw, h->sr_vals, h->sr_idx, st, &bans, h->sr_hist[cur], Tm, t);
-    BeamNUpdArgs u;
-    u.B = B; u.H = H; u.V = V; u.Tm = Tm; u.bw = bw; u.t = t;
-    u.vals = h->sr_vals; u.idx = h->sr_idx; u.h_next = h->sr_hn; u.c_next = h->dgru ? nullptr : h->sr_cn;
-    u.fin_old = h->sr_eos[cur]; u.hist_old = h->sr_hist[cur];
-    u.h_new = h->sr_h[cur ^ 1]; u.c_new = h->sr_c[cur ^ 1]; u.cum_new = h->sr_cum[cur ^ 1];
-    u.fin_new = h->sr_eos[cur ^ 1]; u.hist_new = h->sr_hist[cur ^ 1]; u.tok_new = h->sr_tok[cur ^ 1];
-    hipLaunchKernelGGL(beam_nbest_update_kernel, dim3(bw, B), dim3(128), 0, st, u);
-    hipLaunchKernelGGL(beam_nbest_stop_kernel, dim3(1), dim3(256), 0, st, h->sr_eos[cur ^ 1], bw * B, t, n_steps_out);
+    hipLaunchKernelGGL(beam_update_kernel<true>, dim3(bw, B), dim3(128), 0, st, beam_update_args(h, bw, t, cur, nullptr));
+    hipLaunchKernelGGL(search_stop_kernel, dim3(1), dim3(256), 0, st, (const int64_t*)nullptr, h->sr_eos[cur ^ 1], bw * B, t, n_steps_out);
     cur ^= 1; nb = bw;
   }
-  hipLaunchKernelGGL(search_finish_kernel, dim3(1), dim3(1), 0, st, n_steps_out, Tm);
+  search_end(h, n_steps_out, st);
   hipLaunchKernelGGL(beam_nbest_rank_kernel, dim3(cdiv(B, 256)), dim3(256), 0, st, h->sr_cum[cur], h->sr_eos[cur], n_steps_out, B, bw,
                      length_alpha, cum_out, len_out, score_out, h->bs_order);
-  hipLaunchKernelGGL(beam_nbest_gather_kernel, dim3(cdiv(bw * Tm * B, 256)), dim3(256), 0, st, h->sr_hist[cur], h->bs_order, tokens_out,
+  hipLaunchKernelGGL(beam_gather_kernel, dim3(cdiv(bw * Tm * B, 256)), dim3(256), 0, st, h->sr_hist[cur], h->bs_order, tokens_out,
                      B, Tm, bw);
   LAUNCH_OK();
   return RECNET_OK;

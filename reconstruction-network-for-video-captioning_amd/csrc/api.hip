@@ -23,6 +23,7 @@
 #include <ctype.h>
 #include <string.h>
 #include <algorithm>
+#include <functional>
 #include <string>
 #include <vector>
 

@@ -325,11 +325,11 @@ static void dec_invariants(recnet_handle* h, const float* enc, hipStream_t st, b
   gemm(h, h->enc_lp, 0, h->ldD, h->U_w, 0, h->ldD, h->Uv, A, nullptr, B * F, A, D, 1.f, 0, st);
   gemm_to_at(h, h->enc_lp, 0, h->ldD, h->Wc_w, 0, h->ldD, h->P, h->ld4H, B * F, 4 * H, D, st);
 }
-static void embed_fwd(recnet_handle* h, const int64_t* targets, const int64_t* tokens, int rows, int train, int t0, hipStream_t st,
-                      size_t row0 = 0) {
+// `rows` embedding rows into dst (operand type, row stride ldE); B: the kernel's rows per step (row = (t - t0) * B + b)
+static void embed_fwd(recnet_handle* h, const int64_t* targets, const int64_t* tokens, void* dst, int rows, int B, int train, int t0,
+                      hipStream_t st) {
   const DropDesc dd = mkdrop(h, RN_SITE_DEC_EMBED, h->c.embedding_dropout, train);
-  void* dst = at_off(h, h->emb_lp, row0 * h->ldE);
-  if (h->lp) hipLaunchKernelGGL(embed_fwd_kernel<bf16_t>, dim3(rows), dim3(128), 0, st, h->dP.embedding_weight, targets, tokens, (bf16_t*)dst, h->ldE, h->B, h->E, h->V, h->c.embedding_scale, dd, t0);
-  else hipLaunchKernelGGL(embed_fwd_kernel<float>, dim3(rows), dim3(128), 0, st, h->dP.embedding_weight, targets, tokens, (float*)dst, h->ldE, h->B, h->E, h->V, h->c.embedding_scale, dd, t0);
+  if (h->lp) hipLaunchKernelGGL(embed_fwd_kernel<bf16_t>, dim3(rows), dim3(128), 0, st, h->dP.embedding_weight, targets, tokens, (bf16_t*)dst, h->ldE, B, h->E, h->V, h->c.embedding_scale, dd, t0);
+  else hipLaunchKernelGGL(embed_fwd_kernel<float>, dim3(rows), dim3(128), 0, st, h->dP.embedding_weight, targets, tokens, (float*)dst, h->ldE, B, h->E, h->V, h->c.embedding_scale, dd, t0);
 }
 

@@ -41,7 +41,7 @@ static int dec_fwd_chain(recnet_handle* h, const float* enc, const int64_t* targ
   } else if (fork_xe) {
     fork_to(h, EV_XE_FORK, st, h->s2);
     gate_bias(h->dP.rnn_bias_ih_l0, h->dP.rnn_bias_hh_l0, h->bsum_d, H, h->dgru, h->s2);   // Xe's bias
-    embed_fwd(h, targets, nullptr, T * B, train, 0, h->s2);
+    embed_fwd(h, targets, nullptr, h->emb_lp, T * B, B, train, 0, h->s2);
     gemm(h, h->emb_lp, 0, h->ldE, h->We_w, 0, h->ldE, h->Xe, 4 * H, h->bsum_d, T * B, 4 * H, E, 1.f, 0, h->s2);
     hipEventRecord(h->ev[EV_XE_JOIN], h->s2);
   }
@@ -51,7 +51,7 @@ static int dec_fwd_chain(recnet_handle* h, const float* enc, const int64_t* targ
     hipStreamWaitEvent(st, h->ev[EV_XE_JOIN], 0);
   } else if (!free_tokens) {
     // all T teacher-forced input embeddings at once    (decoder.py:46-48, train.py:25,45)
-    embed_fwd(h, targets, nullptr, T * B, train, 0, st);
+    embed_fwd(h, targets, nullptr, h->emb_lp, T * B, B, train, 0, st);
     // Xe = emb . W_ih[:, :E]^T + b_ih + b_hh
     gemm(h, h->emb_lp, 0, h->ldE, h->We_w, 0, h->ldE, h->Xe, 4 * H, h->bsum_d, T * B, 4 * H, E, 1.f, 0, st);
   } else {
@@ -120,7 +120,7 @@ static int dec_fwd_chain(recnet_handle* h, const float* enc, const int64_t* targ
     if (free_tokens) {
       const int64_t* fed = t == 0 ? h->sr_tok[0] : free_tokens + (size_t)(t - 1) * B;
       hipMemcpyAsync(h->in_tok + (size_t)t * B, fed, (size_t)B * 8, hipMemcpyDeviceToDevice, st);
-      embed_fwd(h, nullptr, fed, B, train, t, st, (size_t)t * B);
+      embed_fwd(h, nullptr, fed, at_off(h, h->emb_lp, (size_t)t * B * h->ldE), B, B, train, t, st);
       gemm(h, at_off(h, h->emb_lp, (size_t)t * B * h->ldE), 0, h->ldE, h->We_w, 0, h->ldE, h->Xe + (size_t)t * B * 4 * H, 4 * H,
            h->bsum_d, B, 4 * H, E, 1.f, 0, st);
     }

@@ -4,6 +4,20 @@
 // =============================================================================================
 // inference search on the device (eval.py:19-120): the per-sample Python loops of the reference become kernels
 // =============================================================================================
+// Arg-max over the 256 threads of a block on 256 floats / ints of LDS each: the larger value wins, the lowest index among equal
+// values.  Every thread brings its own candidate; after the call sv[0] / si[0] hold the winner, for every thread to read.
+__device__ __forceinline__ void block_argmax256(float value, int index, float* sv, int* si) {
+  const int tid = threadIdx.x;
+  sv[tid] = value; si[tid] = index;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (tid < w) {
+      const float y = sv[tid + w]; const int j = si[tid + w];
+      if (y > sv[tid] || (y == sv[tid] && j < si[tid])) { sv[tid] = y; si[tid] = j; }
+    }
+    __syncthreads();
+  }
+}
 // out[row] = argmax_v x[row, v]  (lowest index among equal maxima), one workgroup per row
 __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restrict__ x, int ld, int cols, int64_t* __restrict__ out) {
   __shared__ float sv[256]; __shared__ int si[256];
@@ -13,15 +27,7 @@ __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restric
     const float y = x[(size_t)row * ld + v];
     if (y > best || (y == best && v < bi)) { best = y; bi = v; }
   }
-  sv[tid] = best; si[tid] = bi;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (tid < w) {
-      const float y = sv[tid + w]; const int j = si[tid + w];
-      if (y > sv[tid] || (y == sv[tid] && j < si[tid])) { sv[tid] = y; si[tid] = j; }
-    }
-    __syncthreads();
-  }
+  block_argmax256(best, bi, sv, si);
   if (tid == 0) out[row] = si[0];
 }
 // ---- sampling: one token per row drawn from softmax(x / temperature) restricted to the top_k largest logits, by Gumbel-max
@@ -113,15 +119,7 @@ template <bool RES> __global__ __launch_bounds__(256) void sample_rows_kernel(co
     }
   }
   mx = block_max256(mx, sf);
-  sv[tid] = best; si[tid] = bi;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (tid < w) {
-      const float y = sv[tid + w]; const int j = si[tid + w];
-      if (y > sv[tid] || (y == sv[tid] && j < si[tid])) { sv[tid] = y; si[tid] = j; }
-    }
-    __syncthreads();
-  }
+  block_argmax256(best, bi, sv, si);
   float sum = 0.f;
   for (int v = tid; v < V; v += 256) {
     const float xv = x[v]; const uint32_t key = sr_key(xv);
@@ -184,16 +182,19 @@ __global__ __launch_bounds__(256) void caption_logprob_kernel(const float* __res
   }
   sum_out[b] = s; len_out[b] = e + 1;
 }
-// record the step's tokens; the reference stops after the first step whose tokens are all <PAD> (eval.py:30,116)
-__global__ void search_stop_kernel(const int64_t* __restrict__ tokens, int n, int t, int32_t* __restrict__ n_steps) {
-  __shared__ int any;
-  if (threadIdx.x == 0) any = 0;
+// The search stops after the first step that leaves nothing alive.  tokens given: some token of the step is not <PAD> (the reference
+// stops after the first step whose tokens are all <PAD>, eval.py:30,116); tokens null: some hypothesis of fin is not finished (the
+// N-best search).
+__global__ void search_stop_kernel(const int64_t* __restrict__ tokens, const int32_t* __restrict__ fin, int n, int t,
+                                   int32_t* __restrict__ n_steps) {
+  __shared__ int live;
+  if (threadIdx.x == 0) live = 0;
   __syncthreads();
   int a = 0;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) a |= (tokens[i] != 0);
-  if (a) atomicOr(&any, 1);
+  for (int i = threadIdx.x; i < n; i += blockDim.x) a |= tokens ? tokens[i] != 0 : fin[i] == 0;
+  if (a) atomicOr(&live, 1);
   __syncthreads();
-  if (threadIdx.x == 0 && !any && *n_steps == 0) *n_steps = t + 1;
+  if (threadIdx.x == 0 && !live && *n_steps == 0) *n_steps = t + 1;
 }
 __global__ void search_finish_kernel(int32_t* n_steps, int tm) { if (*n_steps == 0) *n_steps = tm; }
 // scores[b, i*V + v] = log(sigmoid(logits_i[b, v])) + cum[i, b] / len(i, b)^0.7   (eval.py:51-62)
@@ -221,15 +222,7 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(float* __restrict__ scor
       const float y = x[v];
       if (y > best || (y == best && v < bi)) { best = y; bi = v; }
     }
-    sv[tid] = best; si[tid] = bi;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-      if (tid < w) {
-        const float y = sv[tid + w]; const int q = si[tid + w];
-        if (y > sv[tid] || (y == sv[tid] && q < si[tid])) { sv[tid] = y; si[tid] = q; }
-      }
-      __syncthreads();
-    }
+    block_argmax256(best, bi, sv, si);
     if (tid == 0) {
       vals[b * k + j] = sv[0]; idx[b * k + j] = si[0];
       if (si[0] < n) x[si[0]] = -INFINITY;
@@ -237,40 +230,45 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(float* __restrict__ scor
     __syncthreads();
   }
 }
-// regather the hypotheses: new beam k of caption b continues old beam src = idx / V with token idx % V (eval.py:66-114)
+// Regather the hypotheses: new beam k of caption b continues old beam src = idx / V with token idx % V (eval.py:66-114).  Two forms of
+// the per-hypothesis <EOS> word.  Reference search (NBEST false): the position of the last <EOS>, -1 without one; once the search has
+// stopped the hypotheses are frozen.  N-best search (NBEST true): fin = position of the first <EOS> + 1 (the length), 0 while it has
+// none; only <EOS> (2) finishes a hypothesis, and a finished one stays so.
 struct BeamUpdArgs {
   int B, H, V, Tm, bw, t;
   const float* vals; const int32_t* idx;                 // [B][bw]
-  const float* h_next; const float* c_next;              // [nb_old][B][H] states after this step
-  const int32_t* last_eos_old; const int64_t* hist_old;  // [nb_old][B], [nb_old][B][Tm]
-  float* h_new; float* c_new; float* cum_new; int32_t* last_eos_new; int64_t* hist_new; int64_t* tok_new;
-  const int32_t* n_steps;                                // != 0: the search already stopped (eval.py:116)
+  const float* h_next; const float* c_next;              // [nb_old][B][H] states after this step (c_next null: a GRU has no c)
+  const int32_t* eos_old; const int64_t* hist_old;       // [nb_old][B], [nb_old][B][Tm]
+  float* h_new; float* c_new; float* cum_new; int32_t* eos_new; int64_t* hist_new; int64_t* tok_new;
+  const int32_t* n_steps;                                // reference search only; != 0: the search already stopped (eval.py:116)
 };
-__global__ __launch_bounds__(128) void beam_update_kernel(const BeamUpdArgs p) {
+template <bool NBEST> __global__ __launch_bounds__(128) void beam_update_kernel(const BeamUpdArgs p) {
   const int k = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
   int flat = p.idx[b * p.bw + k];
   // The reference leaves its loop at the first step whose tokens are all <PAD>; the device loop has a fixed trip
   // count, so from then on the hypotheses are carried over unchanged (same beam order, <PAD> appended).
-  if (*p.n_steps != 0) flat = k * p.V;
+  if (!NBEST && *p.n_steps != 0) flat = k * p.V;
   const int src = flat / p.V, tok = flat % p.V;
   const size_t so = ((size_t)src * p.B + b), dn = ((size_t)k * p.B + b);
   for (int j = tid; j < p.H; j += 128) {
     p.h_new[dn * p.H + j] = p.h_next[so * p.H + j];
-    p.c_new[dn * p.H + j] = p.c_next[so * p.H + j];
+    if (p.c_next) p.c_new[dn * p.H + j] = p.c_next[so * p.H + j];
   }
   for (int j = tid; j < p.Tm; j += 128) p.hist_new[dn * p.Tm + j] = j < p.t ? p.hist_old[so * p.Tm + j] : (j == p.t ? (int64_t)tok : 0);
   if (tid == 0) {
+    const int e = p.eos_old[so];
     p.cum_new[dn] = p.vals[b * p.bw + k];
-    p.last_eos_new[dn] = tok == 2 ? p.t : p.last_eos_old[so];
+    p.eos_new[dn] = NBEST ? (e ? e : (tok == 2 ? p.t + 1 : 0)) : (tok == 2 ? p.t : e);
     p.tok_new[dn] = tok;
   }
 }
-// best[t][b] = hist[beam 0][b][t]
-__global__ void beam_best_kernel(const int64_t* __restrict__ hist, int64_t* __restrict__ best, int B, int Tm) {
+// tokens[r][t][b] = hist[order[r][b]][b][t] for the bw ranks of order; order null: beam 0 (bw = 1, the reference search's best)
+__global__ void beam_gather_kernel(const int64_t* __restrict__ hist, const int32_t* __restrict__ order, int64_t* __restrict__ tokens,
+                                   int B, int Tm, int bw) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B * Tm) return;
-  const int t = i / B, b = i % B;
-  best[i] = hist[(size_t)b * Tm + t];
+  if (i >= bw * Tm * B) return;
+  const int b = i % B, t = (i / B) % Tm, r = i / (B * Tm);
+  tokens[i] = hist[((size_t)(order ? order[r * B + b] : 0) * B + b) * Tm + t];
 }
 
 // =============================================================================================
@@ -430,43 +428,6 @@ void beam_select_kernel(const typename BeamSelArgsOf<CONSTRAINED>::type p) {
     }
   }
 }
-// regather the hypotheses of the N-best search: new beam k of caption b continues old beam src = idx / V with token idx % V.
-// fin = position of the hypothesis's <EOS> + 1 (its length), 0 while it has none; only <EOS> (2) finishes a hypothesis.
-struct BeamNUpdArgs {
-  int B, H, V, Tm, bw, t;
-  const float* vals; const int32_t* idx;                 // [B][bw]
-  const float* h_next; const float* c_next;              // [nb_old][B][H] states after this step (c_next unused by a GRU)
-  const int32_t* fin_old; const int64_t* hist_old;       // [nb_old][B], [nb_old][B][Tm]
-  float* h_new; float* c_new; float* cum_new; int32_t* fin_new; int64_t* hist_new; int64_t* tok_new;
-};
-__global__ __launch_bounds__(128) void beam_nbest_update_kernel(const BeamNUpdArgs p) {
-  const int k = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-  const int flat = p.idx[b * p.bw + k];
-  const int src = flat / p.V, tok = flat % p.V;
-  const size_t so = ((size_t)src * p.B + b), dn = ((size_t)k * p.B + b);
-  for (int j = tid; j < p.H; j += 128) {
-    p.h_new[dn * p.H + j] = p.h_next[so * p.H + j];
-    if (p.c_next) p.c_new[dn * p.H + j] = p.c_next[so * p.H + j];
-  }
-  for (int j = tid; j < p.Tm; j += 128) p.hist_new[dn * p.Tm + j] = j < p.t ? p.hist_old[so * p.Tm + j] : (j == p.t ? (int64_t)tok : 0);
-  if (tid == 0) {
-    const int f = p.fin_old[so];
-    p.cum_new[dn] = p.vals[b * p.bw + k];
-    p.fin_new[dn] = f ? f : (tok == 2 ? p.t + 1 : 0);
-    p.tok_new[dn] = tok;
-  }
-}
-// the search stops after the first step at which every hypothesis of every caption is finished
-__global__ void beam_nbest_stop_kernel(const int32_t* __restrict__ fin, int n, int t, int32_t* __restrict__ n_steps) {
-  __shared__ int live;
-  if (threadIdx.x == 0) live = 0;
-  __syncthreads();
-  int a = 0;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) a |= (fin[i] == 0);
-  if (a) atomicOr(&live, 1);
-  __syncthreads();
-  if (threadIdx.x == 0 && !live && *n_steps == 0) *n_steps = t + 1;
-}
 // final ranking, one thread per caption: len = fin, or n_steps without an <EOS>; score = cum / len^alpha (alpha = 0: cum);
 // descending score, lowest beam index among equals.  order[r][b] = the beam that takes rank r.
 __global__ __launch_bounds__(256) void beam_nbest_rank_kernel(const float* __restrict__ cum, const int32_t* __restrict__ fin,
@@ -490,12 +451,4 @@ __global__ __launch_bounds__(256) void beam_nbest_rank_kernel(const float* __res
     const int f = fin[bi * B + b];
     cum_out[r * B + b] = cum[bi * B + b]; len_out[r * B + b] = f ? f : ns; score_out[r * B + b] = best; order[r * B + b] = bi;
   }
-}
-// tokens[r][t][b] = hist[order[r][b]][b][t]
-__global__ void beam_nbest_gather_kernel(const int64_t* __restrict__ hist, const int32_t* __restrict__ order, int64_t* __restrict__ tokens,
-                                         int B, int Tm, int bw) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= bw * Tm * B) return;
-  const int b = i % B, t = (i / B) % Tm, r = i / (B * Tm);
-  tokens[i] = hist[((size_t)order[r * B + b] * B + b) * Tm + t];
 }

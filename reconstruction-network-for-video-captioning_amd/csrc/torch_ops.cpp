@@ -214,14 +214,18 @@ std::tuple<at::Tensor, at::Tensor> sample_rows(int64_t h, const at::Tensor& logi
                         (uint32_t)seed, (int32_t)t, toks.data_ptr<int64_t>(), lps.data_ptr<float>(), stream()), "sample_rows");
   return {toks, lps};
 }
-// logits [nb, rows, V], cum [nb, rows] float, finished [nb, rows] int32 -> vals [rows, beam_width], idx [rows, beam_width] int32
-std::tuple<at::Tensor, at::Tensor> beam_select_rows(int64_t h, const at::Tensor& logits, const at::Tensor& cum, const at::Tensor& finished,
-                                                    int64_t beam_width) {
+// the checks of the selection inputs: logits [nb, rows, V], cum [nb, rows] float, finished [nb, rows] int32, the width
+static void chk_select(const at::Tensor& logits, const at::Tensor& cum, const at::Tensor& finished, int64_t beam_width) {
   chk(logits, at::kFloat, "logits"); chk(cum, at::kFloat, "cum"); chk(finished, at::kInt, "finished");
   TORCH_CHECK(logits.dim() == 3 && logits.size(0) >= 1 && logits.size(1) >= 1 && logits.size(2) >= 1 && logits.size(1) <= INT32_MAX &&
               logits.size(2) <= INT32_MAX && logits.size(0) <= 8, "recnet: logits must be [nb <= 8, rows, V], got ", logits.sizes());
   shape(cum, {logits.size(0), logits.size(1)}, "cum"); shape(finished, {logits.size(0), logits.size(1)}, "finished");
   TORCH_CHECK(beam_width >= 1 && beam_width <= 8 && beam_width <= logits.size(2), "recnet: beam_width must be in [1, min(8, V)], got ", beam_width);
+}
+// logits [nb, rows, V], cum [nb, rows] float, finished [nb, rows] int32 -> vals [rows, beam_width], idx [rows, beam_width] int32
+std::tuple<at::Tensor, at::Tensor> beam_select_rows(int64_t h, const at::Tensor& logits, const at::Tensor& cum, const at::Tensor& finished,
+                                                    int64_t beam_width) {
+  chk_select(logits, cum, finished, beam_width);
   auto vals = at::empty({logits.size(1), beam_width}, logits.options());
   auto idx = at::empty({logits.size(1), beam_width}, logits.options().dtype(at::kInt));
   ok(recnet_beam_select_rows(H(h), logits.data_ptr<float>(), cum.data_ptr<float>(), finished.data_ptr<int32_t>(), (int32_t)logits.size(0),
@@ -231,15 +235,19 @@ std::tuple<at::Tensor, at::Tensor> beam_select_rows(int64_t h, const at::Tensor&
 }
 // tokens [beam_width, Tm, B] rank-major, cum / score [beam_width, B] float, len [beam_width, B] int32, n_steps [1] int32
 // (the width is checked here before the outputs are allocated and zeroed; length_alpha by the library, behind those fills)
-std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> beam_search_nbest(int64_t h, const at::Tensor& enc, int64_t beam_width,
-                                                                                         double length_alpha) {
-  chk_enc(h, enc);
-  TORCH_CHECK(beam_width >= 1 && beam_width <= 8 && beam_width <= dim(h, RECNET_DIM_V), "recnet: beam_width must be in [1, min(8, V)], got ", beam_width);
+using NbestOut = std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor>;
+static NbestOut nbest_outputs(int64_t h, const at::Tensor& enc, int64_t beam_width) {
   const int64_t B = enc.size(0);
   auto toks = at::zeros({beam_width, recnet_dim(H(h), RECNET_DIM_TM), B}, enc.options().dtype(at::kLong));
   auto cum = at::zeros({beam_width, B}, enc.options()), score = at::zeros({beam_width, B}, enc.options());
   auto len = at::zeros({beam_width, B}, enc.options().dtype(at::kInt));
   auto n = at::zeros({1}, enc.options().dtype(at::kInt));
+  return {toks, cum, len, score, n};
+}
+NbestOut beam_search_nbest(int64_t h, const at::Tensor& enc, int64_t beam_width, double length_alpha) {
+  chk_enc(h, enc);
+  TORCH_CHECK(beam_width >= 1 && beam_width <= 8 && beam_width <= dim(h, RECNET_DIM_V), "recnet: beam_width must be in [1, min(8, V)], got ", beam_width);
+  auto [toks, cum, len, score, n] = nbest_outputs(h, enc, beam_width);
   ok(recnet_beam_search_nbest(H(h), enc.data_ptr<float>(), (int32_t)beam_width, (float)length_alpha, toks.data_ptr<int64_t>(),
                               cum.data_ptr<float>(), len.data_ptr<int32_t>(), score.data_ptr<float>(), n.data_ptr<int32_t>(), stream()),
      "beam_search_nbest");
@@ -264,11 +272,7 @@ std::tuple<at::Tensor, at::Tensor> beam_select_rows_constrained(int64_t h, const
                                                                 const at::Tensor& finished, const c10::optional<at::Tensor>& hist, int64_t t,
                                                                 int64_t beam_width, int64_t no_repeat_ngram, int64_t min_length,
                                                                 at::IntArrayRef banned) {
-  chk(logits, at::kFloat, "logits"); chk(cum, at::kFloat, "cum"); chk(finished, at::kInt, "finished");
-  TORCH_CHECK(logits.dim() == 3 && logits.size(0) >= 1 && logits.size(1) >= 1 && logits.size(2) >= 1 && logits.size(1) <= INT32_MAX &&
-              logits.size(2) <= INT32_MAX && logits.size(0) <= 8, "recnet: logits must be [nb <= 8, rows, V], got ", logits.sizes());
-  shape(cum, {logits.size(0), logits.size(1)}, "cum"); shape(finished, {logits.size(0), logits.size(1)}, "finished");
-  TORCH_CHECK(beam_width >= 1 && beam_width <= 8 && beam_width <= logits.size(2), "recnet: beam_width must be in [1, min(8, V)], got ", beam_width);
+  chk_select(logits, cum, finished, beam_width);
   TORCH_CHECK(t >= 0 && t < INT32_MAX, "recnet: t out of range");
   chk_constraints(no_repeat_ngram, min_length);
   const auto ids = ban_ids(banned);
@@ -288,19 +292,13 @@ std::tuple<at::Tensor, at::Tensor> beam_select_rows_constrained(int64_t h, const
                                          vals.data_ptr<float>(), idx.data_ptr<int32_t>(), stream()), "beam_select_rows_constrained");
   return {vals, idx};
 }
-std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> beam_search_nbest_constrained(int64_t h, const at::Tensor& enc,
-                                                                                                     int64_t beam_width, double length_alpha,
-                                                                                                     int64_t no_repeat_ngram, int64_t min_length,
-                                                                                                     at::IntArrayRef banned) {
+NbestOut beam_search_nbest_constrained(int64_t h, const at::Tensor& enc, int64_t beam_width, double length_alpha, int64_t no_repeat_ngram,
+                                       int64_t min_length, at::IntArrayRef banned) {
   chk_enc(h, enc);
   TORCH_CHECK(beam_width >= 1 && beam_width <= 8 && beam_width <= dim(h, RECNET_DIM_V), "recnet: beam_width must be in [1, min(8, V)], got ", beam_width);
   chk_constraints(no_repeat_ngram, min_length);
   const auto ids = ban_ids(banned);
-  const int64_t B = enc.size(0);
-  auto toks = at::zeros({beam_width, recnet_dim(H(h), RECNET_DIM_TM), B}, enc.options().dtype(at::kLong));
-  auto cum = at::zeros({beam_width, B}, enc.options()), score = at::zeros({beam_width, B}, enc.options());
-  auto len = at::zeros({beam_width, B}, enc.options().dtype(at::kInt));
-  auto n = at::zeros({1}, enc.options().dtype(at::kInt));
+  auto [toks, cum, len, score, n] = nbest_outputs(h, enc, beam_width);
   ok(recnet_beam_search_nbest_constrained(H(h), enc.data_ptr<float>(), (int32_t)beam_width, (float)length_alpha, (int32_t)no_repeat_ngram,
                                           (int32_t)min_length, ids.data(), (int32_t)ids.size(), toks.data_ptr<int64_t>(), cum.data_ptr<float>(),
                                           len.data_ptr<int32_t>(), score.data_ptr<float>(), n.data_ptr<int32_t>(), stream()),

@@ -21,21 +21,50 @@ from . import _ops
 from .engine import Engine
 
 
-def _engine(decoder, encoder_outputs):
-    B, F = encoder_outputs.shape[0], encoder_outputs.shape[1]
-    key = (B, F, encoder_outputs.device)
+def _cached_engine(decoder, encoder_outputs, reconstructor=None, caption_max_len=None):
+    """The engine the calls of this module run on, cached on the decoder.  Without the optional arguments: the decoder alone, under
+    the key Decoder.forward uses — the two share one engine.  caption_max_len: that caption length instead of the engine's default
+    (Tm is baked into the handle), under a key of its own.  reconstructor (with caption_max_len: the cml / T^2 rescale is baked in
+    as well): decoder AND reconstructor bound, keyed by the reconstructor's kind and rebuilt for another reconstructor object."""
+    B, F, dev = encoder_outputs.shape[0], encoder_outputs.shape[1], encoder_outputs.device
+    shared = reconstructor is None and caption_max_len is None
+    if reconstructor is not None:
+        key = ("rec", reconstructor.kind, B, F, dev, int(caption_max_len))
+    else:
+        key = (B, F, dev) if shared else ("nbest", B, F, dev, int(caption_max_len))
     eng = decoder._step_engines.get(key)
+    if reconstructor is not None and eng is not None:
+        eng = eng[0] if eng[1] is reconstructor else None
     if eng is None:
-        eng = Engine(decoder.dims(B, F), None, decoder.precision, decoder.hyper(), device=encoder_outputs.device)
+        dims, hy = decoder.dims(B, F), decoder.hyper()
+        if caption_max_len is not None:
+            hy.update(caption_max_len=int(caption_max_len))
+        if reconstructor is not None:
+            dims.update(R=reconstructor.hidden_size, RA=getattr(reconstructor, "attn_size", 0), rec_cell=reconstructor.model_name)
+            hy.update(reconstructor_decoder_dropout=reconstructor.decoder_dropout_p)
+        eng = Engine(dims, getattr(reconstructor, "kind", None), decoder.precision, hy, device=dev)
         eng.bind_decoder({k: v.data for k, v in decoder.named_tensors().items()})
-        decoder._step_engines[key] = eng
+        if reconstructor is not None:
+            eng.bind_reconstructor({k: v.data for k, v in reconstructor.named_tensors().items()})
+        decoder._step_engines[key] = eng if reconstructor is None else (eng, reconstructor)
     # The HIP optimiser updates the parameters through raw pointers (no torch `_version` bump), so a cached "packed"
     # flag can go stale between two evaluations of a training run.  Re-packing costs a few microseconds next to a
     # 31-step search: always do it.
     eng.pack_weights()
-    eng._pver = decoder.weights_signature()
-    eng._inv_sig = None          # the search recomputes the invariants itself
+    if shared:
+        eng._pver = decoder.weights_signature()
+        eng._inv_sig = None          # the search recomputes the invariants itself
     return eng
+
+
+# The two named forms of _cached_engine: the points at which the tests put a poisoned engine in, to show that the argument checks
+# come before any engine is asked for.
+def _rec_engine(config, decoder, reconstructor, encoder_outputs):
+    return _cached_engine(decoder, encoder_outputs, reconstructor, config.caption_max_len)
+
+
+def _nbest_engine(config, decoder, encoder_outputs):
+    return _cached_engine(decoder, encoder_outputs, caption_max_len=config.caption_max_len)
 
 
 def _check_start(config, input, hidden):
@@ -50,7 +79,7 @@ def greedy_search(config, decoder, input, hidden, encoder_outputs):
     """eval.py:19-33.  Returns output_indices: list over steps of lists over the batch (python ints), like the
     reference's list of lists of 0-d tensors."""
     _check_start(config, input, hidden)
-    eng = _engine(decoder, encoder_outputs)
+    eng = _cached_engine(decoder, encoder_outputs)
     toks, n = _ops.load().greedy_search(int(eng.handle.value), encoder_outputs.contiguous())
     n = int(n.item())
     return toks[:n].cpu().tolist()
@@ -59,7 +88,7 @@ def greedy_search(config, decoder, input, hidden, encoder_outputs):
 def beam_search(config, beam_width, vocab, decoder, input, hidden, encoder_outputs):
     """eval.py:36-120.  Returns top1_output_list: one token list per caption."""
     _check_start(config, input, hidden)
-    eng = _engine(decoder, encoder_outputs)
+    eng = _cached_engine(decoder, encoder_outputs)
     best, n = _ops.load().beam_search(int(eng.handle.value), encoder_outputs.contiguous(), int(beam_width))
     n = int(n.item())
     return best[:n].t().cpu().tolist()
@@ -76,7 +105,7 @@ def sample_search(config, decoder, input, hidden, encoder_outputs, temperature=1
     if int(top_k) != top_k or not 0 <= top_k <= decoder.output_size:
         raise ValueError("top_k must be an integer in [0, %d] (got %r)" % (decoder.output_size, top_k))
     _check_start(config, input, hidden)
-    eng = _engine(decoder, encoder_outputs)
+    eng = _cached_engine(decoder, encoder_outputs)
     toks, lps, n = _ops.load().sample_search(int(eng.handle.value), encoder_outputs.contiguous(), float(temperature), int(top_k),
                                              int(seed) & 0xFFFFFFFF)
     n = int(n.item())
@@ -136,7 +165,7 @@ def _caption_tensor(config, decoder, B, captions):
 
 def _score(decoder, encoder_outputs, tokens, temperature, reuse_features):
     """Device tensors (logprobs [T, B], caption_logprob [B], lengths [B]) of checked tokens [T, B]."""
-    eng = _engine(decoder, encoder_outputs)
+    eng = _cached_engine(decoder, encoder_outputs)
     enc = None if reuse_features else encoder_outputs.contiguous()
     return _ops.load().score_captions(int(eng.handle.value), enc, tokens.to(encoder_outputs.device).contiguous(), float(temperature))
 
@@ -177,26 +206,6 @@ def canonical_captions(captions, T=None, eos=2, pad=0):
     return out
 
 
-def _rec_engine(config, decoder, reconstructor, encoder_outputs):
-    """An engine with decoder AND reconstructor bound, cached on the decoder like _engine's, keyed by the reconstructor's kind
-    as well; the packed weight images are refreshed on every call (see _engine)."""
-    B, F = encoder_outputs.shape[0], encoder_outputs.shape[1]
-    key = ("rec", reconstructor.kind, B, F, encoder_outputs.device, int(config.caption_max_len))   # (Tm and the cml / T^2 rescale are baked in)
-    hit = decoder._step_engines.get(key)
-    if hit is None or hit[1] is not reconstructor:
-        dims = decoder.dims(B, F)
-        dims.update(R=reconstructor.hidden_size, RA=getattr(reconstructor, "attn_size", 0), rec_cell=reconstructor.model_name)
-        hy = decoder.hyper()
-        hy.update(reconstructor_decoder_dropout=reconstructor.decoder_dropout_p, caption_max_len=config.caption_max_len)
-        eng = Engine(dims, reconstructor.kind, decoder.precision, hy, device=encoder_outputs.device)
-        eng.bind_decoder({k: v.data for k, v in decoder.named_tensors().items()})
-        eng.bind_reconstructor({k: v.data for k, v in reconstructor.named_tensors().items()})
-        hit = decoder._step_engines[key] = (eng, reconstructor)
-    eng = hit[0]
-    eng.pack_weights()
-    return eng
-
-
 def _check_reconstructor(config, decoder, reconstructor, encoder_outputs):
     if getattr(reconstructor, "kind", None) not in ("global", "local"):
         raise ValueError("reconstructor must be a GlobalReconstructor or a LocalReconstructor (got %r)" % (type(reconstructor).__name__,))
@@ -213,6 +222,18 @@ def _check_reconstructor(config, decoder, reconstructor, encoder_outputs):
                          % (reconstructor.caption_max_len, config.caption_max_len))
     if reconstructor.precision != decoder.precision:
         raise ValueError("decoder (%s) and reconstructor (%s) must share one precision" % (decoder.precision, reconstructor.precision))
+
+
+def _check_recon_weight(config, decoder, reconstructor, encoder_outputs, recon_weight):
+    """The checks of best_of_n / best_of_beam on their reranking arguments; returns (the reconstructor takes part, the weight)."""
+    if reconstructor is None and recon_weight != 0:
+        raise ValueError("recon_weight = %r needs a reconstructor" % (recon_weight,))
+    if reconstructor is None or recon_weight == 0:
+        return False, 0.0
+    if not (isinstance(recon_weight, numbers.Real) and math.isfinite(recon_weight)):   # (numpy scalars are numbers.Real too)
+        raise ValueError("recon_weight must be a finite number (got %r)" % (recon_weight,))
+    _check_reconstructor(config, decoder, reconstructor, encoder_outputs)
+    return True, float(recon_weight)
 
 
 def _rec_errors(config, decoder, reconstructor, encoder_outputs, tokens, want_recon=False):
@@ -275,14 +296,7 @@ def best_of_n(config, decoder, input, hidden, encoder_outputs, n, temperature=1.
     reconstructor.  Returns (captions: [B] token lists cut after their <EOS>, chosen k [B], score [B])."""
     if int(n) != n or n < 1:
         raise ValueError("n must be a positive integer (got %r)" % (n,))
-    use_rec = reconstructor is not None and recon_weight != 0
-    if reconstructor is None and recon_weight != 0:
-        raise ValueError("recon_weight = %r needs a reconstructor" % (recon_weight,))
-    if use_rec:
-        if not (isinstance(recon_weight, numbers.Real) and math.isfinite(recon_weight)):   # (numpy scalars are numbers.Real too)
-            raise ValueError("recon_weight must be a finite number (got %r)" % (recon_weight,))
-        recon_weight = float(recon_weight)
-        _check_reconstructor(config, decoder, reconstructor, encoder_outputs)
+    use_rec, recon_weight = _check_recon_weight(config, decoder, reconstructor, encoder_outputs, recon_weight)
     cands = [sample_search(config, decoder, input, hidden, encoder_outputs, temperature, top_k, (seed + k) & 0xFFFFFFFF)[0]
              for k in range(int(n))]
     caps, lens, checked = [], [], []
@@ -297,24 +311,9 @@ def best_of_n(config, decoder, input, hidden, encoder_outputs, n, temperature=1.
         t_star = max(tokens.shape[0] for tokens in checked)
         errs = [_rec_errors(config, decoder, reconstructor, encoder_outputs, canonical_captions(tokens, t_star))[0] for tokens in checked]
         errs = torch.stack(errs).cpu().tolist()
-    ks, scores = pick_best_of_n(caps, lens, errs, recon_weight if use_rec else 0.0)
+    ks, scores = pick_best_of_n(caps, lens, errs, recon_weight)
     out = [[cands[k][t][b] for t in range(lens[k][b])] for b, k in enumerate(ks)]
     return out, ks, scores
-
-
-def _nbest_engine(config, decoder, encoder_outputs):
-    """_engine with the caption length of `config` (Tm is baked into the handle), cached under its own key."""
-    B, F = encoder_outputs.shape[0], encoder_outputs.shape[1]
-    key = ("nbest", B, F, encoder_outputs.device, int(config.caption_max_len))
-    eng = decoder._step_engines.get(key)
-    if eng is None:
-        hy = decoder.hyper()
-        hy.update(caption_max_len=int(config.caption_max_len))
-        eng = Engine(decoder.dims(B, F), None, decoder.precision, hy, device=encoder_outputs.device)
-        eng.bind_decoder({k: v.data for k, v in decoder.named_tensors().items()})
-        decoder._step_engines[key] = eng
-    eng.pack_weights()           # (see _engine)
-    return eng
 
 
 def _check_beam(decoder, beam_width, length_alpha):
@@ -357,13 +356,9 @@ def _beam_nbest(config, decoder, input, hidden, encoder_outputs, beam_width, len
     ids = _check_constraints(config, decoder, beam_width, no_repeat_ngram, min_length, banned_tokens)
     _check_start(config, input, hidden)
     eng = _nbest_engine(config, decoder, encoder_outputs)
-    if no_repeat_ngram or min_length or ids:
-        toks, cum, ln, score, n = _ops.load().beam_search_nbest_constrained(int(eng.handle.value), encoder_outputs.contiguous(),
-                                                                            int(beam_width), float(length_alpha), int(no_repeat_ngram),
-                                                                            int(min_length), ids)
-    else:
-        toks, cum, ln, score, n = _ops.load().beam_search_nbest(int(eng.handle.value), encoder_outputs.contiguous(), int(beam_width),
-                                                                float(length_alpha))
+    # (constraints all off: the library launches the unconstrained selection, recnet_beam_search_nbest's own path)
+    toks, cum, ln, score, n = _ops.load().beam_search_nbest_constrained(int(eng.handle.value), encoder_outputs.contiguous(), int(beam_width),
+                                                                        float(length_alpha), int(no_repeat_ngram), int(min_length), ids)
     return toks[:, :int(n.item())], cum, ln, score
 
 
@@ -398,14 +393,7 @@ def best_of_beam(config, decoder, input, hidden, encoder_outputs, beam_width, le
     the reconstruction error as it is, all ranks at the common T = n_steps (the global error depends on T).  no_repeat_ngram /
     min_length / banned_tokens are beam_search_nbest's.  Returns what best_of_n returns: (captions: [B] token lists cut after
     their <EOS>, chosen k [B], score [B])."""
-    use_rec = reconstructor is not None and recon_weight != 0
-    if reconstructor is None and recon_weight != 0:
-        raise ValueError("recon_weight = %r needs a reconstructor" % (recon_weight,))
-    if use_rec:
-        if not (isinstance(recon_weight, numbers.Real) and math.isfinite(recon_weight)):
-            raise ValueError("recon_weight must be a finite number (got %r)" % (recon_weight,))
-        recon_weight = float(recon_weight)
-        _check_reconstructor(config, decoder, reconstructor, encoder_outputs)
+    use_rec, recon_weight = _check_recon_weight(config, decoder, reconstructor, encoder_outputs, recon_weight)
     toks, cum, ln, _ = _beam_nbest(config, decoder, input, hidden, encoder_outputs, beam_width, length_alpha, no_repeat_ngram,
                                    min_length, banned_tokens)
     errs = None
@@ -413,7 +401,7 @@ def best_of_beam(config, decoder, input, hidden, encoder_outputs, beam_width, le
         errs = torch.stack([_rec_errors(config, decoder, reconstructor, encoder_outputs, toks[r])[0]
                             for r in range(int(beam_width))]).cpu().tolist()
     lens = ln.cpu().tolist()
-    ks, scores = pick_best_of_n(cum.cpu().tolist(), lens, errs, recon_weight if use_rec else 0.0)
+    ks, scores = pick_best_of_n(cum.cpu().tolist(), lens, errs, recon_weight)
     toks = toks.cpu().tolist()
     out = [[toks[k][t][b] for t in range(lens[k][b])] for b, k in enumerate(ks)]
     return out, ks, scores
