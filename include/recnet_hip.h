@@ -196,6 +196,18 @@ int recnet_sample_rows(recnet_handle* h, const float* logits, int32_t rows, int3
  * rows [0, n_steps) are meaningful, later rows hold what the fixed-length loop went on to draw. */
 int recnet_sample_search(recnet_handle* h, const float* enc, float temperature, int32_t top_k, uint32_t seed,
                          int64_t* tokens_out, float* logprobs_out, int32_t* n_steps_out, void* stream);
+/* ---- nucleus (top-p) sampling, composed with top_k (the reference has no counterpart).  The two calls above
+ * with one more cut: after the top_k cut, only the shortest prefix of the allowed entries (value descending, index ascending) whose
+ * mass reaches top_p of the allowed mass is drawn from.  Masses are integers, floor(exp(s_v - max s) * 2^32) in fp32, summed exactly:
+ * the set is a pure function of the logits, the same on every call.  Entries equal to the cut value are admitted lowest index first,
+ * only as many as the target needs.  0 < top_p <= 1; top_p = 1 is no nucleus cut (tokens and log-probabilities of the calls above,
+ * bit for bit); top_p < 1 needs V < 2^21.  n_allowed_out (int32, [rows] resp. [caption_max_len+1][B], may be NULL) = the size of the
+ * set each token was drawn from, always >= 1; logprobs_out is the log-probability under that set. */
+int recnet_sample_rows_nucleus(recnet_handle* h, const float* logits, int32_t rows, int32_t V, float temperature, int32_t top_k,
+                               float top_p, uint32_t seed, int32_t t, int64_t* tokens_out, float* logprobs_out, int32_t* n_allowed_out,
+                               void* stream);
+int recnet_sample_search_nucleus(recnet_handle* h, const float* enc, float temperature, int32_t top_k, float top_p, uint32_t seed,
+                                 int64_t* tokens_out, float* logprobs_out, int32_t* n_allowed_out, int32_t* n_steps_out, void* stream);
 
 /* ---- scoring: how probable is a GIVEN token / caption under the model (the reference has no counterpart).
  * recnet_logprob_rows: logprobs_out[r] = s_k - logsumexp_v s_v with s_v = logits[r, v] / temperature and k = tokens[r] (the maximum

@@ -155,6 +155,8 @@ EXPORTS["recnet_greedy_search"] = (_i, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_
 EXPORTS["recnet_beam_search"] = (_i, [C.c_void_p, C.c_void_p, _i, C.c_void_p, C.c_void_p, C.c_void_p])
 EXPORTS["recnet_sample_rows"] = (_i, [C.c_void_p, C.c_void_p, _i, _i, _f, _i, C.c_uint32, _i, C.c_void_p, C.c_void_p, C.c_void_p])
 EXPORTS["recnet_sample_search"] = (_i, [C.c_void_p, C.c_void_p, _f, _i, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
+EXPORTS["recnet_sample_rows_nucleus"] = (_i, [C.c_void_p, C.c_void_p, _i, _i, _f, _i, _f, C.c_uint32, _i] + [C.c_void_p] * 4)
+EXPORTS["recnet_sample_search_nucleus"] = (_i, [C.c_void_p, C.c_void_p, _f, _i, _f, C.c_uint32] + [C.c_void_p] * 5)
 EXPORTS["recnet_beam_select_rows"] = (_i, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _i, _i, _i, _i, C.c_void_p, C.c_void_p, C.c_void_p])
 EXPORTS["recnet_beam_search_nbest"] = (_i, [C.c_void_p, C.c_void_p, _i, _f] + [C.c_void_p] * 6)
 # (added at ABI version 12 without a bump: load() fails on a library that lacks them)

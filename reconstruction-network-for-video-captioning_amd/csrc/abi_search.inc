@@ -215,6 +215,51 @@ int recnet_sample_search(recnet_handle* h, const float* enc, float temperature, 
   return RECNET_OK;
 }
 
+// ---- nucleus (top-p) sampling on what the top-k cut leaves (the reference has no counterpart; DESIGN.md section 13).  Entry points
+// of their own: recnet_sample_rows / recnet_sample_search above keep their kernels.
+static int check_sample_nucleus(float temperature, int top_k, float top_p, int V) {
+  int r = check_sample(temperature, top_k, V); if (r) return r;
+  if (!(top_p > 0.f) || !(top_p <= 1.f)) return fail(RECNET_EINVAL, "top_p must be in (0, 1]");    // (refuses NaN too)
+  if (top_p < 1.f && V >= (1 << 21)) return fail(RECNET_EINVAL, "top_p < 1 needs V < 2^21 (the integer masses sum in 53 bits)");
+  return RECNET_OK;
+}
+// launch_sample_rows with the nucleus cut; n_allowed [rows] may be null
+static void launch_sample_rows_nucleus(const float* logits, int rows, int V, int B, float temperature, int top_k, float top_p,
+                                       uint32_t seed, int t, int64_t* tokens, float* logprobs, int32_t* n_allowed, hipStream_t st) {
+  SampleNucArgs a;
+  a.x = logits; a.V = V; a.k = top_k == V ? 0 : top_k; a.B = B; a.t = t;
+  a.temp = temperature; a.key = rn_site_key(seed, RN_SITE_SAMPLE); a.tok = tokens; a.lp = logprobs;
+  a.top_p = top_p; a.n_allowed = n_allowed;
+  if (V <= SR_ROW_LDS_MAX) hipLaunchKernelGGL((sample_rows_kernel<true, true>), dim3(rows), dim3(256), (size_t)V * 4, st, a);
+  else hipLaunchKernelGGL((sample_rows_kernel<false, true>), dim3(rows), dim3(256), 0, st, a);
+}
+
+int recnet_sample_rows_nucleus(recnet_handle* h, const float* logits, int32_t rows, int32_t V, float temperature, int32_t top_k,
+                               float top_p, uint32_t seed, int32_t t, int64_t* tokens_out, float* logprobs_out, int32_t* n_allowed_out,
+                               void* stream) {
+  REQUIRE_WS(h);
+  if (!logits || !tokens_out || !logprobs_out) return fail(RECNET_EINVAL, "null argument");
+  if (rows < 1 || V < 1 || t < 0) return fail(RECNET_EINVAL, "rows and V must be positive, t non-negative");
+  int r = check_sample_nucleus(temperature, top_k, top_p, V); if (r) return r;
+  launch_sample_rows_nucleus(logits, rows, V, rows, temperature, top_k, top_p, seed, t, tokens_out, logprobs_out, n_allowed_out,
+                             (hipStream_t)stream);
+  LAUNCH_OK();
+  return RECNET_OK;
+}
+
+int recnet_sample_search_nucleus(recnet_handle* h, const float* enc, float temperature, int32_t top_k, float top_p, uint32_t seed,
+                                 int64_t* tokens_out, float* logprobs_out, int32_t* n_allowed_out, int32_t* n_steps_out, void* stream) {
+  int r = search_check(h, enc && tokens_out && logprobs_out && n_steps_out); if (r) return r;
+  r = check_sample_nucleus(temperature, top_k, top_p, h->V); if (r) return r;
+  hipStream_t st = (hipStream_t)stream;
+  search_one_per_caption(h, enc, tokens_out, n_steps_out, st, [&](int t, int64_t* out_t) {
+    launch_sample_rows_nucleus(h->sr_logits, h->B, h->V, h->B, temperature, top_k, top_p, seed, t, out_t,
+                               logprobs_out + (size_t)t * h->B, n_allowed_out ? n_allowed_out + (size_t)t * h->B : nullptr, st);
+  });
+  LAUNCH_OK();
+  return RECNET_OK;
+}
+
 // ---- scoring given captions (the reference has no counterpart; the loop is train.py:25,45 in eval mode)
 static void launch_logprob_rows(const float* logits, const int64_t* tokens, int rows, int V, float temperature, float* logprobs,
                                 hipStream_t st) {

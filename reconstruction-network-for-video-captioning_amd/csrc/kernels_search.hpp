@@ -55,12 +55,70 @@ struct SampleArgs {
   float temp; uint32_t key;            // key = rn_site_key(seed, RN_SITE_SAMPLE)
   int64_t* tok; float* lp;             // [rows]
 };
+// The nucleus form (tests/nucleus_ref.py restates it): after the top-k cut, the shortest prefix of the allowed
+// entries, in the same order, whose mass reaches top_p of the mass of all of them.  top_p = 1: no nucleus cut, the select is skipped.
+struct SampleNucArgs : SampleArgs {
+  float top_p;                         // in (0, 1]; below 1: V < 2^21, so that the sum of the masses stays below 2^53
+  int32_t* n_allowed;                  // [rows], the size of the set drawn from (may be null)
+};
+template <bool NUC> struct SampleArgsOf { typedef SampleArgs type; };
+template <> struct SampleArgsOf<true> { typedef SampleNucArgs type; };
+// the float of an order-preserving key (-0 and +0 come back as +0)
+__device__ __forceinline__ float sr_unkey(uint32_t k) { return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu)); }
+// The integer mass of an entry: floor(exp(s - m) * 2^32), s - m <= 0 and the exponential in fp32 (rn_exp, the one of the
+// log-probability).  The scale is a power of two, so the product is exact; the clamps make the conversion defined for every input
+// (a NaN becomes 0), and everything the select does with the masses afterwards is integer arithmetic.
+__device__ __forceinline__ unsigned long long sr_mass(float xv, float temp, float m) {
+  const float f = fminf(fmaxf(rn_exp(xv / temp - m) * 0x1p32f, 0.f), 0x1p32f);
+  return f >= 0x1p32f ? 1ull << 32 : (unsigned long long)(uint32_t)f;
+}
+// inclusive prefix sum of 64-bit words over the 256 threads of a block, in thread order; sm: 4 words of LDS scratch
+__device__ __forceinline__ unsigned long long block_scan256_u64(unsigned long long c, unsigned long long* sm) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  unsigned long long s = c;
+  for (int o = 1; o < 64; o <<= 1) { const unsigned long long y = __shfl_up(s, o); if (lane >= o) s += y; }
+  __syncthreads();
+  if (lane == 63) sm[w] = s;
+  __syncthreads();
+  for (int j = 0; j < w; ++j) s += sm[j];
+  return s;
+}
+// Of the entries equal to the cut value (key == thr) the `need` lowest indices are admitted, need >= 1 and fewer than there are:
+// every thread counts its equal entries over a contiguous index chunk, a scan, and the thread that owns the need-th one walks to it
+// and publishes its index + 1 in sel[0], which every thread takes as `cut`.  A statement of sample_rows_kernel on its x, V, tid, thr,
+// sw, sel and cut — a macro, not a function, so that the top-k cut expands to the statements it always had and the instantiations
+// without a nucleus keep their code to the instruction.
+#define SR_EQUAL_CUT(NEED)                                                                                   \
+  {                                                                                                          \
+    const int C = (V + 255) / 256, v0 = tid * C, v1 = v0 + C < V ? v0 + C : V;                               \
+    int c = 0;                                                                                               \
+    for (int v = v0; v < v1; ++v) c += sr_key(x[v]) == thr;                                                  \
+    const int incl = block_scan256(c, sw), excl = incl - c;                                                  \
+    if (excl < NEED && NEED <= incl) {                                                                       \
+      int need = NEED - excl;                                                                                \
+      for (int v = v0; v < v1; ++v)                                                                          \
+        if (sr_key(x[v]) == thr && --need == 0) { sel[0] = v + 1; break; }                                   \
+    }                                                                                                        \
+    __syncthreads();                                                                                         \
+    cut = (int)sel[0];                                                                                       \
+  }
 // One workgroup per row.  (1) k > 0: the k-th largest key by a radix select, 8 bits per pass from the top — an LDS histogram of the
 // entries that share the prefix found so far, a scan from the top bin down, one thread owns the bin the k-th entry falls in; entries
 // equal to the cut value are admitted lowest index first (the order of topk_rows_kernel), by a count over contiguous index chunks
 // where they are more than the cut leaves room for.  (2) max of s = x / temp and arg-max of s + g over the allowed entries, lowest
 // index among equals.  (3) sum exp(s - max).  Reads the logits only.
-template <bool RES> __global__ __launch_bounds__(256) void sample_rows_kernel(const SampleArgs p) {
+// NUC, top_p < 1, between (1) and (2): the allowed set is a prefix of one total order (key descending, index ascending), and so is
+// the nucleus; the same radix walk finds its end by mass instead of by count.  One pass takes m = max s over the allowed entries.
+// Then per 8 bits a histogram of 256 64-bit sums (ds_add_u64) of the integer masses sr_mass of the allowed entries that share the
+// prefix found so far, a 64-bit scan from the top bin down, and the one thread whose bin crosses the remaining target publishes
+// digit, remaining target and bin mass; the first pass's grand total Q gives target = max(1, ceil(top_p * Q)) in float64 (exact:
+// Q < 2^53).  Integer sums do not depend on the order the atomics arrive in: two calls give the same nucleus.  After four passes
+// the cut value and the mass still missing at it are known; its entries all carry one mass q, so ceil(missing / q) of them are
+// admitted, lowest indices first (SR_EQUAL_CUT), and the result is again (thr, cut): (2) and (3) are unchanged.  The sel64 words a
+// pass reads are given defaults inside that pass, so a row of NaN / inf, whose masses are meaningless, leaves a meaningless but
+// in-range (thr, cut).  (3) also counts the allowed entries for n_allowed.
+template <bool RES, bool NUC = false> __global__ __launch_bounds__(256)
+void sample_rows_kernel(const typename SampleArgsOf<NUC>::type p) {
   extern __shared__ float sr_row[];
   __shared__ int hist[256]; __shared__ float sv[256]; __shared__ int si[256]; __shared__ int sw[4]; __shared__ float sf[4];
   __shared__ uint32_t sel[3];
@@ -91,18 +149,52 @@ template <bool RES> __global__ __launch_bounds__(256) void sample_rows_kernel(co
       prefix |= sel[0] << shift; krem = (int)sel[1]; ceq = (int)sel[2];
     }
     thr = prefix;
-    if (krem < ceq) {            // more entries equal to the cut value than the cut admits: the krem lowest indices
-      const int C = (V + 255) / 256, v0 = tid * C, v1 = v0 + C < V ? v0 + C : V;
-      int c = 0;
-      for (int v = v0; v < v1; ++v) c += sr_key(x[v]) == thr;
-      const int incl = block_scan256(c, sw), excl = incl - c;
-      if (excl < krem && krem <= incl) {
-        int need = krem - excl;
-        for (int v = v0; v < v1; ++v)
-          if (sr_key(x[v]) == thr && --need == 0) { sel[0] = v + 1; break; }
+    if (krem < ceq) SR_EQUAL_CUT(krem)   // more entries equal to the cut value than the cut admits: the krem lowest indices
+  }
+  if constexpr (NUC) {
+    if (p.top_p < 1.f) {                                               // (uniform over the grid)
+      __shared__ unsigned long long hist64[256], sw64[5], sel64[3];
+      float m = -INFINITY;
+      for (int v = tid; v < V; v += 256) {
+        const float xv = x[v]; const uint32_t key = sr_key(xv);
+        if (key > thr || (key == thr && v < cut)) m = fmaxf(m, xv / p.temp);
       }
-      __syncthreads();
-      cut = (int)sel[0];
+      m = block_max256(m, sf);
+      uint32_t prefix = 0; unsigned long long rem = 1ull, qeq = 0ull;
+      for (int shift = 24; shift >= 0; shift -= 8) {
+        hist64[tid] = 0ull;
+        __syncthreads();
+        if (tid == 0) { sel64[0] = 0ull; sel64[1] = 1ull; sel64[2] = 0ull; }   // (what the pass leaves when no bin crosses: NaN rows)
+        const uint32_t hi = shift == 24 ? 0u : 0xFFFFFFFFu << (shift + 8);
+        for (int v = tid; v < V; v += 256) {
+          const float xv = x[v]; const uint32_t key = sr_key(xv);
+          if (((key ^ prefix) & hi) == 0 && (key > thr || (key == thr && v < cut)))
+            atomicAdd(&hist64[(key >> shift) & 255], sr_mass(xv, p.temp, m));
+        }
+        __syncthreads();
+        const unsigned long long c = hist64[255 - tid];                // thread order = bins from the top down
+        const unsigned long long incl = block_scan256_u64(c, sw64), excl = incl - c;
+        if (shift == 24) {                                             // the grand total Q: target = max(1, ceil(top_p * Q))
+          if (tid == 255) sw64[4] = incl;                              // (a word the scan does not use)
+          __syncthreads();
+          const double tq = ceil((double)p.top_p * (double)sw64[4]);
+          rem = tq >= 1.0 ? (unsigned long long)tq : 1ull;             // (tq <= Q < 2^53; a NaN takes the 1)
+        }
+        if (excl < rem && rem <= incl) { sel64[0] = 255 - tid; sel64[1] = rem - excl; sel64[2] = c; }
+        __syncthreads();
+        prefix |= (uint32_t)sel64[0] << shift; rem = sel64[1]; qeq = sel64[2];
+      }
+      // the entries equal to the cut value carry one mass q each: qeq / q of them are allowed, ceil(rem / q) are admitted
+      unsigned long long q = sr_mass(sr_unkey(prefix), p.temp, m);
+      q = q ? q : 1ull;
+      const unsigned long long neq64 = (rem + q - 1ull) / q;
+      if (prefix != thr) cut = V;                                      // above the top-k cut value: no index cut so far
+      thr = prefix;
+      if (neq64 < qeq / q) {
+        const int neq = (int)neq64;
+        if (tid == 0) sel[0] = (uint32_t)V;                            // (published before the scan's barriers inside)
+        SR_EQUAL_CUT(neq)
+      }
     }
   }
   const uint32_t base = ((uint32_t)p.t * (uint32_t)p.B + (uint32_t)row) * (uint32_t)V;
@@ -120,12 +212,18 @@ template <bool RES> __global__ __launch_bounds__(256) void sample_rows_kernel(co
   }
   mx = block_max256(mx, sf);
   block_argmax256(best, bi, sv, si);
-  float sum = 0.f;
+  float sum = 0.f; int na = 0;
   for (int v = tid; v < V; v += 256) {
     const float xv = x[v]; const uint32_t key = sr_key(xv);
-    if (key > thr || (key == thr && v < cut)) sum += rn_exp(xv / p.temp - mx);
+    if (key > thr || (key == thr && v < cut)) { sum += rn_exp(xv / p.temp - mx); if (NUC) ++na; }
   }
   sum = block_sum256(sum, sf);
+  if constexpr (NUC) {
+    if (p.n_allowed) {                                                 // (uniform over the grid)
+      na = block_scan256(na, sw);
+      if (tid == 255) p.n_allowed[row] = na;
+    }
+  }
   if (tid == 0) {
     const int tok = si[0] < V ? si[0] : 0;                             // (no entry compared: NaN logits)
     p.tok[row] = tok;

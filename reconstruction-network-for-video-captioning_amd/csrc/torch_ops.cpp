@@ -14,6 +14,7 @@
 //   beam_search_nbest, beam_select_rows                 N-best beam search on log-probabilities (no counterpart)
 //   beam_search_nbest_constrained, beam_select_rows_constrained   the same with no-repeat n-grams, a minimum length, banned ids (section 12)
 //   sample_search, sample_rows                          sampling (no counterpart in the reference; loop shape of eval.py:19-33)
+//   sample_search_nucleus, sample_rows_nucleus          the same with a nucleus (top-p) cut behind the top-k cut
 //   score_captions                                      teacher-forced log-probabilities of given captions (train.py:25,45, eval mode)
 //   reconstruction_error                                per-caption reconstruction error and the reconstruction (train.py:96-102 / :125-128, eval mode)
 #include <ATen/ATen.h>
@@ -214,6 +215,34 @@ std::tuple<at::Tensor, at::Tensor> sample_rows(int64_t h, const at::Tensor& logi
                         (uint32_t)seed, (int32_t)t, toks.data_ptr<int64_t>(), lps.data_ptr<float>(), stream()), "sample_rows");
   return {toks, lps};
 }
+// the nucleus forms: one more cut (top_p) and one more output, the size of the set every token was drawn from
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> sample_search_nucleus(int64_t h, const at::Tensor& enc, double temperature, int64_t top_k,
+                                                                                 double top_p, int64_t seed) {
+  chk_enc(h, enc);
+  auto toks = at::zeros({recnet_dim(H(h), RECNET_DIM_TM), enc.size(0)}, enc.options().dtype(at::kLong));
+  auto lps = at::zeros({recnet_dim(H(h), RECNET_DIM_TM), enc.size(0)}, enc.options());
+  auto na = at::zeros({recnet_dim(H(h), RECNET_DIM_TM), enc.size(0)}, enc.options().dtype(at::kInt));
+  auto n = at::zeros({1}, enc.options().dtype(at::kInt));
+  TORCH_CHECK(top_k >= INT32_MIN && top_k <= INT32_MAX, "recnet: top_k out of range");
+  ok(recnet_sample_search_nucleus(H(h), enc.data_ptr<float>(), (float)temperature, (int32_t)top_k, (float)top_p, (uint32_t)seed,
+                                  toks.data_ptr<int64_t>(), lps.data_ptr<float>(), na.data_ptr<int32_t>(), n.data_ptr<int32_t>(), stream()),
+     "sample_search_nucleus");
+  return {toks, lps, na, n};
+}
+std::tuple<at::Tensor, at::Tensor, at::Tensor> sample_rows_nucleus(int64_t h, const at::Tensor& logits, double temperature, int64_t top_k,
+                                                                   double top_p, int64_t seed, int64_t t) {
+  chk(logits, at::kFloat, "logits");
+  TORCH_CHECK(logits.dim() == 2 && logits.size(0) >= 1 && logits.size(1) >= 1 && logits.size(0) <= INT32_MAX && logits.size(1) <= INT32_MAX,
+              "recnet: logits must be [rows, V], got ", logits.sizes());
+  TORCH_CHECK(top_k >= INT32_MIN && top_k <= INT32_MAX && t >= 0 && t <= INT32_MAX, "recnet: top_k / t out of range");
+  auto toks = at::empty({logits.size(0)}, logits.options().dtype(at::kLong));
+  auto lps = at::empty({logits.size(0)}, logits.options());
+  auto na = at::empty({logits.size(0)}, logits.options().dtype(at::kInt));
+  ok(recnet_sample_rows_nucleus(H(h), logits.data_ptr<float>(), (int32_t)logits.size(0), (int32_t)logits.size(1), (float)temperature,
+                                (int32_t)top_k, (float)top_p, (uint32_t)seed, (int32_t)t, toks.data_ptr<int64_t>(), lps.data_ptr<float>(),
+                                na.data_ptr<int32_t>(), stream()), "sample_rows_nucleus");
+  return {toks, lps, na};
+}
 // the checks of the selection inputs: logits [nb, rows, V], cum [nb, rows] float, finished [nb, rows] int32, the width
 static void chk_select(const at::Tensor& logits, const at::Tensor& cum, const at::Tensor& finished, int64_t beam_width) {
   chk(logits, at::kFloat, "logits"); chk(cum, at::kFloat, "cum"); chk(finished, at::kInt, "finished");
@@ -371,6 +400,8 @@ TORCH_LIBRARY(recnet, m) {
   m.def("beam_search(int handle, Tensor encoder_outputs, int beam_width) -> (Tensor tokens, Tensor n_steps)");
   m.def("sample_search(int handle, Tensor encoder_outputs, float temperature, int top_k, int seed) -> (Tensor tokens, Tensor logprobs, Tensor n_steps)");
   m.def("sample_rows(int handle, Tensor logits, float temperature, int top_k, int seed, int t) -> (Tensor tokens, Tensor logprobs)");
+  m.def("sample_search_nucleus(int handle, Tensor encoder_outputs, float temperature, int top_k, float top_p, int seed) -> (Tensor tokens, Tensor logprobs, Tensor n_allowed, Tensor n_steps)");
+  m.def("sample_rows_nucleus(int handle, Tensor logits, float temperature, int top_k, float top_p, int seed, int t) -> (Tensor tokens, Tensor logprobs, Tensor n_allowed)");
   m.def("beam_select_rows(int handle, Tensor logits, Tensor cum, Tensor finished, int beam_width) -> (Tensor vals, Tensor idx)");
   m.def("beam_search_nbest(int handle, Tensor encoder_outputs, int beam_width, float length_alpha) -> (Tensor tokens, Tensor cum, Tensor lengths, Tensor score, Tensor n_steps)");
   m.def("beam_select_rows_constrained(int handle, Tensor logits, Tensor cum, Tensor finished, Tensor? hist, int t, int beam_width, int no_repeat_ngram, int min_length, int[] banned) -> (Tensor vals, Tensor idx)");
@@ -397,6 +428,8 @@ TORCH_LIBRARY_IMPL(recnet, CUDA, m) {
   m.impl("beam_search", beam_search);
   m.impl("sample_search", sample_search);
   m.impl("sample_rows", sample_rows);
+  m.impl("sample_search_nucleus", sample_search_nucleus);
+  m.impl("sample_rows_nucleus", sample_rows_nucleus);
   m.impl("beam_select_rows", beam_select_rows);
   m.impl("beam_search_nbest", beam_search_nbest);
   m.impl("beam_select_rows_constrained", beam_select_rows_constrained);

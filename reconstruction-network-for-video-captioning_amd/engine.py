@@ -307,10 +307,14 @@ class Engine:
                    "recnet_beam_select_rows_constrained")
         return vals, idx
 
-    def sample_search(self, enc, temperature=1.0, top_k=0, seed=0):
+    def sample_search(self, enc, temperature=1.0, top_k=0, seed=0, top_p=1.0):
         """The loop of greedy_search with a draw from softmax(logits / temperature) over the top_k largest logits in place of
         the arg-max (recnet_sample_search; the reference has none).  Returns (tokens [Tm, B] int64, logprobs [Tm, B] float32,
-        n_steps int32[1]) device tensors; only rows [:n_steps] are meaningful.  The library checks temperature / top_k."""
+        n_steps int32[1]) device tensors; only rows [:n_steps] are meaningful.  The library checks temperature / top_k.
+        top_p other than 1.0: the nucleus cut of sample_search_nucleus, without its n_allowed."""
+        if top_p != 1.0:
+            toks, lps, _, n = self.sample_search_nucleus(enc, temperature, top_k, top_p, seed)
+            return toks, lps, n
         d = self.dims
         _chk_tensor(enc, (d["B"], d["F"], d["D"]), torch.float32, "encoder_outputs")
         Tm = self.hyper["caption_max_len"] + 1
@@ -321,9 +325,44 @@ class Engine:
                                                  _ptr(toks), _ptr(lps), _ptr(n), _stream()), "recnet_sample_search")
         return toks, lps, n
 
-    def sample_rows(self, logits, temperature=1.0, top_k=0, seed=0, t=0):
+    def sample_search_nucleus(self, enc, temperature=1.0, top_k=0, top_p=1.0, seed=0):
+        """sample_search with a nucleus cut behind the top_k cut (recnet_sample_search_nucleus): every draw is
+        from the shortest prefix of the allowed entries whose mass reaches top_p.  Returns (tokens [Tm, B] int64, logprobs [Tm, B]
+        float32, n_allowed [Tm, B] int32: the size of the set each token was drawn from, n_steps int32[1]).  The library checks
+        temperature / top_k / top_p (0 < top_p <= 1; 1 = no nucleus cut)."""
+        d = self.dims
+        _chk_tensor(enc, (d["B"], d["F"], d["D"]), torch.float32, "encoder_outputs")
+        Tm = self.hyper["caption_max_len"] + 1
+        toks = torch.zeros(Tm, d["B"], dtype=torch.int64, device=self.device)
+        lps = torch.zeros(Tm, d["B"], dtype=torch.float32, device=self.device)
+        na = torch.zeros(Tm, d["B"], dtype=torch.int32, device=self.device)
+        n = torch.zeros(1, dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.recnet_sample_search_nucleus(self.handle, _ptr(enc), float(temperature), int(top_k), float(top_p),
+                                                         seed & 0xFFFFFFFF, _ptr(toks), _ptr(lps), _ptr(na), _ptr(n), _stream()),
+                   "recnet_sample_search_nucleus")
+        return toks, lps, na, n
+
+    def sample_rows_nucleus(self, logits, temperature=1.0, top_k=0, top_p=1.0, seed=0, t=0):
+        """sample_rows with the nucleus cut (recnet_sample_rows_nucleus).  Returns (tokens [rows] int64, logprobs [rows] float32,
+        n_allowed [rows] int32); `logits` is only read."""
+        if logits.dim() != 2:
+            raise RuntimeError("logits: expected [rows, V], got %s" % (tuple(logits.shape),))
+        rows, V = logits.shape
+        _chk_tensor(logits, (rows, V), torch.float32, "logits")
+        toks = torch.empty(rows, dtype=torch.int64, device=logits.device)
+        lps = torch.empty(rows, dtype=torch.float32, device=logits.device)
+        na = torch.empty(rows, dtype=torch.int32, device=logits.device)
+        _lib.check(self.lib.recnet_sample_rows_nucleus(self.handle, _ptr(logits), int(rows), int(V), float(temperature), int(top_k),
+                                                       float(top_p), seed & 0xFFFFFFFF, int(t), _ptr(toks), _ptr(lps), _ptr(na),
+                                                       _stream()), "recnet_sample_rows_nucleus")
+        return toks, lps, na
+
+    def sample_rows(self, logits, temperature=1.0, top_k=0, seed=0, t=0, top_p=1.0):
         """One draw per row of caller-supplied device logits [rows, V] (recnet_sample_rows; no decoder needed).  Returns
-        (tokens [rows] int64, logprobs [rows] float32); `logits` is only read."""
+        (tokens [rows] int64, logprobs [rows] float32); `logits` is only read.  top_p other than 1.0: the nucleus cut of
+        sample_rows_nucleus, without its n_allowed."""
+        if top_p != 1.0:
+            return self.sample_rows_nucleus(logits, temperature, top_k, top_p, seed, t)[:2]
         if logits.dim() != 2:
             raise RuntimeError("logits: expected [rows, V], got %s" % (tuple(logits.shape),))
         rows, V = logits.shape

@@ -230,6 +230,15 @@ def _split_constraints(search_method, n):
     return search_method[:n], dict(search_method[n])
 
 
+def _split_top_p(search_method, n):
+    """A sampling search method is its n fields, optionally followed by top_p; returns (the n fields, top_p or 1.0)."""
+    if len(search_method) == n:
+        return search_method, 1.0
+    if len(search_method) != n + 1:
+        raise ValueError("the %r method takes %d fields and an optional top_p (got %r)" % (search_method[0], n, search_method))
+    return search_method[:n], search_method[n]
+
+
 @torch.no_grad()
 def evaluate(config, score_batches, decoder, search_method, idx2word, references, reconstructor=None):
     """score_batches: iterable of (vids, enc [B,F,D]) with B == config.batch_size (the score loader repeats its last
@@ -241,7 +250,9 @@ def evaluate(config, score_batches, decoder, search_method, idx2word, references
     log-probabilities) or ("beam_recon", width, length_alpha, recon_weight) (search.best_of_beam: its hypotheses reranked with the
     reconstruction error of `reconstructor`).  The two beam forms take an optional trailing dict with the keys no_repeat_ngram,
     min_length and banned_tokens (the constraints of search.beam_search_nbest): ("beam_nbest", width, length_alpha, {...}),
-    ("beam_recon", width, length_alpha, recon_weight, {...}).
+    ("beam_recon", width, length_alpha, recon_weight, {...}).  The three sampling forms take an optional trailing top_p, the nucleus
+    cut of search.sample_search (1.0, the default, is none): ("sample", temperature, top_k, seed, top_p), ("best_of", n, temperature,
+    top_k, seed, top_p), ("best_of_recon", n, temperature, top_k, seed, recon_weight, top_p).
     references: {vid: [caption strings]}.  Returns the score dict of metrics.score_all."""
     decoder.eval()
     dev = next(decoder.parameters()).device
@@ -263,18 +274,18 @@ def evaluate(config, score_batches, decoder, search_method, idx2word, references
             if method == "beam":
                 caps = beam_search(config, search_method[1], None, decoder, inp, hid, enc)
             elif method == "sample":
-                _, temperature, top_k, seed = search_method
-                steps, _ = sample_search(config, decoder, inp, hid, enc, temperature, top_k, seed)
+                (_, temperature, top_k, seed), top_p = _split_top_p(search_method, 4)
+                steps, _ = sample_search(config, decoder, inp, hid, enc, temperature, top_k, seed, top_p)
                 caps = list(map(list, zip(*steps)))
             elif method == "best_of":
-                _, n, temperature, top_k, seed = search_method
-                caps = best_of_n(config, decoder, inp, hid, enc, n, temperature, top_k, seed)[0]
+                (_, n, temperature, top_k, seed), top_p = _split_top_p(search_method, 5)
+                caps = best_of_n(config, decoder, inp, hid, enc, n, temperature, top_k, seed, top_p=top_p)[0]
             elif method == "best_of_recon":
-                _, n, temperature, top_k, seed, recon_weight = search_method
+                (_, n, temperature, top_k, seed, recon_weight), top_p = _split_top_p(search_method, 6)
                 if reconstructor is None:
                     raise ValueError('the "best_of_recon" method needs a reconstructor')
                 reconstructor.eval()
-                caps = best_of_n(config, decoder, inp, hid, enc, n, temperature, top_k, seed, reconstructor, recon_weight)[0]
+                caps = best_of_n(config, decoder, inp, hid, enc, n, temperature, top_k, seed, reconstructor, recon_weight, top_p)[0]
             elif method == "beam_nbest":
                 (_, width, length_alpha), constraints = _split_constraints(search_method, 3)     # (search_method itself stays: it is parsed again for the next batch)
                 caps = [hyps[0][0] for hyps in beam_search_nbest(config, decoder, inp, hid, enc, width, length_alpha, **constraints)]

@@ -94,20 +94,27 @@ def beam_search(config, beam_width, vocab, decoder, input, hidden, encoder_outpu
     return best[:n].t().cpu().tolist()
 
 
-def sample_search(config, decoder, input, hidden, encoder_outputs, temperature=1.0, top_k=0, seed=0):
+def sample_search(config, decoder, input, hidden, encoder_outputs, temperature=1.0, top_k=0, seed=0, top_p=1.0):
     """greedy_search's loop (eval.py:19-33) with one draw per caption and step from softmax(logits / temperature) restricted
     to the top_k largest logits (0: no restriction; 1: the arg-max) — the reference has no counterpart.  The draw is a pure
     function of (seed, step, caption, vocabulary index): the same seed gives the same captions.  Returns (tokens, logprobs),
     both [n_steps][B] lists like greedy_search's; logprobs[t][b] is the log-probability of tokens[t][b] under the
     distribution it was drawn from.  Like the reference's loop this one goes on after a caption's <EOS> (see
-    sequence_logprob)."""
+    sequence_logprob).  top_p < 1 adds a nucleus cut behind the top_k cut (recnet_sample_search_nucleus):
+    of the entries top_k leaves, only the most probable ones whose mass reaches top_p are drawn from, and logprobs are under
+    that set; top_p = 1.0 is the call without it."""
     _check_temperature(temperature)
     if int(top_k) != top_k or not 0 <= top_k <= decoder.output_size:
         raise ValueError("top_k must be an integer in [0, %d] (got %r)" % (decoder.output_size, top_k))
+    _check_top_p(top_p)
     _check_start(config, input, hidden)
     eng = _cached_engine(decoder, encoder_outputs)
-    toks, lps, n = _ops.load().sample_search(int(eng.handle.value), encoder_outputs.contiguous(), float(temperature), int(top_k),
-                                             int(seed) & 0xFFFFFFFF)
+    if top_p == 1.0:
+        toks, lps, n = _ops.load().sample_search(int(eng.handle.value), encoder_outputs.contiguous(), float(temperature), int(top_k),
+                                                 int(seed) & 0xFFFFFFFF)
+    else:
+        toks, lps, _, n = _ops.load().sample_search_nucleus(int(eng.handle.value), encoder_outputs.contiguous(), float(temperature),
+                                                            int(top_k), float(top_p), int(seed) & 0xFFFFFFFF)
     n = int(n.item())
     return toks[:n].cpu().tolist(), lps[:n].cpu().tolist()
 
@@ -130,6 +137,11 @@ def sequence_logprob(tokens, logprobs, eos=2):
 def _check_temperature(temperature):
     if not (isinstance(temperature, (int, float)) and math.isfinite(temperature) and temperature > 0):
         raise ValueError("temperature must be a positive finite number (got %r)" % (temperature,))
+
+
+def _check_top_p(top_p):
+    if not (isinstance(top_p, numbers.Real) and 0 < top_p <= 1):            # (refuses NaN too)
+        raise ValueError("top_p must be a number in (0, 1] (got %r)" % (top_p,))
 
 
 def _caption_tensor(config, decoder, B, captions):
@@ -283,7 +295,7 @@ def pick_best_of_n(caption_logprobs, lengths, rec_errors=None, recon_weight=0.0)
 
 
 def best_of_n(config, decoder, input, hidden, encoder_outputs, n, temperature=1.0, top_k=0, seed=0, reconstructor=None,
-              recon_weight=0.0):
+              recon_weight=0.0, top_p=1.0):
     """n sampled candidates per video, ranked by the model's own length-normalised log-probability.  Candidate k is
     sample_search's rollout with seed (seed + k) & 0xFFFFFFFF; every candidate set is scored by score_captions at temperature
     1 (the sampler's own log-probabilities are under the tempered / cut distribution), the invariants of the features computed
@@ -293,11 +305,14 @@ def best_of_n(config, decoder, input, hidden, encoder_outputs, n, temperature=1.
     on T, so the candidates of one video must share it) and passed to the reconstruction error; the n x B errors are read back
     once.  That costs one more decoder chain pass per candidate set — the reconstruction error runs its own teacher-forced
     forward instead of reusing the scorer's states — which keeps the log-probability half bit for bit what it is without a
-    reconstructor.  Returns (captions: [B] token lists cut after their <EOS>, chosen k [B], score [B])."""
+    reconstructor.  top_p is sample_search's nucleus cut on the rollouts; like temperature and top_k it shapes the candidates
+    only, the scores stay those of the full distribution at temperature 1.  Returns (captions: [B] token lists cut after their
+    <EOS>, chosen k [B], score [B])."""
     if int(n) != n or n < 1:
         raise ValueError("n must be a positive integer (got %r)" % (n,))
+    _check_top_p(top_p)
     use_rec, recon_weight = _check_recon_weight(config, decoder, reconstructor, encoder_outputs, recon_weight)
-    cands = [sample_search(config, decoder, input, hidden, encoder_outputs, temperature, top_k, (seed + k) & 0xFFFFFFFF)[0]
+    cands = [sample_search(config, decoder, input, hidden, encoder_outputs, temperature, top_k, (seed + k) & 0xFFFFFFFF, top_p)[0]
              for k in range(int(n))]
     caps, lens, checked = [], [], []
     for k, toks in enumerate(cands):
