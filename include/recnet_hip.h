@@ -20,8 +20,8 @@
 extern "C" {
 #endif
 
-/* 12 still: recnet_beam_select_rows_constrained / recnet_beam_search_nbest_constrained were added without changing any existing
- * entry.  A library built before them is still caught: a binding that resolves every declared symbol fails on the first one missing. */
+/* 12 still: recnet_beam_select_rows_constrained / recnet_beam_search_nbest_constrained, and after them
+ * recnet_beam_select_rows_diverse / recnet_beam_search_nbest_diverse, were added without changing any existing entry.  A library built before them is still caught: a binding that resolves every declared symbol fails on the first one missing. */
 #define RECNET_ABI_VERSION 12
 #define RECNET_ATTN_NONE 0
 #define RECNET_ATTN_SOFTMAX 1
@@ -300,6 +300,31 @@ int recnet_beam_search_nbest_constrained(recnet_handle* h, const float* enc, int
                                          int32_t no_repeat_ngram, int32_t min_length, const int32_t* banned, int32_t n_banned,
                                          int64_t* tokens_out, float* cum_out, int32_t* len_out, float* score_out, int32_t* n_steps_out,
                                          void* stream);
+
+/* ---- Diverse (group) N-best beam search (Vijayakumar et al., "Diverse Beam Search"; no counterpart in the reference; DESIGN.md
+ * section 14).  beam_width = n_groups * w: slot k of a caption belongs to group k / w.  At step 0 every group selects from the one
+ * start hypothesis; from step 1 on group g selects only from its own w hypotheses.  The groups of a step are decided in the order
+ * g = 0, 1, ..: a live candidate (i, v) of group g is ordered by cum_i + log_softmax(logits_i)[v] - diversity_penalty * c, c = the
+ * number of slots of the groups before g whose candidate selected at this step carries token v and came from a live hypothesis
+ * (the <PAD> of a finished one is not counted; a finished hypothesis is never penalised).  The group keeps its w largest, the
+ * lowest idx = i * V + v among equals (i: the slot), and the j-th becomes slot g * w + j.  The value a hypothesis carries is the
+ * UN-penalised one: cum stays the model's log-probability, recnet_score_captions reproduces it, and inside a group the slots are
+ * ordered by the penalised value, not by cum.  The constraints of section 12 apply as they do there.  The final rank runs over all
+ * beam_width slots as in recnet_beam_search_nbest; different groups may return the same caption.  n_groups = 1 launches the kernels
+ * of the entries above and returns their bits, for any penalty; group 0 is never penalised.
+ * recnet_beam_select_rows_diverse: one grouped selection on caller-supplied arrays, the arguments of
+ * recnet_beam_select_rows_constrained; nb must be 1 (every group selects from hypothesis 0) or beam_width; vals_out holds the
+ * un-penalised values.  recnet_beam_search_nbest_diverse: recnet_beam_search_nbest_constrained with the grouped selection at every
+ * step; group_out [beam_width][B] int32 (may be NULL): the group of each returned rank.  RECNET_EINVAL before any launch: everything
+ * the constrained entries refuse, n_groups < 1 or not a divisor of beam_width, diversity_penalty negative or not finite. */
+int recnet_beam_select_rows_diverse(recnet_handle* h, const float* logits, const float* cum, const int32_t* finished,
+                                    const int64_t* hist, int32_t nb, int32_t rows, int32_t V, int32_t Tm, int32_t t, int32_t beam_width,
+                                    int32_t n_groups, float diversity_penalty, int32_t no_repeat_ngram, int32_t min_length,
+                                    const int32_t* banned, int32_t n_banned, float* vals_out, int32_t* idx_out, void* stream);
+int recnet_beam_search_nbest_diverse(recnet_handle* h, const float* enc, int32_t beam_width, float length_alpha, int32_t n_groups,
+                                     float diversity_penalty, int32_t no_repeat_ngram, int32_t min_length, const int32_t* banned,
+                                     int32_t n_banned, int64_t* tokens_out, float* cum_out, int32_t* len_out, float* score_out,
+                                     int32_t* group_out, int32_t* n_steps_out, void* stream);
 
 /* ---- forward_decoder, train.py:17-75 (teacher forcing, train.py:38,45).
  * enc [B,F,D]; targets [caption_max_len+1, B] int64 (time-major, <PAD>=0, <EOS>=2);

@@ -162,7 +162,9 @@ EXPORTS["recnet_beam_search_nbest"] = (_i, [C.c_void_p, C.c_void_p, _i, _f] + [C
 # (added at ABI version 12 without a bump: load() fails on a library that lacks them)
 EXPORTS["recnet_beam_select_rows_constrained"] = (_i, [C.c_void_p] * 5 + [_i] * 8 + [C.POINTER(_i), _i, C.c_void_p, C.c_void_p, C.c_void_p])
 EXPORTS["recnet_beam_search_nbest_constrained"] = (_i, [C.c_void_p, C.c_void_p, _i, _f, _i, _i, C.POINTER(_i), _i] + [C.c_void_p] * 6)
-EXPORTS["recnet_logprob_rows"] = (_i, [C.c_void_p, C.c_void_p, C.c_void_p, _i, _i, _f, C.c_void_p, C.c_void_p])
+EXPORTS["recnet_beam_select_rows_diverse"] = (_i, [C.c_void_p] * 5 + [_i] * 7 + [_f, _i, _i, C.POINTER(_i), _i, C.c_void_p, C.c_void_p, C.c_void_p])
+EXPORTS["recnet_beam_search_nbest_diverse"] = (_i, [C.c_void_p, C.c_void_p, _i, _f, _i, _f, _i, _i, C.POINTER(_i), _i] + [C.c_void_p] * 7)
+EXPORTS["recnet_logprob_rows"] =(_i, [C.c_void_p, C.c_void_p, C.c_void_p, _i, _i, _f, C.c_void_p, C.c_void_p])
 EXPORTS["recnet_score_captions"] = (_i, [C.c_void_p, C.c_void_p, C.c_void_p, _i, _f, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
 EXPORTS["recnet_reconstruction_error"] = (_i, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _i, C.c_void_p, C.c_void_p, C.c_void_p])
 EXPORTS["recnet_reconstructor_step"] = (_i, [C.c_void_p] * 5 + [_i] + [C.c_void_p] * 3 + [_i, C.c_uint32, _i, C.c_void_p])

@@ -440,11 +440,35 @@ static int check_beam_bans(int no_repeat_ngram, int min_length, const int32_t* b
   return RECNET_OK;
 }
 // bans == nullptr or all off: the unconstrained instantiation; else the constrained one on hist [nb][rows][Tm] at step t
+// n_groups > 1 (it divides bw, nb is 1 or bw): the grouped selection of DESIGN.md section 14 at group width bw / n_groups
 static void launch_beam_select(const float* logits, const float* cum, const int32_t* fin, int nb, int rows, int V, int bw, float* vals,
                                int32_t* idx, hipStream_t st, const BeamBans* bans = nullptr, const int64_t* hist = nullptr, int Tm = 0,
-                               int t = 0) {
+                               int t = 0, int n_groups = 1, float diversity_penalty = 0.f) {
   BeamSelCArgs a;
   a.x = logits; a.cum = cum; a.fin = fin; a.nb = nb; a.rows = rows; a.V = V; a.vals = vals; a.idx = idx;
+  if (n_groups > 1) {
+    BeamGrpArgs q;
+    q.G = n_groups; q.lam = diversity_penalty;
+    const int w = bw / n_groups;
+    if (!bans || !bans->on()) {
+      const BeamSelArgs& u = a;
+      switch (w) {
+#define RN_BSEL(W) case W: hipLaunchKernelGGL((beam_select_groups_kernel<W>), dim3(rows), dim3(256), 0, st, u, q); break;
+        RN_BSEL(1) RN_BSEL(2) RN_BSEL(3) RN_BSEL(4)
+#undef RN_BSEL
+      }
+      return;
+    }
+    a.hist = hist; a.Tm = Tm; a.t = t; a.ngram = bans->ngram; a.min_len = bans->min_len; a.n_banned = bans->n_banned;
+    for (int k = 0; k < 16; ++k) a.banned[k] = bans->banned[k];
+    const size_t sm = (size_t)(8 + nb * bs_ban_stride(t)) * 4;
+    switch (w) {
+#define RN_BSEL(W) case W: hipLaunchKernelGGL((beam_select_groups_kernel<W, true>), dim3(rows), dim3(256), sm, st, a, q); break;
+      RN_BSEL(1) RN_BSEL(2) RN_BSEL(3) RN_BSEL(4)
+#undef RN_BSEL
+    }
+    return;
+  }
   if (!bans || !bans->on()) {
     const BeamSelArgs& u = a;
     switch (bw) {
@@ -496,22 +520,43 @@ int recnet_beam_select_rows_constrained(recnet_handle* h, const float* logits, c
   return RECNET_OK;
 }
 
-int recnet_beam_search_nbest_constrained(recnet_handle* h, const float* enc, int32_t beam_width, float length_alpha,
-                                         int32_t no_repeat_ngram, int32_t min_length, const int32_t* banned, int32_t n_banned,
-                                         int64_t* tokens_out, float* cum_out, int32_t* len_out, float* score_out, int32_t* n_steps_out,
-                                         void* stream) {
-  int r = search_check(h, enc && tokens_out && cum_out && len_out && score_out && n_steps_out); if (r) return r;
-  r = check_beam(beam_width, h->V, length_alpha); if (r) return r;
+// the groups of the diverse form (DESIGN.md section 14), checked: one group = the selection as it was
+static int check_beam_groups(int beam_width, int n_groups, float diversity_penalty) {
+  if (n_groups < 1 || beam_width % n_groups != 0) return fail(RECNET_EINVAL, "n_groups must be at least 1 and divide beam_width");
+  if (!std::isfinite(diversity_penalty) || diversity_penalty < 0.f) return fail(RECNET_EINVAL, "diversity_penalty must be finite and >= 0");
+  return RECNET_OK;
+}
+
+int recnet_beam_select_rows_diverse(recnet_handle* h, const float* logits, const float* cum, const int32_t* finished,
+                                    const int64_t* hist, int32_t nb, int32_t rows, int32_t V, int32_t Tm, int32_t t, int32_t beam_width,
+                                    int32_t n_groups, float diversity_penalty, int32_t no_repeat_ngram, int32_t min_length,
+                                    const int32_t* banned, int32_t n_banned, float* vals_out, int32_t* idx_out, void* stream) {
+  REQUIRE_WS(h);
+  int r = check_select_rows(logits, cum, finished, nb, rows, V, beam_width, vals_out, idx_out); if (r) return r;
+  r = check_beam_groups(beam_width, n_groups, diversity_penalty); if (r) return r;
+  if (nb != 1 && nb != beam_width) return fail(RECNET_EINVAL, "nb must be 1 or beam_width");
+  if (Tm < 1 || t < 0 || t >= Tm) return fail(RECNET_EINVAL, "Tm must be positive and t in [0, Tm)");
   BeamBans bans;
-  r = check_beam_bans(no_repeat_ngram, min_length, banned, n_banned, beam_width, h->V, h->Tm, h->Tm - 1, &bans); if (r) return r;
-  hipStream_t st = (hipStream_t)stream;
-  const int B = h->B, V = h->V, Tm = h->Tm, bw = beam_width;
+  r = check_beam_bans(no_repeat_ngram, min_length, banned, n_banned, beam_width, V, Tm, t, &bans); if (r) return r;
+  if (no_repeat_ngram > 0 && !hist) return fail(RECNET_EINVAL, "null argument");
+  launch_beam_select(logits, cum, finished, nb, rows, V, beam_width, vals_out, idx_out, (hipStream_t)stream, &bans, hist, Tm, t, n_groups,
+                     diversity_penalty);
+  LAUNCH_OK();
+  return RECNET_OK;
+}
+
+// The loop of the N-best searches on checked arguments.  group_out (may be null): the group of each returned rank.
+static void beam_search_nbest_run(recnet_handle* h, const float* enc, int bw, float length_alpha, const BeamBans& bans, int n_groups,
+                                  float diversity_penalty, int64_t* tokens_out, float* cum_out, int32_t* len_out, float* score_out,
+                                  int32_t* group_out, int32_t* n_steps_out, hipStream_t st) {
+  const int B = h->B, V = h->V, Tm = h->Tm;
   search_begin(h, enc, n_steps_out, 0, st);
   const DecStepRows rows = dec_rows_beams(h);
   int cur = 0, nb = 1;
   for (int t = 0; t < Tm; ++t) {   // all nb * B hypotheses in one decode step, the captions' Uv / P shared by their beams
     dec_step(h, nb * B, B, rows, h->sr_tok[cur], h->sr_h[cur], h->sr_c[cur], h->sr_scores, h->sr_hn, h->sr_cn, 0, t, st);
-    launch_beam_select(h->sr_scores, h->sr_cum[cur], h->sr_eos[cur], nb, B, V, bw, h->sr_vals, h->sr_idx, st, &bans, h->sr_hist[cur], Tm, t);
+    launch_beam_select(h->sr_scores, h->sr_cum[cur], h->sr_eos[cur], nb, B, V, bw, h->sr_vals, h->sr_idx, st, &bans, h->sr_hist[cur], Tm, t,
+                       n_groups, diversity_penalty);
     hipLaunchKernelGGL(beam_update_kernel<true>, dim3(bw, B), dim3(128), 0, st, beam_update_args(h, bw, t, cur, nullptr));
     hipLaunchKernelGGL(search_stop_kernel, dim3(1), dim3(256), 0, st, (const int64_t*)nullptr, h->sr_eos[cur ^ 1], bw * B, t, n_steps_out);
     cur ^= 1; nb = bw;
@@ -521,6 +566,35 @@ int recnet_beam_search_nbest_constrained(recnet_handle* h, const float* enc, int
                      length_alpha, cum_out, len_out, score_out, h->bs_order);
   hipLaunchKernelGGL(beam_gather_kernel, dim3(cdiv(bw * Tm * B, 256)), dim3(256), 0, st, h->sr_hist[cur], h->bs_order, tokens_out,
                      B, Tm, bw);
+  if (group_out)
+    hipLaunchKernelGGL(beam_group_kernel, dim3(cdiv(bw * B, 256)), dim3(256), 0, st, (const int32_t*)h->bs_order, bw / n_groups, bw * B, group_out);
+}
+
+int recnet_beam_search_nbest_constrained(recnet_handle* h, const float* enc, int32_t beam_width, float length_alpha,
+                                         int32_t no_repeat_ngram, int32_t min_length, const int32_t* banned, int32_t n_banned,
+                                         int64_t* tokens_out, float* cum_out, int32_t* len_out, float* score_out, int32_t* n_steps_out,
+                                         void* stream) {
+  int r = search_check(h, enc && tokens_out && cum_out && len_out && score_out && n_steps_out); if (r) return r;
+  r = check_beam(beam_width, h->V, length_alpha); if (r) return r;
+  BeamBans bans;
+  r = check_beam_bans(no_repeat_ngram, min_length, banned, n_banned, beam_width, h->V, h->Tm, h->Tm - 1, &bans); if (r) return r;
+  beam_search_nbest_run(h, enc, beam_width, length_alpha, bans, 1, 0.f, tokens_out, cum_out, len_out, score_out, nullptr, n_steps_out,
+                        (hipStream_t)stream);
+  LAUNCH_OK();
+  return RECNET_OK;
+}
+
+int recnet_beam_search_nbest_diverse(recnet_handle* h, const float* enc, int32_t beam_width, float length_alpha, int32_t n_groups,
+                                     float diversity_penalty, int32_t no_repeat_ngram, int32_t min_length, const int32_t* banned,
+                                     int32_t n_banned, int64_t* tokens_out, float* cum_out, int32_t* len_out, float* score_out,
+                                     int32_t* group_out, int32_t* n_steps_out, void* stream) {
+  int r = search_check(h, enc && tokens_out && cum_out && len_out && score_out && n_steps_out); if (r) return r;
+  r = check_beam(beam_width, h->V, length_alpha); if (r) return r;
+  r = check_beam_groups(beam_width, n_groups, diversity_penalty); if (r) return r;
+  BeamBans bans;
+  r = check_beam_bans(no_repeat_ngram, min_length, banned, n_banned, beam_width, h->V, h->Tm, h->Tm - 1, &bans); if (r) return r;
+  beam_search_nbest_run(h, enc, beam_width, length_alpha, bans, n_groups, diversity_penalty, tokens_out, cum_out, len_out, score_out,
+                        group_out, n_steps_out, (hipStream_t)stream);
   LAUNCH_OK();
   return RECNET_OK;
 }

@@ -526,6 +526,160 @@ void beam_select_kernel(const typename BeamSelArgsOf<CONSTRAINED>::type p) {
     }
   }
 }
+// ---- diverse (group) beam search (Vijayakumar et al., "Diverse Beam Search"; the reference has no counterpart; DESIGN.md section 14
+// states the definition, tests/beam_diverse_ref.py restates it): the BW = G * W slots of a caption are G groups of W.  The groups of a
+// step are decided one after the other, and a live candidate of group g pays lam for every slot of the groups before it whose winner
+// of THIS step came from a live hypothesis and carries the same token.  The penalty orders the selection only: vals is the
+// un-penalised value.
+struct BeamGrpArgs { int G; float lam; };        // G >= 2 groups (one group is beam_select_kernel's), lam finite and >= 0
+// beam_select_kernel's launch shape and its phases (0) and (1), once for all nb hypotheses (nb = 1: every group selects from
+// hypothesis 0; else nb = G * W and group g owns hypotheses g * W .. g * W + W - 1).  Then per group, inside the workgroup: (2) the
+// walk over the group's candidates with a list of W, (3) W arg-max rounds.  The thread that owned a winner recomputes its
+// un-penalised value from the index (the same expression as the walk's: the same bits), writes the output pair and, for a live
+// hypothesis, appends the token to s_tok, the at most 7 tokens chosen so far in this step (a token chosen twice stands twice); a
+// barrier, then the next group.  A penalised candidate is worth less than its pure value (lam * c >= 0, the subtraction is monotone),
+// so one that does not beat the tail of the thread's list with its PURE value cannot enter it: the penalty is looked up behind the
+// compare that guards an insertion, as the ban lists are, and the candidate is then compared again with its penalised value.  A
+// thread only meets the tokens v = tid (mod 256): once per group it reads s_tok and keeps the one chosen token of its residue and
+// its count in registers (`pmany`: two different ones, then the list is scanned).  A candidate with count 0 is compared by exactly
+// the word beam_select_kernel forms: group 0, and every group at lam = 0, select what that kernel selects at width W, bit for bit.
+template <int W, bool CONSTRAINED = false> __global__ __launch_bounds__(256)
+void beam_select_groups_kernel(const typename BeamSelArgsOf<CONSTRAINED>::type p, const BeamGrpArgs q) {
+  __shared__ float sf[4]; __shared__ float s_mx[8], s_ls[8]; __shared__ unsigned long long wc[2][4];
+  __shared__ int s_tok[8]; __shared__ int s_ntok;
+  extern __shared__ __attribute__((aligned(16))) int bs_ban[];
+  const int r = blockIdx.x, tid = threadIdx.x, V = p.V, nb = p.nb, BW = q.G * W;
+  int S = 0;
+  if constexpr (CONSTRAINED) {                                         // (0) the ban lists, as in beam_select_kernel
+    S = bs_ban_stride(p.t);
+    const int ln = tid & 63, t = p.t, n = p.ngram;
+    const int ng = n >= 1 && t >= n - 1 ? t - n + 1 : 0;
+    const int used = ng + p.n_banned + (t < p.min_len ? 1 : 0);                 // <= t + 17
+    for (int i = tid >> 6; i < nb; i += 4) {
+      const bool live = p.fin[i * p.rows + r] == 0;
+      int cnt = 0;
+      for (int c = 0; c < used; c += 64) {                                      // (uniform over the wave)
+        const int j = c + ln;
+        int id = -1;
+        if (live && j < ng) {
+          const int64_t* hs = p.hist + ((size_t)i * p.rows + r) * p.Tm;
+          bool same = true;
+          for (int k = 0; k + 1 < n; ++k) same &= hs[j + k] == hs[t - n + 1 + k];
+          const int64_t w = hs[j + n - 1];
+          if (same && w >= 0 && w < V) id = (int)w;
+        } else if (live && j < used) {
+          const int s = j - ng;
+          id = 2;
+#pragma unroll
+          for (int k = 0; k < 16; ++k)
+            if (s == k && k < p.n_banned) id = p.banned[k];
+        }
+        const unsigned long long m = __ballot(id >= 0);
+        if (id >= 0) bs_ban[8 + i * S + cnt + __popcll(m & ((1ull << ln) - 1ull))] = id;
+        cnt += __popcll(m);
+      }
+      if (ln == 0) bs_ban[i] = cnt;
+    }
+  }
+  for (int i = 0; i < nb; ++i) {                                       // (1) row maximum and sum, logprob_rows_kernel's order
+    if (p.fin[i * p.rows + r]) continue;                               // (uniform over the workgroup)
+    const float* x = p.x + ((size_t)i * p.rows + r) * V;
+    float mx = -INFINITY, sum = 0.f;
+    for (int v = tid; v < V; v += 256) mx = fmaxf(mx, x[v]);
+    mx = block_max256(mx, sf);
+    for (int v = tid; v < V; v += 256) sum += rn_exp(x[v] - mx);
+    sum = block_sum256(sum, sf);
+    if (tid == 0) { s_mx[i] = mx; s_ls[i] = logf(sum); }
+  }
+  if (tid == 0) s_ntok = 0;
+  __syncthreads();
+  const int lane = tid & 63, wave = tid >> 6;
+  for (int g = 0; g < q.G; ++g) {
+    const int nt = s_ntok;                                             // (<= 7: the last group appends nothing that is read)
+    int ptok = -1, pcnt = 0; bool pmany = false;                       // the chosen token this thread can meet, and how often chosen
+    for (int j = 0; j < nt; ++j) {
+      const int id = s_tok[j];
+      if ((id & 255) == tid) {
+        if (ptok < 0 || ptok == id) { ptok = id; ++pcnt; } else pmany = true;
+      }
+    }
+    unsigned long long lc[W];
+#pragma unroll
+    for (int k = 0; k < W; ++k) lc[k] = 0ull;
+    const int i0 = nb == 1 ? 0 : g * W, i1 = nb == 1 ? 1 : g * W + W;
+    for (int i = i0; i < i1; ++i) {                                    // (2)
+      const float c = p.cum[i * p.rows + r];
+      const bool fin = p.fin[i * p.rows + r] != 0;
+      const float* x = p.x + ((size_t)i * p.rows + r) * V;
+      const float mx = fin ? 0.f : s_mx[i], ls = fin ? 0.f : s_ls[i];
+      const int n = fin ? (V < W + 1 ? V : W + 1) : V;
+      const int nban = CONSTRAINED ? bs_ban[i] : 0;                    // (0 for a finished hypothesis)
+      const int* ban = bs_ban + 8 + i * S;
+      int mine = -1; bool many = false;                                // the banned id this thread can meet: v = tid (mod 256)
+      if constexpr (CONSTRAINED) {
+        for (int j = 0; j < nban; ++j) {
+          const int id = ban[j];
+          if ((id & 255) == tid) { many |= mine >= 0 && mine != id; mine = id; }
+        }
+      }
+      for (int v = tid; v < n; v += 256) {
+        const float y = fin ? (v == 0 ? c : -INFINITY) : c + ((x[v] - mx) - ls);
+        unsigned long long e = bs_pack(y, i * V + v);
+        if (e > lc[W - 1]) {
+          bool offered = true;
+          if constexpr (CONSTRAINED) {
+            offered = v != mine;
+            if (many)                                                  // (two banned ids 256 apart or more: rare)
+              for (int j = 0; j < nban; ++j) offered &= ban[j] != v;
+          }
+          if (offered) {
+            int cnt = v == ptok ? pcnt : 0;
+            if (pmany) {                                               // (two chosen tokens 256 apart or more: rare)
+              cnt = 0;
+              for (int j = 0; j < nt; ++j) cnt += s_tok[j] == v;
+            }
+            if (cnt > 0 && !fin) e = bs_pack(y - q.lam * (float)cnt, i * V + v);
+#pragma unroll
+            for (int k = 0; k < W; ++k)
+              if (e > lc[k]) { const unsigned long long d = lc[k]; lc[k] = e; e = d; }
+          }
+        }
+      }
+    }
+    for (int k = 0; k < W; ++k) {                                      // (3)
+      unsigned long long e = lc[0];
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long d = __shfl_xor(e, o);
+        e = d > e ? d : e;
+      }
+      if (lane == 0) wc[k & 1][wave] = e;
+      __syncthreads();
+      e = wc[k & 1][0];
+#pragma unroll
+      for (int w = 1; w < 4; ++w) e = wc[k & 1][w] > e ? wc[k & 1][w] : e;
+      const size_t o = (size_t)r * BW + g * W + k;
+      if (e != 0ull && lc[0] == e) {           // (candidates are distinct: their indices are) the one thread that owned the winner
+        const int j = bs_index(e), i = j / V, v = j - i * V;
+        const float c = p.cum[i * p.rows + r];
+        const bool fin = p.fin[i * p.rows + r] != 0;
+        const float y = fin ? (v == 0 ? c : -INFINITY) : c + ((p.x[((size_t)i * p.rows + r) * V + v] - s_mx[i]) - s_ls[i]);
+        p.vals[o] = bs_value(bs_pack(y, j)); p.idx[o] = j;
+        if (!fin) { const int at = s_ntok; s_tok[at & 7] = v; s_ntok = at + 1; }
+#pragma unroll
+        for (int s = 0; s + 1 < W; ++s) lc[s] = lc[s + 1];
+        lc[W - 1] = 0ull;
+      }
+      if (e == 0ull && tid == 0) { p.vals[o] = -INFINITY; p.idx[o] = 0; }     // (fewer than W candidates compared: NaN-free inputs never get here)
+    }
+    __syncthreads();                                                   // s_tok / s_ntok of this group, and wc, before the next
+  }
+}
+// group[r][b] = order[r][b] / w: the group of the slot that took rank r (n = bw * B entries)
+__global__ void beam_group_kernel(const int32_t* __restrict__ order, int w, int n, int32_t* __restrict__ group) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) group[i] = order[i] / w;
+}
 // final ranking, one thread per caption: len = fin, or n_steps without an <EOS>; score = cum / len^alpha (alpha = 0: cum);
 // descending score, lowest beam index among equals.  order[r][b] = the beam that takes rank r.
 __global__ __launch_bounds__(256) void beam_nbest_rank_kernel(const float* __restrict__ cum, const int32_t* __restrict__ fin,

@@ -13,6 +13,7 @@
 //   greedy_search, beam_search                          eval.py:19-120
 //   beam_search_nbest, beam_select_rows                 N-best beam search on log-probabilities (no counterpart)
 //   beam_search_nbest_constrained, beam_select_rows_constrained   the same with no-repeat n-grams, a minimum length, banned ids (section 12)
+//   beam_search_nbest_diverse, beam_select_rows_diverse  the same in groups with a Hamming penalty between them (section 14)
 //   sample_search, sample_rows                          sampling (no counterpart in the reference; loop shape of eval.py:19-33)
 //   sample_search_nucleus, sample_rows_nucleus          the same with a nucleus (top-p) cut behind the top-k cut
 //   score_captions                                      teacher-forced log-probabilities of given captions (train.py:25,45, eval mode)
@@ -20,6 +21,8 @@
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
 #include <torch/library.h>
+
+#include <cmath>
 
 #include "../../include/recnet_hip.h"
 
@@ -296,6 +299,16 @@ static void chk_constraints(int64_t no_repeat_ngram, int64_t min_length) {
   TORCH_CHECK(no_repeat_ngram >= 0 && no_repeat_ngram <= INT32_MAX && min_length >= 0 && min_length <= INT32_MAX,
               "recnet: no_repeat_ngram / min_length out of range");
 }
+// hist [nb, rows, Tm] int64 of a selection on `logits`, checked: its pointer and Tm (undefined: null, and a Tm no step reaches)
+static const int64_t* hist_arg(const c10::optional<at::Tensor>& hist, const at::Tensor& logits, int64_t* Tm) {
+  *Tm = INT32_MAX;                   // (no hist: only min_length / the static bans can be on, and they read no history)
+  if (!hist.has_value() || !hist->defined()) return nullptr;
+  chk(*hist, at::kLong, "hist");
+  TORCH_CHECK(hist->dim() == 3 && hist->size(0) == logits.size(0) && hist->size(1) == logits.size(1) && hist->size(2) >= 1 &&
+              hist->size(2) <= INT32_MAX, "recnet: hist must be [nb, rows, Tm], got ", hist->sizes());
+  *Tm = hist->size(2);
+  return hist->data_ptr<int64_t>();
+}
 // beam_select_rows plus hist [nb, rows, Tm] int64 (undefined: allowed when no_repeat_ngram = 0) and the step t
 std::tuple<at::Tensor, at::Tensor> beam_select_rows_constrained(int64_t h, const at::Tensor& logits, const at::Tensor& cum,
                                                                 const at::Tensor& finished, const c10::optional<at::Tensor>& hist, int64_t t,
@@ -305,14 +318,8 @@ std::tuple<at::Tensor, at::Tensor> beam_select_rows_constrained(int64_t h, const
   TORCH_CHECK(t >= 0 && t < INT32_MAX, "recnet: t out of range");
   chk_constraints(no_repeat_ngram, min_length);
   const auto ids = ban_ids(banned);
-  int64_t Tm = INT32_MAX;            // (no hist: only min_length / the static bans can be on, and they read no history)
-  const int64_t* hp = nullptr;
-  if (hist.has_value() && hist->defined()) {
-    chk(*hist, at::kLong, "hist");
-    TORCH_CHECK(hist->dim() == 3 && hist->size(0) == logits.size(0) && hist->size(1) == logits.size(1) && hist->size(2) >= 1 &&
-                hist->size(2) <= INT32_MAX, "recnet: hist must be [nb, rows, Tm], got ", hist->sizes());
-    Tm = hist->size(2); hp = hist->data_ptr<int64_t>();
-  }
+  int64_t Tm;
+  const int64_t* hp = hist_arg(hist, logits, &Tm);
   auto vals = at::empty({logits.size(1), beam_width}, logits.options());
   auto idx = at::empty({logits.size(1), beam_width}, logits.options().dtype(at::kInt));
   ok(recnet_beam_select_rows_constrained(H(h), logits.data_ptr<float>(), cum.data_ptr<float>(), finished.data_ptr<int32_t>(), hp,
@@ -333,6 +340,50 @@ NbestOut beam_search_nbest_constrained(int64_t h, const at::Tensor& enc, int64_t
                                           len.data_ptr<int32_t>(), score.data_ptr<float>(), n.data_ptr<int32_t>(), stream()),
      "beam_search_nbest_constrained");
   return {toks, cum, len, score, n};
+}
+// ---- the diverse forms: the constrained forms in n_groups groups with a penalty between them
+static void chk_groups(int64_t beam_width, int64_t n_groups, double diversity_penalty) {
+  TORCH_CHECK(n_groups >= 1 && beam_width % n_groups == 0, "recnet: n_groups must be at least 1 and divide beam_width, got ", n_groups);
+  TORCH_CHECK(std::isfinite(diversity_penalty) && diversity_penalty >= 0.0, "recnet: diversity_penalty must be finite and >= 0, got ",
+              diversity_penalty);
+}
+std::tuple<at::Tensor, at::Tensor> beam_select_rows_diverse(int64_t h, const at::Tensor& logits, const at::Tensor& cum,
+                                                            const at::Tensor& finished, const c10::optional<at::Tensor>& hist, int64_t t,
+                                                            int64_t beam_width, int64_t n_groups, double diversity_penalty,
+                                                            int64_t no_repeat_ngram, int64_t min_length, at::IntArrayRef banned) {
+  chk_select(logits, cum, finished, beam_width);
+  chk_groups(beam_width, n_groups, diversity_penalty);
+  TORCH_CHECK(logits.size(0) == 1 || logits.size(0) == beam_width, "recnet: nb must be 1 or beam_width, got ", logits.size(0));
+  TORCH_CHECK(t >= 0 && t < INT32_MAX, "recnet: t out of range");
+  chk_constraints(no_repeat_ngram, min_length);
+  const auto ids = ban_ids(banned);
+  int64_t Tm;
+  const int64_t* hp = hist_arg(hist, logits, &Tm);
+  auto vals = at::empty({logits.size(1), beam_width}, logits.options());
+  auto idx = at::empty({logits.size(1), beam_width}, logits.options().dtype(at::kInt));
+  ok(recnet_beam_select_rows_diverse(H(h), logits.data_ptr<float>(), cum.data_ptr<float>(), finished.data_ptr<int32_t>(), hp,
+                                     (int32_t)logits.size(0), (int32_t)logits.size(1), (int32_t)logits.size(2), (int32_t)Tm, (int32_t)t,
+                                     (int32_t)beam_width, (int32_t)n_groups, (float)diversity_penalty, (int32_t)no_repeat_ngram,
+                                     (int32_t)min_length, ids.data(), (int32_t)ids.size(), vals.data_ptr<float>(), idx.data_ptr<int32_t>(),
+                                     stream()), "beam_select_rows_diverse");
+  return {vals, idx};
+}
+// beam_search_nbest_constrained's outputs and, behind score, group [beam_width, B] int32: the group of each returned rank
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> beam_search_nbest_diverse(
+    int64_t h, const at::Tensor& enc, int64_t beam_width, double length_alpha, int64_t n_groups, double diversity_penalty,
+    int64_t no_repeat_ngram, int64_t min_length, at::IntArrayRef banned) {
+  chk_enc(h, enc);
+  TORCH_CHECK(beam_width >= 1 && beam_width <= 8 && beam_width <= dim(h, RECNET_DIM_V), "recnet: beam_width must be in [1, min(8, V)], got ", beam_width);
+  chk_groups(beam_width, n_groups, diversity_penalty);
+  chk_constraints(no_repeat_ngram, min_length);
+  const auto ids = ban_ids(banned);
+  auto [toks, cum, len, score, n] = nbest_outputs(h, enc, beam_width);
+  auto group = at::zeros({beam_width, enc.size(0)}, enc.options().dtype(at::kInt));
+  ok(recnet_beam_search_nbest_diverse(H(h), enc.data_ptr<float>(), (int32_t)beam_width, (float)length_alpha, (int32_t)n_groups,
+                                      (float)diversity_penalty, (int32_t)no_repeat_ngram, (int32_t)min_length, ids.data(), (int32_t)ids.size(),
+                                      toks.data_ptr<int64_t>(), cum.data_ptr<float>(), len.data_ptr<int32_t>(), score.data_ptr<float>(),
+                                      group.data_ptr<int32_t>(), n.data_ptr<int32_t>(), stream()), "beam_search_nbest_diverse");
+  return {toks, cum, len, score, group, n};
 }
 // tokens [T, B] with every entry in [0, V): the caller's duty (search.score_captions checks it)
 std::tuple<at::Tensor, at::Tensor, at::Tensor> score_captions(int64_t h, const c10::optional<at::Tensor>& enc, const at::Tensor& tokens,
@@ -406,6 +457,8 @@ TORCH_LIBRARY(recnet, m) {
   m.def("beam_search_nbest(int handle, Tensor encoder_outputs, int beam_width, float length_alpha) -> (Tensor tokens, Tensor cum, Tensor lengths, Tensor score, Tensor n_steps)");
   m.def("beam_select_rows_constrained(int handle, Tensor logits, Tensor cum, Tensor finished, Tensor? hist, int t, int beam_width, int no_repeat_ngram, int min_length, int[] banned) -> (Tensor vals, Tensor idx)");
   m.def("beam_search_nbest_constrained(int handle, Tensor encoder_outputs, int beam_width, float length_alpha, int no_repeat_ngram, int min_length, int[] banned) -> (Tensor tokens, Tensor cum, Tensor lengths, Tensor score, Tensor n_steps)");
+  m.def("beam_select_rows_diverse(int handle, Tensor logits, Tensor cum, Tensor finished, Tensor? hist, int t, int beam_width, int n_groups, float diversity_penalty, int no_repeat_ngram, int min_length, int[] banned) -> (Tensor vals, Tensor idx)");
+  m.def("beam_search_nbest_diverse(int handle, Tensor encoder_outputs, int beam_width, float length_alpha, int n_groups, float diversity_penalty, int no_repeat_ngram, int min_length, int[] banned) -> (Tensor tokens, Tensor cum, Tensor lengths, Tensor score, Tensor group, Tensor n_steps)");
   m.def("score_captions(int handle, Tensor? encoder_outputs, Tensor tokens, float temperature) -> (Tensor logprobs, Tensor caption_logprob, Tensor lengths)");
   m.def("reconstruction_error(int handle, Tensor encoder_outputs, Tensor? tokens, Tensor? decoder_hiddens, bool want_recon) -> (Tensor err, Tensor recon)");
 }
@@ -434,6 +487,8 @@ TORCH_LIBRARY_IMPL(recnet, CUDA, m) {
   m.impl("beam_search_nbest", beam_search_nbest);
   m.impl("beam_select_rows_constrained", beam_select_rows_constrained);
   m.impl("beam_search_nbest_constrained", beam_search_nbest_constrained);
+  m.impl("beam_select_rows_diverse", beam_select_rows_diverse);
+  m.impl("beam_search_nbest_diverse", beam_search_nbest_diverse);
   m.impl("score_captions", score_captions);
   m.impl("reconstruction_error", reconstruction_error);
 }

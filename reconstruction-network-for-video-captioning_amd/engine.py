@@ -307,6 +307,57 @@ class Engine:
                    "recnet_beam_select_rows_constrained")
         return vals, idx
 
+    def beam_search_nbest_diverse(self, enc, beam_width, length_alpha=0.0, n_groups=1, diversity_penalty=0.0, no_repeat_ngram=0,
+                                  min_length=0, banned_tokens=()):
+        """Diverse (group) N-best beam search (recnet_beam_search_nbest_diverse): beam_search_nbest with the
+        beam in n_groups groups of beam_width / n_groups slots, decided one after the other inside every step; a live candidate pays
+        diversity_penalty for each slot of an earlier group that chose its token at this step.  cum stays the un-penalised
+        log-probability.  Returns beam_search_nbest's tensors with group [bw, B] int32 (the group of each returned rank) before
+        n_steps: (tokens, cum, len, score, group, n_steps).  The library checks the arguments before any launch of its own."""
+        d = self.dims
+        _chk_tensor(enc, (d["B"], d["F"], d["D"]), torch.float32, "encoder_outputs")
+        Tm, B, bw = self.hyper["caption_max_len"] + 1, d["B"], (int(beam_width) if 1 <= int(beam_width) <= 8 else 1)
+        toks = torch.zeros(bw, Tm, B, dtype=torch.int64, device=self.device)
+        cum = torch.zeros(bw, B, dtype=torch.float32, device=self.device)
+        ln = torch.zeros(bw, B, dtype=torch.int32, device=self.device)
+        score = torch.zeros(bw, B, dtype=torch.float32, device=self.device)
+        group = torch.zeros(bw, B, dtype=torch.int32, device=self.device)
+        n = torch.zeros(1, dtype=torch.int32, device=self.device)
+        ban, n_ban = self._ban_array(banned_tokens)
+        _lib.check(self.lib.recnet_beam_search_nbest_diverse(self.handle, _ptr(enc), int(beam_width), float(length_alpha), int(n_groups),
+                                                             float(diversity_penalty), int(no_repeat_ngram), int(min_length), ban, n_ban,
+                                                             _ptr(toks), _ptr(cum), _ptr(ln), _ptr(score), _ptr(group), _ptr(n), _stream()),
+                   "recnet_beam_search_nbest_diverse")
+        return toks, cum, ln, score, group, n
+
+    def beam_select_rows_diverse(self, logits, cum, finished, beam_width, n_groups, diversity_penalty, hist=None, t=0, no_repeat_ngram=0,
+                                 min_length=0, banned_tokens=()):
+        """One grouped selection step on caller-supplied device arrays (recnet_beam_select_rows_diverse): the
+        arguments of beam_select_rows with nb = 1 (every group selects from hypothesis 0) or nb = beam_width (group g selects from
+        hypotheses g * w .. g * w + w - 1, w = beam_width / n_groups).  Returns (vals [rows, bw] float32, idx [rows, bw] int32):
+        slot g * w + j holds the j-th of group g by its penalised value, vals its UN-penalised value, idx = i * V + v."""
+        if logits.dim() != 3:
+            raise RuntimeError("logits: expected [nb, rows, V], got %s" % (tuple(logits.shape),))
+        nb, rows, V = logits.shape
+        _chk_tensor(logits, (nb, rows, V), torch.float32, "logits")
+        _chk_tensor(cum, (nb, rows), torch.float32, "cum")
+        _chk_tensor(finished, (nb, rows), torch.int32, "finished")
+        bw = max(int(beam_width), 1)
+        vals = torch.empty(rows, bw, dtype=torch.float32, device=logits.device)
+        idx = torch.empty(rows, bw, dtype=torch.int32, device=logits.device)
+        Tm = 0x7FFFFFFF              # (no hist: only min_length / the static bans can be on, and they read no history)
+        if hist is not None:
+            if hist.dim() != 3:
+                raise RuntimeError("hist: expected [nb, rows, Tm], got %s" % (tuple(hist.shape),))
+            Tm = hist.shape[2]
+            _chk_tensor(hist, (nb, rows, Tm), torch.int64, "hist")
+        ban, n_ban = self._ban_array(banned_tokens)
+        _lib.check(self.lib.recnet_beam_select_rows_diverse(self.handle, _ptr(logits), _ptr(cum), _ptr(finished), _ptr(hist), int(nb),
+                                                            int(rows), int(V), int(Tm), int(t), int(beam_width), int(n_groups),
+                                                            float(diversity_penalty), int(no_repeat_ngram), int(min_length), ban, n_ban,
+                                                            _ptr(vals), _ptr(idx), _stream()), "recnet_beam_select_rows_diverse")
+        return vals, idx
+
     def sample_search(self, enc, temperature=1.0, top_k=0, seed=0, top_p=1.0):
         """The loop of greedy_search with a draw from softmax(logits / temperature) over the top_k largest logits in place of
         the arg-max (recnet_sample_search; the reference has none).  Returns (tokens [Tm, B] int64, logprobs [Tm, B] float32,

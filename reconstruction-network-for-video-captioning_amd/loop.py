@@ -214,7 +214,7 @@ class Trainer:
 
 
 # ---------------------------------------------------------------------- scoring, eval.py:123-169
-_CONSTRAINT_KEYS = ("no_repeat_ngram", "min_length", "banned_tokens")
+_CONSTRAINT_KEYS = ("no_repeat_ngram", "min_length", "banned_tokens", "n_groups", "diversity_penalty")
 
 
 def _split_constraints(search_method, n):
@@ -249,7 +249,8 @@ def evaluate(config, score_batches, decoder, search_method, idx2word, references
     ("beam_nbest", width, length_alpha) (search.beam_search_nbest: the first-ranked hypothesis of the beam search on
     log-probabilities) or ("beam_recon", width, length_alpha, recon_weight) (search.best_of_beam: its hypotheses reranked with the
     reconstruction error of `reconstructor`).  The two beam forms take an optional trailing dict with the keys no_repeat_ngram,
-    min_length and banned_tokens (the constraints of search.beam_search_nbest): ("beam_nbest", width, length_alpha, {...}),
+    min_length and banned_tokens (the constraints of search.beam_search_nbest) and n_groups and diversity_penalty (its diverse
+    form): ("beam_nbest", width, length_alpha, {...}),
     ("beam_recon", width, length_alpha, recon_weight, {...}).  The three sampling forms take an optional trailing top_p, the nucleus
     cut of search.sample_search (1.0, the default, is none): ("sample", temperature, top_k, seed, top_p), ("best_of", n, temperature,
     top_k, seed, top_p), ("best_of_recon", n, temperature, top_k, seed, recon_weight, top_p).

@@ -364,21 +364,40 @@ def _check_constraints(config, decoder, beam_width, no_repeat_ngram, min_length,
     return ids
 
 
+def _check_groups(beam_width, n_groups, diversity_penalty):
+    """The checks of the diverse search on a checked beam_width."""
+    if not isinstance(n_groups, numbers.Real) or int(n_groups) != n_groups or n_groups < 1 or beam_width % int(n_groups) != 0:
+        raise ValueError("n_groups must be an integer >= 1 that divides beam_width = %d (got %r)" % (beam_width, n_groups))
+    if not (isinstance(diversity_penalty, numbers.Real) and math.isfinite(diversity_penalty) and diversity_penalty >= 0):
+        raise ValueError("diversity_penalty must be a finite number >= 0 (got %r)" % (diversity_penalty,))
+
+
 def _beam_nbest(config, decoder, input, hidden, encoder_outputs, beam_width, length_alpha, no_repeat_ngram=0, min_length=0,
-                banned_tokens=()):
-    """Device tensors (tokens [bw, n_steps, B], cum [bw, B], len [bw, B], score [bw, B]) of the checked search."""
+                banned_tokens=(), n_groups=1, diversity_penalty=0.0, want_groups=False):
+    """Device tensors (tokens [bw, n_steps, B], cum [bw, B], len [bw, B], score [bw, B]) of the checked search; want_groups: and
+    group [bw, B], the group of each rank."""
     _check_beam(decoder, beam_width, length_alpha)
     ids = _check_constraints(config, decoder, beam_width, no_repeat_ngram, min_length, banned_tokens)
+    _check_groups(beam_width, n_groups, diversity_penalty)
     _check_start(config, input, hidden)
     eng = _nbest_engine(config, decoder, encoder_outputs)
-    # (constraints all off: the library launches the unconstrained selection, recnet_beam_search_nbest's own path)
-    toks, cum, ln, score, n = _ops.load().beam_search_nbest_constrained(int(eng.handle.value), encoder_outputs.contiguous(), int(beam_width),
-                                                                        float(length_alpha), int(no_repeat_ngram), int(min_length), ids)
-    return toks[:, :int(n.item())], cum, ln, score
+    if int(n_groups) == 1:
+        # (constraints all off: the library launches the unconstrained selection, recnet_beam_search_nbest's own path)
+        toks, cum, ln, score, n = _ops.load().beam_search_nbest_constrained(int(eng.handle.value), encoder_outputs.contiguous(),
+                                                                            int(beam_width), float(length_alpha), int(no_repeat_ngram),
+                                                                            int(min_length), ids)
+        group = torch.zeros_like(ln) if want_groups else None
+    else:
+        toks, cum, ln, score, group, n = _ops.load().beam_search_nbest_diverse(int(eng.handle.value), encoder_outputs.contiguous(),
+                                                                               int(beam_width), float(length_alpha), int(n_groups),
+                                                                               float(diversity_penalty), int(no_repeat_ngram),
+                                                                               int(min_length), ids)
+    out = (toks[:, :int(n.item())], cum, ln, score)
+    return out + (group,) if want_groups else out
 
 
 def beam_search_nbest(config, decoder, input, hidden, encoder_outputs, beam_width, length_alpha=0.0, no_repeat_ngram=0, min_length=0,
-                      banned_tokens=()):
+                      banned_tokens=(), n_groups=1, diversity_penalty=0.0, return_groups=False):
     """Beam search on the model's own log-probabilities (the reference has no counterpart: its beam_search scores by
     log(sigmoid(logit))).  A hypothesis' value is the sum of log_softmax(logits_t)[token_t] over its steps — what score_captions
     and sequence_logprob return for it; a hypothesis with <EOS> is finished and carried with <PAD>; at every step the beam_width
@@ -391,26 +410,51 @@ def beam_search_nbest(config, decoder, input, hidden, encoder_outputs, beam_widt
     no_repeat_ngram = n > 0: no n-gram occurs twice in a hypothesis; min_length = m: no <EOS> before m tokens; banned_tokens: at
     most 16 ids that are never emitted (not <EOS>).  They remove candidates inside the selection, so the beam keeps its width; the
     values are not renormalised: cum is still the model's log-probability of the hypothesis, the one score_captions returns.  They
-    need beam_width + len(banned_tokens) + caption_max_len + 1 <= V."""
-    toks, cum, ln, score = _beam_nbest(config, decoder, input, hidden, encoder_outputs, beam_width, length_alpha, no_repeat_ngram,
-                                       min_length, banned_tokens)
-    toks, cum, ln, score = toks.cpu().tolist(), cum.cpu().tolist(), ln.cpu().tolist(), score.cpu().tolist()
+    need beam_width + len(banned_tokens) + caption_max_len + 1 <= V.
+    n_groups = G > 1 (a divisor of beam_width) is diverse beam search (recnet_beam_search_nbest_diverse): the
+    beam is G groups of beam_width / G hypotheses that are extended separately; inside a step the groups are decided one after the
+    other, and a candidate pays diversity_penalty for every hypothesis of an earlier group that chose its token at this step.  The
+    penalty steers the selection only: cum, length and score are as above, and the final order runs over all groups.  Different
+    groups may still return the same caption (nbest_diversity counts).  return_groups: the tuples get the group of the hypothesis
+    as a fifth field.  n_groups = 1 is the search above for any penalty."""
+    out = _beam_nbest(config, decoder, input, hidden, encoder_outputs, beam_width, length_alpha, no_repeat_ngram, min_length,
+                      banned_tokens, n_groups, diversity_penalty, bool(return_groups))
+    toks, cum, ln, score = (x.cpu().tolist() for x in out[:4])
     B = encoder_outputs.shape[0]
-    return [[([toks[r][t][b] for t in range(ln[r][b])], cum[r][b], ln[r][b], score[r][b]) for r in range(int(beam_width))]
+    hyps = [[([toks[r][t][b] for t in range(ln[r][b])], cum[r][b], ln[r][b], score[r][b]) for r in range(int(beam_width))]
             for b in range(B)]
+    if return_groups:
+        group = out[4].cpu().tolist()
+        hyps = [[h + (group[r][b],) for r, h in enumerate(hb)] for b, hb in enumerate(hyps)]
+    return hyps
+
+
+def nbest_diversity(hyps):
+    """How different the hypotheses of each caption are: hyps as beam_search_nbest returns them (per caption a list of tuples whose
+    first field is the token list; bare token lists are taken as well).  Returns per caption (distinct captions, distinct-1,
+    distinct-2): the number of different token lists, and the distinct unigrams / bigrams of the list divided by their total (0.0
+    when there is none).  Host only."""
+    out = []
+    for hb in hyps:
+        caps = [tuple(h[0]) if isinstance(h, tuple) else tuple(h) for h in hb]
+        uni = [x for c in caps for x in c]
+        bi = [c[j:j + 2] for c in caps for j in range(len(c) - 1)]
+        out.append((len(set(caps)), len(set(uni)) / len(uni) if uni else 0.0, len(set(bi)) / len(bi) if bi else 0.0))
+    return out
 
 
 def best_of_beam(config, decoder, input, hidden, encoder_outputs, beam_width, length_alpha=0.0, reconstructor=None,
-                 recon_weight=0.0, no_repeat_ngram=0, min_length=0, banned_tokens=()):
+                 recon_weight=0.0, no_repeat_ngram=0, min_length=0, banned_tokens=(), n_groups=1, diversity_penalty=0.0):
     """The beam_width hypotheses of beam_search_nbest, reranked like best_of_n's candidates: per video the rank k with the largest
     cum / length - recon_weight * rec_error (pick_best_of_n, the lowest k among equals; without a reconstructor or with
     recon_weight = 0 the first term alone).  Every rank of the search is a canonical [n_steps, B] caption set already, so it goes to
     the reconstruction error as it is, all ranks at the common T = n_steps (the global error depends on T).  no_repeat_ngram /
-    min_length / banned_tokens are beam_search_nbest's.  Returns what best_of_n returns: (captions: [B] token lists cut after
-    their <EOS>, chosen k [B], score [B])."""
+    min_length / banned_tokens / n_groups / diversity_penalty are beam_search_nbest's: with groups the reconstructor is given
+    hypotheses that differ.  Returns what best_of_n returns: (captions: [B] token lists cut after their <EOS>, chosen k [B],
+    score [B])."""
     use_rec, recon_weight = _check_recon_weight(config, decoder, reconstructor, encoder_outputs, recon_weight)
     toks, cum, ln, _ = _beam_nbest(config, decoder, input, hidden, encoder_outputs, beam_width, length_alpha, no_repeat_ngram,
-                                   min_length, banned_tokens)
+                                   min_length, banned_tokens, n_groups, diversity_penalty)
     errs = None
     if use_rec:
         errs = torch.stack([_rec_errors(config, decoder, reconstructor, encoder_outputs, toks[r])[0]

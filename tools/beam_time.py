@@ -6,9 +6,11 @@ the calls are alternated over `rounds` rounds so that drift hits them alike; the
 one JSON line.  The selection kernel reads each logit three times (maximum, sum of exponentials, candidates): `select_bytes_read`
 counts all three passes, `select_bytes_unique` the array once.  The `_constrained` rows are the same calls
 with no_repeat_ngram = 2, min_length = 3 and two banned ids, the kernel alone at the last step (t = T - 1) on random histories over
-a 4-letter alphabet: read them against the unconstrained rows of the same run.
+a 4-letter alphabet: read them against the unconstrained rows of the same run.  --groups 8:2,8:4 adds the diverse form (DESIGN.md
+section 14) at those (width, groups): the search and the grouped selection kernel alone at nb = width, penalty --penalty, beside
+the plain selection at the same nb = width: read them against the plain rows of the same width.
 
-    python tools/beam_time.py [--B 100 --F 28 --D 1536 --V 4188 --widths 1,5,8 --reps 10 --warmup 3 --rounds 5]
+    python tools/beam_time.py [--B 100 --F 28 --D 1536 --V 4188 --widths 1,5,8 --reps 10 --warmup 3 --rounds 5 --groups 8:2,8:4]
 """
 import argparse
 import json
@@ -27,6 +29,8 @@ def main():
                  ("rounds", 5), ("constrained", 1)):
         ap.add_argument("--" + k, type=int, default=v)
     ap.add_argument("--widths", default="1,5,8")
+    ap.add_argument("--groups", default="")
+    ap.add_argument("--penalty", type=float, default=0.5)
     ap.add_argument("--length_alpha", type=float, default=0.7)
     ap.add_argument("--precision", default="bf16")
     a = ap.parse_args()
@@ -58,6 +62,10 @@ def main():
         calls["beam_search_nbest_constrained_w%d" % w] = lambda w=w: eng.beam_search_nbest(enc, w, a.length_alpha, **con)
         calls["beam_select_rows_nb8_w%d" % w] = lambda w=w: eng.beam_select_rows(logits, cum, fin, w)
         calls["beam_select_rows_constrained_nb8_w%d" % w] = lambda w=w: eng.beam_select_rows(logits, cum, fin, w, hist=hist, t=Tm - 1, **con)
+    for w, G in ([int(x) for x in wg.split(":")] for wg in a.groups.split(",") if wg):
+        calls["beam_search_nbest_diverse_w%d_g%d" % (w, G)] = lambda w=w, G=G: eng.beam_search_nbest_diverse(enc, w, a.length_alpha, G, a.penalty)
+        calls["beam_select_rows_diverse_nb%d_w%d_g%d" % (w, w, G)] = lambda w=w, G=G: eng.beam_select_rows_diverse(logits[:w], cum[:w], fin[:w], w, G, a.penalty)
+        calls["beam_select_rows_nb%d_w%d" % (w, w)] = lambda w=w: eng.beam_select_rows(logits[:w], cum[:w], fin[:w], w)
     for fn in calls.values():
         for _ in range(a.warmup):
             fn()
@@ -75,7 +83,7 @@ def main():
             ms[k].append(e0.elapsed_time(e1) / reps)
     assert eng.chain_status() == 0
     out = {"shape": {k: getattr(a, k) for k in ("B", "F", "D", "E", "H", "A", "V")}, "T": Tm, "constraints": {k: list(v) if isinstance(v, tuple) else v for k, v in con.items()},
-           "precision": a.precision, "length_alpha": a.length_alpha, "reps": a.reps, "rounds": a.rounds,
+           "precision": a.precision, "length_alpha": a.length_alpha, "reps": a.reps, "rounds": a.rounds, "groups": a.groups, "penalty": a.penalty,
            "select_bytes_unique": nb * a.B * a.V * 4, "select_bytes_read": 3 * nb * a.B * a.V * 4}
     for k, v in ms.items():
         out[k + "_ms"] = {"median": statistics.median(v), "min": min(v), "max": max(v)}
