@@ -559,7 +559,8 @@ int recnet_debug_occupy(recnet_handle* h, int32_t n_workgroups, int32_t microsec
 int64_t recnet_debug_images_bytes(recnet_handle* h);       /* bytes of device scratch recnet_debug_images_stale needs (256-byte aligned) */
 int recnet_debug_images_stale(recnet_handle* h, void* scratch_dev, int64_t scratch_bytes, int64_t* n_diff_out, void* stream);
 /* Test hook: byte offset inside the bound workspace of a saved tensor of the local reconstructor's forward pass
- * (0: Whr [F][B][RA], 1: beta [F][B][T], 2: Hr [F][B][R], 3: acts [F][B][4R]); -1 if unknown. */
+ * (0: Whr [F][B][RA], 1: beta [F][B][T], 2: Hr [F][B][R], 3: acts [F][B][4R]), or of the dlogits operand of the output layer's
+ * backward products (4: [Tm][B][ldV], ldV = V rounded up to 8, bf16 or fp32 by the precision); -1 if unknown. */
 int64_t recnet_debug_offset(const recnet_handle* h, int32_t which);
 /* Name / start / duration of the dominant kernel's launches inside the last train step are measured
  * by the caller with hipEvents; this returns the ALGORITHMIC bytes of one launch: loop invariants once, every input /

@@ -187,7 +187,8 @@ __global__ __launch_bounds__(256) void occupy_kernel(unsigned long long ticks, u
 }
 int64_t recnet_debug_offset(const recnet_handle* h, int32_t which) {
   if (!h || !h->ws) return -1;
-  const void* p = which == 0 ? (const void*)h->Whr : which == 1 ? (const void*)h->beta : which == 2 ? (const void*)h->Hr : which == 3 ? (const void*)h->acts_r : nullptr;
+  const void* p = which == 0 ? (const void*)h->Whr : which == 1 ? (const void*)h->beta : which == 2 ? (const void*)h->Hr : which == 3 ? (const void*)h->acts_r :
+                  which == 4 ? (const void*)h->dlog_lp : nullptr;
   return p ? (int64_t)((const char*)p - h->ws) : -1;
 }
 // Test hook (include/recnet_hip.h): are the packed operand images what pack_weights would write from the master parameters?

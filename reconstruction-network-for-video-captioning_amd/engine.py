@@ -585,6 +585,23 @@ class Engine:
         base = (self._ws_ptr - self.workspace.data_ptr()) + off
         return self.workspace[base:base + 4 * n].view(torch.float32).clone()
 
+    def poison_dlogits_padding(self, T):
+        """Test hook: NaN into the padding columns [V, ldV) of the first T * B rows of the dlogits operand (recnet_debug_offset 4) —
+        the cross-entropy kernel of a T-step forward owns them, and the output layer's backward products read whole ldV-wide
+        rows.  Returns the number of padding columns per row (0: V is a multiple of 8, nothing to poison)."""
+        V, B, Tm = self.dims["V"], self.dims["B"], self.hyper["caption_max_len"] + 1
+        ldV = (V + 7) // 8 * 8
+        if ldV == V:
+            return 0
+        off = self.lib.recnet_debug_offset(self.handle, 4)
+        assert off >= 0
+        esz = 2 if self.precision == "bf16" else 4
+        base = (self._ws_ptr - self.workspace.data_ptr()) + off
+        rows = self.workspace[base:base + Tm * B * ldV * esz].view(torch.int16 if esz == 2 else torch.int32).view(Tm * B, ldV)
+        assert 1 <= T <= Tm
+        rows[:T * B, V:] = -1     # all bits set: a NaN in either format
+        return ldV - V
+
     def images_stale(self):
         """Test hook: number of 16-bit words in which the packed operand images differ from a fresh re-pack of the master
         parameters (recnet_debug_images_stale); completes a pending update and synchronises."""

@@ -317,7 +317,7 @@ def perplexity(config, decoder, batches):
     for enc, targets in batches:
         enc = torch.as_tensor(enc, dtype=torch.float32).to(dev)
         targets = torch.as_tensor(targets).long().to(dev)
-        _, cap, ln = _score(decoder, enc, _caption_tensor(config, decoder, enc.shape[0], targets), 1.0, False)
+        _, cap, ln = _score(decoder, enc, _caption_tensor(config, decoder, enc.shape[0], targets), 1.0, False, config.caption_max_len)
         total += cap.double().sum()
         count += ln.sum()
     return float(torch.exp(-total / count).item())

@@ -175,9 +175,17 @@ def _caption_tensor(config, decoder, B, captions):
     return captions
 
 
-def _score(decoder, encoder_outputs, tokens, temperature, reuse_features):
-    """Device tensors (logprobs [T, B], caption_logprob [B], lengths [B]) of checked tokens [T, B]."""
-    eng = _cached_engine(decoder, encoder_outputs)
+_SHARED_CML = 30          # Engine's default caption_max_len: the shared engine (Decoder.forward's) takes up to 31 caption rows
+
+
+def _score(decoder, encoder_outputs, tokens, temperature, reuse_features, caption_max_len=None):
+    """Device tensors (logprobs [T, B], caption_logprob [B], lengths [B]) of checked tokens [T, B].  caption_max_len: the config's —
+    another one than the shared engine's runs on the engine keyed by it (_nbest_engine's), whose Tm admits the caption_max_len + 1
+    rows _caption_tensor lets through (the shared engine refused captions of more than 31 rows: T out of range)."""
+    if caption_max_len is None or int(caption_max_len) == _SHARED_CML:
+        eng = _cached_engine(decoder, encoder_outputs)
+    else:
+        eng = _cached_engine(decoder, encoder_outputs, caption_max_len=caption_max_len)
     enc = None if reuse_features else encoder_outputs.contiguous()
     return _ops.load().score_captions(int(eng.handle.value), enc, tokens.to(encoder_outputs.device).contiguous(), float(temperature))
 
@@ -195,7 +203,7 @@ def score_captions(config, decoder, encoder_outputs, captions, temperature=1.0, 
     if encoder_outputs.dim() != 3:
         raise ValueError("encoder_outputs must be [B, F, D] (got %s)" % (tuple(encoder_outputs.shape),))
     tokens = _caption_tensor(config, decoder, encoder_outputs.shape[0], captions)
-    lps, cap, ln = _score(decoder, encoder_outputs, tokens, temperature, reuse_features)
+    lps, cap, ln = _score(decoder, encoder_outputs, tokens, temperature, reuse_features, config.caption_max_len)
     return lps.cpu().tolist(), cap.cpu().tolist(), ln.cpu().tolist()
 
 
@@ -317,7 +325,7 @@ def best_of_n(config, decoder, input, hidden, encoder_outputs, n, temperature=1.
     caps, lens, checked = [], [], []
     for k, toks in enumerate(cands):
         tokens = _caption_tensor(config, decoder, encoder_outputs.shape[0], toks)
-        _, cap, ln = _score(decoder, encoder_outputs, tokens, 1.0, k > 0)
+        _, cap, ln = _score(decoder, encoder_outputs, tokens, 1.0, k > 0, config.caption_max_len)
         caps.append(cap); lens.append(ln); checked.append(tokens)
     caps = torch.stack(caps).cpu().tolist()          # one read-back each for the n x B sums and lengths
     lens = torch.stack(lens).cpu().tolist()

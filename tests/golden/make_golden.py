@@ -84,7 +84,7 @@ def formula_params(sd, seed):
     return _formula({k: tuple(v.shape) for k, v in sd.items()}, seed)
 
 
-def configure(*, B, F, D, V, E, H, A, dec_cell, rec_kind, rec_cell, RA):
+def configure(*, B, F, D, V, E, H, A, dec_cell, rec_kind, rec_cell, RA, cml=30):
     C.device = "cpu"
     C.decoder_model = dec_cell
     C.reconstructor_model = rec_cell
@@ -98,7 +98,7 @@ def configure(*, B, F, D, V, E, H, A, dec_cell, rec_kind, rec_cell, RA):
     C.reconstructor_type = rec_kind or "local"
     C.reconstructor_hidden_size = D
     C.reconstructor_attn_size = RA
-    C.caption_max_len = 30
+    C.caption_max_len = cml
 
 
 ONLY = None   # --only a,b,c : regenerate just these cases
@@ -106,15 +106,16 @@ ONLY = None   # --only a,b,c : regenerate just these cases
 
 def run_case(name, *, B, F, D, V, E, H, A, lens, dec_cell="LSTM", rec_kind=None, rec_cell="LSTM",
              RA=None, train_mode=True, n_steps=3, seed=0, drop_seed=42, full=True, formula_seed=None,
-             tf_ratio=1.0, py_seed=None, out_scale=None, dec_lr=None, rec_lr=None):
+             tf_ratio=1.0, py_seed=None, out_scale=None, dec_lr=None, rec_lr=None, cml=30):
     """tf_ratio < 1 (config.py:71 decoder_teacher_forcing_ratio): forward_decoder draws `random.random() <= ratio` once per
     iteration (train.py:38) from Python's global generator, seeded here with py_seed; the iterations that draw False feed the
     arg-max back (train.py:46-51) and are differentiated like the others.  out_scale: a decisive vocabulary projection, so the
-    arg-max of a free-running iteration is not a coin flip at default init."""
+    arg-max of a free-running iteration is not a coin flip at default init.  cml: config.py:50 caption_max_len (read by
+    train.py:41,66 and handed to the global reconstructor, train.py:181); targets get cml + 1 rows."""
     if ONLY is not None and name not in ONLY:
         return
     RA = RA or A
-    configure(B=B, F=F, D=D, V=V, E=E, H=H, A=A, dec_cell=dec_cell, rec_kind=rec_kind, rec_cell=rec_cell, RA=RA)
+    configure(B=B, F=F, D=D, V=V, E=E, H=H, A=A, dec_cell=dec_cell, rec_kind=rec_kind, rec_cell=rec_cell, RA=RA, cml=cml)
     torch.manual_seed(seed)
     # dec_lr / rec_lr: the reference's own config attributes (config.py:86-87) read by build_decoder / build_reconstructor
     # (train.py:149,186) — larger values make three updates move every parameter far beyond any comparison tolerance
@@ -143,13 +144,15 @@ def run_case(name, *, B, F, D, V, E, H, A, lens, dec_cell="LSTM", rec_kind=None,
     fwd_rec = {"global": ref_train.forward_global_reconstructor,
                "local": ref_train.forward_local_reconstructor}.get(rec_kind)
 
-    enc, targets = make_batch(B, F, D, V, lens, seed + 100)
+    enc, targets = make_batch(B, F, D, V, lens, seed + 100, Tm=cml + 1)
     masks = targets > 0
     out = {"meta_dims": np.array([B, F, D, V, E, H, A, RA], dtype=np.int64),
            "meta_lens": np.array(lens, dtype=np.int64), "meta_drop_seed": np.array(drop_seed),
            "meta_train_mode": np.array(int(train_mode)), "meta_n_steps": np.array(n_steps),
            "meta_formula_seed": np.array(-1 if formula_seed is None else formula_seed),
            "meta_cells": np.array([int(dec_cell == "GRU"), int(rec_cell == "GRU")], dtype=np.int64)}
+    if cml != 30:                                                   # (the older cases keep their files byte for byte)
+        out["meta_caption_max_len"] = np.array(cml, dtype=np.int64)
     if dec_lr is not None or rec_lr is not None:
         out["meta_lr"] = np.array([lr_keep[0] if dec_lr is None else dec_lr, lr_keep[1] if rec_lr is None else rec_lr], dtype=np.float64)
     if full:
@@ -170,14 +173,14 @@ def run_case(name, *, B, F, D, V, E, H, A, lens, dec_cell="LSTM", rec_kind=None,
         tok = torch.full((1, B), 1, dtype=torch.long)
         hid = (torch.zeros(1, B, H), torch.zeros(1, B, H)) if dec_cell == "LSTM" else torch.zeros(1, B, H)
         logits_all, h_all, c_all = [], [], []
-        for t in range(31):
+        for t in range(cml + 1):
             lg, hid = dm(tok, hid, enc)
             tok = targets[t].view(1, -1)
             logits_all.append(lg.numpy().copy())
             h_all.append((hid[0] if dec_cell == "LSTM" else hid)[0].numpy().copy())
             if dec_cell == "LSTM":
                 c_all.append(hid[1][0].numpy().copy())
-            if t == 30 or not bool(masks[t + 1].any()):
+            if t == cml or not bool(masks[t + 1].any()):
                 break
     if full:
         out["step_logits"] = np.stack(logits_all)
@@ -363,6 +366,11 @@ if __name__ == "__main__":
     run_case("lr_global_chain", lens=lens24, rec_kind="global", n_steps=4, dec_lr=1e-2, rec_lr=1e-2, **CHAIN)
     run_case("lr_local_chain", lens=lens24, rec_kind="local", RA=16, n_steps=4, dec_lr=1e-2, rec_lr=1e-2, **CHAIN)
     run_case("lr_gru_global_chain", lens=lens24, dec_cell="GRU", rec_kind="global", rec_cell="GRU", n_steps=4, dec_lr=1e-2, rec_lr=1e-2, **CHAIN)
+    # the two settings of config.py that select other kernels (what V and caption_max_len select): caption_max_len = 44
+    # with captions longer than 32 tokens under the global reconstructor (its cml / T rescale follows the setting), and a
+    # vocabulary above 5120 (min_count <= 3), decoder only; the latter from formula parameters with norms and slices stored
+    run_case("global_cml44", lens=[40, 3, 33, 1, 7], rec_kind="global", n_steps=1, cml=44, B=5, F=4, D=40, V=53, E=12, H=24, A=16)
+    run_case("dec_V5200", B=6, F=3, D=32, V=5200, E=8, H=32, A=16, lens=[5, 2, 6, 0, 3, 1], n_steps=1, full=False, formula_seed=9)
     # full-shape cases (SURVEY.md §8a C1..C3 dims): parameters from formula_params(seed) so they can be
     # regenerated without the reference; only outputs / norms / slices are stored.
     FULL = dict(F=28, D=1536, V=4188, E=468, H=512, A=128)

@@ -9,10 +9,11 @@ import torch
 GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
-def make_batch(B, F, D, V, lens, seed):
+def make_batch(B, F, D, V, lens, seed, Tm=31):
+    """Tm = caption_max_len + 1 rows of targets; the draws do not depend on it (tests/test_golden_util.py)."""
     g = torch.Generator().manual_seed(int(seed))
     enc = torch.randn(B, F, D, generator=g)
-    targets = torch.zeros(31, B, dtype=torch.long)
+    targets = torch.zeros(int(Tm), B, dtype=torch.long)
     for b, L in enumerate(lens):
         L = int(L)
         targets[:L, b] = torch.randint(3, V, (L,), generator=g)
@@ -60,6 +61,11 @@ def cells_of(g):
     if mc is None:
         return ("LSTM", "LSTM")
     return tuple("GRU" if int(x) else "LSTM" for x in mc)
+
+
+def caption_max_len_of(g):
+    """config.py:50 caption_max_len of a golden case; cases written before it was varied are at the reference's 30."""
+    return int(g["meta_caption_max_len"]) if "meta_caption_max_len" in g else 30
 
 
 def load(name):

@@ -45,7 +45,7 @@ def load_case(name):
     if fs >= 0:
         decP = GU.formula_params(GU.decoder_shapes(V, E, H, A, D, cells[0]), fs)
         recP = GU.formula_params(GU.rec_shapes(kind, H, D, RA, cells[1]), fs + 1) if kind else None
-        enc, targets = GU.make_batch(B, F, D, V, g["meta_lens"], int(g["meta_batch_seed"]))
+        enc, targets = GU.make_batch(B, F, D, V, g["meta_lens"], int(g["meta_batch_seed"]), Tm=GU.caption_max_len_of(g) + 1)
     else:
         decP, recP = GU.group(g, "dec_init"), (GU.group(g, "rec_init") if kind else None)
         enc, targets = torch.from_numpy(g["enc"]), torch.from_numpy(g["targets"])
@@ -64,9 +64,9 @@ def rel_err(a, b):
     return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-12))
 
 
-def oracle_grads(decP, recP, kind, enc, targets, train, seed, B_global=None, b_offset=0, cells=("LSTM", "LSTM")):
+def oracle_grads(decP, recP, kind, enc, targets, train, seed, B_global=None, b_offset=0, cells=("LSTM", "LSTM"), caption_max_len=30):
     """Reference gradients (incl. the regulariser term) from the CPU oracle's autograd."""
-    st = O.TrainState(decP, recP, kind, cell=cells[0], rec_cell=cells[1])
+    st = O.TrainState(decP, recP, kind, cell=cells[0], rec_cell=cells[1], caption_max_len=caption_max_len)
     drop = O.Dropper("hash", seed=seed) if train else O.Dropper("eval")
     masks = targets > 0
     dl, rl, hid, ce, mse = st.losses(enc, targets, masks, drop)

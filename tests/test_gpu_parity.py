@@ -20,6 +20,8 @@ SMALL = ["dec_eval", "dec_train", "dec_T31", "dec_T4_samelen", "global_train", "
          "local_eval", "local_T31", "gru_local_train", "gru_global_eval", "gru_dec_train", "gru_global_train",
          "gru_local_train3"]
 FULL = ["full_dec_B8", "full_global_B8", "full_local_B8", "full_gru_global_B8", "full_gru_local_B8"]
+# config.py:48,50 moved (tests/golden/make_golden.py): caption_max_len = 44 with captions of 40 and 33 tokens, V = 5200
+AXES = ["global_cml44", "dec_V5200"]
 REG_SLACK = 3e-4
 
 
@@ -52,12 +54,12 @@ def test_step_api_matches_reference(name, prec):
 
 
 @pytest.mark.parametrize("prec", ["f32", "bf16"])
-@pytest.mark.parametrize("name", SMALL + FULL)
+@pytest.mark.parametrize("name", SMALL + FULL + AXES)
 def test_autograd_api_losses_and_grads(name, prec):
     """forward_decoder / forward_*_reconstructor + loss.backward() (train.py:250-268) against the goldens:
     losses, hidden states, every parameter gradient (norm-regulariser term included)."""
     g, dims, kind, decP, recP, enc, targets = load_case(name)
-    C, dec, rec = make_models(dims, kind, prec, decP, recP, cells=g["_cells"])
+    C, dec, rec = make_models(dims, kind, prec, decP, recP, cells=g["_cells"], caption_max_len=GU.caption_max_len_of(g))
     train = bool(int(g["meta_train_mode"]))
     seed = int(g["meta_drop_seed"])
     dec["model"].train(train)

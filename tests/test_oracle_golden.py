@@ -11,6 +11,8 @@ SMALL_CASES = ["dec_eval", "dec_train", "dec_T31", "dec_T4_samelen", "global_tra
                "local_train", "local_eval", "local_T31", "gru_local_train", "gru_global_eval", "gru_dec_train",
                "gru_global_train", "gru_local_train3"]
 FULL_CASES = ["full_dec_B8", "full_global_B8", "full_local_B8", "full_gru_global_B8", "full_gru_local_B8"]
+# config.py:48,50 moved: caption_max_len = 44 with captions of 40 and 33 tokens (global reconstructor: its cml / T rescale), V = 5200
+AXIS_CASES = ["global_cml44", "dec_V5200"]
 
 
 def _setup(name):
@@ -22,7 +24,7 @@ def _setup(name):
     if fs >= 0:
         decP = GU.formula_params(GU.decoder_shapes(V, E, H, A, D, cells[0]), fs)
         recP = GU.formula_params(GU.rec_shapes(kind, H, D, RA, cells[1]), fs + 1) if kind else None
-        enc, targets = GU.make_batch(B, F, D, V, g["meta_lens"], int(g["meta_batch_seed"]))
+        enc, targets = GU.make_batch(B, F, D, V, g["meta_lens"], int(g["meta_batch_seed"]), Tm=GU.caption_max_len_of(g) + 1)
         assert np.array_equal(targets.numpy(), g["targets"])
     else:
         decP = GU.group(g, "dec_init")
@@ -38,7 +40,7 @@ def _drop(g, it=0):
     return O.Dropper("eval")
 
 
-@pytest.mark.parametrize("name", SMALL_CASES + FULL_CASES)
+@pytest.mark.parametrize("name", SMALL_CASES + FULL_CASES + AXIS_CASES)
 def test_step_api_and_losses(name):
     g, decP, recP, kind, cells, enc, targets = _setup(name)
     masks = targets > 0
@@ -49,7 +51,8 @@ def test_step_api_and_losses(name):
     tok = torch.full((1, B), 1, dtype=torch.long)
     hid = O.zero_hidden(B, H, cells[0])
     T = int(g["T"])
-    assert O.decode_len(masks) == T
+    cml = GU.caption_max_len_of(g)
+    assert targets.shape[0] == cml + 1 and O.decode_len(masks, cml) == T
     for t in range(T):
         lg, hid = O.decoder_step(decP, tok, hid, enc, cell=cells[0], drop=drop, t=t)
         tok = targets[t].view(1, -1)
@@ -60,7 +63,7 @@ def test_step_api_and_losses(name):
         if cells[0] == "LSTM":
             np.testing.assert_allclose(hid[1][0].numpy(), g["step_c"][t], atol=2e-6, rtol=0)
     # sequence API + losses
-    st = O.TrainState(decP, recP, kind, cell=cells[0], rec_cell=cells[1])
+    st = O.TrainState(decP, recP, kind, cell=cells[0], rec_cell=cells[1], caption_max_len=cml)
     dl, rl, hiddens, ce, mse = st.losses(enc, targets, masks, _drop(g))
     np.testing.assert_allclose(hiddens.detach().numpy(), g["hiddens"], atol=2e-6, rtol=0)
     assert abs(float(dl) - float(g["dec_loss"])) <= 2e-6 * max(1.0, abs(float(g["dec_loss"])))
@@ -70,11 +73,11 @@ def test_step_api_and_losses(name):
         assert abs(float(mse) - float(g["rec_mse"])) <= 5e-6
 
 
-@pytest.mark.parametrize("name", SMALL_CASES + FULL_CASES)
+@pytest.mark.parametrize("name", SMALL_CASES + FULL_CASES + AXIS_CASES)
 def test_gradients_and_optimizer(name):
     g, decP, recP, kind, cells, enc, targets = _setup(name)
     masks = targets > 0
-    st = O.TrainState(decP, recP, kind, cell=cells[0], rec_cell=cells[1])
+    st = O.TrainState(decP, recP, kind, cell=cells[0], rec_cell=cells[1], caption_max_len=GU.caption_max_len_of(g))
     n_steps = int(g["meta_n_steps"])
     for it in range(n_steps):
         dl, rl, loss, gn = st.step(enc, targets, masks, _drop(g, it))
