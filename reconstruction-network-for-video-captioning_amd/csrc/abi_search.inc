@@ -176,88 +176,74 @@ int recnet_greedy_search(recnet_handle* h, const float* enc, int64_t* tokens_out
   return RECNET_OK;
 }
 
-// ---- sampling (the reference has no counterpart; the loop shape is eval.py:19-33)
-static int check_sample(float temperature, int top_k, int V) {
+// ---- sampling (the reference has no counterpart; the loop shape is eval.py:19-33) and, top_p given, nucleus (top-p) sampling on
+// what the top-k cut leaves (DESIGN.md section 13).  One launcher and one body per shape of entry; the exports without top_p pass
+// null and keep their kernels, the nucleus exports launch the nucleus kernels at top_p = 1 too (they count n_allowed).
+static int check_sample(float temperature, int top_k, int V, const float* top_p = nullptr) {
   if (!(temperature > 0.f) || !std::isfinite(temperature)) return fail(RECNET_EINVAL, "temperature must be positive and finite");
   if (top_k < 0 || top_k > V) return fail(RECNET_EINVAL, "top_k must be in [0, V]");
+  if (!top_p) return RECNET_OK;
+  if (!(*top_p > 0.f) || !(*top_p <= 1.f)) return fail(RECNET_EINVAL, "top_p must be in (0, 1]");    // (refuses NaN too)
+  if (*top_p < 1.f && V >= (1 << 21)) return fail(RECNET_EINVAL, "top_p < 1 needs V < 2^21 (the integer masses sum in 53 bits)");
   return RECNET_OK;
 }
-// one draw per row of logits [rows][V]; (B, t) place the rows in the counter space of the draw
-static void launch_sample_rows(const float* logits, int rows, int V, int B, float temperature, int top_k, uint32_t seed, int t,
-                               int64_t* tokens, float* logprobs, hipStream_t st) {
-  SampleArgs a;
+// one draw per row of logits [rows][V]; (B, t) place the rows in the counter space of the draw; n_allowed [rows] may be null
+static void launch_sample_rows(const float* logits, int rows, int V, int B, float temperature, int top_k, const float* top_p, uint32_t seed,
+                               int t, int64_t* tokens, float* logprobs, int32_t* n_allowed, hipStream_t st) {
+  SampleNucArgs a;
   a.x = logits; a.V = V; a.k = top_k == V ? 0 : top_k; a.B = B; a.t = t;
   a.temp = temperature; a.key = rn_site_key(seed, RN_SITE_SAMPLE); a.tok = tokens; a.lp = logprobs;
-  if (V <= SR_ROW_LDS_MAX) hipLaunchKernelGGL((sample_rows_kernel<true>), dim3(rows), dim3(256), (size_t)V * 4, st, a);
-  else hipLaunchKernelGGL((sample_rows_kernel<false>), dim3(rows), dim3(256), 0, st, a);
+  a.top_p = top_p ? *top_p : 1.f; a.n_allowed = n_allowed;
+  const SampleArgs& u = a;
+  const bool res = V <= SR_ROW_LDS_MAX;
+  const size_t sm = res ? (size_t)V * 4 : 0;
+  if (top_p) {
+    if (res) hipLaunchKernelGGL((sample_rows_kernel<true, true>), dim3(rows), dim3(256), sm, st, a);
+    else hipLaunchKernelGGL((sample_rows_kernel<false, true>), dim3(rows), dim3(256), sm, st, a);
+  } else {
+    if (res) hipLaunchKernelGGL((sample_rows_kernel<true>), dim3(rows), dim3(256), sm, st, u);
+    else hipLaunchKernelGGL((sample_rows_kernel<false>), dim3(rows), dim3(256), sm, st, u);
+  }
+}
+static int sample_rows_run(recnet_handle* h, const float* logits, int rows, int V, float temperature, int top_k, const float* top_p,
+                           uint32_t seed, int t, int64_t* tokens_out, float* logprobs_out, int32_t* n_allowed_out, void* stream) {
+  REQUIRE_WS(h);
+  if (!logits || !tokens_out || !logprobs_out) return fail(RECNET_EINVAL, "null argument");
+  if (rows < 1 || V < 1 || t < 0) return fail(RECNET_EINVAL, "rows and V must be positive, t non-negative");
+  int r = check_sample(temperature, top_k, V, top_p); if (r) return r;
+  launch_sample_rows(logits, rows, V, rows, temperature, top_k, top_p, seed, t, tokens_out, logprobs_out, n_allowed_out, (hipStream_t)stream);
+  LAUNCH_OK();
+  return RECNET_OK;
+}
+static int sample_search_run(recnet_handle* h, const float* enc, float temperature, int top_k, const float* top_p, uint32_t seed,
+                             int64_t* tokens_out, float* logprobs_out, int32_t* n_allowed_out, int32_t* n_steps_out, void* stream) {
+  int r = search_check(h, enc && tokens_out && logprobs_out && n_steps_out); if (r) return r;
+  r = check_sample(temperature, top_k, h->V, top_p); if (r) return r;
+  hipStream_t st = (hipStream_t)stream;
+  search_one_per_caption(h, enc, tokens_out, n_steps_out, st, [&](int t, int64_t* out_t) {
+    launch_sample_rows(h->sr_logits, h->B, h->V, h->B, temperature, top_k, top_p, seed, t, out_t, logprobs_out + (size_t)t * h->B,
+                       n_allowed_out ? n_allowed_out + (size_t)t * h->B : nullptr, st);
+  });
+  LAUNCH_OK();
+  return RECNET_OK;
 }
 
 int recnet_sample_rows(recnet_handle* h, const float* logits, int32_t rows, int32_t V, float temperature, int32_t top_k,
                        uint32_t seed, int32_t t, int64_t* tokens_out, float* logprobs_out, void* stream) {
-  REQUIRE_WS(h);
-  if (!logits || !tokens_out || !logprobs_out) return fail(RECNET_EINVAL, "null argument");
-  if (rows < 1 || V < 1 || t < 0) return fail(RECNET_EINVAL, "rows and V must be positive, t non-negative");
-  int r = check_sample(temperature, top_k, V); if (r) return r;
-  launch_sample_rows(logits, rows, V, rows, temperature, top_k, seed, t, tokens_out, logprobs_out, (hipStream_t)stream);
-  LAUNCH_OK();
-  return RECNET_OK;
+  return sample_rows_run(h, logits, rows, V, temperature, top_k, nullptr, seed, t, tokens_out, logprobs_out, nullptr, stream);
 }
-
-int recnet_sample_search(recnet_handle* h, const float* enc, float temperature, int32_t top_k, uint32_t seed,
-                         int64_t* tokens_out, float* logprobs_out, int32_t* n_steps_out, void* stream) {
-  int r = search_check(h, enc && tokens_out && logprobs_out && n_steps_out); if (r) return r;
-  r = check_sample(temperature, top_k, h->V); if (r) return r;
-  hipStream_t st = (hipStream_t)stream;
-  search_one_per_caption(h, enc, tokens_out, n_steps_out, st, [&](int t, int64_t* out_t) {
-    launch_sample_rows(h->sr_logits, h->B, h->V, h->B, temperature, top_k, seed, t, out_t, logprobs_out + (size_t)t * h->B, st);
-  });
-  LAUNCH_OK();
-  return RECNET_OK;
-}
-
-// ---- nucleus (top-p) sampling on what the top-k cut leaves (the reference has no counterpart; DESIGN.md section 13).  Entry points
-// of their own: recnet_sample_rows / recnet_sample_search above keep their kernels.
-static int check_sample_nucleus(float temperature, int top_k, float top_p, int V) {
-  int r = check_sample(temperature, top_k, V); if (r) return r;
-  if (!(top_p > 0.f) || !(top_p <= 1.f)) return fail(RECNET_EINVAL, "top_p must be in (0, 1]");    // (refuses NaN too)
-  if (top_p < 1.f && V >= (1 << 21)) return fail(RECNET_EINVAL, "top_p < 1 needs V < 2^21 (the integer masses sum in 53 bits)");
-  return RECNET_OK;
-}
-// launch_sample_rows with the nucleus cut; n_allowed [rows] may be null
-static void launch_sample_rows_nucleus(const float* logits, int rows, int V, int B, float temperature, int top_k, float top_p,
-                                       uint32_t seed, int t, int64_t* tokens, float* logprobs, int32_t* n_allowed, hipStream_t st) {
-  SampleNucArgs a;
-  a.x = logits; a.V = V; a.k = top_k == V ? 0 : top_k; a.B = B; a.t = t;
-  a.temp = temperature; a.key = rn_site_key(seed, RN_SITE_SAMPLE); a.tok = tokens; a.lp = logprobs;
-  a.top_p = top_p; a.n_allowed = n_allowed;
-  if (V <= SR_ROW_LDS_MAX) hipLaunchKernelGGL((sample_rows_kernel<true, true>), dim3(rows), dim3(256), (size_t)V * 4, st, a);
-  else hipLaunchKernelGGL((sample_rows_kernel<false, true>), dim3(rows), dim3(256), 0, st, a);
-}
-
 int recnet_sample_rows_nucleus(recnet_handle* h, const float* logits, int32_t rows, int32_t V, float temperature, int32_t top_k,
                                float top_p, uint32_t seed, int32_t t, int64_t* tokens_out, float* logprobs_out, int32_t* n_allowed_out,
                                void* stream) {
-  REQUIRE_WS(h);
-  if (!logits || !tokens_out || !logprobs_out) return fail(RECNET_EINVAL, "null argument");
-  if (rows < 1 || V < 1 || t < 0) return fail(RECNET_EINVAL, "rows and V must be positive, t non-negative");
-  int r = check_sample_nucleus(temperature, top_k, top_p, V); if (r) return r;
-  launch_sample_rows_nucleus(logits, rows, V, rows, temperature, top_k, top_p, seed, t, tokens_out, logprobs_out, n_allowed_out,
-                             (hipStream_t)stream);
-  LAUNCH_OK();
-  return RECNET_OK;
+  return sample_rows_run(h, logits, rows, V, temperature, top_k, &top_p, seed, t, tokens_out, logprobs_out, n_allowed_out, stream);
 }
-
+int recnet_sample_search(recnet_handle* h, const float* enc, float temperature, int32_t top_k, uint32_t seed,
+                         int64_t* tokens_out, float* logprobs_out, int32_t* n_steps_out, void* stream) {
+  return sample_search_run(h, enc, temperature, top_k, nullptr, seed, tokens_out, logprobs_out, nullptr, n_steps_out, stream);
+}
 int recnet_sample_search_nucleus(recnet_handle* h, const float* enc, float temperature, int32_t top_k, float top_p, uint32_t seed,
                                  int64_t* tokens_out, float* logprobs_out, int32_t* n_allowed_out, int32_t* n_steps_out, void* stream) {
-  int r = search_check(h, enc && tokens_out && logprobs_out && n_steps_out); if (r) return r;
-  r = check_sample_nucleus(temperature, top_k, top_p, h->V); if (r) return r;
-  hipStream_t st = (hipStream_t)stream;
-  search_one_per_caption(h, enc, tokens_out, n_steps_out, st, [&](int t, int64_t* out_t) {
-    launch_sample_rows_nucleus(h->sr_logits, h->B, h->V, h->B, temperature, top_k, top_p, seed, t, out_t,
-                               logprobs_out + (size_t)t * h->B, n_allowed_out ? n_allowed_out + (size_t)t * h->B : nullptr, st);
-  });
-  LAUNCH_OK();
-  return RECNET_OK;
+  return sample_search_run(h, enc, temperature, top_k, &top_p, seed, tokens_out, logprobs_out, n_allowed_out, n_steps_out, stream);
 }
 
 // ---- scoring given captions (the reference has no counterpart; the loop is train.py:25,45 in eval mode)
@@ -446,46 +432,32 @@ static void launch_beam_select(const float* logits, const float* cum, const int3
                                int t = 0, int n_groups = 1, float diversity_penalty = 0.f) {
   BeamSelCArgs a;
   a.x = logits; a.cum = cum; a.fin = fin; a.nb = nb; a.rows = rows; a.V = V; a.vals = vals; a.idx = idx;
-  if (n_groups > 1) {
-    BeamGrpArgs q;
-    q.G = n_groups; q.lam = diversity_penalty;
-    const int w = bw / n_groups;
-    if (!bans || !bans->on()) {
-      const BeamSelArgs& u = a;
-      switch (w) {
-#define RN_BSEL(W) case W: hipLaunchKernelGGL((beam_select_groups_kernel<W>), dim3(rows), dim3(256), 0, st, u, q); break;
-        RN_BSEL(1) RN_BSEL(2) RN_BSEL(3) RN_BSEL(4)
-#undef RN_BSEL
-      }
-      return;
-    }
+  const bool con = bans && bans->on();
+  size_t sm = 0;
+  if (con) {
     a.hist = hist; a.Tm = Tm; a.t = t; a.ngram = bans->ngram; a.min_len = bans->min_len; a.n_banned = bans->n_banned;
     for (int k = 0; k < 16; ++k) a.banned[k] = bans->banned[k];
-    const size_t sm = (size_t)(8 + nb * bs_ban_stride(t)) * 4;
-    switch (w) {
-#define RN_BSEL(W) case W: hipLaunchKernelGGL((beam_select_groups_kernel<W, true>), dim3(rows), dim3(256), sm, st, a, q); break;
-      RN_BSEL(1) RN_BSEL(2) RN_BSEL(3) RN_BSEL(4)
-#undef RN_BSEL
-    }
-    return;
+    sm = (size_t)(8 + nb * bs_ban_stride(t)) * 4;
   }
-  if (!bans || !bans->on()) {
-    const BeamSelArgs& u = a;
+  const BeamSelArgs& u = a;            // (the unconstrained kernels take the base part)
+  BeamGrpArgs q;
+  q.G = n_groups; q.lam = diversity_penalty;
+#define RN_BSEL(W, KERNEL, ...) case W:                                                                       \
+    if (con) hipLaunchKernelGGL((KERNEL<W, true>), dim3(rows), dim3(256), sm, st, a, ##__VA_ARGS__);          \
+    else hipLaunchKernelGGL((KERNEL<W>), dim3(rows), dim3(256), 0, st, u, ##__VA_ARGS__);                     \
+    break;
+  if (n_groups > 1) {
+    switch (bw / n_groups) {
+      RN_BSEL(1, beam_select_groups_kernel, q) RN_BSEL(2, beam_select_groups_kernel, q) RN_BSEL(3, beam_select_groups_kernel, q)
+      RN_BSEL(4, beam_select_groups_kernel, q)
+    }
+  } else {
     switch (bw) {
-#define RN_BSEL(W) case W: hipLaunchKernelGGL((beam_select_kernel<W>), dim3(rows), dim3(256), 0, st, u); break;
-      RN_BSEL(1) RN_BSEL(2) RN_BSEL(3) RN_BSEL(4) RN_BSEL(5) RN_BSEL(6) RN_BSEL(7) RN_BSEL(8)
-#undef RN_BSEL
+      RN_BSEL(1, beam_select_kernel) RN_BSEL(2, beam_select_kernel) RN_BSEL(3, beam_select_kernel) RN_BSEL(4, beam_select_kernel)
+      RN_BSEL(5, beam_select_kernel) RN_BSEL(6, beam_select_kernel) RN_BSEL(7, beam_select_kernel) RN_BSEL(8, beam_select_kernel)
     }
-    return;
   }
-  a.hist = hist; a.Tm = Tm; a.t = t; a.ngram = bans->ngram; a.min_len = bans->min_len; a.n_banned = bans->n_banned;
-  for (int k = 0; k < 16; ++k) a.banned[k] = bans->banned[k];
-  const size_t sm = (size_t)(8 + nb * bs_ban_stride(t)) * 4;
-  switch (bw) {
-#define RN_BSEL(W) case W: hipLaunchKernelGGL((beam_select_kernel<W, true>), dim3(rows), dim3(256), sm, st, a); break;
-    RN_BSEL(1) RN_BSEL(2) RN_BSEL(3) RN_BSEL(4) RN_BSEL(5) RN_BSEL(6) RN_BSEL(7) RN_BSEL(8)
 #undef RN_BSEL
-  }
 }
 
 static int check_select_rows(const float* logits, const float* cum, const int32_t* finished, int nb, int rows, int V, int beam_width,
@@ -496,30 +468,6 @@ static int check_select_rows(const float* logits, const float* cum, const int32_
   return check_beam(beam_width, V, 0.f);
 }
 
-int recnet_beam_select_rows(recnet_handle* h, const float* logits, const float* cum, const int32_t* finished, int32_t nb,
-                            int32_t rows, int32_t V, int32_t beam_width, float* vals_out, int32_t* idx_out, void* stream) {
-  REQUIRE_WS(h);
-  int r = check_select_rows(logits, cum, finished, nb, rows, V, beam_width, vals_out, idx_out); if (r) return r;
-  launch_beam_select(logits, cum, finished, nb, rows, V, beam_width, vals_out, idx_out, (hipStream_t)stream);
-  LAUNCH_OK();
-  return RECNET_OK;
-}
-
-int recnet_beam_select_rows_constrained(recnet_handle* h, const float* logits, const float* cum, const int32_t* finished,
-                                        const int64_t* hist, int32_t nb, int32_t rows, int32_t V, int32_t Tm, int32_t t,
-                                        int32_t beam_width, int32_t no_repeat_ngram, int32_t min_length, const int32_t* banned,
-                                        int32_t n_banned, float* vals_out, int32_t* idx_out, void* stream) {
-  REQUIRE_WS(h);
-  int r = check_select_rows(logits, cum, finished, nb, rows, V, beam_width, vals_out, idx_out); if (r) return r;
-  if (Tm < 1 || t < 0 || t >= Tm) return fail(RECNET_EINVAL, "Tm must be positive and t in [0, Tm)");
-  BeamBans bans;
-  r = check_beam_bans(no_repeat_ngram, min_length, banned, n_banned, beam_width, V, Tm, t, &bans); if (r) return r;
-  if (no_repeat_ngram > 0 && !hist) return fail(RECNET_EINVAL, "null argument");
-  launch_beam_select(logits, cum, finished, nb, rows, V, beam_width, vals_out, idx_out, (hipStream_t)stream, &bans, hist, Tm, t);
-  LAUNCH_OK();
-  return RECNET_OK;
-}
-
 // the groups of the diverse form (DESIGN.md section 14), checked: one group = the selection as it was
 static int check_beam_groups(int beam_width, int n_groups, float diversity_penalty) {
   if (n_groups < 1 || beam_width % n_groups != 0) return fail(RECNET_EINVAL, "n_groups must be at least 1 and divide beam_width");
@@ -527,14 +475,18 @@ static int check_beam_groups(int beam_width, int n_groups, float diversity_penal
   return RECNET_OK;
 }
 
-int recnet_beam_select_rows_diverse(recnet_handle* h, const float* logits, const float* cum, const int32_t* finished,
-                                    const int64_t* hist, int32_t nb, int32_t rows, int32_t V, int32_t Tm, int32_t t, int32_t beam_width,
-                                    int32_t n_groups, float diversity_penalty, int32_t no_repeat_ngram, int32_t min_length,
-                                    const int32_t* banned, int32_t n_banned, float* vals_out, int32_t* idx_out, void* stream) {
+// The one body of the three selection exports below, which differ in what they hand in; diverse: the diverse export, the only one
+// that checks the groups and ties nb to the width (the other two pass one group and any nb in [1, 8]).
+static int beam_select_rows_run(recnet_handle* h, const float* logits, const float* cum, const int32_t* finished, const int64_t* hist,
+                                int nb, int rows, int V, int Tm, int t, int beam_width, bool diverse, int n_groups, float diversity_penalty,
+                                int no_repeat_ngram, int min_length, const int32_t* banned, int n_banned, float* vals_out, int32_t* idx_out,
+                                void* stream) {
   REQUIRE_WS(h);
   int r = check_select_rows(logits, cum, finished, nb, rows, V, beam_width, vals_out, idx_out); if (r) return r;
-  r = check_beam_groups(beam_width, n_groups, diversity_penalty); if (r) return r;
-  if (nb != 1 && nb != beam_width) return fail(RECNET_EINVAL, "nb must be 1 or beam_width");
+  if (diverse) {
+    r = check_beam_groups(beam_width, n_groups, diversity_penalty); if (r) return r;
+    if (nb != 1 && nb != beam_width) return fail(RECNET_EINVAL, "nb must be 1 or beam_width");
+  }
   if (Tm < 1 || t < 0 || t >= Tm) return fail(RECNET_EINVAL, "Tm must be positive and t in [0, Tm)");
   BeamBans bans;
   r = check_beam_bans(no_repeat_ngram, min_length, banned, n_banned, beam_width, V, Tm, t, &bans); if (r) return r;
@@ -543,6 +495,27 @@ int recnet_beam_select_rows_diverse(recnet_handle* h, const float* logits, const
                      diversity_penalty);
   LAUNCH_OK();
   return RECNET_OK;
+}
+
+// (all constraints off and a step inside a history of one: the unconstrained kernel, as recnet_beam_search_nbest forwards below)
+int recnet_beam_select_rows(recnet_handle* h, const float* logits, const float* cum, const int32_t* finished, int32_t nb,
+                            int32_t rows, int32_t V, int32_t beam_width, float* vals_out, int32_t* idx_out, void* stream) {
+  return beam_select_rows_run(h, logits, cum, finished, nullptr, nb, rows, V, 1, 0, beam_width, false, 1, 0.f, 0, 0, nullptr, 0, vals_out,
+                              idx_out, stream);
+}
+int recnet_beam_select_rows_constrained(recnet_handle* h, const float* logits, const float* cum, const int32_t* finished,
+                                        const int64_t* hist, int32_t nb, int32_t rows, int32_t V, int32_t Tm, int32_t t,
+                                        int32_t beam_width, int32_t no_repeat_ngram, int32_t min_length, const int32_t* banned,
+                                        int32_t n_banned, float* vals_out, int32_t* idx_out, void* stream) {
+  return beam_select_rows_run(h, logits, cum, finished, hist, nb, rows, V, Tm, t, beam_width, false, 1, 0.f, no_repeat_ngram, min_length,
+                              banned, n_banned, vals_out, idx_out, stream);
+}
+int recnet_beam_select_rows_diverse(recnet_handle* h, const float* logits, const float* cum, const int32_t* finished,
+                                    const int64_t* hist, int32_t nb, int32_t rows, int32_t V, int32_t Tm, int32_t t, int32_t beam_width,
+                                    int32_t n_groups, float diversity_penalty, int32_t no_repeat_ngram, int32_t min_length,
+                                    const int32_t* banned, int32_t n_banned, float* vals_out, int32_t* idx_out, void* stream) {
+  return beam_select_rows_run(h, logits, cum, finished, hist, nb, rows, V, Tm, t, beam_width, true, n_groups, diversity_penalty,
+                              no_repeat_ngram, min_length, banned, n_banned, vals_out, idx_out, stream);
 }
 
 // The loop of the N-best searches on checked arguments.  group_out (may be null): the group of each returned rank.
@@ -570,20 +543,6 @@ static void beam_search_nbest_run(recnet_handle* h, const float* enc, int bw, fl
     hipLaunchKernelGGL(beam_group_kernel, dim3(cdiv(bw * B, 256)), dim3(256), 0, st, (const int32_t*)h->bs_order, bw / n_groups, bw * B, group_out);
 }
 
-int recnet_beam_search_nbest_constrained(recnet_handle* h, const float* enc, int32_t beam_width, float length_alpha,
-                                         int32_t no_repeat_ngram, int32_t min_length, const int32_t* banned, int32_t n_banned,
-                                         int64_t* tokens_out, float* cum_out, int32_t* len_out, float* score_out, int32_t* n_steps_out,
-                                         void* stream) {
-  int r = search_check(h, enc && tokens_out && cum_out && len_out && score_out && n_steps_out); if (r) return r;
-  r = check_beam(beam_width, h->V, length_alpha); if (r) return r;
-  BeamBans bans;
-  r = check_beam_bans(no_repeat_ngram, min_length, banned, n_banned, beam_width, h->V, h->Tm, h->Tm - 1, &bans); if (r) return r;
-  beam_search_nbest_run(h, enc, beam_width, length_alpha, bans, 1, 0.f, tokens_out, cum_out, len_out, score_out, nullptr, n_steps_out,
-                        (hipStream_t)stream);
-  LAUNCH_OK();
-  return RECNET_OK;
-}
-
 int recnet_beam_search_nbest_diverse(recnet_handle* h, const float* enc, int32_t beam_width, float length_alpha, int32_t n_groups,
                                      float diversity_penalty, int32_t no_repeat_ngram, int32_t min_length, const int32_t* banned,
                                      int32_t n_banned, int64_t* tokens_out, float* cum_out, int32_t* len_out, float* score_out,
@@ -597,6 +556,15 @@ int recnet_beam_search_nbest_diverse(recnet_handle* h, const float* enc, int32_t
                         group_out, n_steps_out, (hipStream_t)stream);
   LAUNCH_OK();
   return RECNET_OK;
+}
+
+// (one group, which every width passes, and no group output: the search as it was)
+int recnet_beam_search_nbest_constrained(recnet_handle* h, const float* enc, int32_t beam_width, float length_alpha,
+                                         int32_t no_repeat_ngram, int32_t min_length, const int32_t* banned, int32_t n_banned,
+                                         int64_t* tokens_out, float* cum_out, int32_t* len_out, float* score_out, int32_t* n_steps_out,
+                                         void* stream) {
+  return recnet_beam_search_nbest_diverse(h, enc, beam_width, length_alpha, 1, 0.f, no_repeat_ngram, min_length, banned, n_banned, tokens_out,
+                                          cum_out, len_out, score_out, nullptr, n_steps_out, stream);
 }
 
 int recnet_beam_search_nbest(recnet_handle* h, const float* enc, int32_t beam_width, float length_alpha, int64_t* tokens_out,

@@ -402,6 +402,90 @@ template <bool CONSTRAINED> struct BeamSelArgsOf { typedef BeamSelArgs type; };
 template <> struct BeamSelArgsOf<true> { typedef BeamSelCArgs type; };
 // dynamic LDS of the constrained form: 8 list lengths, then per hypothesis a ban list of at most t + 17 ids
 __host__ __device__ __forceinline__ int bs_ban_stride(int t) { return t + 17; }
+// The text that beam_select_kernel and beam_select_groups_kernel share, each piece written once: the bit-for-bit promises between the
+// two (and with logprob_rows_kernel) rest on it being ONE text.  Statements on the kernels' own names (p, r, tid, V, nb, S, bs_ban, sf,
+// s_mx, s_ls, wc, lane, wave, lc and the walk's nban, ban, v) — macros like SR_EQUAL_CUT, not functions: the constrained instantiations
+// sit at 104-106 SGPRs, and a function that takes the argument struct (by reference or by value) moves the loads of the 16 banned ids
+// and makes the compiler save scalars into vector lanes; the textual form compiles to the code the kernels
+// had.  What the phases do and why is told at beam_select_kernel.
+// Phase (0), constrained form only: one wave per live hypothesis writes its ban list into LDS; sets S.
+#define BS_BAN_LISTS                                                                                                       \
+  {                                                                                                                        \
+    S = bs_ban_stride(p.t);                                                                                                \
+    const int ln = tid & 63, t = p.t, n = p.ngram;                                                                         \
+    const int ng = n >= 1 && t >= n - 1 ? t - n + 1 : 0;                                                                   \
+    const int used = ng + p.n_banned + (t < p.min_len ? 1 : 0);                 /* <= t + 17 */                            \
+    for (int i = tid >> 6; i < nb; i += 4) {                                                                               \
+      const bool live = p.fin[i * p.rows + r] == 0;                                                                        \
+      int cnt = 0;                                                                                                         \
+      for (int c = 0; c < used; c += 64) {                                      /* (uniform over the wave) */              \
+        const int j = c + ln;                                                                                              \
+        int id = -1;                                                                                                       \
+        if (live && j < ng) {                                                   /* (ng > 0 only with ngram >= 1: hist is not null) */ \
+          const int64_t* hs = p.hist + ((size_t)i * p.rows + r) * p.Tm;                                                    \
+          bool same = true;                                                                                                \
+          for (int k = 0; k + 1 < n; ++k) same &= hs[j + k] == hs[t - n + 1 + k];                                          \
+          const int64_t w = hs[j + n - 1];                                                                                 \
+          if (same && w >= 0 && w < V) id = (int)w;                                                                        \
+        } else if (live && j < used) {                                                                                     \
+          const int s = j - ng;                                                                                            \
+          id = 2;                                                               /* behind the static bans: <EOS> while t < min_len */ \
+          _Pragma("unroll")                                                                                                \
+          for (int k = 0; k < 16; ++k)                                                                                     \
+            if (s == k && k < p.n_banned) id = p.banned[k];                                                                \
+        }                                                                                                                  \
+        const unsigned long long m = __ballot(id >= 0);                                                                    \
+        if (id >= 0) bs_ban[8 + i * S + cnt + __popcll(m & ((1ull << ln) - 1ull))] = id;                                   \
+        cnt += __popcll(m);                                                                                                \
+      }                                                                                                                    \
+      if (ln == 0) bs_ban[i] = cnt;                                                                                        \
+    }                                                                                                                      \
+  }
+// Phase (1): per live hypothesis the maximum and log sum exp(x - max) of its row into s_mx / s_ls, logprob_rows_kernel's formulas and
+// summation order.  The caller's next barrier publishes them (and the ban lists).
+#define BS_ROW_STATS                                                                                                       \
+  for (int i = 0; i < nb; ++i) {                                                                                           \
+    if (p.fin[i * p.rows + r]) continue;                               /* (uniform over the workgroup) */                  \
+    const float* x = p.x + ((size_t)i * p.rows + r) * V;                                                                   \
+    float mx = -INFINITY, sum = 0.f;                                                                                       \
+    for (int v = tid; v < V; v += 256) mx = fmaxf(mx, x[v]);                                                               \
+    mx = block_max256(mx, sf);                                                                                             \
+    for (int v = tid; v < V; v += 256) sum += rn_exp(x[v] - mx);                                                           \
+    sum = block_sum256(sum, sf);                                                                                           \
+    if (tid == 0) { s_mx[i] = mx; s_ls[i] = logf(sum); }                                                                   \
+  }
+// Phase (2), once per hypothesis before the walk: declares `mine`, the banned id this thread can meet (v = tid (mod 256)), and `many`
+// (it has two or more different ones), from the list ban[0 .. nban).
+#define BS_OWN_BAN                                                                                                         \
+  int mine = -1; bool many = false;                                                                                        \
+  if constexpr (CONSTRAINED) {                                                                                             \
+    for (int j = 0; j < nban; ++j) {                                                                                       \
+      const int id = ban[j];                                                                                               \
+      if ((id & 255) == tid) { many |= mine >= 0 && mine != id; mine = id; }                                               \
+    }                                                                                                                      \
+  }
+// Phase (2), behind the compare that guards an insertion: declares `offered`, whether candidate v is not banned.
+#define BS_OFFERED                                                                                                         \
+  bool offered = true;                                                                                                     \
+  if constexpr (CONSTRAINED) {                                                                                             \
+    offered = v != mine;                                                                                                   \
+    if (many)                                                          /* (two banned ids 256 apart or more: rare) */      \
+      for (int j = 0; j < nban; ++j) offered &= ban[j] != v;                                                               \
+  }
+// Phase (3), round K: declares `e`, the largest list head lc[0] of the workgroup (0: no candidate left), the same word in every thread:
+// a butterfly over the wave, then the four wave maxima through wc[K & 1] (two buffers: one barrier per round).
+#define BS_ARGMAX_ROUND(K)                                                                                                 \
+  unsigned long long e = lc[0];                                                                                            \
+  _Pragma("unroll")                                                                                                        \
+  for (int o = 32; o > 0; o >>= 1) {                                                                                       \
+    const unsigned long long d = __shfl_xor(e, o);                                                                         \
+    e = d > e ? d : e;                                                                                                     \
+  }                                                                                                                        \
+  if (lane == 0) wc[(K) & 1][wave] = e;                                                                                    \
+  __syncthreads();                                                                                                         \
+  e = wc[(K) & 1][0];                                                                                                      \
+  _Pragma("unroll")                                                                                                        \
+  for (int w = 1; w < 4; ++w) e = wc[(K) & 1][w] > e ? wc[(K) & 1][w] : e;
 // One workgroup per caption.  (1) Per hypothesis the maximum and sum exp(x - max) of its row, the formulas and summation order of
 // logprob_rows_kernel at temperature 1, so that the two agree on a token to the bit.  (2) Every thread walks its strided share of
 // the nb * V candidates cum_i + ((x_v - max_i) - log sum_i) in ascending flat index and keeps its best BW in registers (the insertion
@@ -425,47 +509,8 @@ void beam_select_kernel(const typename BeamSelArgsOf<CONSTRAINED>::type p) {
   extern __shared__ __attribute__((aligned(16))) int bs_ban[];
   const int r = blockIdx.x, tid = threadIdx.x, V = p.V, nb = p.nb;
   int S = 0;
-  if constexpr (CONSTRAINED) {
-    S = bs_ban_stride(p.t);
-    const int ln = tid & 63, t = p.t, n = p.ngram;
-    const int ng = n >= 1 && t >= n - 1 ? t - n + 1 : 0;
-    const int used = ng + p.n_banned + (t < p.min_len ? 1 : 0);                 // <= t + 17
-    for (int i = tid >> 6; i < nb; i += 4) {
-      const bool live = p.fin[i * p.rows + r] == 0;
-      int cnt = 0;
-      for (int c = 0; c < used; c += 64) {                                      // (uniform over the wave)
-        const int j = c + ln;
-        int id = -1;
-        if (live && j < ng) {                                                   // (ng > 0 only with ngram >= 1: hist is not null)
-          const int64_t* hs = p.hist + ((size_t)i * p.rows + r) * p.Tm;
-          bool same = true;
-          for (int k = 0; k + 1 < n; ++k) same &= hs[j + k] == hs[t - n + 1 + k];
-          const int64_t w = hs[j + n - 1];
-          if (same && w >= 0 && w < V) id = (int)w;
-        } else if (live && j < used) {
-          const int s = j - ng;
-          id = 2;                                                               // behind the static bans: <EOS> while t < min_len
-#pragma unroll
-          for (int k = 0; k < 16; ++k)
-            if (s == k && k < p.n_banned) id = p.banned[k];
-        }
-        const unsigned long long m = __ballot(id >= 0);
-        if (id >= 0) bs_ban[8 + i * S + cnt + __popcll(m & ((1ull << ln) - 1ull))] = id;
-        cnt += __popcll(m);
-      }
-      if (ln == 0) bs_ban[i] = cnt;
-    }
-  }
-  for (int i = 0; i < nb; ++i) {
-    if (p.fin[i * p.rows + r]) continue;                               // (uniform over the workgroup)
-    const float* x = p.x + ((size_t)i * p.rows + r) * V;
-    float mx = -INFINITY, sum = 0.f;
-    for (int v = tid; v < V; v += 256) mx = fmaxf(mx, x[v]);
-    mx = block_max256(mx, sf);
-    for (int v = tid; v < V; v += 256) sum += rn_exp(x[v] - mx);
-    sum = block_sum256(sum, sf);
-    if (tid == 0) { s_mx[i] = mx; s_ls[i] = logf(sum); }
-  }
+  if constexpr (CONSTRAINED) BS_BAN_LISTS
+  BS_ROW_STATS
   __syncthreads();
   unsigned long long lc[BW];
 #pragma unroll
@@ -478,23 +523,12 @@ void beam_select_kernel(const typename BeamSelArgsOf<CONSTRAINED>::type p) {
     const int n = fin ? (V < BW + 1 ? V : BW + 1) : V;
     const int nban = CONSTRAINED ? bs_ban[i] : 0;                      // (0 for a finished hypothesis)
     const int* ban = bs_ban + 8 + i * S;
-    int mine = -1; bool many = false;                                  // the banned id this thread can meet: v = tid (mod 256)
-    if constexpr (CONSTRAINED) {
-      for (int j = 0; j < nban; ++j) {
-        const int id = ban[j];
-        if ((id & 255) == tid) { many |= mine >= 0 && mine != id; mine = id; }
-      }
-    }
+    BS_OWN_BAN
     for (int v = tid; v < n; v += 256) {
       const float y = fin ? (v == 0 ? c : -INFINITY) : c + ((x[v] - mx) - ls);
       unsigned long long e = bs_pack(y, i * V + v);
       if (e > lc[BW - 1]) {
-        bool offered = true;
-        if constexpr (CONSTRAINED) {
-          offered = v != mine;
-          if (many)                                                    // (two banned ids 256 apart or more: rare)
-            for (int j = 0; j < nban; ++j) offered &= ban[j] != v;
-        }
+        BS_OFFERED
         if (offered) {
 #pragma unroll
           for (int k = 0; k < BW; ++k)
@@ -505,17 +539,7 @@ void beam_select_kernel(const typename BeamSelArgsOf<CONSTRAINED>::type p) {
   }
   const int lane = tid & 63, wave = tid >> 6;
   for (int k = 0; k < BW; ++k) {
-    unsigned long long e = lc[0];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const unsigned long long d = __shfl_xor(e, o);
-      e = d > e ? d : e;
-    }
-    if (lane == 0) wc[k & 1][wave] = e;
-    __syncthreads();
-    e = wc[k & 1][0];
-#pragma unroll
-    for (int w = 1; w < 4; ++w) e = wc[k & 1][w] > e ? wc[k & 1][w] : e;
+    BS_ARGMAX_ROUND(k)
     if (e != 0ull && lc[0] == e) {           // (candidates are distinct: their indices are)
 #pragma unroll
       for (int q = 0; q + 1 < BW; ++q) lc[q] = lc[q + 1];
@@ -550,47 +574,8 @@ void beam_select_groups_kernel(const typename BeamSelArgsOf<CONSTRAINED>::type p
   extern __shared__ __attribute__((aligned(16))) int bs_ban[];
   const int r = blockIdx.x, tid = threadIdx.x, V = p.V, nb = p.nb, BW = q.G * W;
   int S = 0;
-  if constexpr (CONSTRAINED) {                                         // (0) the ban lists, as in beam_select_kernel
-    S = bs_ban_stride(p.t);
-    const int ln = tid & 63, t = p.t, n = p.ngram;
-    const int ng = n >= 1 && t >= n - 1 ? t - n + 1 : 0;
-    const int used = ng + p.n_banned + (t < p.min_len ? 1 : 0);                 // <= t + 17
-    for (int i = tid >> 6; i < nb; i += 4) {
-      const bool live = p.fin[i * p.rows + r] == 0;
-      int cnt = 0;
-      for (int c = 0; c < used; c += 64) {                                      // (uniform over the wave)
-        const int j = c + ln;
-        int id = -1;
-        if (live && j < ng) {
-          const int64_t* hs = p.hist + ((size_t)i * p.rows + r) * p.Tm;
-          bool same = true;
-          for (int k = 0; k + 1 < n; ++k) same &= hs[j + k] == hs[t - n + 1 + k];
-          const int64_t w = hs[j + n - 1];
-          if (same && w >= 0 && w < V) id = (int)w;
-        } else if (live && j < used) {
-          const int s = j - ng;
-          id = 2;
-#pragma unroll
-          for (int k = 0; k < 16; ++k)
-            if (s == k && k < p.n_banned) id = p.banned[k];
-        }
-        const unsigned long long m = __ballot(id >= 0);
-        if (id >= 0) bs_ban[8 + i * S + cnt + __popcll(m & ((1ull << ln) - 1ull))] = id;
-        cnt += __popcll(m);
-      }
-      if (ln == 0) bs_ban[i] = cnt;
-    }
-  }
-  for (int i = 0; i < nb; ++i) {                                       // (1) row maximum and sum, logprob_rows_kernel's order
-    if (p.fin[i * p.rows + r]) continue;                               // (uniform over the workgroup)
-    const float* x = p.x + ((size_t)i * p.rows + r) * V;
-    float mx = -INFINITY, sum = 0.f;
-    for (int v = tid; v < V; v += 256) mx = fmaxf(mx, x[v]);
-    mx = block_max256(mx, sf);
-    for (int v = tid; v < V; v += 256) sum += rn_exp(x[v] - mx);
-    sum = block_sum256(sum, sf);
-    if (tid == 0) { s_mx[i] = mx; s_ls[i] = logf(sum); }
-  }
+  if constexpr (CONSTRAINED) BS_BAN_LISTS                              // (0)
+  BS_ROW_STATS                                                         // (1)
   if (tid == 0) s_ntok = 0;
   __syncthreads();
   const int lane = tid & 63, wave = tid >> 6;
@@ -615,23 +600,12 @@ void beam_select_groups_kernel(const typename BeamSelArgsOf<CONSTRAINED>::type p
       const int n = fin ? (V < W + 1 ? V : W + 1) : V;
       const int nban = CONSTRAINED ? bs_ban[i] : 0;                    // (0 for a finished hypothesis)
       const int* ban = bs_ban + 8 + i * S;
-      int mine = -1; bool many = false;                                // the banned id this thread can meet: v = tid (mod 256)
-      if constexpr (CONSTRAINED) {
-        for (int j = 0; j < nban; ++j) {
-          const int id = ban[j];
-          if ((id & 255) == tid) { many |= mine >= 0 && mine != id; mine = id; }
-        }
-      }
+      BS_OWN_BAN
       for (int v = tid; v < n; v += 256) {
         const float y = fin ? (v == 0 ? c : -INFINITY) : c + ((x[v] - mx) - ls);
         unsigned long long e = bs_pack(y, i * V + v);
         if (e > lc[W - 1]) {
-          bool offered = true;
-          if constexpr (CONSTRAINED) {
-            offered = v != mine;
-            if (many)                                                  // (two banned ids 256 apart or more: rare)
-              for (int j = 0; j < nban; ++j) offered &= ban[j] != v;
-          }
+          BS_OFFERED
           if (offered) {
             int cnt = v == ptok ? pcnt : 0;
             if (pmany) {                                               // (two chosen tokens 256 apart or more: rare)
@@ -647,17 +621,7 @@ void beam_select_groups_kernel(const typename BeamSelArgsOf<CONSTRAINED>::type p
       }
     }
     for (int k = 0; k < W; ++k) {                                      // (3)
-      unsigned long long e = lc[0];
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long d = __shfl_xor(e, o);
-        e = d > e ? d : e;
-      }
-      if (lane == 0) wc[k & 1][wave] = e;
-      __syncthreads();
-      e = wc[k & 1][0];
-#pragma unroll
-      for (int w = 1; w < 4; ++w) e = wc[k & 1][w] > e ? wc[k & 1][w] : e;
+      BS_ARGMAX_ROUND(k)
       const size_t o = (size_t)r * BW + g * W + k;
       if (e != 0ull && lc[0] == e) {           // (candidates are distinct: their indices are) the one thread that owned the winner
         const int j = bs_index(e), i = j / V, v = j - i * V;

@@ -197,193 +197,190 @@ std::tuple<at::Tensor, at::Tensor> beam_search(int64_t h, const at::Tensor& enc,
   ok(recnet_beam_search(H(h), enc.data_ptr<float>(), (int32_t)beam_width, best.data_ptr<int64_t>(), n.data_ptr<int32_t>(), stream()), "beam_search");
   return {best, n};
 }
-std::tuple<at::Tensor, at::Tensor, at::Tensor> sample_search(int64_t h, const at::Tensor& enc, double temperature, int64_t top_k, int64_t seed) {
+// ---- sampling: one implementation per shape of call; top_p null: the form without a nucleus, which launches the kernels it always
+// had (n_allowed comes back undefined), else the nucleus form: one more cut and one more output, the size of the set every token
+// was drawn from
+static std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> sample_search_impl(int64_t h, const at::Tensor& enc, double temperature,
+                                                                                     int64_t top_k, const double* top_p, int64_t seed) {
   chk_enc(h, enc);
-  auto toks = at::zeros({recnet_dim(H(h), RECNET_DIM_TM), enc.size(0)}, enc.options().dtype(at::kLong));
-  auto lps = at::zeros({recnet_dim(H(h), RECNET_DIM_TM), enc.size(0)}, enc.options());
+  const int64_t Tm = recnet_dim(H(h), RECNET_DIM_TM), B = enc.size(0);
+  auto toks = at::zeros({Tm, B}, enc.options().dtype(at::kLong));
+  auto lps = at::zeros({Tm, B}, enc.options());
+  at::Tensor na;
+  if (top_p) na = at::zeros({Tm, B}, enc.options().dtype(at::kInt));
   auto n = at::zeros({1}, enc.options().dtype(at::kInt));
   TORCH_CHECK(top_k >= INT32_MIN && top_k <= INT32_MAX, "recnet: top_k out of range");
-  ok(recnet_sample_search(H(h), enc.data_ptr<float>(), (float)temperature, (int32_t)top_k, (uint32_t)seed, toks.data_ptr<int64_t>(),
-                          lps.data_ptr<float>(), n.data_ptr<int32_t>(), stream()), "sample_search");
+  if (top_p)
+    ok(recnet_sample_search_nucleus(H(h), enc.data_ptr<float>(), (float)temperature, (int32_t)top_k, (float)*top_p, (uint32_t)seed,
+                                    toks.data_ptr<int64_t>(), lps.data_ptr<float>(), na.data_ptr<int32_t>(), n.data_ptr<int32_t>(), stream()), "sample_search_nucleus");
+  else
+    ok(recnet_sample_search(H(h), enc.data_ptr<float>(), (float)temperature, (int32_t)top_k, (uint32_t)seed, toks.data_ptr<int64_t>(),
+                            lps.data_ptr<float>(), n.data_ptr<int32_t>(), stream()), "sample_search");
+  return {toks, lps, na, n};
+}
+static std::tuple<at::Tensor, at::Tensor, at::Tensor> sample_rows_impl(int64_t h, const at::Tensor& logits, double temperature, int64_t top_k,
+                                                                       const double* top_p, int64_t seed, int64_t t) {
+  chk(logits, at::kFloat, "logits");
+  TORCH_CHECK(logits.dim() == 2 && logits.size(0) >= 1 && logits.size(1) >= 1 && logits.size(0) <= INT32_MAX && logits.size(1) <= INT32_MAX,
+              "recnet: logits must be [rows, V], got ", logits.sizes());
+  TORCH_CHECK(top_k >= INT32_MIN && top_k <= INT32_MAX && t >= 0 && t <= INT32_MAX, "recnet: top_k / t out of range");
+  const int32_t rows = (int32_t)logits.size(0), V = (int32_t)logits.size(1);
+  auto toks = at::empty({rows}, logits.options().dtype(at::kLong));
+  auto lps = at::empty({rows}, logits.options());
+  at::Tensor na;
+  if (top_p) na = at::empty({rows}, logits.options().dtype(at::kInt));
+  if (top_p)
+    ok(recnet_sample_rows_nucleus(H(h), logits.data_ptr<float>(), rows, V, (float)temperature, (int32_t)top_k, (float)*top_p, (uint32_t)seed,
+                                  (int32_t)t, toks.data_ptr<int64_t>(), lps.data_ptr<float>(), na.data_ptr<int32_t>(), stream()), "sample_rows_nucleus");
+  else
+    ok(recnet_sample_rows(H(h), logits.data_ptr<float>(), rows, V, (float)temperature, (int32_t)top_k, (uint32_t)seed, (int32_t)t,
+                          toks.data_ptr<int64_t>(), lps.data_ptr<float>(), stream()), "sample_rows");
+  return {toks, lps, na};
+}
+std::tuple<at::Tensor, at::Tensor, at::Tensor> sample_search(int64_t h, const at::Tensor& enc, double temperature, int64_t top_k, int64_t seed) {
+  auto [toks, lps, na, n] = sample_search_impl(h, enc, temperature, top_k, nullptr, seed);
   return {toks, lps, n};
 }
 std::tuple<at::Tensor, at::Tensor> sample_rows(int64_t h, const at::Tensor& logits, double temperature, int64_t top_k, int64_t seed, int64_t t) {
-  chk(logits, at::kFloat, "logits");
-  TORCH_CHECK(logits.dim() == 2 && logits.size(0) >= 1 && logits.size(1) >= 1 && logits.size(0) <= INT32_MAX && logits.size(1) <= INT32_MAX,
-              "recnet: logits must be [rows, V], got ", logits.sizes());
-  TORCH_CHECK(top_k >= INT32_MIN && top_k <= INT32_MAX && t >= 0 && t <= INT32_MAX, "recnet: top_k / t out of range");
-  auto toks = at::empty({logits.size(0)}, logits.options().dtype(at::kLong));
-  auto lps = at::empty({logits.size(0)}, logits.options());
-  ok(recnet_sample_rows(H(h), logits.data_ptr<float>(), (int32_t)logits.size(0), (int32_t)logits.size(1), (float)temperature, (int32_t)top_k,
-                        (uint32_t)seed, (int32_t)t, toks.data_ptr<int64_t>(), lps.data_ptr<float>(), stream()), "sample_rows");
+  auto [toks, lps, na] = sample_rows_impl(h, logits, temperature, top_k, nullptr, seed, t);
   return {toks, lps};
 }
-// the nucleus forms: one more cut (top_p) and one more output, the size of the set every token was drawn from
 std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> sample_search_nucleus(int64_t h, const at::Tensor& enc, double temperature, int64_t top_k,
                                                                                  double top_p, int64_t seed) {
-  chk_enc(h, enc);
-  auto toks = at::zeros({recnet_dim(H(h), RECNET_DIM_TM), enc.size(0)}, enc.options().dtype(at::kLong));
-  auto lps = at::zeros({recnet_dim(H(h), RECNET_DIM_TM), enc.size(0)}, enc.options());
-  auto na = at::zeros({recnet_dim(H(h), RECNET_DIM_TM), enc.size(0)}, enc.options().dtype(at::kInt));
-  auto n = at::zeros({1}, enc.options().dtype(at::kInt));
-  TORCH_CHECK(top_k >= INT32_MIN && top_k <= INT32_MAX, "recnet: top_k out of range");
-  ok(recnet_sample_search_nucleus(H(h), enc.data_ptr<float>(), (float)temperature, (int32_t)top_k, (float)top_p, (uint32_t)seed,
-                                  toks.data_ptr<int64_t>(), lps.data_ptr<float>(), na.data_ptr<int32_t>(), n.data_ptr<int32_t>(), stream()),
-     "sample_search_nucleus");
-  return {toks, lps, na, n};
+  return sample_search_impl(h, enc, temperature, top_k, &top_p, seed);
 }
 std::tuple<at::Tensor, at::Tensor, at::Tensor> sample_rows_nucleus(int64_t h, const at::Tensor& logits, double temperature, int64_t top_k,
                                                                    double top_p, int64_t seed, int64_t t) {
-  chk(logits, at::kFloat, "logits");
-  TORCH_CHECK(logits.dim() == 2 && logits.size(0) >= 1 && logits.size(1) >= 1 && logits.size(0) <= INT32_MAX && logits.size(1) <= INT32_MAX,
-              "recnet: logits must be [rows, V], got ", logits.sizes());
-  TORCH_CHECK(top_k >= INT32_MIN && top_k <= INT32_MAX && t >= 0 && t <= INT32_MAX, "recnet: top_k / t out of range");
-  auto toks = at::empty({logits.size(0)}, logits.options().dtype(at::kLong));
-  auto lps = at::empty({logits.size(0)}, logits.options());
-  auto na = at::empty({logits.size(0)}, logits.options().dtype(at::kInt));
-  ok(recnet_sample_rows_nucleus(H(h), logits.data_ptr<float>(), (int32_t)logits.size(0), (int32_t)logits.size(1), (float)temperature,
-                                (int32_t)top_k, (float)top_p, (uint32_t)seed, (int32_t)t, toks.data_ptr<int64_t>(), lps.data_ptr<float>(),
-                                na.data_ptr<int32_t>(), stream()), "sample_rows_nucleus");
-  return {toks, lps, na};
+  return sample_rows_impl(h, logits, temperature, top_k, &top_p, seed, t);
 }
-// the checks of the selection inputs: logits [nb, rows, V], cum [nb, rows] float, finished [nb, rows] int32, the width
-static void chk_select(const at::Tensor& logits, const at::Tensor& cum, const at::Tensor& finished, int64_t beam_width) {
-  chk(logits, at::kFloat, "logits"); chk(cum, at::kFloat, "cum"); chk(finished, at::kInt, "finished");
-  TORCH_CHECK(logits.dim() == 3 && logits.size(0) >= 1 && logits.size(1) >= 1 && logits.size(2) >= 1 && logits.size(1) <= INT32_MAX &&
-              logits.size(2) <= INT32_MAX && logits.size(0) <= 8, "recnet: logits must be [nb <= 8, rows, V], got ", logits.sizes());
-  shape(cum, {logits.size(0), logits.size(1)}, "cum"); shape(finished, {logits.size(0), logits.size(1)}, "finished");
-  TORCH_CHECK(beam_width >= 1 && beam_width <= 8 && beam_width <= logits.size(2), "recnet: beam_width must be in [1, min(8, V)], got ", beam_width);
-}
-// logits [nb, rows, V], cum [nb, rows] float, finished [nb, rows] int32 -> vals [rows, beam_width], idx [rows, beam_width] int32
-std::tuple<at::Tensor, at::Tensor> beam_select_rows(int64_t h, const at::Tensor& logits, const at::Tensor& cum, const at::Tensor& finished,
-                                                    int64_t beam_width) {
-  chk_select(logits, cum, finished, beam_width);
-  auto vals = at::empty({logits.size(1), beam_width}, logits.options());
-  auto idx = at::empty({logits.size(1), beam_width}, logits.options().dtype(at::kInt));
-  ok(recnet_beam_select_rows(H(h), logits.data_ptr<float>(), cum.data_ptr<float>(), finished.data_ptr<int32_t>(), (int32_t)logits.size(0),
-                             (int32_t)logits.size(1), (int32_t)logits.size(2), (int32_t)beam_width, vals.data_ptr<float>(),
-                             idx.data_ptr<int32_t>(), stream()), "beam_select_rows");
-  return {vals, idx};
-}
-// tokens [beam_width, Tm, B] rank-major, cum / score [beam_width, B] float, len [beam_width, B] int32, n_steps [1] int32
-// (the width is checked here before the outputs are allocated and zeroed; length_alpha by the library, behind those fills)
-using NbestOut = std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor>;
-static NbestOut nbest_outputs(int64_t h, const at::Tensor& enc, int64_t beam_width) {
-  const int64_t B = enc.size(0);
-  auto toks = at::zeros({beam_width, recnet_dim(H(h), RECNET_DIM_TM), B}, enc.options().dtype(at::kLong));
-  auto cum = at::zeros({beam_width, B}, enc.options()), score = at::zeros({beam_width, B}, enc.options());
-  auto len = at::zeros({beam_width, B}, enc.options().dtype(at::kInt));
-  auto n = at::zeros({1}, enc.options().dtype(at::kInt));
-  return {toks, cum, len, score, n};
-}
-NbestOut beam_search_nbest(int64_t h, const at::Tensor& enc, int64_t beam_width, double length_alpha) {
-  chk_enc(h, enc);
-  TORCH_CHECK(beam_width >= 1 && beam_width <= 8 && beam_width <= dim(h, RECNET_DIM_V), "recnet: beam_width must be in [1, min(8, V)], got ", beam_width);
-  auto [toks, cum, len, score, n] = nbest_outputs(h, enc, beam_width);
-  ok(recnet_beam_search_nbest(H(h), enc.data_ptr<float>(), (int32_t)beam_width, (float)length_alpha, toks.data_ptr<int64_t>(),
-                              cum.data_ptr<float>(), len.data_ptr<int32_t>(), score.data_ptr<float>(), n.data_ptr<int32_t>(), stream()),
-     "beam_search_nbest");
-  return {toks, cum, len, score, n};
-}
-// ---- the constrained forms: the ids of `banned` travel to the library as a host array
-static std::vector<int32_t> ban_ids(at::IntArrayRef banned) {
-  TORCH_CHECK(banned.size() <= 16, "recnet: at most 16 banned tokens, got ", banned.size());
+// ---- N-best beam search on log-probabilities, its constrained forms (section 12: no-repeat n-grams, a minimum
+// length, banned ids, which travel to the library as a host array) and its diverse forms (section 14: the constrained forms in
+// n_groups groups with a penalty between them).  One implementation of the selection and one of the search; bans / groups null: the
+// form without them, which makes the library call of its own name.
+struct Bans { int64_t no_repeat_ngram, min_length; at::IntArrayRef banned; };
+struct Groups { int64_t n; double penalty; };
+static std::vector<int32_t> ban_ids(const Bans* b) {
   std::vector<int32_t> ids;
-  for (const int64_t v : banned) {
+  if (!b) return ids;
+  TORCH_CHECK(b->no_repeat_ngram >= 0 && b->no_repeat_ngram <= INT32_MAX && b->min_length >= 0 && b->min_length <= INT32_MAX,
+              "recnet: no_repeat_ngram / min_length out of range");
+  TORCH_CHECK(b->banned.size() <= 16, "recnet: at most 16 banned tokens, got ", b->banned.size());
+  for (const int64_t v : b->banned) {
     TORCH_CHECK(v >= 0 && v <= INT32_MAX, "recnet: banned token out of range: ", v);
     ids.push_back((int32_t)v);
   }
   return ids;
 }
-static void chk_constraints(int64_t no_repeat_ngram, int64_t min_length) {
-  TORCH_CHECK(no_repeat_ngram >= 0 && no_repeat_ngram <= INT32_MAX && min_length >= 0 && min_length <= INT32_MAX,
-              "recnet: no_repeat_ngram / min_length out of range");
+static void chk_groups(int64_t beam_width, const Groups* g) {
+  if (!g) return;
+  TORCH_CHECK(g->n >= 1 && beam_width % g->n == 0, "recnet: n_groups must be at least 1 and divide beam_width, got ", g->n);
+  TORCH_CHECK(std::isfinite(g->penalty) && g->penalty >= 0.0, "recnet: diversity_penalty must be finite and >= 0, got ", g->penalty);
 }
-// hist [nb, rows, Tm] int64 of a selection on `logits`, checked: its pointer and Tm (undefined: null, and a Tm no step reaches)
-static const int64_t* hist_arg(const c10::optional<at::Tensor>& hist, const at::Tensor& logits, int64_t* Tm) {
-  *Tm = INT32_MAX;                   // (no hist: only min_length / the static bans can be on, and they read no history)
-  if (!hist.has_value() || !hist->defined()) return nullptr;
-  chk(*hist, at::kLong, "hist");
-  TORCH_CHECK(hist->dim() == 3 && hist->size(0) == logits.size(0) && hist->size(1) == logits.size(1) && hist->size(2) >= 1 &&
-              hist->size(2) <= INT32_MAX, "recnet: hist must be [nb, rows, Tm], got ", hist->sizes());
-  *Tm = hist->size(2);
-  return hist->data_ptr<int64_t>();
+// logits [nb, rows, V], cum [nb, rows] float, finished [nb, rows] int32 -> vals [rows, beam_width], idx [rows, beam_width] int32;
+// with bans: hist [nb, rows, Tm] int64 (undefined: allowed when no_repeat_ngram = 0: null, and a Tm no step reaches) and the step t
+static std::tuple<at::Tensor, at::Tensor> select_rows_impl(int64_t h, const at::Tensor& logits, const at::Tensor& cum, const at::Tensor& finished,
+                                                           int64_t beam_width, const c10::optional<at::Tensor>* hist, int64_t t,
+                                                           const Bans* b, const Groups* g) {
+  chk(logits, at::kFloat, "logits"); chk(cum, at::kFloat, "cum"); chk(finished, at::kInt, "finished");
+  TORCH_CHECK(logits.dim() == 3 && logits.size(0) >= 1 && logits.size(1) >= 1 && logits.size(2) >= 1 && logits.size(1) <= INT32_MAX &&
+              logits.size(2) <= INT32_MAX && logits.size(0) <= 8, "recnet: logits must be [nb <= 8, rows, V], got ", logits.sizes());
+  shape(cum, {logits.size(0), logits.size(1)}, "cum"); shape(finished, {logits.size(0), logits.size(1)}, "finished");
+  TORCH_CHECK(beam_width >= 1 && beam_width <= 8 && beam_width <= logits.size(2), "recnet: beam_width must be in [1, min(8, V)], got ", beam_width);
+  chk_groups(beam_width, g);
+  if (g) TORCH_CHECK(logits.size(0) == 1 || logits.size(0) == beam_width, "recnet: nb must be 1 or beam_width, got ", logits.size(0));
+  if (b) TORCH_CHECK(t >= 0 && t < INT32_MAX, "recnet: t out of range");
+  const auto ids = ban_ids(b);
+  int64_t Tm = INT32_MAX;            // (no hist: only min_length / the static bans can be on, and they read no history)
+  const int64_t* hp = nullptr;
+  if (b && hist->has_value() && (*hist)->defined()) {
+    const at::Tensor& hs = **hist;
+    chk(hs, at::kLong, "hist");
+    TORCH_CHECK(hs.dim() == 3 && hs.size(0) == logits.size(0) && hs.size(1) == logits.size(1) && hs.size(2) >= 1 && hs.size(2) <= INT32_MAX,
+                "recnet: hist must be [nb, rows, Tm], got ", hs.sizes());
+    Tm = hs.size(2); hp = hs.data_ptr<int64_t>();
+  }
+  auto vals = at::empty({logits.size(1), beam_width}, logits.options());
+  auto idx = at::empty({logits.size(1), beam_width}, logits.options().dtype(at::kInt));
+  const float* x = logits.data_ptr<float>(); const float* c = cum.data_ptr<float>(); const int32_t* f = finished.data_ptr<int32_t>();
+  const int32_t nb = (int32_t)logits.size(0), rows = (int32_t)logits.size(1), V = (int32_t)logits.size(2), bw = (int32_t)beam_width;
+  if (g)
+    ok(recnet_beam_select_rows_diverse(H(h), x, c, f, hp, nb, rows, V, (int32_t)Tm, (int32_t)t, bw, (int32_t)g->n, (float)g->penalty,
+                                       (int32_t)b->no_repeat_ngram, (int32_t)b->min_length, ids.data(), (int32_t)ids.size(),
+                                       vals.data_ptr<float>(), idx.data_ptr<int32_t>(), stream()), "beam_select_rows_diverse");
+  else if (b)
+    ok(recnet_beam_select_rows_constrained(H(h), x, c, f, hp, nb, rows, V, (int32_t)Tm, (int32_t)t, bw, (int32_t)b->no_repeat_ngram,
+                                           (int32_t)b->min_length, ids.data(), (int32_t)ids.size(), vals.data_ptr<float>(),
+                                           idx.data_ptr<int32_t>(), stream()), "beam_select_rows_constrained");
+  else
+    ok(recnet_beam_select_rows(H(h), x, c, f, nb, rows, V, bw, vals.data_ptr<float>(), idx.data_ptr<int32_t>(), stream()), "beam_select_rows");
+  return {vals, idx};
 }
-// beam_select_rows plus hist [nb, rows, Tm] int64 (undefined: allowed when no_repeat_ngram = 0) and the step t
+// tokens [beam_width, Tm, B] rank-major, cum / score [beam_width, B] float, len [beam_width, B] int32, n_steps [1] int32 and, with
+// groups, group [beam_width, B] int32, the group of each returned rank (undefined without)
+// (the width is checked here before the outputs are allocated and zeroed; length_alpha by the library, behind those fills)
+using NbestOut = std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor>;
+using NbestGroupOut = std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor>;
+static NbestGroupOut nbest_impl(int64_t h, const at::Tensor& enc, int64_t beam_width, double length_alpha, const Bans* b, const Groups* g) {
+  chk_enc(h, enc);
+  TORCH_CHECK(beam_width >= 1 && beam_width <= 8 && beam_width <= dim(h, RECNET_DIM_V), "recnet: beam_width must be in [1, min(8, V)], got ", beam_width);
+  chk_groups(beam_width, g);
+  const auto ids = ban_ids(b);
+  const int64_t B = enc.size(0);
+  auto toks = at::zeros({beam_width, recnet_dim(H(h), RECNET_DIM_TM), B}, enc.options().dtype(at::kLong));
+  auto cum = at::zeros({beam_width, B}, enc.options()), score = at::zeros({beam_width, B}, enc.options());
+  auto len = at::zeros({beam_width, B}, enc.options().dtype(at::kInt));
+  auto n = at::zeros({1}, enc.options().dtype(at::kInt));
+  at::Tensor group;
+  if (g) group = at::zeros({beam_width, B}, enc.options().dtype(at::kInt));
+  const float* e = enc.data_ptr<float>(); const int32_t bw = (int32_t)beam_width; const float la = (float)length_alpha;
+  int64_t* tp = toks.data_ptr<int64_t>(); float* cp = cum.data_ptr<float>(); int32_t* lp = len.data_ptr<int32_t>();
+  float* sp = score.data_ptr<float>(); int32_t* np = n.data_ptr<int32_t>();
+  if (g)
+    ok(recnet_beam_search_nbest_diverse(H(h), e, bw, la, (int32_t)g->n, (float)g->penalty, (int32_t)b->no_repeat_ngram, (int32_t)b->min_length,
+                                        ids.data(), (int32_t)ids.size(), tp, cp, lp, sp, group.data_ptr<int32_t>(), np, stream()), "beam_search_nbest_diverse");
+  else if (b)
+    ok(recnet_beam_search_nbest_constrained(H(h), e, bw, la, (int32_t)b->no_repeat_ngram, (int32_t)b->min_length, ids.data(), (int32_t)ids.size(),
+                                            tp, cp, lp, sp, np, stream()), "beam_search_nbest_constrained");
+  else
+    ok(recnet_beam_search_nbest(H(h), e, bw, la, tp, cp, lp, sp, np, stream()), "beam_search_nbest");
+  return {toks, cum, len, score, group, n};
+}
+static NbestOut without_group(const NbestGroupOut& o) {
+  return {std::get<0>(o), std::get<1>(o), std::get<2>(o), std::get<3>(o), std::get<5>(o)};
+}
+std::tuple<at::Tensor, at::Tensor> beam_select_rows(int64_t h, const at::Tensor& logits, const at::Tensor& cum, const at::Tensor& finished,
+                                                    int64_t beam_width) {
+  return select_rows_impl(h, logits, cum, finished, beam_width, nullptr, 0, nullptr, nullptr);
+}
 std::tuple<at::Tensor, at::Tensor> beam_select_rows_constrained(int64_t h, const at::Tensor& logits, const at::Tensor& cum,
                                                                 const at::Tensor& finished, const c10::optional<at::Tensor>& hist, int64_t t,
                                                                 int64_t beam_width, int64_t no_repeat_ngram, int64_t min_length,
                                                                 at::IntArrayRef banned) {
-  chk_select(logits, cum, finished, beam_width);
-  TORCH_CHECK(t >= 0 && t < INT32_MAX, "recnet: t out of range");
-  chk_constraints(no_repeat_ngram, min_length);
-  const auto ids = ban_ids(banned);
-  int64_t Tm;
-  const int64_t* hp = hist_arg(hist, logits, &Tm);
-  auto vals = at::empty({logits.size(1), beam_width}, logits.options());
-  auto idx = at::empty({logits.size(1), beam_width}, logits.options().dtype(at::kInt));
-  ok(recnet_beam_select_rows_constrained(H(h), logits.data_ptr<float>(), cum.data_ptr<float>(), finished.data_ptr<int32_t>(), hp,
-                                         (int32_t)logits.size(0), (int32_t)logits.size(1), (int32_t)logits.size(2), (int32_t)Tm, (int32_t)t,
-                                         (int32_t)beam_width, (int32_t)no_repeat_ngram, (int32_t)min_length, ids.data(), (int32_t)ids.size(),
-                                         vals.data_ptr<float>(), idx.data_ptr<int32_t>(), stream()), "beam_select_rows_constrained");
-  return {vals, idx};
-}
-NbestOut beam_search_nbest_constrained(int64_t h, const at::Tensor& enc, int64_t beam_width, double length_alpha, int64_t no_repeat_ngram,
-                                       int64_t min_length, at::IntArrayRef banned) {
-  chk_enc(h, enc);
-  TORCH_CHECK(beam_width >= 1 && beam_width <= 8 && beam_width <= dim(h, RECNET_DIM_V), "recnet: beam_width must be in [1, min(8, V)], got ", beam_width);
-  chk_constraints(no_repeat_ngram, min_length);
-  const auto ids = ban_ids(banned);
-  auto [toks, cum, len, score, n] = nbest_outputs(h, enc, beam_width);
-  ok(recnet_beam_search_nbest_constrained(H(h), enc.data_ptr<float>(), (int32_t)beam_width, (float)length_alpha, (int32_t)no_repeat_ngram,
-                                          (int32_t)min_length, ids.data(), (int32_t)ids.size(), toks.data_ptr<int64_t>(), cum.data_ptr<float>(),
-                                          len.data_ptr<int32_t>(), score.data_ptr<float>(), n.data_ptr<int32_t>(), stream()),
-     "beam_search_nbest_constrained");
-  return {toks, cum, len, score, n};
-}
-// ---- the diverse forms: the constrained forms in n_groups groups with a penalty between them
-static void chk_groups(int64_t beam_width, int64_t n_groups, double diversity_penalty) {
-  TORCH_CHECK(n_groups >= 1 && beam_width % n_groups == 0, "recnet: n_groups must be at least 1 and divide beam_width, got ", n_groups);
-  TORCH_CHECK(std::isfinite(diversity_penalty) && diversity_penalty >= 0.0, "recnet: diversity_penalty must be finite and >= 0, got ",
-              diversity_penalty);
+  const Bans b{no_repeat_ngram, min_length, banned};
+  return select_rows_impl(h, logits, cum, finished, beam_width, &hist, t, &b, nullptr);
 }
 std::tuple<at::Tensor, at::Tensor> beam_select_rows_diverse(int64_t h, const at::Tensor& logits, const at::Tensor& cum,
                                                             const at::Tensor& finished, const c10::optional<at::Tensor>& hist, int64_t t,
                                                             int64_t beam_width, int64_t n_groups, double diversity_penalty,
                                                             int64_t no_repeat_ngram, int64_t min_length, at::IntArrayRef banned) {
-  chk_select(logits, cum, finished, beam_width);
-  chk_groups(beam_width, n_groups, diversity_penalty);
-  TORCH_CHECK(logits.size(0) == 1 || logits.size(0) == beam_width, "recnet: nb must be 1 or beam_width, got ", logits.size(0));
-  TORCH_CHECK(t >= 0 && t < INT32_MAX, "recnet: t out of range");
-  chk_constraints(no_repeat_ngram, min_length);
-  const auto ids = ban_ids(banned);
-  int64_t Tm;
-  const int64_t* hp = hist_arg(hist, logits, &Tm);
-  auto vals = at::empty({logits.size(1), beam_width}, logits.options());
-  auto idx = at::empty({logits.size(1), beam_width}, logits.options().dtype(at::kInt));
-  ok(recnet_beam_select_rows_diverse(H(h), logits.data_ptr<float>(), cum.data_ptr<float>(), finished.data_ptr<int32_t>(), hp,
-                                     (int32_t)logits.size(0), (int32_t)logits.size(1), (int32_t)logits.size(2), (int32_t)Tm, (int32_t)t,
-                                     (int32_t)beam_width, (int32_t)n_groups, (float)diversity_penalty, (int32_t)no_repeat_ngram,
-                                     (int32_t)min_length, ids.data(), (int32_t)ids.size(), vals.data_ptr<float>(), idx.data_ptr<int32_t>(),
-                                     stream()), "beam_select_rows_diverse");
-  return {vals, idx};
+  const Bans b{no_repeat_ngram, min_length, banned};
+  const Groups g{n_groups, diversity_penalty};
+  return select_rows_impl(h, logits, cum, finished, beam_width, &hist, t, &b, &g);
 }
-// beam_search_nbest_constrained's outputs and, behind score, group [beam_width, B] int32: the group of each returned rank
-std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> beam_search_nbest_diverse(
+NbestOut beam_search_nbest(int64_t h, const at::Tensor& enc, int64_t beam_width, double length_alpha) {
+  return without_group(nbest_impl(h, enc, beam_width, length_alpha, nullptr, nullptr));
+}
+NbestOut beam_search_nbest_constrained(int64_t h, const at::Tensor& enc, int64_t beam_width, double length_alpha, int64_t no_repeat_ngram,
+                                       int64_t min_length, at::IntArrayRef banned) {
+  const Bans b{no_repeat_ngram, min_length, banned};
+  return without_group(nbest_impl(h, enc, beam_width, length_alpha, &b, nullptr));
+}
+NbestGroupOut beam_search_nbest_diverse(
     int64_t h, const at::Tensor& enc, int64_t beam_width, double length_alpha, int64_t n_groups, double diversity_penalty,
     int64_t no_repeat_ngram, int64_t min_length, at::IntArrayRef banned) {
-  chk_enc(h, enc);
-  TORCH_CHECK(beam_width >= 1 && beam_width <= 8 && beam_width <= dim(h, RECNET_DIM_V), "recnet: beam_width must be in [1, min(8, V)], got ", beam_width);
-  chk_groups(beam_width, n_groups, diversity_penalty);
-  chk_constraints(no_repeat_ngram, min_length);
-  const auto ids = ban_ids(banned);
-  auto [toks, cum, len, score, n] = nbest_outputs(h, enc, beam_width);
-  auto group = at::zeros({beam_width, enc.size(0)}, enc.options().dtype(at::kInt));
-  ok(recnet_beam_search_nbest_diverse(H(h), enc.data_ptr<float>(), (int32_t)beam_width, (float)length_alpha, (int32_t)n_groups,
-                                      (float)diversity_penalty, (int32_t)no_repeat_ngram, (int32_t)min_length, ids.data(), (int32_t)ids.size(),
-                                      toks.data_ptr<int64_t>(), cum.data_ptr<float>(), len.data_ptr<int32_t>(), score.data_ptr<float>(),
-                                      group.data_ptr<int32_t>(), n.data_ptr<int32_t>(), stream()), "beam_search_nbest_diverse");
-  return {toks, cum, len, score, group, n};
+  const Bans b{no_repeat_ngram, min_length, banned};
+  const Groups g{n_groups, diversity_penalty};
+  return nbest_impl(h, enc, beam_width, length_alpha, &b, &g);
 }
 // tokens [T, B] with every entry in [0, V): the caller's duty (search.score_captions checks it)
 std::tuple<at::Tensor, at::Tensor, at::Tensor> score_captions(int64_t h, const c10::optional<at::Tensor>& enc, const at::Tensor& tokens,

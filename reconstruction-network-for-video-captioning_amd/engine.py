@@ -239,6 +239,41 @@ class Engine:
             raise RuntimeError("banned_tokens: ids must fit an int32 (got %r)" % (ids,))
         return ((C.c_int32 * len(ids))(*ids) if ids else None), len(ids)
 
+    def _nbest_outputs(self, enc, beam_width, with_group=False):
+        """The check of enc and the zeroed output set of the N-best searches (for a width outside [1, 8] with one rank):
+        (tokens [bw, Tm, B] int64, cum, len, score [bw, B], group [bw, B] int32 or None, n_steps int32[1])."""
+        d = self.dims
+        _chk_tensor(enc, (d["B"], d["F"], d["D"]), torch.float32, "encoder_outputs")
+        Tm, B, bw = self.hyper["caption_max_len"] + 1, d["B"], (int(beam_width) if 1 <= int(beam_width) <= 8 else 1)
+        toks = torch.zeros(bw, Tm, B, dtype=torch.int64, device=self.device)
+        cum = torch.zeros(bw, B, dtype=torch.float32, device=self.device)
+        ln = torch.zeros(bw, B, dtype=torch.int32, device=self.device)
+        score = torch.zeros(bw, B, dtype=torch.float32, device=self.device)
+        group = torch.zeros(bw, B, dtype=torch.int32, device=self.device) if with_group else None
+        n = torch.zeros(1, dtype=torch.int32, device=self.device)
+        return toks, cum, ln, score, group, n
+
+    @staticmethod
+    def _select_rows_args(logits, cum, finished, beam_width, hist):
+        """The checks of the selection inputs (logits [nb, rows, V] float32, cum [nb, rows] float32, finished [nb, rows] int32, hist
+        None or [nb, rows, Tm] int64) and the outputs: (nb, rows, V, Tm, vals [rows, bw] float32, idx [rows, bw] int32)."""
+        if logits.dim() != 3:
+            raise RuntimeError("logits: expected [nb, rows, V], got %s" % (tuple(logits.shape),))
+        nb, rows, V = logits.shape
+        _chk_tensor(logits, (nb, rows, V), torch.float32, "logits")
+        _chk_tensor(cum, (nb, rows), torch.float32, "cum")
+        _chk_tensor(finished, (nb, rows), torch.int32, "finished")
+        bw = max(int(beam_width), 1)
+        vals = torch.empty(rows, bw, dtype=torch.float32, device=logits.device)
+        idx = torch.empty(rows, bw, dtype=torch.int32, device=logits.device)
+        Tm = 0x7FFFFFFF              # (no hist: only min_length / the static bans can be on, and they read no history)
+        if hist is not None:
+            if hist.dim() != 3:
+                raise RuntimeError("hist: expected [nb, rows, Tm], got %s" % (tuple(hist.shape),))
+            Tm = hist.shape[2]
+            _chk_tensor(hist, (nb, rows, Tm), torch.int64, "hist")
+        return int(nb), int(rows), int(V), int(Tm), vals, idx
+
     def beam_search_nbest(self, enc, beam_width, length_alpha=0.0, no_repeat_ngram=0, min_length=0, banned_tokens=()):
         """N-best beam search on log-probabilities (recnet_beam_search_nbest; the reference has none).
         no_repeat_ngram / min_length / banned_tokens (all off by default, and then the call is
@@ -250,14 +285,7 @@ class Engine:
         beam_width in [1, min(8, V)] and length_alpha finite and >= 0 before any launch of its own; the output tensors are
         allocated and zeroed here first (for a width outside [1, 8] with one rank), so a refused call has still run those fills:
         search.beam_search_nbest checks its arguments before anything at all."""
-        d = self.dims
-        _chk_tensor(enc, (d["B"], d["F"], d["D"]), torch.float32, "encoder_outputs")
-        Tm, B, bw = self.hyper["caption_max_len"] + 1, d["B"], (int(beam_width) if 1 <= int(beam_width) <= 8 else 1)
-        toks = torch.zeros(bw, Tm, B, dtype=torch.int64, device=self.device)
-        cum = torch.zeros(bw, B, dtype=torch.float32, device=self.device)
-        ln = torch.zeros(bw, B, dtype=torch.int32, device=self.device)
-        score = torch.zeros(bw, B, dtype=torch.float32, device=self.device)
-        n = torch.zeros(1, dtype=torch.int32, device=self.device)
+        toks, cum, ln, score, _, n = self._nbest_outputs(enc, beam_width)
         if no_repeat_ngram == 0 and min_length == 0 and len(banned_tokens) == 0:
             _lib.check(self.lib.recnet_beam_search_nbest(self.handle, _ptr(enc), int(beam_width), float(length_alpha), _ptr(toks),
                                                          _ptr(cum), _ptr(ln), _ptr(score), _ptr(n), _stream()),
@@ -279,30 +307,17 @@ class Engine:
         With t given (the step, and hist [nb, rows, Tm] int64: the tokens generated so far in entries [0, t); needed for
         no_repeat_ngram only) the call is recnet_beam_select_rows_constrained's: what a live hypothesis does not offer is
         DESIGN.md section 12's."""
-        if logits.dim() != 3:
-            raise RuntimeError("logits: expected [nb, rows, V], got %s" % (tuple(logits.shape),))
-        nb, rows, V = logits.shape
-        _chk_tensor(logits, (nb, rows, V), torch.float32, "logits")
-        _chk_tensor(cum, (nb, rows), torch.float32, "cum")
-        _chk_tensor(finished, (nb, rows), torch.int32, "finished")
-        bw = max(int(beam_width), 1)
-        vals = torch.empty(rows, bw, dtype=torch.float32, device=logits.device)
-        idx = torch.empty(rows, bw, dtype=torch.int32, device=logits.device)
+        # (without the step, hist is refused below, unread)
+        nb, rows, V, Tm, vals, idx = self._select_rows_args(logits, cum, finished, beam_width, hist if t is not None else None)
         if t is None:
             if hist is not None or no_repeat_ngram != 0 or min_length != 0 or len(banned_tokens) != 0:
                 raise RuntimeError("the constrained selection needs the step t")
-            _lib.check(self.lib.recnet_beam_select_rows(self.handle, _ptr(logits), _ptr(cum), _ptr(finished), int(nb), int(rows), int(V),
+            _lib.check(self.lib.recnet_beam_select_rows(self.handle, _ptr(logits), _ptr(cum), _ptr(finished), nb, rows, V,
                                                         int(beam_width), _ptr(vals), _ptr(idx), _stream()), "recnet_beam_select_rows")
             return vals, idx
-        Tm = 0x7FFFFFFF              # (no hist: only min_length / the static bans can be on, and they read no history)
-        if hist is not None:
-            if hist.dim() != 3:
-                raise RuntimeError("hist: expected [nb, rows, Tm], got %s" % (tuple(hist.shape),))
-            Tm = hist.shape[2]
-            _chk_tensor(hist, (nb, rows, Tm), torch.int64, "hist")
         ban, n_ban = self._ban_array(banned_tokens)
-        _lib.check(self.lib.recnet_beam_select_rows_constrained(self.handle, _ptr(logits), _ptr(cum), _ptr(finished), _ptr(hist), int(nb),
-                                                                int(rows), int(V), int(Tm), int(t), int(beam_width), int(no_repeat_ngram),
+        _lib.check(self.lib.recnet_beam_select_rows_constrained(self.handle, _ptr(logits), _ptr(cum), _ptr(finished), _ptr(hist), nb,
+                                                                rows, V, Tm, int(t), int(beam_width), int(no_repeat_ngram),
                                                                 int(min_length), ban, n_ban, _ptr(vals), _ptr(idx), _stream()),
                    "recnet_beam_select_rows_constrained")
         return vals, idx
@@ -314,15 +329,7 @@ class Engine:
         diversity_penalty for each slot of an earlier group that chose its token at this step.  cum stays the un-penalised
         log-probability.  Returns beam_search_nbest's tensors with group [bw, B] int32 (the group of each returned rank) before
         n_steps: (tokens, cum, len, score, group, n_steps).  The library checks the arguments before any launch of its own."""
-        d = self.dims
-        _chk_tensor(enc, (d["B"], d["F"], d["D"]), torch.float32, "encoder_outputs")
-        Tm, B, bw = self.hyper["caption_max_len"] + 1, d["B"], (int(beam_width) if 1 <= int(beam_width) <= 8 else 1)
-        toks = torch.zeros(bw, Tm, B, dtype=torch.int64, device=self.device)
-        cum = torch.zeros(bw, B, dtype=torch.float32, device=self.device)
-        ln = torch.zeros(bw, B, dtype=torch.int32, device=self.device)
-        score = torch.zeros(bw, B, dtype=torch.float32, device=self.device)
-        group = torch.zeros(bw, B, dtype=torch.int32, device=self.device)
-        n = torch.zeros(1, dtype=torch.int32, device=self.device)
+        toks, cum, ln, score, group, n = self._nbest_outputs(enc, beam_width, with_group=True)
         ban, n_ban = self._ban_array(banned_tokens)
         _lib.check(self.lib.recnet_beam_search_nbest_diverse(self.handle, _ptr(enc), int(beam_width), float(length_alpha), int(n_groups),
                                                              float(diversity_penalty), int(no_repeat_ngram), int(min_length), ban, n_ban,
@@ -336,27 +343,38 @@ class Engine:
         arguments of beam_select_rows with nb = 1 (every group selects from hypothesis 0) or nb = beam_width (group g selects from
         hypotheses g * w .. g * w + w - 1, w = beam_width / n_groups).  Returns (vals [rows, bw] float32, idx [rows, bw] int32):
         slot g * w + j holds the j-th of group g by its penalised value, vals its UN-penalised value, idx = i * V + v."""
-        if logits.dim() != 3:
-            raise RuntimeError("logits: expected [nb, rows, V], got %s" % (tuple(logits.shape),))
-        nb, rows, V = logits.shape
-        _chk_tensor(logits, (nb, rows, V), torch.float32, "logits")
-        _chk_tensor(cum, (nb, rows), torch.float32, "cum")
-        _chk_tensor(finished, (nb, rows), torch.int32, "finished")
-        bw = max(int(beam_width), 1)
-        vals = torch.empty(rows, bw, dtype=torch.float32, device=logits.device)
-        idx = torch.empty(rows, bw, dtype=torch.int32, device=logits.device)
-        Tm = 0x7FFFFFFF              # (no hist: only min_length / the static bans can be on, and they read no history)
-        if hist is not None:
-            if hist.dim() != 3:
-                raise RuntimeError("hist: expected [nb, rows, Tm], got %s" % (tuple(hist.shape),))
-            Tm = hist.shape[2]
-            _chk_tensor(hist, (nb, rows, Tm), torch.int64, "hist")
+        nb, rows, V, Tm, vals, idx = self._select_rows_args(logits, cum, finished, beam_width, hist)
         ban, n_ban = self._ban_array(banned_tokens)
-        _lib.check(self.lib.recnet_beam_select_rows_diverse(self.handle, _ptr(logits), _ptr(cum), _ptr(finished), _ptr(hist), int(nb),
-                                                            int(rows), int(V), int(Tm), int(t), int(beam_width), int(n_groups),
+        _lib.check(self.lib.recnet_beam_select_rows_diverse(self.handle, _ptr(logits), _ptr(cum), _ptr(finished), _ptr(hist), nb,
+                                                            rows, V, Tm, int(t), int(beam_width), int(n_groups),
                                                             float(diversity_penalty), int(no_repeat_ngram), int(min_length), ban, n_ban,
                                                             _ptr(vals), _ptr(idx), _stream()), "recnet_beam_select_rows_diverse")
         return vals, idx
+
+    def _sample_search_outputs(self, enc, nucleus):
+        """The check of enc and the zeroed outputs of the sampling searches: (tokens [Tm, B] int64, logprobs [Tm, B] float32,
+        n_allowed [Tm, B] int32 or None, n_steps int32[1])."""
+        d = self.dims
+        _chk_tensor(enc, (d["B"], d["F"], d["D"]), torch.float32, "encoder_outputs")
+        Tm = self.hyper["caption_max_len"] + 1
+        toks = torch.zeros(Tm, d["B"], dtype=torch.int64, device=self.device)
+        lps = torch.zeros(Tm, d["B"], dtype=torch.float32, device=self.device)
+        na = torch.zeros(Tm, d["B"], dtype=torch.int32, device=self.device) if nucleus else None
+        n = torch.zeros(1, dtype=torch.int32, device=self.device)
+        return toks, lps, na, n
+
+    @staticmethod
+    def _sample_rows_outputs(logits, nucleus):
+        """The check of logits [rows, V] float32 and the outputs of one draw per row: (rows, V, tokens [rows] int64, logprobs [rows]
+        float32, n_allowed [rows] int32 or None)."""
+        if logits.dim() != 2:
+            raise RuntimeError("logits: expected [rows, V], got %s" % (tuple(logits.shape),))
+        rows, V = logits.shape
+        _chk_tensor(logits, (rows, V), torch.float32, "logits")
+        toks = torch.empty(rows, dtype=torch.int64, device=logits.device)
+        lps = torch.empty(rows, dtype=torch.float32, device=logits.device)
+        na = torch.empty(rows, dtype=torch.int32, device=logits.device) if nucleus else None
+        return int(rows), int(V), toks, lps, na
 
     def sample_search(self, enc, temperature=1.0, top_k=0, seed=0, top_p=1.0):
         """The loop of greedy_search with a draw from softmax(logits / temperature) over the top_k largest logits in place of
@@ -366,12 +384,7 @@ class Engine:
         if top_p != 1.0:
             toks, lps, _, n = self.sample_search_nucleus(enc, temperature, top_k, top_p, seed)
             return toks, lps, n
-        d = self.dims
-        _chk_tensor(enc, (d["B"], d["F"], d["D"]), torch.float32, "encoder_outputs")
-        Tm = self.hyper["caption_max_len"] + 1
-        toks = torch.zeros(Tm, d["B"], dtype=torch.int64, device=self.device)
-        lps = torch.zeros(Tm, d["B"], dtype=torch.float32, device=self.device)
-        n = torch.zeros(1, dtype=torch.int32, device=self.device)
+        toks, lps, _, n = self._sample_search_outputs(enc, False)
         _lib.check(self.lib.recnet_sample_search(self.handle, _ptr(enc), float(temperature), int(top_k), seed & 0xFFFFFFFF,
                                                  _ptr(toks), _ptr(lps), _ptr(n), _stream()), "recnet_sample_search")
         return toks, lps, n
@@ -381,13 +394,7 @@ class Engine:
         from the shortest prefix of the allowed entries whose mass reaches top_p.  Returns (tokens [Tm, B] int64, logprobs [Tm, B]
         float32, n_allowed [Tm, B] int32: the size of the set each token was drawn from, n_steps int32[1]).  The library checks
         temperature / top_k / top_p (0 < top_p <= 1; 1 = no nucleus cut)."""
-        d = self.dims
-        _chk_tensor(enc, (d["B"], d["F"], d["D"]), torch.float32, "encoder_outputs")
-        Tm = self.hyper["caption_max_len"] + 1
-        toks = torch.zeros(Tm, d["B"], dtype=torch.int64, device=self.device)
-        lps = torch.zeros(Tm, d["B"], dtype=torch.float32, device=self.device)
-        na = torch.zeros(Tm, d["B"], dtype=torch.int32, device=self.device)
-        n = torch.zeros(1, dtype=torch.int32, device=self.device)
+        toks, lps, na, n = self._sample_search_outputs(enc, True)
         _lib.check(self.lib.recnet_sample_search_nucleus(self.handle, _ptr(enc), float(temperature), int(top_k), float(top_p),
                                                          seed & 0xFFFFFFFF, _ptr(toks), _ptr(lps), _ptr(na), _ptr(n), _stream()),
                    "recnet_sample_search_nucleus")
@@ -396,14 +403,8 @@ class Engine:
     def sample_rows_nucleus(self, logits, temperature=1.0, top_k=0, top_p=1.0, seed=0, t=0):
         """sample_rows with the nucleus cut (recnet_sample_rows_nucleus).  Returns (tokens [rows] int64, logprobs [rows] float32,
         n_allowed [rows] int32); `logits` is only read."""
-        if logits.dim() != 2:
-            raise RuntimeError("logits: expected [rows, V], got %s" % (tuple(logits.shape),))
-        rows, V = logits.shape
-        _chk_tensor(logits, (rows, V), torch.float32, "logits")
-        toks = torch.empty(rows, dtype=torch.int64, device=logits.device)
-        lps = torch.empty(rows, dtype=torch.float32, device=logits.device)
-        na = torch.empty(rows, dtype=torch.int32, device=logits.device)
-        _lib.check(self.lib.recnet_sample_rows_nucleus(self.handle, _ptr(logits), int(rows), int(V), float(temperature), int(top_k),
+        rows, V, toks, lps, na = self._sample_rows_outputs(logits, True)
+        _lib.check(self.lib.recnet_sample_rows_nucleus(self.handle, _ptr(logits), rows, V, float(temperature), int(top_k),
                                                        float(top_p), seed & 0xFFFFFFFF, int(t), _ptr(toks), _ptr(lps), _ptr(na),
                                                        _stream()), "recnet_sample_rows_nucleus")
         return toks, lps, na
@@ -414,13 +415,8 @@ class Engine:
         sample_rows_nucleus, without its n_allowed."""
         if top_p != 1.0:
             return self.sample_rows_nucleus(logits, temperature, top_k, top_p, seed, t)[:2]
-        if logits.dim() != 2:
-            raise RuntimeError("logits: expected [rows, V], got %s" % (tuple(logits.shape),))
-        rows, V = logits.shape
-        _chk_tensor(logits, (rows, V), torch.float32, "logits")
-        toks = torch.empty(rows, dtype=torch.int64, device=logits.device)
-        lps = torch.empty(rows, dtype=torch.float32, device=logits.device)
-        _lib.check(self.lib.recnet_sample_rows(self.handle, _ptr(logits), int(rows), int(V), float(temperature), int(top_k),
+        rows, V, toks, lps, _ = self._sample_rows_outputs(logits, False)
+        _lib.check(self.lib.recnet_sample_rows(self.handle, _ptr(logits), rows, V, float(temperature), int(top_k),
                                                seed & 0xFFFFFFFF, int(t), _ptr(toks), _ptr(lps), _stream()),
                    "recnet_sample_rows")
         return toks, lps

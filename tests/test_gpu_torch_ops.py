@@ -1,5 +1,7 @@
 """torch.ops.recnet.* on the device: the ops called directly (not through api.py) reproduce the golden losses /
-gradients of the reference, the fused train_step op equals fwd_bwd + optimizer_step, and malformed tensors raise."""
+gradients of the reference, the fused train_step op equals fwd_bwd + optimizer_step, malformed tensors raise, and every
+member of the sampling and the N-best selection family gives the bits of its Engine method (and of its siblings with the
+extra arguments off)."""
 import numpy as np
 import pytest
 import torch
@@ -77,3 +79,60 @@ def test_ops_validate_their_tensors():
         ops.forward_decoder(0, enc.cuda(), targets.cuda(), T, w, True, 1)
     with pytest.raises((RuntimeError, NotImplementedError)):
         ops.forward_decoder(h, enc, targets, T, w.cpu(), True, 1)          # CPU tensors: no kernel registered
+
+
+def _bits(outs):
+    return [o.view(torch.int32) if o.dtype == torch.float32 else o for o in outs]
+
+
+def _same(a, b):
+    return len(a) == len(b) and all(torch.equal(x, y) for x, y in zip(_bits(a), _bits(b)))
+
+
+@pytest.mark.parametrize("family", ["sample_rows", "sample_search", "beam_select_rows"])
+def test_search_family_ops_equal_their_engine_methods(family):
+    """The op and the Engine method of every member share one implementation per layer: equal bits, member by member.  The
+    smallest shape that wraps the 256-thread stride with two hypotheses: rows = 3, V = 300, nb = 2, width 2."""
+    from tests.test_gpu_beam import _rows_engine
+    ops = _ops.load()
+    gen = torch.Generator().manual_seed(11)
+    x = torch.randn(2, 3, 300, generator=gen).cuda()
+    if family == "sample_rows":
+        eng, x2 = _rows_engine(), x[0].contiguous()
+        h = int(eng.handle.value)
+        plain = ops.sample_rows(h, x2, 0.7, 40, 5, 3)
+        assert _same(plain, eng.sample_rows(x2, 0.7, 40, 5, 3))
+        assert _same(ops.sample_rows_nucleus(h, x2, 0.7, 40, 0.8, 5, 3), eng.sample_rows_nucleus(x2, 0.7, 40, 0.8, 5, 3))
+        tok, lp, na = ops.sample_rows_nucleus(h, x2, 0.7, 40, 1.0, 5, 3)      # (no nucleus cut: the plain draw, and the count)
+        assert _same((tok, lp), plain) and (na == 40).all()
+    elif family == "sample_search":
+        from tests.test_gpu_nucleus import _engine_for
+        from tests.test_gpu_sample import _decoder
+        from tests.test_search_oracle import load_search_case
+        g, P, enc = load_search_case("search_small")
+        encd = enc.cuda()
+        eng = _engine_for(_decoder(g, P, "f32")[0], encd)
+        h = int(eng.handle.value)
+        assert _same(ops.sample_search(h, encd, 0.5, 5, 3), eng.sample_search(encd, 0.5, 5, 3))
+        assert _same(ops.sample_search_nucleus(h, encd, 0.5, 5, 0.8, 3), eng.sample_search_nucleus(encd, 0.5, 5, 0.8, 3))
+    else:
+        eng = _rows_engine()
+        h = int(eng.handle.value)
+        cum = torch.randn(2, 3, generator=gen).cuda()
+        fin = torch.tensor([[0, 0, 4], [0, 0, 0]], dtype=torch.int32).cuda()
+        hist = torch.randint(3, 300, (2, 3, 5), generator=gen).cuda()
+        hist[:, :, 2] = hist[:, :, 0]                                          # (a repeated token: the bigram rule bans its follower)
+        plain = eng.beam_select_rows(x, cum, fin, 2)
+        for other in (ops.beam_select_rows(h, x, cum, fin, 2),
+                      eng.beam_select_rows(x, cum, fin, 2, hist=hist, t=3), ops.beam_select_rows_constrained(h, x, cum, fin, hist, 3, 2, 0, 0, []),
+                      eng.beam_select_rows_diverse(x, cum, fin, 2, 1, 2.5, hist=hist, t=3),
+                      ops.beam_select_rows_diverse(h, x, cum, fin, hist, 3, 2, 1, 2.5, 0, 0, [])):
+            assert _same(plain, other)
+        con = eng.beam_select_rows(x, cum, fin, 2, hist=hist, t=3, no_repeat_ngram=2, min_length=4, banned_tokens=(7,))
+        for other in (ops.beam_select_rows_constrained(h, x, cum, fin, hist, 3, 2, 2, 4, [7]),
+                      eng.beam_select_rows_diverse(x, cum, fin, 2, 1, 2.5, hist=hist, t=3, no_repeat_ngram=2, min_length=4, banned_tokens=(7,)),
+                      ops.beam_select_rows_diverse(h, x, cum, fin, hist, 3, 2, 1, 2.5, 2, 4, [7])):
+            assert _same(con, other)
+        two = eng.beam_select_rows_diverse(x, cum, fin, 2, 2, 0.5, hist=hist, t=3, no_repeat_ngram=2)
+        assert _same(two, ops.beam_select_rows_diverse(h, x, cum, fin, hist, 3, 2, 2, 0.5, 2, 0, []))
+    torch.cuda.synchronize()
