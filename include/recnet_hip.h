@@ -21,7 +21,7 @@ extern "C" {
 #endif
 
 /* 12 still: recnet_beam_select_rows_constrained / recnet_beam_search_nbest_constrained, and after them
- * recnet_beam_select_rows_diverse / recnet_beam_search_nbest_diverse, were added without changing any existing entry.  A library built before them is still caught: a binding that resolves every declared symbol fails on the first one missing. */
+ * recnet_beam_select_rows_diverse / recnet_beam_search_nbest_diverse, and recnet_consensus_rows, were added without changing any existing entry.  A library built before them is still caught: a binding that resolves every declared symbol fails on the first one missing. */
 #define RECNET_ABI_VERSION 12
 #define RECNET_ATTN_NONE 0
 #define RECNET_ATTN_SOFTMAX 1
@@ -325,6 +325,28 @@ int recnet_beam_search_nbest_diverse(recnet_handle* h, const float* enc, int32_t
                                      float diversity_penalty, int32_t no_repeat_ngram, int32_t min_length, const int32_t* banned,
                                      int32_t n_banned, int64_t* tokens_out, float* cum_out, int32_t* len_out, float* score_out,
                                      int32_t* group_out, int32_t* n_steps_out, void* stream);
+
+/* ---- Consensus (minimum-Bayes-risk) scoring of hypotheses against a reference set by n-gram overlap (no counterpart in the
+ * reference; added at version 12 without changing any existing entry).
+ * The WORDS of a caption, a column t_0 .. t_{T-1} of tokens, are the tokens before its first <EOS> (2), at most T; every other id
+ * is an ordinary word, <PAD> (0) included; whatever stands behind the first <EOS> is ignored.  L = the number of words.  For
+ * n = 1..4 let c_n(g) be the occurrences of n-gram g in the caption.  For a hypothesis h and a reference r, exact integers:
+ *   M_n(h, r) = sum_g min(h_n(g), r_n(g)) * r_n(g)        Q_n(c) = sum_g c_n(g)^2
+ *   sim(h, r) = 1/4 * sum_{n=1..4} [ M_n / sqrt(Q_n(h) * Q_n(r)) if Q_n(h) > 0 and Q_n(r) > 0, else 0 ] * exp(-(L_h - L_r)^2 / (2 sigma^2))
+ * (coco CIDEr's clipped cosine and Gaussian length penalty with a uniform idf).  The utility of hypothesis i is
+ *   util_i = (sum_j sim(i, j)) / N_r   without weights,     util_i = sum_j w_j * sim(i, j)   with weights (widened to double),
+ * summed in float64 over j ASCENDING, one term after the other from 0.0: two hypotheses with the same words get the same bits.
+ * n-grams are equal when their tokens are; nothing is hashed.  hyp [N_h][T_h][B] int64, B innermost (what
+ * recnet_beam_search_nbest leaves); ref [N_r][T_r][B], or NULL: the hypotheses are their own references, the term j = i included
+ * (N_r and T_r are then ignored).  weights [N_r][B] float or NULL.  util_out [N_h][B] double; optional (NULL: not written)
+ * sim_out [N_h][N_r][B] double, counts_out [N_h][N_r][B][4] int32 (M_n), q_hyp_out [N_h][B][4], q_ref_out [N_r][B][4],
+ * len_hyp_out [N_h][B], len_ref_out [N_r][B] int32.  One launch, integer counting, no atomics: two calls give the same bits.
+ * RECNET_EINVAL before any launch: N_h / N_r outside [1, 32], T_h / T_r outside [1, 64], B < 1, sigma not positive and finite, a
+ * NULL hyp or util_out.  Tokens must lie in [0, 2^31): the caller's duty (they are compared as 32-bit ids).  The handle supplies
+ * the device only: no decoder needs to be bound, and B is the argument, not the handle's. */
+int recnet_consensus_rows(recnet_handle* h, const int64_t* hyp, int32_t N_h, int32_t T_h, const int64_t* ref, int32_t N_r, int32_t T_r,
+                          int32_t B, const float* weights, double sigma, double* util_out, double* sim_out, int32_t* counts_out,
+                          int32_t* q_hyp_out, int32_t* q_ref_out, int32_t* len_hyp_out, int32_t* len_ref_out, void* stream);
 
 /* ---- forward_decoder, train.py:17-75 (teacher forcing, train.py:38,45).
  * enc [B,F,D]; targets [caption_max_len+1, B] int64 (time-major, <PAD>=0, <EOS>=2);

@@ -164,6 +164,7 @@ EXPORTS["recnet_beam_select_rows_constrained"] = (_i, [C.c_void_p] * 5 + [_i] * 
 EXPORTS["recnet_beam_search_nbest_constrained"] = (_i, [C.c_void_p, C.c_void_p, _i, _f, _i, _i, C.POINTER(_i), _i] + [C.c_void_p] * 6)
 EXPORTS["recnet_beam_select_rows_diverse"] = (_i, [C.c_void_p] * 5 + [_i] * 7 + [_f, _i, _i, C.POINTER(_i), _i, C.c_void_p, C.c_void_p, C.c_void_p])
 EXPORTS["recnet_beam_search_nbest_diverse"] = (_i, [C.c_void_p, C.c_void_p, _i, _f, _i, _f, _i, _i, C.POINTER(_i), _i] + [C.c_void_p] * 7)
+EXPORTS["recnet_consensus_rows"] = (_i, [C.c_void_p, C.c_void_p, _i, _i, C.c_void_p, _i, _i, _i, C.c_void_p, _d] + [C.c_void_p] * 8)
 EXPORTS["recnet_logprob_rows"] =(_i, [C.c_void_p, C.c_void_p, C.c_void_p, _i, _i, _f, C.c_void_p, C.c_void_p])
 EXPORTS["recnet_score_captions"] = (_i, [C.c_void_p, C.c_void_p, C.c_void_p, _i, _f, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
 EXPORTS["recnet_reconstruction_error"] = (_i, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _i, C.c_void_p, C.c_void_p, C.c_void_p])

@@ -572,3 +572,30 @@ int recnet_beam_search_nbest(recnet_handle* h, const float* enc, int32_t beam_wi
   return recnet_beam_search_nbest_constrained(h, enc, beam_width, length_alpha, 0, 0, nullptr, 0, tokens_out, cum_out, len_out, score_out,
                                               n_steps_out, stream);
 }
+
+// ---- consensus (minimum-Bayes-risk) scoring by n-gram overlap (the reference has no counterpart; DESIGN.md section 16)
+// One launch.  Grid: the caption columns times tiles of HT hypotheses, HT chosen so that about two workgroups per CU exist (B = 100
+// alone would leave most of the chip idle); the integers do not depend on the tiling, so neither do the outputs.
+int recnet_consensus_rows(recnet_handle* h, const int64_t* hyp, int32_t N_h, int32_t T_h, const int64_t* ref, int32_t N_r, int32_t T_r,
+                          int32_t B, const float* weights, double sigma, double* util_out, double* sim_out, int32_t* counts_out,
+                          int32_t* q_hyp_out, int32_t* q_ref_out, int32_t* len_hyp_out, int32_t* len_ref_out, void* stream) {
+  REQUIRE_WS(h);
+  if (!hyp || !util_out) return fail(RECNET_EINVAL, "null argument");
+  if (!ref) { N_r = N_h; T_r = T_h; }
+  if (N_h < 1 || N_h > 32 || N_r < 1 || N_r > 32) return fail(RECNET_EINVAL, "N_h and N_r must be in [1, 32]");
+  if (T_h < 1 || T_h > 64 || T_r < 1 || T_r > 64) return fail(RECNET_EINVAL, "T_h and T_r must be in [1, 64]");
+  if (B < 1) return fail(RECNET_EINVAL, "B must be positive");
+  if (!(sigma > 0.0) || !std::isfinite(sigma)) return fail(RECNET_EINVAL, "sigma must be positive and finite");
+  ConsensusArgs a;
+  a.hyp = hyp; a.ref = ref; a.w = weights; a.sigma = sigma; a.Nh = N_h; a.Nr = N_r; a.Th = T_h; a.Tr = T_r; a.B = B;
+  a.util = util_out; a.sim = sim_out; a.counts = counts_out; a.q_hyp = q_hyp_out; a.q_ref = q_ref_out; a.len_hyp = len_hyp_out;
+  a.len_ref = len_ref_out;
+  int tiles = cdiv(2L * (h->ncu > 0 ? h->ncu : 256), B);
+  if (tiles > N_h) tiles = N_h;
+  a.HT = cdiv(N_h, tiles);
+  tiles = cdiv(N_h, a.HT);
+  const size_t sm = (size_t)cs_lds_words(N_r, T_r, T_h, a.HT) * 4;
+  hipLaunchKernelGGL(consensus_rows_kernel, dim3(B, tiles), dim3(256), sm, (hipStream_t)stream, a);
+  LAUNCH_OK();
+  return RECNET_OK;
+}

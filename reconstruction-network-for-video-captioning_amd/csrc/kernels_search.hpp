@@ -668,3 +668,195 @@ __global__ __launch_bounds__(256) void beam_nbest_rank_kernel(const float* __res
     cum_out[r * B + b] = cum[bi * B + b]; len_out[r * B + b] = f ? f : ns; score_out[r * B + b] = best; order[r * B + b] = bi;
   }
 }
+
+// ---- consensus (minimum-Bayes-risk) reranking: n-gram overlap of hypotheses with a reference set
+// The words of a caption column are its tokens before the first <EOS> (2), at most T.  With c_n(g) the occurrences of n-gram g,
+//   Q_n(c) = sum_g c_n(g)^2 = sum over the positions p of c of c_n(g(p)),
+//   M_n(h, r) = sum_g min(h_n(g), r_n(g)) r_n(g) = sum over the positions q of r of min(h_n(g(q)), r_n(g(q))),
+// so every count is "how many positions of caption y start the n-gram that starts at position q of caption x": the match run
+// run(p, q) = min(4, equal consecutive words from (p, q)) gives all four orders in one walk over y.  Integers only up to here, in
+// any order; the finishing is float64, one thread per hypothesis walking the references upward.
+struct ConsensusArgs {
+  const int64_t* hyp;        // [Nh][Th][B]
+  const int64_t* ref;        // [Nr][Tr][B]; null: the hypotheses are their own references (Nr = Nh, Tr = Th)
+  const float* w;            // [Nr][B] or null: util = sum_j w_j sim_ij; null: (sum_j sim_ij) / Nr
+  double sigma;              // of the Gaussian length penalty, > 0
+  int Nh, Nr, Th, Tr, B, HT; // HT: hypotheses per workgroup (grid = B x ceil(Nh / HT))
+  double* util;              // [Nh][B]
+  double* sim;               // [Nh][Nr][B] or null
+  int32_t* counts;           // [Nh][Nr][B][4] (M_n) or null
+  int32_t* q_hyp;            // [Nh][B][4] or null
+  int32_t* q_ref;            // [Nr][B][4] or null
+  int32_t* len_hyp;          // [Nh][B] or null
+  int32_t* len_ref;          // [Nr][B] or null
+};
+constexpr int CS_PAD = 3;    // words a 4-gram window reads behind a caption's last position
+// LDS words of one workgroup: tokens of the references and of the tile's hypotheses (rows padded by CS_PAD), the references' own
+// counts per position, lengths, packed Q of both, packed M of the tile's pairs
+__host__ __device__ inline int cs_lds_words(int Nr, int Tr, int Th, int HT) {
+  return Nr * (Tr + CS_PAD) + HT * (Th + CS_PAD) + Nr * Tr + Nr + HT + 2 * Nr + 2 * HT + 2 * HT * Nr;
+}
+// the smallest power of two >= T (T in [1, 64]): the lanes one caption's positions take in a wave
+__host__ __device__ inline int cs_seg(int T) { int W = 1; while (W < T) W <<= 1; return W; }
+// For the n-gram windows (r0), (r0 r1), .. (r0 .. r3): how many positions p < Ly of y start them, in four byte fields (each <= 64).
+// y holds -1 from its length on, CS_PAD entries behind its row included; the caller passes -2 for a word behind x's length: the
+// two never match, and no real word (>= 0) matches either.
+__device__ inline uint32_t cs_count4(const int* y, int Ly, int r0, int r1, int r2, int r3) {
+  uint32_t c = 0;
+  int a0 = y[0], a1 = y[1], a2 = y[2];
+  for (int p = 0; p < Ly; ++p) {
+    const int a3 = y[p + 3];
+    const bool e1 = a0 == r0, e2 = e1 && a1 == r1, e3 = e2 && a2 == r2, e4 = e3 && a3 == r3;
+    c += (uint32_t)e1 + ((uint32_t)e2 << 8) + ((uint32_t)e3 << 16) + ((uint32_t)e4 << 24);
+    a0 = a1; a1 = a2; a2 = a3;
+  }
+  return c;
+}
+// the four words from position q of x (length L), -2 behind the length
+#define CS_WINDOW(x, q, L)                                                                                        \
+  const int r0 = (q) < (L) ? (x)[(q)] : -2, r1 = (q) + 1 < (L) ? (x)[(q) + 1] : -2, r2 = (q) + 2 < (L) ? (x)[(q) + 2] : -2, \
+            r3 = (q) + 3 < (L) ? (x)[(q) + 3] : -2;
+// four byte fields -> fields of 16 bits in two words (sums over <= 64 positions of values <= 64 stay below 2^16)
+#define CS_WIDEN(c, lo, hi) lo = ((c) & 0xffu) | (((c) >> 8 & 0xffu) << 16); hi = ((c) >> 16 & 0xffu) | (((c) >> 24) << 16);
+// sum over the W lanes of a segment (W a power of two, the segment aligned to it)
+#define CS_SEG_SUM(lo, hi, W)                                                                                     \
+  for (int off = (W) >> 1; off > 0; off >>= 1) { lo += __shfl_xor(lo, off); hi += __shfl_xor(hi, off); }
+// Own counts of ncap captions tok [ncap][S] (lengths len): own [ncap][T] (may be null) gets the byte fields of every position, q2
+// [ncap][2] the packed Q_1..Q_4.  A wave takes 64 / W captions at a time, one lane per position.
+__device__ inline void cs_own_counts(const int* tok, int S, int T, const int* len, int ncap, uint32_t* own, uint32_t* q2, int tid) {
+  const int W = cs_seg(T), per = 64 / W, lane = tid & 63, sub = lane / W, q = lane % W;
+  for (int base = (tid >> 6) * per; base < ncap; base += 4 * per) {     // (uniform in the wave: every lane takes part in the sums)
+    const int c = base + sub;
+    uint32_t cnt = 0, lo, hi;
+    if (c < ncap && q < T) {
+      const int* x = tok + c * S;
+      const int L = len[c];
+      CS_WINDOW(x, q, L)
+      cnt = cs_count4(x, L, r0, r1, r2, r3);
+      if (own) own[c * T + q] = cnt;
+    }
+    CS_WIDEN(cnt, lo, hi)
+    CS_SEG_SUM(lo, hi, W)
+    if (c < ncap && q == 0) { q2[2 * c] = lo; q2[2 * c + 1] = hi; }
+  }
+}
+__device__ inline uint32_t cs_min_bytes(uint32_t a, uint32_t b) {
+  uint32_t m = 0;
+#pragma unroll
+  for (int s = 0; s < 32; s += 8) { const uint32_t x = a >> s & 0xffu, y = b >> s & 0xffu; m |= (x < y ? x : y) << s; }
+  return m;
+}
+// One workgroup per (caption column b, tile of HT hypotheses).  (0) tokens of all references and of the tile into LDS as int32
+// (exact for ids below 2^31), lengths, -1 from the length on.  (1) own counts and Q.  (2) per pair (hypothesis of the tile,
+// reference) and reference position q: min(count in the hypothesis, own count), summed over q inside the wave -> M.  (3) one
+// thread per hypothesis: sim and util in float64 over j ascending.
+__global__ __launch_bounds__(256) void consensus_rows_kernel(const ConsensusArgs a) {
+  extern __shared__ __attribute__((aligned(16))) int cs_lds[];
+  const int tid = threadIdx.x, b = blockIdx.x, B = a.B, Nr = a.Nr, Tr = a.Tr, Th = a.Th, HT = a.HT;
+  const int i0 = blockIdx.y * HT, nh = a.Nh - i0 < HT ? a.Nh - i0 : HT;
+  const int Sr = Tr + CS_PAD, Sh = Th + CS_PAD;
+  int* rt = cs_lds;                                   // [Nr][Sr]
+  int* ht = rt + Nr * Sr;                             // [HT][Sh]
+  uint32_t* own = (uint32_t*)(ht + HT * Sh);          // [Nr][Tr]
+  int* rl = (int*)(own + Nr * Tr);                    // [Nr]
+  int* hl = rl + Nr;                                  // [HT]
+  uint32_t* rq = (uint32_t*)(hl + HT);                // [Nr][2]
+  uint32_t* hq = rq + 2 * Nr;                         // [HT][2]
+  uint32_t* M = hq + 2 * HT;                          // [HT][Nr][2]
+  const int64_t* rsrc = a.ref ? a.ref : a.hyp;
+  // (0)
+  for (int e = tid; e < Nr * Sr; e += 256) {
+    const int c = e / Sr, t = e - c * Sr;
+    rt[e] = t < Tr ? (int)rsrc[((size_t)c * Tr + t) * B + b] : -1;
+  }
+  for (int e = tid; e < nh * Sh; e += 256) {
+    const int c = e / Sh, t = e - c * Sh;
+    ht[e] = t < Th ? (int)a.hyp[((size_t)(i0 + c) * Th + t) * B + b] : -1;
+  }
+  __syncthreads();
+  for (int c = tid; c < Nr + nh; c += 256) {
+    const bool r = c < Nr;
+    const int* x = r ? rt + c * Sr : ht + (c - Nr) * Sh;
+    const int T = r ? Tr : Th;
+    int L = 0;
+    while (L < T && x[L] != 2) ++L;
+    if (r) rl[c] = L; else hl[c - Nr] = L;
+  }
+  __syncthreads();
+  for (int e = tid; e < Nr * Sr; e += 256) {
+    const int c = e / Sr, t = e - c * Sr;
+    if (t >= rl[c]) rt[e] = -1;
+  }
+  for (int e = tid; e < nh * Sh; e += 256) {
+    const int c = e / Sh, t = e - c * Sh;
+    if (t >= hl[c]) ht[e] = -1;
+  }
+  __syncthreads();
+  // (1)
+  cs_own_counts(rt, Sr, Tr, rl, Nr, own, rq, tid);
+  cs_own_counts(ht, Sh, Th, hl, nh, nullptr, hq, tid);
+  __syncthreads();
+  // (2)
+  {
+    const int W = cs_seg(Tr), per = 64 / W, lane = tid & 63, sub = lane / W, q = lane % W, npairs = nh * Nr;
+    for (int base = (tid >> 6) * per; base < npairs; base += 4 * per) {
+      const int pr = base + sub;
+      uint32_t m = 0, lo, hi;
+      if (pr < npairs && q < Tr) {
+        const int i = pr / Nr, j = pr - i * Nr;
+        const int* x = rt + j * Sr;
+        const int L = rl[j];
+        CS_WINDOW(x, q, L)
+        m = cs_min_bytes(cs_count4(ht + i * Sh, hl[i], r0, r1, r2, r3), own[j * Tr + q]);
+      }
+      CS_WIDEN(m, lo, hi)
+      CS_SEG_SUM(lo, hi, W)
+      if (pr < npairs && q == 0) { M[2 * pr] = lo; M[2 * pr + 1] = hi; }
+    }
+  }
+  __syncthreads();
+  // the integer outputs (the references' by the first tile alone)
+  if (a.counts)
+    for (int e = tid; e < nh * Nr * 4; e += 256) {
+      const int pr = e >> 2, n = e & 3, i = pr / Nr, j = pr - i * Nr;
+      a.counts[(((size_t)(i0 + i) * Nr + j) * B + b) * 4 + n] = (int32_t)(M[2 * pr + (n >> 1)] >> ((n & 1) * 16) & 0xffffu);
+    }
+  if (a.q_hyp)
+    for (int e = tid; e < nh * 4; e += 256) {
+      const int i = e >> 2, n = e & 3;
+      a.q_hyp[((size_t)(i0 + i) * B + b) * 4 + n] = (int32_t)(hq[2 * i + (n >> 1)] >> ((n & 1) * 16) & 0xffffu);
+    }
+  if (a.len_hyp)
+    for (int i = tid; i < nh; i += 256) a.len_hyp[(size_t)(i0 + i) * B + b] = hl[i];
+  if (blockIdx.y == 0) {
+    if (a.q_ref)
+      for (int e = tid; e < Nr * 4; e += 256) {
+        const int j = e >> 2, n = e & 3;
+        a.q_ref[((size_t)j * B + b) * 4 + n] = (int32_t)(rq[2 * j + (n >> 1)] >> ((n & 1) * 16) & 0xffffu);
+      }
+    if (a.len_ref)
+      for (int j = tid; j < Nr; j += 256) a.len_ref[(size_t)j * B + b] = rl[j];
+  }
+  // (3)
+  if (tid < nh) {
+    const int i = tid;
+    const uint32_t qh0 = hq[2 * i], qh1 = hq[2 * i + 1];
+    const int Lh = hl[i];
+    double u = 0.0;
+    for (int j = 0; j < Nr; ++j) {
+      const uint32_t m0 = M[2 * (i * Nr + j)], m1 = M[2 * (i * Nr + j) + 1], qr0 = rq[2 * j], qr1 = rq[2 * j + 1];
+      double s = 0.0;
+#pragma unroll
+      for (int n = 0; n < 4; ++n) {
+        const uint32_t sh = (n & 1) * 16;
+        const uint32_t m = (n < 2 ? m0 : m1) >> sh & 0xffffu, qh = (n < 2 ? qh0 : qh1) >> sh & 0xffffu, qr = (n < 2 ? qr0 : qr1) >> sh & 0xffffu;
+        if (qh > 0 && qr > 0) s += (double)m / sqrt((double)(qh * qr));
+      }
+      const double d = (double)(Lh - rl[j]);
+      s = 0.25 * s * exp(-(d * d) / (2.0 * a.sigma * a.sigma));
+      if (a.sim) a.sim[((size_t)(i0 + i) * Nr + j) * B + b] = s;
+      u += a.w ? (double)a.w[(size_t)j * B + b] * s : s;
+    }
+    a.util[(size_t)(i0 + i) * B + b] = a.w ? u : u / (double)Nr;
+  }
+}

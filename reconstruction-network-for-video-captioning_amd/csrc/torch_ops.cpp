@@ -18,6 +18,7 @@
 //   sample_search_nucleus, sample_rows_nucleus          the same with a nucleus (top-p) cut behind the top-k cut
 //   score_captions                                      teacher-forced log-probabilities of given captions (train.py:25,45, eval mode)
 //   reconstruction_error                                per-caption reconstruction error and the reconstruction (train.py:96-102 / :125-128, eval mode)
+//   consensus_rows                                      n-gram consensus (minimum-Bayes-risk) utilities of hypotheses against a reference set (no counterpart; section 16)
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
 #include <torch/library.h>
@@ -428,6 +429,42 @@ std::tuple<at::Tensor, at::Tensor> reconstruction_error(int64_t h, const at::Ten
                                  want_recon ? recon.data_ptr<float>() : nullptr, stream()), "reconstruction_error");
   return {err, recon};
 }
+// ---- consensus scoring by n-gram overlap.  hyp [N_h, T_h, B] int64, ref [N_r, T_r, B] int64 or undefined
+// (the hypotheses are their own references), weights [N_r, B] float or undefined.  Returns util [N_h, B] double, sim [N_h, N_r, B]
+// double (want_sim) and counts [N_h, N_r, B, 4], q_hyp [N_h, B, 4], q_ref [N_r, B, 4], len_hyp [N_h, B], len_ref [N_r, B] int32
+// (want_counts); what is not asked for comes back as an empty tensor.  Tokens in [0, 2^31): the caller's duty.
+using ConsensusOut = std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor>;
+ConsensusOut consensus_rows(int64_t h, const at::Tensor& hyp, const c10::optional<at::Tensor>& ref, const c10::optional<at::Tensor>& weights,
+                            double sigma, bool want_sim, bool want_counts) {
+  chk(hyp, at::kLong, "hyp");
+  TORCH_CHECK(hyp.dim() == 3 && hyp.size(0) >= 1 && hyp.size(0) <= 32 && hyp.size(1) >= 1 && hyp.size(1) <= 64 && hyp.size(2) >= 1 &&
+              hyp.size(2) <= INT32_MAX, "recnet: hyp must be [N_h in [1, 32], T_h in [1, 64], B >= 1], got ", hyp.sizes());
+  const int64_t Nh = hyp.size(0), Th = hyp.size(1), B = hyp.size(2);
+  int64_t Nr = Nh, Tr = Th;
+  const int64_t* rp = nullptr;
+  if (ref.has_value() && ref->defined()) {
+    chk(*ref, at::kLong, "ref");
+    TORCH_CHECK(ref->dim() == 3 && ref->size(0) >= 1 && ref->size(0) <= 32 && ref->size(1) >= 1 && ref->size(1) <= 64 && ref->size(2) == B,
+                "recnet: ref must be [N_r in [1, 32], T_r in [1, 64], B = ", B, "], got ", ref->sizes());
+    Nr = ref->size(0); Tr = ref->size(1); rp = ref->data_ptr<int64_t>();
+  }
+  if (weights.has_value() && weights->defined())
+    TORCH_CHECK(weights->dim() == 2 && weights->size(0) == Nr && weights->size(1) == B, "recnet: weights must be [N_r = ", Nr, ", B = ", B,
+                "], got ", weights->sizes());
+  const auto f64 = hyp.options().dtype(at::kDouble), i32 = hyp.options().dtype(at::kInt);
+  auto util = at::empty({Nh, B}, f64);
+  auto sim = want_sim ? at::empty({Nh, Nr, B}, f64) : at::empty({0}, f64);
+  auto counts = at::empty({0}, i32), qh = at::empty({0}, i32), qr = at::empty({0}, i32), lh = at::empty({0}, i32), lr = at::empty({0}, i32);
+  if (want_counts) {
+    counts = at::empty({Nh, Nr, B, 4}, i32); qh = at::empty({Nh, B, 4}, i32); qr = at::empty({Nr, B, 4}, i32);
+    lh = at::empty({Nh, B}, i32); lr = at::empty({Nr, B}, i32);
+  }
+  auto ip = [&](at::Tensor& t) { return want_counts ? t.data_ptr<int32_t>() : nullptr; };
+  ok(recnet_consensus_rows(H(h), hyp.data_ptr<int64_t>(), (int32_t)Nh, (int32_t)Th, rp, (int32_t)Nr, (int32_t)Tr, (int32_t)B,
+                           fptr(weights, "weights"), sigma, util.data_ptr<double>(), want_sim ? sim.data_ptr<double>() : nullptr, ip(counts),
+                           ip(qh), ip(qr), ip(lh), ip(lr), stream()), "consensus_rows");
+  return {util, sim, counts, qh, qr, lh, lr};
+}
 
 }  // namespace
 
@@ -458,6 +495,7 @@ TORCH_LIBRARY(recnet, m) {
   m.def("beam_search_nbest_diverse(int handle, Tensor encoder_outputs, int beam_width, float length_alpha, int n_groups, float diversity_penalty, int no_repeat_ngram, int min_length, int[] banned) -> (Tensor tokens, Tensor cum, Tensor lengths, Tensor score, Tensor group, Tensor n_steps)");
   m.def("score_captions(int handle, Tensor? encoder_outputs, Tensor tokens, float temperature) -> (Tensor logprobs, Tensor caption_logprob, Tensor lengths)");
   m.def("reconstruction_error(int handle, Tensor encoder_outputs, Tensor? tokens, Tensor? decoder_hiddens, bool want_recon) -> (Tensor err, Tensor recon)");
+  m.def("consensus_rows(int handle, Tensor hyp, Tensor? ref, Tensor? weights, float sigma, bool want_sim, bool want_counts) -> (Tensor util, Tensor sim, Tensor counts, Tensor q_hyp, Tensor q_ref, Tensor len_hyp, Tensor len_ref)");
 }
 
 // The handle is an int, so dispatch cannot key on a tensor for every op: ops with tensor arguments are registered for the
@@ -488,6 +526,7 @@ TORCH_LIBRARY_IMPL(recnet, CUDA, m) {
   m.impl("beam_search_nbest_diverse", beam_search_nbest_diverse);
   m.impl("score_captions", score_captions);
   m.impl("reconstruction_error", reconstruction_error);
+  m.impl("consensus_rows", consensus_rows);
 }
 TORCH_LIBRARY_IMPL(recnet, CompositeExplicitAutograd, m) {
   m.impl("add_reg_grad", add_reg_grad);

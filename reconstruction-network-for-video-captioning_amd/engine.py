@@ -435,6 +435,40 @@ class Engine:
                                                 _ptr(lps), _stream()), "recnet_logprob_rows")
         return lps
 
+    def consensus_rows(self, hyp, ref=None, weights=None, sigma=6.0, want_sim=False, want_counts=False):
+        """Consensus (minimum-Bayes-risk) utilities of hypotheses against a reference set by n-gram overlap (recnet_consensus_rows;
+        DESIGN.md section 16; no decoder needed, and B is the tensors', not the engine's).  hyp [N_h, T_h, B] int64 as
+        beam_search_nbest leaves its tokens; ref [N_r, T_r, B] int64, or None: the hypotheses are their own references, the term
+        j = i included; weights [N_r, B] float32 or None (uniform 1 / N_r).  Tokens in [0, 2^31): the caller's duty
+        (search.consensus_scores checks).  Returns util [N_h, B] float64; with want_sim (util, sim [N_h, N_r, B] float64); with
+        want_counts a dict of int32 tensors follows: counts [N_h, N_r, B, 4] (M_n), q_hyp [N_h, B, 4], q_ref [N_r, B, 4], len_hyp
+        [N_h, B], len_ref [N_r, B].  The library checks the ranges of N, T and sigma; the inputs are only read."""
+        if hyp.dim() != 3:
+            raise RuntimeError("hyp: expected [N_h, T_h, B], got %s" % (tuple(hyp.shape),))
+        Nh, Th, B = hyp.shape
+        _chk_tensor(hyp, (Nh, Th, B), torch.int64, "hyp")
+        Nr, Tr = Nh, Th
+        if ref is not None:
+            if ref.dim() != 3:
+                raise RuntimeError("ref: expected [N_r, T_r, B], got %s" % (tuple(ref.shape),))
+            Nr, Tr = ref.shape[:2]
+            _chk_tensor(ref, (Nr, Tr, B), torch.int64, "ref")
+        if weights is not None:
+            _chk_tensor(weights, (Nr, B), torch.float32, "weights")
+        dev = hyp.device
+        util = torch.empty(Nh, B, dtype=torch.float64, device=dev)
+        sim = torch.empty(Nh, Nr, B, dtype=torch.float64, device=dev) if want_sim else None
+        ints = None
+        if want_counts:
+            ints = {k: torch.empty(*s, dtype=torch.int32, device=dev) for k, s in
+                    (("counts", (Nh, Nr, B, 4)), ("q_hyp", (Nh, B, 4)), ("q_ref", (Nr, B, 4)), ("len_hyp", (Nh, B)), ("len_ref", (Nr, B)))}
+        ip = [_ptr(ints[k] if ints else None) for k in ("counts", "q_hyp", "q_ref", "len_hyp", "len_ref")]
+        _lib.check(self.lib.recnet_consensus_rows(self.handle, _ptr(hyp), int(Nh), int(Th), _ptr(ref), int(Nr), int(Tr), int(B),
+                                                  _ptr(weights), float(sigma), _ptr(util), _ptr(sim), *ip, _stream()),
+                   "recnet_consensus_rows")
+        out = (util,) + ((sim,) if want_sim else ()) + ((ints,) if want_counts else ())
+        return out[0] if len(out) == 1 else out
+
     def score_captions(self, enc, tokens, temperature=1.0):
         """Teacher-forced log-probabilities of given captions, eval mode (recnet_score_captions).  tokens [T, B] int64 with every
         entry in [0, V) (the caller's duty: search.score_captions checks); enc None reuses the invariants of the previous call.

@@ -254,6 +254,10 @@ def evaluate(config, score_batches, decoder, search_method, idx2word, references
     ("beam_recon", width, length_alpha, recon_weight, {...}).  The three sampling forms take an optional trailing top_p, the nucleus
     cut of search.sample_search (1.0, the default, is none): ("sample", temperature, top_k, seed, top_p), ("best_of", n, temperature,
     top_k, seed, top_p), ("best_of_recon", n, temperature, top_k, seed, recon_weight, top_p).
+    ("best_of_consensus", n, temperature, top_k, seed, consensus_weight[, top_p]) is "best_of" with consensus_weight times the
+    consensus utility of each candidate among the n added to its score, and ("beam_consensus", width, length_alpha,
+    consensus_weight[, {...}]) is "beam_nbest" reranked the same way (search.consensus_scores: n-gram overlap with the other
+    candidates, no reconstructor and no references needed; the dict is the one above, groups being the natural partner).
     references: {vid: [caption strings]}.  Returns the score dict of metrics.score_all."""
     decoder.eval()
     dev = next(decoder.parameters()).device
@@ -287,6 +291,12 @@ def evaluate(config, score_batches, decoder, search_method, idx2word, references
                     raise ValueError('the "best_of_recon" method needs a reconstructor')
                 reconstructor.eval()
                 caps = best_of_n(config, decoder, inp, hid, enc, n, temperature, top_k, seed, reconstructor, recon_weight, top_p)[0]
+            elif method == "best_of_consensus":
+                (_, n, temperature, top_k, seed, consensus_weight), top_p = _split_top_p(search_method, 6)
+                caps = best_of_n(config, decoder, inp, hid, enc, n, temperature, top_k, seed, top_p=top_p, consensus_weight=consensus_weight)[0]
+            elif method == "beam_consensus":
+                (_, width, length_alpha, consensus_weight), constraints = _split_constraints(search_method, 4)
+                caps = best_of_beam(config, decoder, inp, hid, enc, width, length_alpha, consensus_weight=consensus_weight, **constraints)[0]
             elif method == "beam_nbest":
                 (_, width, length_alpha), constraints = _split_constraints(search_method, 3)     # (search_method itself stays: it is parsed again for the next batch)
                 caps = [hyps[0][0] for hyps in beam_search_nbest(config, decoder, inp, hid, enc, width, length_alpha, **constraints)]

@@ -7,7 +7,9 @@ forward in eval mode (recnet_score_captions); best_of_n ranks sampled candidates
 question the model was built around — how well does the reconstructor recover a video's features from the decoder states of
 a caption (recnet_reconstruction_error) — and best_of_n can rank by that as well.  beam_search_nbest is a second beam search,
 standard in its scoring (sums of log-softmax, recnet_beam_search_nbest): it returns all beam_width hypotheses with scores that
-compare with score_captions / sequence_logprob, and best_of_beam reranks them by the reconstructor.
+compare with score_captions / sequence_logprob, and best_of_beam reranks them by the reconstructor.  consensus_scores ranks candidates
+by their n-gram overlap with one another (minimum-Bayes-risk selection, recnet_consensus_rows): best_of_n and best_of_beam add it to
+their score on request, on the candidates where the searches leave them.
 
 Differences from the reference that a caller can observe: `input` / `hidden` must be the start state the
 reference's own `evaluate()` builds (<SOS> tokens, zero hidden state, eval.py:131-141) — that is the only
@@ -281,16 +283,142 @@ def reconstruction_errors(config, decoder, reconstructor, encoder_outputs, capti
     return (err.cpu().tolist(), recon) if want_recon else err.cpu().tolist()
 
 
-def pick_best_of_n(caption_logprobs, lengths, rec_errors=None, recon_weight=0.0):
+# ---- consensus (minimum-Bayes-risk) reranking by n-gram overlap (recnet_consensus_rows)
+CONSENSUS_MAX_N, CONSENSUS_MAX_T = 32, 64
+_DEVICE_ENGINES = {}
+
+
+def _consensus_engine(device):
+    """A handle that supplies the device only (no decoder is bound), cached per device: recnet_consensus_rows takes its shapes as
+    arguments.  Like _rec_engine / _nbest_engine the point at which the tests put a poisoned engine in."""
+    dev = torch.device(device)
+    if dev.type == "cuda" and dev.index is None and torch.cuda.is_available():
+        dev = torch.device("cuda", torch.cuda.current_device())
+    eng = _DEVICE_ENGINES.get(dev)
+    if eng is None:
+        eng = _DEVICE_ENGINES[dev] = Engine(dict(B=2, F=2, D=8, E=4, H=8, A=4, V=8), None, "f32", device=dev)
+    return eng
+
+
+def _pad_eos(tokens, T, eos=2):
+    """tokens [T0, B] continued to T >= T0 rows with <EOS>: the words of every caption stay what they are (<PAD> rows would add
+    words to a caption without an <EOS>: to the consensus <PAD> is a word like any other)."""
+    T0, B = tokens.shape
+    return tokens if T == T0 else torch.cat([tokens, tokens.new_full((T - T0, B), eos)], dim=0)
+
+
+def _consensus_utilities(hyp):
+    """Host table [N][B] of the self-consensus utilities of checked device captions hyp [N, T, B]: one launch, one read-back."""
+    eng = _consensus_engine(hyp.device)
+    return _ops.load().consensus_rows(int(eng.handle.value), hyp, None, None, 6.0, False, False)[0].cpu().tolist()
+
+
+def _check_consensus_weight(config, consensus_weight, n):
+    """The checks of best_of_n / best_of_beam on consensus_weight; returns it as a float (0.0: the consensus takes no part)."""
+    if not (isinstance(consensus_weight, numbers.Real) and math.isfinite(consensus_weight)):
+        raise ValueError("consensus_weight must be a finite number (got %r)" % (consensus_weight,))
+    if consensus_weight == 0:
+        return 0.0
+    if n > CONSENSUS_MAX_N:
+        raise ValueError("consensus_weight != 0 takes at most %d candidates (got n = %r)" % (CONSENSUS_MAX_N, n))
+    if config.caption_max_len + 1 > CONSENSUS_MAX_T:
+        raise ValueError("consensus_weight != 0 needs caption_max_len + 1 <= %d (got %d)" % (CONSENSUS_MAX_T, config.caption_max_len + 1))
+    return float(consensus_weight)
+
+
+def _consensus_set(captions, name):
+    """The checks of consensus_scores on one caption set; returns it as a [N, T, B] LongTensor (where it lives, if a tensor)."""
+    if isinstance(captions, torch.Tensor):
+        if captions.dim() != 3 or captions.dtype != torch.long:
+            raise ValueError("%s must be a [N, T, B] LongTensor (got %s %s)" % (name, captions.dtype, tuple(captions.shape)))
+        N, T, B = captions.shape
+        sets = None
+    else:
+        sets = [[list(r) for r in c] for c in captions]
+        N = len(sets)
+        T = max((len(c) for c in sets), default=0)
+        B = len(sets[0][0]) if N and sets[0] else 0
+    if not 1 <= N <= CONSENSUS_MAX_N:
+        raise ValueError("%s must hold between 1 and %d caption sets (got %d)" % (name, CONSENSUS_MAX_N, N))
+    if sets is not None:
+        for k, c in enumerate(sets):
+            if not 1 <= len(c) <= CONSENSUS_MAX_T:
+                raise ValueError("%s[%d] must have between 1 and %d steps (got %d)" % (name, k, CONSENSUS_MAX_T, len(c)))
+            for t, r in enumerate(c):
+                if len(r) != B:
+                    raise ValueError("%s[%d][%d] holds %d tokens, %s[0][0] %d" % (name, k, t, len(r), name, B))
+                for b, v in enumerate(r):
+                    if int(v) != v or not 0 <= v < 2 ** 31:
+                        raise ValueError("%s[%d][%d][%d] = %r is not a token in [0, 2^31)" % (name, k, t, b, v))
+    if not 1 <= T <= CONSENSUS_MAX_T:
+        raise ValueError("%s must have between 1 and %d steps (got %d)" % (name, CONSENSUS_MAX_T, T))
+    if B < 1:
+        raise ValueError("%s must hold at least one caption per step (got B = %d)" % (name, B))
+    if sets is not None:
+        return torch.stack([_pad_eos(torch.tensor(c, dtype=torch.long), T) for c in sets])
+    lo, hi = (int(x) for x in torch.stack([captions.min(), captions.max()]).tolist())      # one read-back
+    if lo < 0 or hi >= 2 ** 31:
+        raise ValueError("%s holds the token %d, outside [0, 2^31)" % (name, lo if lo < 0 else hi))
+    return captions
+
+
+def consensus_scores(captions, refs=None, weights=None, sigma=6.0, want_sim=False, device=None):
+    """Consensus (minimum-Bayes-risk) utilities by n-gram overlap, on the device (recnet_consensus_rows).
+    The words of a caption column are its tokens before the first <EOS> (2); every other id, <PAD> included, is a word.  With
+    c_n(g) the occurrences of n-gram g (n = 1..4), M_n(h, r) = sum_g min(h_n(g), r_n(g)) r_n(g) and Q_n(c) = sum_g c_n(g)^2,
+        sim(h, r) = 1/4 sum_n [M_n / sqrt(Q_n(h) Q_n(r)), 0 where a Q is 0] * exp(-(L_h - L_r)^2 / (2 sigma^2))
+    — coco CIDEr's clipped cosine and length penalty with a uniform idf.  U_i = (sum_j sim(i, j)) / N_r, or sum_j w_j sim(i, j)
+    with weights [N_r][B] (finite, >= 0), summed in float64 over j ascending.  refs None: the captions are their own references,
+    the term j = i included; candidates with the same words then get bit-equal utilities.
+    captions / refs: a [N, T, B] LongTensor, or a list of N caption sets [T_k][B] (what the searches return; the T_k may differ: a
+    shorter set is continued with <EOS> rows, which leaves its words as they are).  N <= 32, T <= 64, tokens in [0, 2^31).  The call
+    needs a device, not a decoder: the tensor's, or `device` (for lists and CPU tensors; default: the current HIP device).  Returns
+    U [N][B] as Python floats, or (U, sim [N][N_r][B]) with want_sim.  Arguments are checked before any engine is asked for."""
+    if not (isinstance(sigma, numbers.Real) and math.isfinite(sigma) and sigma > 0):
+        raise ValueError("sigma must be a positive finite number (got %r)" % (sigma,))
+    hyp = _consensus_set(captions, "captions")
+    ref = None if refs is None else _consensus_set(refs, "refs")
+    if ref is not None and ref.shape[2] != hyp.shape[2]:
+        raise ValueError("refs hold %d captions per step, captions %d" % (ref.shape[2], hyp.shape[2]))
+    Nr, B = (hyp if ref is None else ref).shape[0], hyp.shape[2]
+    w = None
+    if weights is not None:
+        w = weights.detach().to("cpu", torch.float64) if isinstance(weights, torch.Tensor) else None
+        if w is None:
+            rows = [list(r) for r in weights]
+            if len(rows) != Nr or any(len(r) != B for r in rows):
+                raise ValueError("weights must be [N_r = %d][B = %d]" % (Nr, B))
+            w = torch.tensor(rows, dtype=torch.float64)
+        if tuple(w.shape) != (Nr, B):
+            raise ValueError("weights must be [N_r = %d][B = %d] (got %s)" % (Nr, B, tuple(w.shape)))
+        if not bool((torch.isfinite(w) & (w >= 0)).all()):
+            raise ValueError("weights must be finite and >= 0")
+    if device is not None:
+        dev = torch.device(device)
+    else:
+        dev = hyp.device if hyp.is_cuda else (ref.device if ref is not None and ref.is_cuda else torch.device("cuda"))
+    eng = _consensus_engine(dev)
+    dev = eng.device
+    out = _ops.load().consensus_rows(int(eng.handle.value), hyp.to(dev).contiguous(), None if ref is None else ref.to(dev).contiguous(),
+                                     None if w is None else w.to(dev, torch.float32).contiguous(), float(sigma), bool(want_sim), False)
+    util = out[0].cpu().tolist()
+    return (util, out[1].cpu().tolist()) if want_sim else util
+
+
+def pick_best_of_n(caption_logprobs, lengths, rec_errors=None, recon_weight=0.0, consensus=None, consensus_weight=0.0):
     """The selection rule of best_of_n on host tables [n][B]: for each caption the candidate k with the largest score
-    caption_logprobs[k][b] / lengths[k][b] - recon_weight * rec_errors[k][b], the lowest k among equals (rec_errors None: the
-    first term alone).  Returns (chosen k [B], score [B])."""
+    caption_logprobs[k][b] / lengths[k][b] - recon_weight * rec_errors[k][b] + consensus_weight * consensus[k][b], the lowest k
+    among equals (rec_errors None: without the second term; consensus None: without the third — the call without the two new
+    arguments computes what it always did).  consensus: the utilities of consensus_scores; candidates with the same words carry
+    the same bits there, so duplicates are decided by k on every run.  Returns (chosen k [B], score [B])."""
     n = len(caption_logprobs)
     B = len(caption_logprobs[0]) if n else 0
 
     def score(k, b):
         s = caption_logprobs[k][b] / lengths[k][b]
-        return s if rec_errors is None else s - recon_weight * rec_errors[k][b]
+        if rec_errors is not None:
+            s = s - recon_weight * rec_errors[k][b]
+        return s if consensus is None else s + consensus_weight * consensus[k][b]
     ks, scores = [], []
     for b in range(B):
         best_k, best = 0, score(0, b)
@@ -303,7 +431,7 @@ def pick_best_of_n(caption_logprobs, lengths, rec_errors=None, recon_weight=0.0)
 
 
 def best_of_n(config, decoder, input, hidden, encoder_outputs, n, temperature=1.0, top_k=0, seed=0, reconstructor=None,
-              recon_weight=0.0, top_p=1.0):
+              recon_weight=0.0, top_p=1.0, consensus_weight=0.0):
     """n sampled candidates per video, ranked by the model's own length-normalised log-probability.  Candidate k is
     sample_search's rollout with seed (seed + k) & 0xFFFFFFFF; every candidate set is scored by score_captions at temperature
     1 (the sampler's own log-probabilities are under the tempered / cut distribution), the invariants of the features computed
@@ -314,12 +442,16 @@ def best_of_n(config, decoder, input, hidden, encoder_outputs, n, temperature=1.
     once.  That costs one more decoder chain pass per candidate set — the reconstruction error runs its own teacher-forced
     forward instead of reusing the scorer's states — which keeps the log-probability half bit for bit what it is without a
     reconstructor.  top_p is sample_search's nucleus cut on the rollouts; like temperature and top_k it shapes the candidates
-    only, the scores stay those of the full distribution at temperature 1.  Returns (captions: [B] token lists cut after their
-    <EOS>, chosen k [B], score [B])."""
+    only, the scores stay those of the full distribution at temperature 1.  consensus_weight != 0 adds consensus_weight * U_k to
+    the score, U the consensus utilities of the n candidates among themselves (consensus_scores): the
+    candidate sets are stacked on the device at the common length of the longest rollout, one more launch, and the n x B utilities
+    are one more read-back; it needs n <= 32 and caption_max_len + 1 <= 64.  consensus_weight = 0 launches nothing new.  Returns
+    (captions: [B] token lists cut after their <EOS>, chosen k [B], score [B])."""
     if int(n) != n or n < 1:
         raise ValueError("n must be a positive integer (got %r)" % (n,))
     _check_top_p(top_p)
     use_rec, recon_weight = _check_recon_weight(config, decoder, reconstructor, encoder_outputs, recon_weight)
+    consensus_weight = _check_consensus_weight(config, consensus_weight, n)
     cands = [sample_search(config, decoder, input, hidden, encoder_outputs, temperature, top_k, (seed + k) & 0xFFFFFFFF, top_p)[0]
              for k in range(int(n))]
     caps, lens, checked = [], [], []
@@ -334,7 +466,11 @@ def best_of_n(config, decoder, input, hidden, encoder_outputs, n, temperature=1.
         t_star = max(tokens.shape[0] for tokens in checked)
         errs = [_rec_errors(config, decoder, reconstructor, encoder_outputs, canonical_captions(tokens, t_star))[0] for tokens in checked]
         errs = torch.stack(errs).cpu().tolist()
-    ks, scores = pick_best_of_n(caps, lens, errs, recon_weight)
+    util = None
+    if consensus_weight != 0:
+        t_star = max(tokens.shape[0] for tokens in checked)
+        util = _consensus_utilities(torch.stack([_pad_eos(tokens.to(encoder_outputs.device), t_star) for tokens in checked]))
+    ks, scores = pick_best_of_n(caps, lens, errs, recon_weight, util, consensus_weight)
     out = [[cands[k][t][b] for t in range(lens[k][b])] for b, k in enumerate(ks)]
     return out, ks, scores
 
@@ -452,23 +588,28 @@ def nbest_diversity(hyps):
 
 
 def best_of_beam(config, decoder, input, hidden, encoder_outputs, beam_width, length_alpha=0.0, reconstructor=None,
-                 recon_weight=0.0, no_repeat_ngram=0, min_length=0, banned_tokens=(), n_groups=1, diversity_penalty=0.0):
+                 recon_weight=0.0, no_repeat_ngram=0, min_length=0, banned_tokens=(), n_groups=1, diversity_penalty=0.0,
+                 consensus_weight=0.0):
     """The beam_width hypotheses of beam_search_nbest, reranked like best_of_n's candidates: per video the rank k with the largest
     cum / length - recon_weight * rec_error (pick_best_of_n, the lowest k among equals; without a reconstructor or with
     recon_weight = 0 the first term alone).  Every rank of the search is a canonical [n_steps, B] caption set already, so it goes to
     the reconstruction error as it is, all ranks at the common T = n_steps (the global error depends on T).  no_repeat_ngram /
     min_length / banned_tokens / n_groups / diversity_penalty are beam_search_nbest's: with groups the reconstructor is given
-    hypotheses that differ.  Returns what best_of_n returns: (captions: [B] token lists cut after their <EOS>, chosen k [B],
-    score [B])."""
+    hypotheses that differ.  consensus_weight != 0 adds consensus_weight * U_k, the consensus utilities of the ranks among
+    themselves (consensus_scores) on the search's own device tensor: one more launch and one more read-back,
+    of the beam_width x B utilities; it needs caption_max_len + 1 <= 64, and 0 launches nothing new.  Returns what best_of_n
+    returns: (captions: [B] token lists cut after their <EOS>, chosen k [B], score [B])."""
     use_rec, recon_weight = _check_recon_weight(config, decoder, reconstructor, encoder_outputs, recon_weight)
+    consensus_weight = _check_consensus_weight(config, consensus_weight, 1)
     toks, cum, ln, _ = _beam_nbest(config, decoder, input, hidden, encoder_outputs, beam_width, length_alpha, no_repeat_ngram,
                                    min_length, banned_tokens, n_groups, diversity_penalty)
     errs = None
     if use_rec:
         errs = torch.stack([_rec_errors(config, decoder, reconstructor, encoder_outputs, toks[r])[0]
                             for r in range(int(beam_width))]).cpu().tolist()
+    util = _consensus_utilities(toks.contiguous()) if consensus_weight != 0 else None
     lens = ln.cpu().tolist()
-    ks, scores = pick_best_of_n(cum.cpu().tolist(), lens, errs, recon_weight)
+    ks, scores = pick_best_of_n(cum.cpu().tolist(), lens, errs, recon_weight, util, consensus_weight)
     toks = toks.cpu().tolist()
     out = [[toks[k][t][b] for t in range(lens[k][b])] for b, k in enumerate(ks)]
     return out, ks, scores
