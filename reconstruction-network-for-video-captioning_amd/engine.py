@@ -129,6 +129,14 @@ class Engine:
                               float(hy["adam_beta2"]), float(hy["adam_eps"])) for w, n in ((0, "decoder"), (1, "reconstructor"))}
         self.captured_steps = weakref.WeakSet()      # live api.GraphedStep objects: their graphs hold opt_hyper as kernel arguments
 
+    @classmethod
+    def device_only(cls, device=None, precision="f32"):
+        """A handle that supplies a device and nothing else, for the entries that take their shapes as arguments (the row kernels
+        of the searches, recnet_consensus_rows, the GEMM hooks; precision is what the `gemm` hook dispatches on)."""
+        # Any handle will do, so the dims are placeholders: those entries ask the handle for a bound workspace (REQUIRE_WS in
+        # csrc/host_common.inc) and for nothing else — no dims, no weights.
+        return cls(dict(B=2, F=2, D=8, E=4, H=8, A=4, V=8), None, precision, device=device)
+
     def __del__(self):
         try:
             if getattr(self, "handle", None) is not None and self.handle.value:

@@ -239,26 +239,50 @@ def _split_top_p(search_method, n):
     return search_method[:n], search_method[n]
 
 
+def _by_caption(steps):
+    """[n_steps][B] token lists (greedy_search, sample_search) as one token list per caption."""
+    return list(map(list, zip(*steps)))
+
+
+# The search methods evaluate() takes besides "greedy": name -> (the fields behind the name, the optional trailing field, whether
+# `reconstructor` is needed, the call).  A method is (name, *fields) or (name, *fields, tail).  The tail "top_p" is the nucleus cut
+# of search.sample_search (default 1.0: none); the tail "constraints" is a dict with keys of _CONSTRAINT_KEYS, the constraints and
+# groups of search.beam_search_nbest (default: none).  The call gets the five leading arguments of every runner, the fields, the tail
+# and the reconstructor, and returns one token list per caption; it looks its runner up in the module's globals when it runs.
+_TAILS = {"top_p": _split_top_p, "constraints": _split_constraints}
+_METHODS = {
+    # the reference's beam search; read by position, without an arity check: fields behind the width are ignored
+    "beam": (("width",), None, False, lambda a, f, _, rec: beam_search(a[0], f[0], None, *a[1:])),
+    # one sampled rollout
+    "sample": (("temperature", "top_k", "seed"), "top_p", False, lambda a, f, top_p, rec: _by_caption(sample_search(*a, *f, top_p)[0])),
+    # search.best_of_n: the best of n sampled candidates by the model's length-normalised log-probability, ...
+    "best_of": (("n", "temperature", "top_k", "seed"), "top_p", False, lambda a, f, top_p, rec: best_of_n(*a, *f, top_p=top_p)[0]),
+    # ... with recon_weight times the reconstruction error of `reconstructor` subtracted from the score, ...
+    "best_of_recon": (("n", "temperature", "top_k", "seed", "recon_weight"), "top_p", True,
+                      lambda a, f, top_p, rec: best_of_n(*a, *f[:4], rec, f[4], top_p)[0]),
+    # ... with consensus_weight times the consensus utility of each candidate among the n added to it (search.consensus_scores:
+    # n-gram overlap with the other candidates, no reconstructor and no references needed)
+    "best_of_consensus": (("n", "temperature", "top_k", "seed", "consensus_weight"), "top_p", False,
+                          lambda a, f, top_p, rec: best_of_n(*a, *f[:4], top_p=top_p, consensus_weight=f[4])[0]),
+    # search.beam_search_nbest: the first-ranked hypothesis of the beam search on log-probabilities
+    "beam_nbest": (("width", "length_alpha"), "constraints", False,
+                   lambda a, f, con, rec: [hyps[0][0] for hyps in beam_search_nbest(*a, *f, **con)]),
+    # search.best_of_beam: its hypotheses reranked with the reconstruction error of `reconstructor`, ...
+    "beam_recon": (("width", "length_alpha", "recon_weight"), "constraints", True,
+                   lambda a, f, con, rec: best_of_beam(*a, *f[:2], rec, f[2], **con)[0]),
+    # ... or with their consensus utility (groups are the natural partner)
+    "beam_consensus": (("width", "length_alpha", "consensus_weight"), "constraints", False,
+                       lambda a, f, con, rec: best_of_beam(*a, *f[:2], consensus_weight=f[2], **con)[0]),
+}
+
+
 @torch.no_grad()
 def evaluate(config, score_batches, decoder, search_method, idx2word, references, reconstructor=None):
     """score_batches: iterable of (vids, enc [B,F,D]) with B == config.batch_size (the score loader repeats its last
-    sample to fill the batch, dataset/MSVD.py:76-93; "PAD" ids are dropped like eval.py:145).  search_method: "greedy",
-    ("beam", width), ("sample", temperature, top_k, seed) or ("best_of", n, temperature, top_k, seed) (search.best_of_n: the
-    best of n sampled candidates by the model's length-normalised log-probability) or ("best_of_recon", n, temperature, top_k,
-    seed, recon_weight) (the same with recon_weight times the reconstruction error of `reconstructor` subtracted from the score),
-    ("beam_nbest", width, length_alpha) (search.beam_search_nbest: the first-ranked hypothesis of the beam search on
-    log-probabilities) or ("beam_recon", width, length_alpha, recon_weight) (search.best_of_beam: its hypotheses reranked with the
-    reconstruction error of `reconstructor`).  The two beam forms take an optional trailing dict with the keys no_repeat_ngram,
-    min_length and banned_tokens (the constraints of search.beam_search_nbest) and n_groups and diversity_penalty (its diverse
-    form): ("beam_nbest", width, length_alpha, {...}),
-    ("beam_recon", width, length_alpha, recon_weight, {...}).  The three sampling forms take an optional trailing top_p, the nucleus
-    cut of search.sample_search (1.0, the default, is none): ("sample", temperature, top_k, seed, top_p), ("best_of", n, temperature,
-    top_k, seed, top_p), ("best_of_recon", n, temperature, top_k, seed, recon_weight, top_p).
-    ("best_of_consensus", n, temperature, top_k, seed, consensus_weight[, top_p]) is "best_of" with consensus_weight times the
-    consensus utility of each candidate among the n added to its score, and ("beam_consensus", width, length_alpha,
-    consensus_weight[, {...}]) is "beam_nbest" reranked the same way (search.consensus_scores: n-gram overlap with the other
-    candidates, no reconstructor and no references needed; the dict is the one above, groups being the natural partner).
-    references: {vid: [caption strings]}.  Returns the score dict of metrics.score_all."""
+    sample to fill the batch, dataset/MSVD.py:76-93; "PAD" ids are dropped like eval.py:145).  search_method: "greedy", or a
+    tuple or list in one of the forms of _METHODS, such as ("beam", 5) or ("beam_nbest", 5, 0.7, {"min_length": 3}); it is
+    parsed again for every batch.  reconstructor: for the methods that rerank by it.  references: {vid: [caption strings]}.
+    Returns the score dict of metrics.score_all."""
     decoder.eval()
     dev = next(decoder.parameters()).device
     B, H = config.batch_size, decoder.hidden_size
@@ -272,42 +296,18 @@ def evaluate(config, score_batches, decoder, search_method, idx2word, references
         if isinstance(search_method, str):
             if search_method != "greedy":
                 raise NotImplementedError("Unknown search method: {}".format(search_method))
-            steps = greedy_search(config, decoder, inp, hid, enc)                     # [n_steps][B]
-            caps = list(map(list, zip(*steps)))
+            caps = _by_caption(greedy_search(config, decoder, inp, hid, enc))
         else:
-            method = search_method[0]
-            if method == "beam":
-                caps = beam_search(config, search_method[1], None, decoder, inp, hid, enc)
-            elif method == "sample":
-                (_, temperature, top_k, seed), top_p = _split_top_p(search_method, 4)
-                steps, _ = sample_search(config, decoder, inp, hid, enc, temperature, top_k, seed, top_p)
-                caps = list(map(list, zip(*steps)))
-            elif method == "best_of":
-                (_, n, temperature, top_k, seed), top_p = _split_top_p(search_method, 5)
-                caps = best_of_n(config, decoder, inp, hid, enc, n, temperature, top_k, seed, top_p=top_p)[0]
-            elif method == "best_of_recon":
-                (_, n, temperature, top_k, seed, recon_weight), top_p = _split_top_p(search_method, 6)
+            name = search_method[0]
+            if not isinstance(name, str) or name not in _METHODS:
+                raise NotImplementedError("Unknown search method: {}".format(name))
+            fields, tail, needs_reconstructor, run = _METHODS[name]
+            head, extra = _TAILS[tail](search_method, 1 + len(fields)) if tail else (search_method, None)
+            if needs_reconstructor:
                 if reconstructor is None:
-                    raise ValueError('the "best_of_recon" method needs a reconstructor')
+                    raise ValueError('the "%s" method needs a reconstructor' % name)
                 reconstructor.eval()
-                caps = best_of_n(config, decoder, inp, hid, enc, n, temperature, top_k, seed, reconstructor, recon_weight, top_p)[0]
-            elif method == "best_of_consensus":
-                (_, n, temperature, top_k, seed, consensus_weight), top_p = _split_top_p(search_method, 6)
-                caps = best_of_n(config, decoder, inp, hid, enc, n, temperature, top_k, seed, top_p=top_p, consensus_weight=consensus_weight)[0]
-            elif method == "beam_consensus":
-                (_, width, length_alpha, consensus_weight), constraints = _split_constraints(search_method, 4)
-                caps = best_of_beam(config, decoder, inp, hid, enc, width, length_alpha, consensus_weight=consensus_weight, **constraints)[0]
-            elif method == "beam_nbest":
-                (_, width, length_alpha), constraints = _split_constraints(search_method, 3)     # (search_method itself stays: it is parsed again for the next batch)
-                caps = [hyps[0][0] for hyps in beam_search_nbest(config, decoder, inp, hid, enc, width, length_alpha, **constraints)]
-            elif method == "beam_recon":
-                (_, width, length_alpha, recon_weight), constraints = _split_constraints(search_method, 4)
-                if reconstructor is None:
-                    raise ValueError('the "beam_recon" method needs a reconstructor')
-                reconstructor.eval()
-                caps = best_of_beam(config, decoder, inp, hid, enc, width, length_alpha, reconstructor, recon_weight, **constraints)[0]
-            else:
-                raise NotImplementedError("Unknown search method: {}".format(method))
+            caps = run((config, decoder, inp, hid, enc), head[1:], extra, reconstructor)
         for vid, c in zip(vids, caps):
             if vid != "PAD" and vid not in res:
                 res[vid] = [metrics.indices_to_sentence(c, idx2word)]

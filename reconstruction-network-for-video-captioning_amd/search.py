@@ -294,10 +294,9 @@ def _consensus_engine(device):
     dev = torch.device(device)
     if dev.type == "cuda" and dev.index is None and torch.cuda.is_available():
         dev = torch.device("cuda", torch.cuda.current_device())
-    eng = _DEVICE_ENGINES.get(dev)
-    if eng is None:
-        eng = _DEVICE_ENGINES[dev] = Engine(dict(B=2, F=2, D=8, E=4, H=8, A=4, V=8), None, "f32", device=dev)
-    return eng
+    if dev not in _DEVICE_ENGINES:
+        _DEVICE_ENGINES[dev] = Engine.device_only(dev)
+    return _DEVICE_ENGINES[dev]
 
 
 def _pad_eos(tokens, T, eos=2):
@@ -430,6 +429,20 @@ def pick_best_of_n(caption_logprobs, lengths, rec_errors=None, recon_weight=0.0,
     return ks, scores
 
 
+def _rerank(caption_logprobs, lengths, recon_weight, rec_args, rec_tokens, consensus_weight, hyp):
+    """The tail of best_of_n / best_of_beam on host tables [n][B] of sums and lengths.  rec_tokens: the n candidate sets as
+    _rec_errors takes them behind its leading arguments rec_args (checked, canonical, one common T), or None: no reconstruction
+    error; the n x B errors are read back once.  hyp: the candidates stacked [n, T, B] on the device, or None: no consensus."""
+    errs = None if rec_tokens is None else torch.stack([_rec_errors(*rec_args, tokens)[0] for tokens in rec_tokens]).cpu().tolist()
+    util = None if hyp is None else _consensus_utilities(hyp)
+    return pick_best_of_n(caption_logprobs, lengths, errs, recon_weight, util, consensus_weight)
+
+
+def _cut_winners(tokens, ks, lengths):
+    """Per caption b the tokens[k][t][b] of its winner k = ks[b], cut after their <EOS> (at lengths[k][b])."""
+    return [[tokens[k][t][b] for t in range(lengths[k][b])] for b, k in enumerate(ks)]
+
+
 def best_of_n(config, decoder, input, hidden, encoder_outputs, n, temperature=1.0, top_k=0, seed=0, reconstructor=None,
               recon_weight=0.0, top_p=1.0, consensus_weight=0.0):
     """n sampled candidates per video, ranked by the model's own length-normalised log-probability.  Candidate k is
@@ -459,20 +472,12 @@ def best_of_n(config, decoder, input, hidden, encoder_outputs, n, temperature=1.
         tokens = _caption_tensor(config, decoder, encoder_outputs.shape[0], toks)
         _, cap, ln = _score(decoder, encoder_outputs, tokens, 1.0, k > 0, config.caption_max_len)
         caps.append(cap); lens.append(ln); checked.append(tokens)
-    caps = torch.stack(caps).cpu().tolist()          # one read-back each for the n x B sums and lengths
-    lens = torch.stack(lens).cpu().tolist()
-    errs = None
-    if use_rec:
-        t_star = max(tokens.shape[0] for tokens in checked)
-        errs = [_rec_errors(config, decoder, reconstructor, encoder_outputs, canonical_captions(tokens, t_star))[0] for tokens in checked]
-        errs = torch.stack(errs).cpu().tolist()
-    util = None
-    if consensus_weight != 0:
-        t_star = max(tokens.shape[0] for tokens in checked)
-        util = _consensus_utilities(torch.stack([_pad_eos(tokens.to(encoder_outputs.device), t_star) for tokens in checked]))
-    ks, scores = pick_best_of_n(caps, lens, errs, recon_weight, util, consensus_weight)
-    out = [[cands[k][t][b] for t in range(lens[k][b])] for b, k in enumerate(ks)]
-    return out, ks, scores
+    caps, lens = (torch.stack(x).cpu().tolist() for x in (caps, lens))      # one read-back each for the n x B sums and lengths
+    t_star = max(tokens.shape[0] for tokens in checked)
+    rec_tokens = [canonical_captions(tokens, t_star) for tokens in checked] if use_rec else None
+    hyp = torch.stack([_pad_eos(tokens.to(encoder_outputs.device), t_star) for tokens in checked]) if consensus_weight != 0 else None
+    ks, scores = _rerank(caps, lens, recon_weight, (config, decoder, reconstructor, encoder_outputs), rec_tokens, consensus_weight, hyp)
+    return _cut_winners(cands, ks, lens), ks, scores
 
 
 def _check_beam(decoder, beam_width, length_alpha):
@@ -603,13 +608,8 @@ def best_of_beam(config, decoder, input, hidden, encoder_outputs, beam_width, le
     consensus_weight = _check_consensus_weight(config, consensus_weight, 1)
     toks, cum, ln, _ = _beam_nbest(config, decoder, input, hidden, encoder_outputs, beam_width, length_alpha, no_repeat_ngram,
                                    min_length, banned_tokens, n_groups, diversity_penalty)
-    errs = None
-    if use_rec:
-        errs = torch.stack([_rec_errors(config, decoder, reconstructor, encoder_outputs, toks[r])[0]
-                            for r in range(int(beam_width))]).cpu().tolist()
-    util = _consensus_utilities(toks.contiguous()) if consensus_weight != 0 else None
     lens = ln.cpu().tolist()
-    ks, scores = pick_best_of_n(cum.cpu().tolist(), lens, errs, recon_weight, util, consensus_weight)
-    toks = toks.cpu().tolist()
-    out = [[toks[k][t][b] for t in range(lens[k][b])] for b, k in enumerate(ks)]
-    return out, ks, scores
+    ks, scores = _rerank(cum.cpu().tolist(), lens, recon_weight, (config, decoder, reconstructor, encoder_outputs),
+                         [toks[r] for r in range(int(beam_width))] if use_rec else None, consensus_weight,
+                         toks.contiguous() if consensus_weight != 0 else None)
+    return _cut_winners(toks.cpu().tolist(), ks, lens), ks, scores

@@ -187,7 +187,7 @@ RUN_CAPTIONS = {("search_small_b", 3, 7): 4, ("search_small_b", 5, 7): 3, ("sear
 
 
 if __name__ == "__main__":
-    from tests.test_search_oracle import load_search_case
+    from tests.golden_util import load_search_case
     for name, bw, cml, cap in SEARCH_RUNS:
         g, P, enc = load_search_case(name)
         r = beam_search_nbest(P, enc, bw, LENGTH_ALPHA, cml, g["_cell"])

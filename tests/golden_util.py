@@ -73,6 +73,39 @@ def load(name):
     return {k: z[k] for k in z.files}
 
 
+CASES = ["search_small", "search_small_b", "search_eos", "search_stop", "search_gru", "search_gru_b", "search_gru_stop"]
+
+
+def load_search_case(name):
+    """(golden, decoder parameters, features) of one of the search goldens (CASES)."""
+    g = load(name)
+    B, F, D, V, E, H, A = [int(x) for x in g["meta_dims"]]
+    g["_cell"] = cells_of(g)[0]
+    P = formula_params(decoder_shapes(V, E, H, A, D, g["_cell"]), int(g["meta_seed"]))
+    sc = float(g["meta_scale"])
+    P["out.weight"] = P["out.weight"] * sc
+    P["out.bias"] = P["out.bias"] * sc
+    P["out.bias"][2] += float(g["meta_eos_bias"])
+    P["out.bias"][0] += float(g["meta_pad_bias"])
+    return g, P, torch.from_numpy(g["enc"])
+
+
+RECSTEP_CASES = ["recstep_global_eval", "recstep_global_train", "recstep_local_eval", "recstep_local_train",
+                 "recstep_global_gru", "recstep_local_gru"]
+
+
+def load_recstep_case(name):
+    """(golden, dims, kind, cell, reconstructor parameters, seeded decoder hiddens [T, 1, B, H]) of one of RECSTEP_CASES."""
+    g = load(name)
+    B, T, F, H, R, RA = [int(x) for x in g["meta_dims"]]
+    kind = "global" if "global" in name else "local"
+    cell = "GRU" if int(g["meta_gru"]) else "LSTM"
+    P = formula_params(rec_shapes(kind, H, R, RA, cell), int(g["meta_seed"]))
+    gen = torch.Generator().manual_seed(int(g["meta_seed"]) + 50)
+    hid = torch.tanh(torch.randn(T, 1, B, H, generator=gen)) * 0.6
+    return g, (B, T, F, H, R, RA), kind, cell, P, hid
+
+
 def group(g, prefix):
     """{'key': tensor} for every entry 'prefix/key'."""
     n = len(prefix) + 1

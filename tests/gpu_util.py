@@ -15,6 +15,16 @@ TOL = {
     # bf16: 3 Adam steps of lr 1e-5: a sign flip of a tiny gradient moves a parameter by up to 2*lr per step
     "bf16": dict(loss=1e-3, hid=1e-2, grad=2e-2, param=6e-5, cos=0.9995),
 }
+REG_SLACK = 3e-4
+# update-path bars at learning rates of 1e-2: ||(got - init) - (ref - init)|| / ||ref - init|| per tensor, and the same for the
+# Adam moments.  An update that did not happen is an error of 1.0 (0.25 for one of four); bf16 operand rounding flips the sign of
+# near-zero gradient elements, each of which moves its parameter by 2 lr instead of 0 in the first step.
+LR_TOL = {"f32": dict(move=2e-3, m=1e-3, v=2e-3), "bf16": dict(move=8e-2, m=3e-2, v=6e-2)}
+
+
+def moved(got, ref, init):
+    d = np.linalg.norm((ref - init).astype(np.float64))
+    return float(np.linalg.norm(((got - init) - (ref - init)).astype(np.float64)) / max(d, 1e-30)), d
 
 
 def make_models(dims, kind, precision, decP, recP, device="cuda", batch=None, cells=("LSTM", "LSTM"), attn_normalize="none",

@@ -19,8 +19,8 @@ EOS = 2
 
 def row_bar(prec, amax, temperature):
     """Error bar of one log-probability: a logit minus a log-sum-exp of logits, each within the per-step logits bar of
-    tests/test_gpu_parity.py (TOL[prec]["hid"] * 4 * max(1, max |logit|)), divided by the temperature.  The _lp_bar of
-    tests/test_gpu_sample.py."""
+    tests/test_gpu_parity.py (TOL[prec]["hid"] * 4 * max(1, max |logit|)), divided by the temperature.  The lp_bar of
+    tests/search_kit.py."""
     return 2.0 * TOL[prec]["hid"] * 4 * max(1.0, float(amax)) / temperature
 
 

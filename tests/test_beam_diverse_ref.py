@@ -12,7 +12,7 @@ from tests import beam_constrained_ref as CR
 from tests import beam_diverse_ref as DR
 from tests import beam_ref as BR
 from tests import score_ref as SC
-from tests.test_search_oracle import load_search_case
+from tests.golden_util import load_search_case
 
 
 @functools.lru_cache(maxsize=None)

@@ -8,7 +8,7 @@ import pytest
 
 from tests import beam_ref as BR
 from tests import score_ref as SC
-from tests.test_search_oracle import CASES, load_search_case
+from tests.golden_util import CASES, load_search_case
 
 
 @functools.lru_cache(maxsize=None)

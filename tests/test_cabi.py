@@ -140,7 +140,7 @@ def test_product_path_fails_loudly_without_gpu():
         pytest.skip("GPU present")
     from recnet_amd.engine import Engine
     with pytest.raises(RuntimeError, match="needs a GPU"):
-        Engine(dict(B=2, F=2, D=8, E=4, H=8, A=4, V=8), None, "bf16")
+        Engine.device_only()
 
 
 def test_missing_library_is_an_error_not_a_fallback(monkeypatch, tmp_path):

@@ -5,7 +5,7 @@ argument checks.
 
 Indices / tokens are compared outside the decisions the restatement marks as near-ties (margin below 1e-3; the caps on how many
 those may be are held without a GPU by tests/test_beam_ref.py).  A candidate is a cum plus a log-probability: it is held to the
-row bar of tests/test_gpu_sample.py's _lp_bar at temperature 1 (= score_ref.row_bar) plus two units in the last place of |cum|; a
+row bar of tests/search_kit.py's lp_bar at temperature 1 (= score_ref.row_bar) plus two units in the last place of |cum|; a
 hypothesis' cum to its length times the row bar.  Every test prints its worst error / bar."""
 import functools
 
@@ -18,9 +18,10 @@ from recnet_amd import _ops, search
 from tests import beam_ref as BR
 from tests import golden_util as GU
 from tests import score_ref as SC
+from tests.golden_util import load_search_case
 from tests.gpu_util import make_models
 from tests.sample_ref import NEAR_TIE
-from tests.test_search_oracle import load_search_case
+from tests.search_kit import decoder_for, rows_engine
 
 pytestmark = pytest.mark.gpu
 
@@ -30,15 +31,9 @@ Engine, _lib = R.engine.Engine, R.engine._lib
 
 # ------------------------------------------------------------------------------------------------ 1. the selection kernel alone
 @functools.lru_cache(maxsize=None)
-def _rows_engine():
-    """A handle for recnet_beam_select_rows: it supplies the device only, no decoder is bound."""
-    return Engine(dict(B=2, F=2, D=8, E=4, H=8, A=4, V=8), None, "f32")
-
-
-@functools.lru_cache(maxsize=None)
 def _row_results(V):
     """Every kernel-alone case at vocabulary V, device (two calls) and restatement side by side (computed once)."""
-    eng = _rows_engine()
+    eng = rows_engine()
     out = []
     for nb in BR.ROW_NB:
         for kind in BR.ROW_KINDS:
@@ -93,26 +88,6 @@ def test_select_rows(V):
 
 
 # ------------------------------------------------------------------------------------------------ 2. the search
-class _Cfg:
-    caption_max_len = 30
-    decoder_model = "LSTM"
-
-
-def _decoder(g, P, prec, cml=30):
-    B, F, D, V, E, H, A = [int(x) for x in g["meta_dims"]]
-    cell = g["_cell"]
-    dec = R.Decoder(cell, 1, D, E, 1, H, A, V, 0.5, 0.5, 0.5, precision=prec)
-    dec.load_state_dict(P)
-    dec = dec.cuda().eval()
-    cfg = _Cfg()
-    cfg.batch_size, cfg.decoder_model, cfg.caption_max_len = B, cell, cml
-    inp = torch.full((1, B), 1, dtype=torch.long, device="cuda")
-    hid = (torch.zeros(1, B, H, device="cuda"), torch.zeros(1, B, H, device="cuda"))
-    if cell == "GRU":
-        hid = hid[0]
-    return dec, cfg, inp, hid
-
-
 @pytest.mark.parametrize("name,bw,cml,cap", BR.SEARCH_RUNS)
 def test_search_matches_the_restatement(name, bw, cml, cap):
     """fp32 path: n_steps (when no caption is excluded), tokens, len and the rank order equal the restatement on the captions without
@@ -120,7 +95,7 @@ def test_search_matches_the_restatement(name, bw, cml, cap):
     compared up to that decision: the first t0 tokens of each of its returned hypotheses against the restatement's beams."""
     g, P, enc = load_search_case(name)
     r = BR.beam_search_nbest(P, enc, bw, BR.LENGTH_ALPHA, cml, g["_cell"])
-    dec, cfg, inp, hid = _decoder(g, P, "f32", cml)
+    dec, cfg, inp, hid = decoder_for(g, P, "f32", cml)
     toks, cum, ln, score = search._beam_nbest(cfg, dec, inp, hid, enc.cuda(), bw, BR.LENGTH_ALPHA)
     toks, cum, ln, score = toks.cpu().numpy(), cum.cpu().numpy().astype(np.float64), ln.cpu().numpy(), score.cpu().numpy().astype(np.float64)
     keep = BR.comparable_captions(r)
@@ -169,7 +144,7 @@ def test_self_consistency(name, prec):
     score_captions on each returned rank reproduces len exactly and cum within len x the row bar of the precision; a second call
     gives the same bits; every rank is canonical."""
     g, P, enc = load_search_case(name)
-    dec, cfg, inp, hid = _decoder(g, P, prec)
+    dec, cfg, inp, hid = decoder_for(g, P, prec)
     encd = enc.cuda()
     greedy = np.array(R.greedy_search(cfg, dec, inp, hid, encd), dtype=np.int64)      # [n][B]
     t1, _, l1, _ = search._beam_nbest(cfg, dec, inp, hid, encd, 1, 0.0)
@@ -248,7 +223,7 @@ def test_best_of_beam_and_evaluate(kind):
 # ------------------------------------------------------------------------------------------------ 4. errors
 def test_library_refuses_bad_arguments_and_recovers():
     g, P, enc = load_search_case("search_small")
-    dec, cfg, inp, hid = _decoder(g, P, "f32")
+    dec, cfg, inp, hid = decoder_for(g, P, "f32")
     encd = enc.cuda()
     B, F, V = enc.shape[0], enc.shape[1], int(g["meta_dims"][3])
     eng = Engine(dec.dims(B, F), None, "f32", dec.hyper(), device=encd.device)

@@ -20,9 +20,10 @@ from tests import beam_constrained_ref as CR
 from tests import beam_ref as BR
 from tests import golden_util as GU
 from tests import score_ref as SC
+from tests.golden_util import load_search_case
 from tests.gpu_util import make_models
 from tests.sample_ref import NEAR_TIE
-from tests.test_search_oracle import load_search_case
+from tests.search_kit import Cfg, decoder_for, rows_engine
 
 pytestmark = pytest.mark.gpu
 
@@ -30,15 +31,9 @@ Engine, _lib = R.engine.Engine, R.engine._lib
 
 
 # ------------------------------------------------------------------------------------------------ 1. the selection kernel alone
-@functools.lru_cache(maxsize=None)
-def _rows_engine():
-    """A handle for recnet_beam_select_rows_constrained: it supplies the device only, no decoder is bound."""
-    return Engine(dict(B=2, F=2, D=8, E=4, H=8, A=4, V=8), None, "f32")
-
-
 def _run_case(c, bws):
     """One kernel-alone case on the device (two calls per width) next to the restatement; returns the worst error / bar."""
-    eng = _rows_engine()
+    eng = rows_engine()
     x, cum, fin, hist = c["x"], c["cum"], c["fin"], c["hist"]
     nb, rows, V = x.shape
     t, n, m, banned = c["t"], c["n"], c["m"], c["banned"]
@@ -124,26 +119,6 @@ def test_select_rows_constrained_long_rows():
 
 
 # ------------------------------------------------------------------------------------------------ 2. the search
-class _Cfg:
-    caption_max_len = 30
-    decoder_model = "LSTM"
-
-
-def _decoder(g, P, prec, cml=30):
-    B, F, D, V, E, H, A = [int(x) for x in g["meta_dims"]]
-    cell = g["_cell"]
-    dec = R.Decoder(cell, 1, D, E, 1, H, A, V, 0.5, 0.5, 0.5, precision=prec)
-    dec.load_state_dict(P)
-    dec = dec.cuda().eval()
-    cfg = _Cfg()
-    cfg.batch_size, cfg.decoder_model, cfg.caption_max_len = B, cell, cml
-    inp = torch.full((1, B), 1, dtype=torch.long, device="cuda")
-    hid = (torch.zeros(1, B, H, device="cuda"), torch.zeros(1, B, H, device="cuda"))
-    if cell == "GRU":
-        hid = hid[0]
-    return dec, cfg, inp, hid
-
-
 @functools.lru_cache(maxsize=None)
 def _ref(name, bw, cml, n, m, banned):
     g, P, enc = load_search_case(name)
@@ -161,7 +136,7 @@ def test_search_matches_the_restatement(run):
     name, bw, cml = run["name"], run["bw"], run["cml"]
     g, P, enc = load_search_case(name)
     r = _ref(name, bw, cml, run["n"], run["m"], run["banned"])
-    dec, cfg, inp, hid = _decoder(g, P, "f32", cml)
+    dec, cfg, inp, hid = decoder_for(g, P, "f32", cml)
     toks, cum, ln, score = search._beam_nbest(cfg, dec, inp, hid, enc.cuda(), bw, BR.LENGTH_ALPHA, **_kw(run))
     toks, cum, ln, score = toks.cpu().numpy(), cum.cpu().numpy().astype(np.float64), ln.cpu().numpy(), score.cpu().numpy().astype(np.float64)
     keep = CR.comparable_captions(r)
@@ -214,7 +189,7 @@ def test_what_the_device_returns(run, prec):
     depends on the restatement alone."""
     name, bw, cml, n, m, banned = run["name"], run["bw"], run["cml"], run["n"], run["m"], run["banned"]
     g, P, enc = load_search_case(name)
-    dec, cfg, inp, hid = _decoder(g, P, prec, cml)
+    dec, cfg, inp, hid = decoder_for(g, P, prec, cml)
     encd = enc.cuda()
     amax = _ref(name, bw, cml, n, m, banned)["amax"].max()
     a = search._beam_nbest(cfg, dec, inp, hid, encd, bw, BR.LENGTH_ALPHA, **_kw(run))
@@ -254,7 +229,7 @@ def test_what_the_device_returns(run, prec):
 @pytest.mark.parametrize("bw", [1, 3, 8])
 def test_constraints_off_is_the_unconstrained_search(bw):
     g, P, enc = load_search_case("search_gru")
-    dec, cfg, inp, hid = _decoder(g, P, "f32", 7)
+    dec, cfg, inp, hid = decoder_for(g, P, "f32", 7)
     eng = search._nbest_engine(cfg, dec, enc.cuda())
     ops = _ops.load()
     a = ops.beam_search_nbest(int(eng.handle.value), enc.cuda(), bw, 0.7)
@@ -324,7 +299,7 @@ def test_best_of_beam_and_evaluate(kind):
 # ------------------------------------------------------------------------------------------------ 4. errors
 def test_library_refuses_bad_arguments_and_recovers():
     g, P, enc = load_search_case("search_small")
-    dec, cfg, inp, hid = _decoder(g, P, "f32", 7)
+    dec, cfg, inp, hid = decoder_for(g, P, "f32", 7)
     encd = enc.cuda()
     B, F, V = enc.shape[0], enc.shape[1], int(g["meta_dims"][3])
     hy = dec.hyper()
@@ -373,7 +348,7 @@ def test_library_refuses_bad_arguments_and_recovers():
     # ... and beam_width + n_banned + caption_max_len + 1 <= V for the search, in the library and in the custom op
     torch.manual_seed(3)
     dec12 = R.Decoder("LSTM", 1, 8, 4, 1, 8, 4, 12, 0.5, 0.5, 0.5, precision="f32").cuda().eval()
-    cfg12 = _Cfg()
+    cfg12 = Cfg()
     cfg12.batch_size, cfg12.decoder_model, cfg12.caption_max_len = 2, "LSTM", 7
     enc12 = torch.randn(2, 2, 8, device="cuda")
     small = search._nbest_engine(cfg12, dec12, enc12)
@@ -409,6 +384,6 @@ def test_library_refuses_bad_arguments_and_recovers():
 
 def _tight(cfg, V):
     """The config with a caption_max_len that leaves no room for a width-8 constrained search in a vocabulary of V."""
-    c = _Cfg()
+    c = Cfg()
     c.batch_size, c.decoder_model, c.caption_max_len = cfg.batch_size, cfg.decoder_model, V - 8
     return c

@@ -8,8 +8,6 @@ Indices / tokens are compared outside the decisions the restatement marks as nea
 test_beam_diverse_ref.py holds the cap of 0.6 on the compared share without a GPU).  Values are held to section 11's bar: the row
 bar of score_ref plus two units in the last place of |cum|; a hypothesis' cum to its length times the row bar.  Every test prints
 its worst error / bar."""
-import functools
-
 import numpy as np
 import pytest
 import torch
@@ -20,9 +18,10 @@ from tests import beam_diverse_ref as DR
 from tests import beam_ref as BR
 from tests import golden_util as GU
 from tests import score_ref as SC
+from tests.golden_util import load_search_case
 from tests.gpu_util import make_models
 from tests.sample_ref import NEAR_TIE
-from tests.test_search_oracle import load_search_case
+from tests.search_kit import decoder_for, rows_engine
 
 pytestmark = pytest.mark.gpu
 
@@ -30,19 +29,13 @@ Engine, _lib = R.engine.Engine, R.engine._lib
 
 
 # ------------------------------------------------------------------------------------------------ 1. the selection kernel alone
-@functools.lru_cache(maxsize=None)
-def _rows_engine():
-    """A handle for recnet_beam_select_rows_diverse: it supplies the device only, no decoder is bound."""
-    return Engine(dict(B=2, F=2, D=8, E=4, H=8, A=4, V=8), None, "f32")
-
-
 def _dev(a):
     return None if a is None else torch.from_numpy(a).cuda()
 
 
 @pytest.mark.parametrize("V", DR.ROW_VS)
 def test_select_rows_groups(V):
-    eng = _rows_engine()
+    eng = rows_engine()
     worst, cases, compared, labels = 0.0, 0, 0, set()
     for bw, G in DR.ROW_BW_G:
         if bw > V:
@@ -94,26 +87,6 @@ def test_select_rows_groups(V):
 
 
 # ------------------------------------------------------------------------------------------------ 2. the search
-class _Cfg:
-    caption_max_len = 30
-    decoder_model = "LSTM"
-
-
-def _decoder(g, P, prec, cml=30):
-    B, F, D, V, E, H, A = [int(x) for x in g["meta_dims"]]
-    cell = g["_cell"]
-    dec = R.Decoder(cell, 1, D, E, 1, H, A, V, 0.5, 0.5, 0.5, precision=prec)
-    dec.load_state_dict(P)
-    dec = dec.cuda().eval()
-    cfg = _Cfg()
-    cfg.batch_size, cfg.decoder_model, cfg.caption_max_len = B, cell, cml
-    inp = torch.full((1, B), 1, dtype=torch.long, device="cuda")
-    hid = (torch.zeros(1, B, H, device="cuda"), torch.zeros(1, B, H, device="cuda"))
-    if cell == "GRU":
-        hid = hid[0]
-    return dec, cfg, inp, hid
-
-
 @pytest.mark.parametrize("run", DR.RUNS, ids=DR.run_id)
 def test_search_matches_the_restatement(run):
     """fp32 path: n_steps (when no caption is excluded), tokens, len, the rank order and the group of every rank equal the
@@ -123,7 +96,7 @@ def test_search_matches_the_restatement(run):
     w = bw // G
     g, P, enc = load_search_case(name)
     r = DR.beam_search_nbest(P, enc, bw, G, lam, BR.LENGTH_ALPHA, cml, g["_cell"], n_, m_, banned)
-    dec, cfg, inp, hid = _decoder(g, P, "f32", cml)
+    dec, cfg, inp, hid = decoder_for(g, P, "f32", cml)
     kw = dict(no_repeat_ngram=n_, min_length=m_, banned_tokens=banned, n_groups=G, diversity_penalty=lam)
     toks, cum, ln, score, group = search._beam_nbest(cfg, dec, inp, hid, enc.cuda(), bw, BR.LENGTH_ALPHA, want_groups=True, **kw)
     toks, cum, ln, score, group = (toks.cpu().numpy(), cum.cpu().numpy().astype(np.float64), ln.cpu().numpy(),
@@ -186,7 +159,7 @@ def test_exact_properties(name, prec):
     """One group is the existing search bit for bit, through the new entry; lambda = 0 gives G copies of the width-w search and
     lambda > 0 leaves group 0 that search, bit for bit in tokens and cum; score_captions reproduces cum on every rank."""
     g, P, enc = load_search_case(name)
-    dec, cfg, inp, hid = _decoder(g, P, prec)
+    dec, cfg, inp, hid = decoder_for(g, P, prec)
     encd = enc.cuda()
     eng = search._nbest_engine(cfg, dec, encd)
     ops, h = _ops.load(), int(eng.handle.value)
@@ -282,7 +255,7 @@ def test_best_of_beam_and_evaluate(kind):
 # ------------------------------------------------------------------------------------------------ 4. errors
 def test_library_refuses_bad_arguments_and_recovers():
     g, P, enc = load_search_case("search_small")
-    dec, cfg, inp, hid = _decoder(g, P, "f32", 7)
+    dec, cfg, inp, hid = decoder_for(g, P, "f32", 7)
     encd = enc.cuda()
     B, F, V = enc.shape[0], enc.shape[1], int(g["meta_dims"][3])
     hy = dec.hyper()

@@ -15,8 +15,9 @@ import recnet_amd as R
 from recnet_amd import _ops, metrics, search
 from tests import consensus_ref as CR
 from tests import golden_util as GU
+from tests.golden_util import load_search_case
 from tests.gpu_util import make_models
-from tests.test_search_oracle import load_search_case
+from tests.search_kit import decoder_for, rows_engine
 
 pytestmark = pytest.mark.gpu
 
@@ -25,12 +26,6 @@ INTS = ("counts", "q_hyp", "q_ref", "len_hyp", "len_ref")
 
 
 # ------------------------------------------------------------------------------------------------ 1. the kernel alone
-@functools.lru_cache(maxsize=None)
-def _rows_engine():
-    """A handle for recnet_consensus_rows: it supplies the device only, no decoder is bound."""
-    return Engine(dict(B=2, F=2, D=8, E=4, H=8, A=4, V=8), None, "f32")
-
-
 @functools.lru_cache(maxsize=None)
 def _case(shape, vocab):
     """The case, its restatement without weights and with them: computed once, shared, never written to."""
@@ -49,7 +44,7 @@ def _bits(t):
 @pytest.mark.parametrize("vocab", sorted(CR.VOCABS))
 @pytest.mark.parametrize("shape", CR.SHAPES, ids=CR.case_id)
 def test_kernel_against_the_restatement(shape, vocab):
-    eng = _rows_engine()
+    eng = rows_engine()
     c, want, want_w = _case(shape, vocab)
     hyp, ref, w = _dev(c["hyp"]), _dev(c["ref"]), _dev(c["weights"])
     hyp0, ref0 = hyp.clone(), None if ref is None else ref.clone()
@@ -97,7 +92,7 @@ def test_hand_case_on_the_device():
     H = CR.HAND
     hyp = np.full((3, 6, 1), CR.EOS, np.int64)
     hyp[0, :, 0], hyp[1, :5, 0], hyp[2, :, 0] = CR.HAND_H, CR.HAND_R, CR.HAND_H
-    util, sim, ints = _rows_engine().consensus_rows(_dev(hyp), want_sim=True, want_counts=True)
+    util, sim, ints = rows_engine().consensus_rows(_dev(hyp), want_sim=True, want_counts=True)
     assert ints["counts"][0, 1, 0].tolist() == H["M"] and ints["q_hyp"][0, 0].tolist() == H["Qh"] and ints["q_ref"][1, 0].tolist() == H["Qr"]
     got = [sim[0, 1, 0].item(), sim[1, 0, 0].item(), sim[0, 0, 0].item()] + util[:, 0].tolist()
     exp = [H["sim_hr"], H["sim_rh"], H["sim_hh"]] + list(H["util"])
@@ -107,7 +102,7 @@ def test_hand_case_on_the_device():
 
 
 def test_library_refuses_bad_arguments_and_recovers():
-    eng = _rows_engine()
+    eng = rows_engine()
     hyp = _dev(CR.make_case((2, None, 4, None, 3), "forty")["hyp"])
     good = eng.consensus_rows(hyp)
     z = lambda *s: torch.zeros(*s, dtype=torch.long, device="cuda")
@@ -145,26 +140,6 @@ def test_library_refuses_bad_arguments_and_recovers():
 
 
 # ------------------------------------------------------------------------------------------------ 2. the searches
-class _Cfg:
-    caption_max_len = 30
-    decoder_model = "LSTM"
-
-
-def _decoder(g, P, prec, cml=30):
-    B, F, D, V, E, H, A = [int(x) for x in g["meta_dims"]]
-    cell = g["_cell"]
-    dec = R.Decoder(cell, 1, D, E, 1, H, A, V, 0.5, 0.5, 0.5, precision=prec)
-    dec.load_state_dict(P)
-    dec = dec.cuda().eval()
-    cfg = _Cfg()
-    cfg.batch_size, cfg.decoder_model, cfg.caption_max_len = B, cell, cml
-    inp = torch.full((1, B), 1, dtype=torch.long, device="cuda")
-    hid = (torch.zeros(1, B, H, device="cuda"), torch.zeros(1, B, H, device="cuda"))
-    if cell == "GRU":
-        hid = hid[0]
-    return dec, cfg, inp, hid
-
-
 def _against_restatement(sets, util):
     """|util - restatement| of host caption sets (lists [T_k][B], continued with <EOS> as consensus_scores does)."""
     T = max(len(s) for s in sets)
@@ -176,7 +151,7 @@ def _against_restatement(sets, util):
 @pytest.mark.parametrize("prec", ["f32", "bf16"])
 def test_best_of_n_with_the_consensus_term(name, prec, monkeypatch):
     g, P, enc = load_search_case(name)
-    dec, cfg, inp, hid = _decoder(g, P, prec)
+    dec, cfg, inp, hid = decoder_for(g, P, prec)
     encd = enc.cuda()
     n, temp, top_k, seed, cw = 4, 1.3, 0, 5, 0.5
     got = R.best_of_n(cfg, dec, inp, hid, encd, n, temp, top_k, seed, consensus_weight=cw)
@@ -204,7 +179,7 @@ def test_best_of_n_with_the_consensus_term(name, prec, monkeypatch):
 @pytest.mark.parametrize("prec", ["f32", "bf16"])
 def test_best_of_beam_with_the_consensus_term(name, prec, monkeypatch):
     g, P, enc = load_search_case(name)
-    dec, cfg, inp, hid = _decoder(g, P, prec)
+    dec, cfg, inp, hid = decoder_for(g, P, prec)
     encd = enc.cuda()
     bw, cw = 8, 0.5
     worst = 0.0

@@ -8,7 +8,7 @@ pytestmark = pytest.mark.gpu
 
 def _engine(prec):
     from recnet_amd.engine import Engine
-    return Engine(dict(B=2, F=2, D=8, E=4, H=8, A=4, V=8), None, prec)
+    return Engine.device_only(precision=prec)
 
 
 def _ref(A, B, a_col, b_col):

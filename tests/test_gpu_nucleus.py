@@ -6,7 +6,7 @@ The size of the set a token was drawn from is held to the restatement's band [n_
 the mass: the two exponentials' rounding, tests/nucleus_ref.py; tests/test_nucleus_ref.py holds without a GPU that the band is
 a single size on at least 3/4 of the rows of every vocabulary and on every step of the search runs).  Token and
 log-probability are then compared at the device's own size: tokens outside the restatement's near-tie decisions,
-log-probabilities within the bar of tests/test_gpu_sample.py, 2 * 4e-5 * max(1, max |logit|) / temperature."""
+log-probabilities within the bar of tests/search_kit.py, 2 * 4e-5 * max(1, max |logit|) / temperature."""
 import functools
 
 import numpy as np
@@ -14,13 +14,12 @@ import pytest
 import torch
 
 import recnet_amd as R
-from recnet_amd.engine import Engine, _lib      # the engine's own _lib: the module whose RecNetError it raises
+from recnet_amd.engine import _lib      # the engine's own _lib: the module whose RecNetError it raises
 from tests import nucleus_ref as NR
 from tests import sample_ref as SR
 from tests import score_ref as SC
-from tests.test_gpu_sample import _decoder, _lp_bar, _rows_engine
-from tests.test_nucleus_ref import _row_sizes
-from tests.test_search_oracle import load_search_case
+from tests.golden_util import load_search_case
+from tests.search_kit import bound_engine, decoder_for, lp_bar, nucleus_row_sizes, rows_engine
 
 pytestmark = pytest.mark.gpu
 
@@ -33,7 +32,7 @@ def _device_logits(V, rows, quantised):
 @functools.lru_cache(maxsize=None)
 def _row_results(V):
     """Every kernel-alone case at vocabulary V, device and restatement side by side (computed once, shared by the tests)."""
-    eng = _rows_engine()
+    eng = rows_engine()
     out = []
     for case in NR.row_cases(V):
         rows, quantised, top_k, temperature, top_p, t, seed = case
@@ -41,7 +40,7 @@ def _row_results(V):
         xd = _device_logits(V, rows, quantised)
         tok, lp, na = eng.sample_rows_nucleus(xd, temperature, top_k, top_p, seed, t)
         untouched = torch.equal(xd.cpu().view(torch.int32), torch.from_numpy(x).view(torch.int32))
-        n, n_lo, n_hi, b = _row_sizes(V)[(rows, quantised, top_k, temperature, top_p)]
+        n, n_lo, n_hi, b = nucleus_row_sizes(V)[(rows, quantised, top_k, temperature, top_p)]
         out.append(dict(case=case, x=x, tok=tok.cpu().numpy(), lp=lp.cpu().numpy(), na=na.cpu().numpy().astype(np.int64),
                         n_lo=n_lo, n_hi=n_hi, untouched=untouched))
     return out
@@ -83,7 +82,7 @@ def test_nucleus_rows_logprobs(V):
         _, rl, margin = _restated_at_device_size(r)
         keep = margin >= SR.NEAR_TIE
         err = np.abs(r["lp"][keep].astype(np.float64) - rl[keep])
-        bar = _lp_bar(np.abs(r["x"]).max(), temperature)
+        bar = lp_bar(np.abs(r["x"]).max(), temperature)
         if err.size:
             worst = max(worst, float(err.max() / bar))
             assert err.max() <= bar, (r["case"], float(err.max()), bar)
@@ -93,7 +92,7 @@ def test_nucleus_rows_logprobs(V):
 @pytest.mark.parametrize("V", SR.ROW_VS)
 def test_top_p_one_is_sample_rows(V):
     """No nucleus cut: the tokens and the bits of the log-probabilities of recnet_sample_rows; n_allowed is top_k, or V."""
-    eng = _rows_engine()
+    eng = rows_engine()
     for rows in (1, 7):
         for quantised in (False, True):
             xd = _device_logits(V, rows, quantised)
@@ -110,7 +109,7 @@ def test_top_p_one_is_sample_rows(V):
 @pytest.mark.parametrize("V", SR.ROW_VS)
 def test_one_entry_left_is_the_arg_max(V):
     """top_k = 1 with any top_p, and a tiny top_p with any top_k: numpy's arg-max, log-probability 0, n_allowed 1."""
-    eng = _rows_engine()
+    eng = rows_engine()
     for quantised in (False, True):
         x = SR.row_logits(V, 7, quantised)
         xd = _device_logits(V, 7, quantised)
@@ -123,7 +122,7 @@ def test_one_entry_left_is_the_arg_max(V):
 def test_determinism_where_the_band_is_widest():
     """V = 12500, quantised, top_p = 0.999: hundreds of equal values at the cut and a band up to 20 sizes wide — the integer
     masses make the size a pure function of the logits, so two calls agree in every output."""
-    eng = _rows_engine()
+    eng = rows_engine()
     xd = _device_logits(12500, 7, True)
     for top_k, temperature in ((0, 1.0), (12499, 2.0)):
         a = eng.sample_rows_nucleus(xd, temperature, top_k, 0.999, 6, 3)
@@ -133,23 +132,15 @@ def test_determinism_where_the_band_is_widest():
 
 
 # ------------------------------------------------------------------------------------------------ search
-def _engine_for(dec, encd):
-    B, F = encd.shape[0], encd.shape[1]
-    eng = Engine(dec.dims(B, F), None, "f32", dec.hyper(), device=encd.device)
-    eng.bind_decoder({k: v.data for k, v in dec.named_tensors().items()})
-    eng.pack_weights()
-    return eng
-
-
 @pytest.mark.parametrize("name,seed,temperature,top_k,top_p", NR.SEARCH_RUNS)
 def test_nucleus_search_matches_the_restated_loop(name, seed, temperature, top_k, top_p):
     """fp32 path: n_steps, tokens, log-probabilities and n_allowed equal the restatement's loop on every compared entry (no
     caption is excluded for these runs); the *_stop goldens end after one step.  search.sample_search returns the same tokens."""
     g, P, enc = load_search_case(name)
     run = NR.sample_search(P, enc, temperature, top_k, top_p, seed, cell=g["_cell"])
-    dec, cfg, inp, hid = _decoder(g, P, "f32")
+    dec, cfg, inp, hid = decoder_for(g, P, "f32")
     encd = enc.cuda()
-    toks, lps, na, n = _engine_for(dec, encd).sample_search_nucleus(encd, temperature, top_k, top_p, seed)
+    toks, lps, na, n = bound_engine(dec, *encd.shape[:2], "f32").sample_search_nucleus(encd, temperature, top_k, top_p, seed)
     n = int(n.item())
     rt = run["tokens"]
     assert n == rt.shape[0]
@@ -163,7 +154,7 @@ def test_nucleus_search_matches_the_restated_loop(name, seed, temperature, top_k
     worst = 0.0
     for t in range(n):
         err = np.abs(lps[t] - run["logprobs"][t])[keep[t]]
-        bar = _lp_bar(run["amax"][t], temperature)
+        bar = lp_bar(run["amax"][t], temperature)
         worst = max(worst, float(err.max() / bar))
         assert err.max() <= bar, (t, float(err.max()), bar)
     print(name, "worst log-probability error / bar:", worst)
@@ -174,13 +165,13 @@ def test_nucleus_search_matches_the_restated_loop(name, seed, temperature, top_k
 def test_top_p_one_through_sample_search_is_the_call_without_it():
     for name in ("search_small", "search_gru"):
         g, P, enc = load_search_case(name)
-        dec, cfg, inp, hid = _decoder(g, P, "f32")
+        dec, cfg, inp, hid = decoder_for(g, P, "f32")
         encd = enc.cuda()
         for temperature, top_k, seed in ((1.0, 0, 2), (0.5, 5, 3)):
             a = R.sample_search(cfg, dec, inp, hid, encd, temperature, top_k, seed)
             b = R.sample_search(cfg, dec, inp, hid, encd, temperature, top_k, seed, top_p=1.0)
             assert a == b
-        eng = _engine_for(dec, encd)
+        eng = bound_engine(dec, *encd.shape[:2], "f32")
         u = eng.sample_search(encd, 1.0, 0, 2)
         v = eng.sample_search(encd, 1.0, 0, 2, top_p=1.0)
         w = eng.sample_search_nucleus(encd, 1.0, 0, 1.0, 2)
@@ -205,7 +196,7 @@ def test_best_of_n_with_a_nucleus(name, seed):
     score = np.sort(np.array(sums) / np.array(lens), axis=0)
     assert (score[-1] - score[-2]).min() > 0.03
     rk, rscores = R.pick_best_of_n(sums, lens)
-    dec, cfg, inp, hid = _decoder(g, P, "f32")
+    dec, cfg, inp, hid = decoder_for(g, P, "f32")
     caps, ks, scores = R.best_of_n(cfg, dec, inp, hid, enc.cuda(), 3, temperature=1.0, top_k=0, seed=seed, top_p=0.8)
     assert ks == rk
     for b in range(enc.shape[0]):
@@ -249,10 +240,10 @@ def test_evaluate_takes_a_trailing_top_p():
 
 def test_library_refuses_a_bad_top_p_and_recovers():
     g, P, enc = load_search_case("search_small")
-    dec, cfg, inp, hid = _decoder(g, P, "f32")
+    dec, cfg, inp, hid = decoder_for(g, P, "f32")
     encd = enc.cuda()
     V = int(g["meta_dims"][3])
-    eng = _engine_for(dec, encd)
+    eng = bound_engine(dec, *encd.shape[:2], "f32")
     x = torch.from_numpy(SR.row_logits(V, 3, False)).cuda()
     for bad in (0.0, -0.1, 1.5, float("nan")):
         with pytest.raises(_lib.RecNetError, match="top_p"):

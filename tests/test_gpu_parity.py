@@ -12,7 +12,7 @@ import torch
 import recnet_amd as R
 from oracle import recnet_oracle as O
 from tests import golden_util as GU
-from tests.gpu_util import TOL, cosine, load_case, make_models, oracle_grads, rel_err
+from tests.gpu_util import LR_TOL, REG_SLACK, TOL, cosine, load_case, make_models, moved, oracle_grads, rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -22,7 +22,6 @@ SMALL = ["dec_eval", "dec_train", "dec_T31", "dec_T4_samelen", "global_train", "
 FULL = ["full_dec_B8", "full_global_B8", "full_local_B8", "full_gru_global_B8", "full_gru_local_B8"]
 # config.py:48,50 moved (tests/golden/make_golden.py): caption_max_len = 44 with captions of 40 and 33 tokens, V = 5200
 AXES = ["global_cml44", "dec_V5200"]
-REG_SLACK = 3e-4
 
 
 @pytest.mark.parametrize("prec", ["f32", "bf16"])
@@ -148,17 +147,6 @@ def test_fused_train_steps_match_reference_optimizer(name, prec):
 
 
 LR_CASES = ["lr_global_chain", "lr_local_chain", "lr_gru_global_chain"]
-# update-path bars at learning rates of 1e-2: ||(got - init) - (ref - init)|| / ||ref - init|| per tensor, and the same for the
-# Adam moments.  An update that did not happen is an error of 1.0 (0.25 for one of four); bf16 operand rounding flips the sign of
-# near-zero gradient elements, each of which moves its parameter by 2 lr instead of 0 in the first step.
-LR_TOL = {"f32": dict(move=2e-3, m=1e-3, v=2e-3), "bf16": dict(move=8e-2, m=3e-2, v=6e-2)}
-
-
-def _moved(got, ref, init):
-    d = np.linalg.norm((ref - init).astype(np.float64))
-    return float(np.linalg.norm(((got - init) - (ref - init)).astype(np.float64)) / max(d, 1e-30)), d
-
-
 @pytest.mark.parametrize("prec", ["f32", "bf16"])
 @pytest.mark.parametrize("mode", ["eager", "graph", "graph_split_update"])
 @pytest.mark.parametrize("name", LR_CASES)
@@ -221,7 +209,7 @@ def test_benchmarked_update_path_matches_reference_optimizer(name, mode, prec):
         fl = md["_state"].flat()
         for k, v in GU.group(g, "%s_after%d" % (grp, n)).items():
             got = md["model"].state_dict()[k].cpu().numpy()
-            e, d = _moved(got, v.numpy(), init[k].numpy())
+            e, d = moved(got, v.numpy(), init[k].numpy())
             assert d > 1e-3, (grp, k, d)
             if e > lt["move"]:
                 bad.append((grp, k, "param", e))

@@ -6,7 +6,7 @@ import pytest
 import torch
 
 import recnet_amd as R
-from tests.test_recstep_oracle import CASES, case_inputs
+from tests.golden_util import RECSTEP_CASES, load_recstep_case
 
 pytestmark = pytest.mark.gpu
 
@@ -16,9 +16,9 @@ class _C:            # the globals the reference's loops read (config.TrainConfi
 
 
 @pytest.mark.parametrize("prec", ["f32", "bf16"])
-@pytest.mark.parametrize("name", CASES)
+@pytest.mark.parametrize("name", RECSTEP_CASES)
 def test_reference_time_loops_over_package_modules(name, prec):
-    g, (B, T, F, H, Rr, RA), kind, cell, P, hid = case_inputs(name)
+    g, (B, T, F, H, Rr, RA), kind, cell, P, hid = load_recstep_case(name)
     C = _C
     C.batch_size, C.reconstructor_hidden_size, C.encoder_output_len, C.reconstructor_model = B, Rr, F, cell
     C.reconstructor_n_layers = 1
@@ -63,7 +63,7 @@ def test_reference_time_loops_over_package_modules(name, prec):
 
 
 def test_eval_mode_switches_dropout_off_and_state_dict_round_trips():
-    g, (B, T, F, H, Rr, RA), kind, cell, P, hid = case_inputs("recstep_local_train")
+    g, (B, T, F, H, Rr, RA), kind, cell, P, hid = load_recstep_case("recstep_local_train")
     m = R.LocalReconstructor(model_name=cell, n_layers=1, decoder_hidden_size=H, hidden_size=Rr, dropout=0.5,
                              decoder_dropout=0.5, attn_size=RA, precision="f32").to("cuda")
     m.load_state_dict(P)
@@ -85,7 +85,7 @@ def test_two_batches_at_the_same_address_are_not_confused(kind):
     """the loop invariants (pooled states / U_r . hiddens) were keyed on (data_ptr, _version); the caching
     allocator hands a freed batch's address to the next batch with _version 0.  Two different decoder_hiddens at ONE
     address, weights unchanged (eval mode): the second call has to see the second batch."""
-    g, (B, T, F, H, Rr, RA), _, cell, P, hid = case_inputs("recstep_%s_eval" % kind)
+    g, (B, T, F, H, Rr, RA), _, cell, P, hid = load_recstep_case("recstep_%s_eval" % kind)
     if kind == "global":
         m = R.GlobalReconstructor(model_name=cell, n_layers=1, decoder_hidden_size=H, hidden_size=Rr, dropout=0.5,
                                   decoder_dropout=0.5, caption_max_len=30, precision="f32")
@@ -126,7 +126,7 @@ def test_two_batches_at_the_same_address_are_not_confused(kind):
 
 def test_wrong_shaped_hidden_is_a_runtime_error_not_a_device_write():
     """the torch.ops layer sizes its outputs from the handle and checks every tensor against recnet_dim."""
-    g, (B, T, F, H, Rr, RA), kind, cell, P, hid = case_inputs("recstep_local_eval")
+    g, (B, T, F, H, Rr, RA), kind, cell, P, hid = load_recstep_case("recstep_local_eval")
     m = R.LocalReconstructor(model_name=cell, n_layers=1, decoder_hidden_size=H, hidden_size=Rr, dropout=0.5,
                              decoder_dropout=0.5, attn_size=RA, precision="f32").to("cuda").eval()
     m.load_state_dict(P)

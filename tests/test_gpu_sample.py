@@ -13,28 +13,18 @@ import pytest
 import torch
 
 import recnet_amd as R
-from recnet_amd.engine import Engine, _lib      # the engine's own _lib: the module whose RecNetError it raises
+from recnet_amd.engine import _lib      # the engine's own _lib: the module whose RecNetError it raises
 from tests import sample_ref as SR
-from tests.gpu_util import TOL
-from tests.test_search_oracle import CASES, load_search_case
+from tests.golden_util import CASES, load_search_case
+from tests.search_kit import bound_engine, decoder_for, lp_bar, rows_engine
 
 pytestmark = pytest.mark.gpu
-
-
-def _lp_bar(logit_abs_max, temperature):
-    return 2.0 * (TOL["f32"]["hid"] * 4 * max(1.0, float(logit_abs_max))) / temperature
-
-
-@functools.lru_cache(maxsize=None)
-def _rows_engine():
-    """A handle for recnet_sample_rows: it supplies the device only, no decoder is bound."""
-    return Engine(dict(B=2, F=2, D=8, E=4, H=8, A=4, V=8), None, "f32")
 
 
 @functools.lru_cache(maxsize=None)
 def _row_results(V):
     """Every kernel-alone case at vocabulary V, device and restatement side by side (computed once, shared by the tests)."""
-    eng = _rows_engine()
+    eng = rows_engine()
     out = []
     for rows, quantised, top_k, temperature, t, seed in SR.row_cases(V):
         x = SR.row_logits(V, rows, quantised)
@@ -75,7 +65,7 @@ def test_sample_rows_logprobs(V):
         rows, quantised, top_k, temperature, t, seed = r["case"]
         keep = r["margin"] >= SR.NEAR_TIE
         err = np.abs(r["lp"][keep].astype(np.float64) - r["ref_lp"][keep])
-        bar = _lp_bar(np.abs(r["x"]).max(), temperature)
+        bar = lp_bar(np.abs(r["x"]).max(), temperature)
         if err.size:
             worst = max(worst, float(err.max() / bar))
             assert err.max() <= bar, (r["case"], float(err.max()), bar)
@@ -83,33 +73,13 @@ def test_sample_rows_logprobs(V):
 
 
 # ------------------------------------------------------------------------------------------------ search
-class _Cfg:
-    caption_max_len = 30
-    decoder_model = "LSTM"
-
-
-def _decoder(g, P, prec):
-    B, F, D, V, E, H, A = [int(x) for x in g["meta_dims"]]
-    cell = g["_cell"]
-    dec = R.Decoder(cell, 1, D, E, 1, H, A, V, 0.5, 0.5, 0.5, precision=prec)
-    dec.load_state_dict(P)
-    dec = dec.cuda().eval()
-    cfg = _Cfg()
-    cfg.batch_size, cfg.decoder_model = B, cell
-    inp = torch.full((1, B), 1, dtype=torch.long, device="cuda")
-    hid = (torch.zeros(1, B, H, device="cuda"), torch.zeros(1, B, H, device="cuda"))
-    if cell == "GRU":
-        hid = hid[0]
-    return dec, cfg, inp, hid
-
-
 @pytest.mark.parametrize("name,seed,temperature,top_k", SR.SEARCH_RUNS)
 def test_sample_search_matches_the_restated_loop(name, seed, temperature, top_k):
     """fp32 path: n_steps, tokens and log-probabilities equal the restatement's loop outside excluded captions; the *_stop
     goldens end after one step."""
     g, P, enc = load_search_case(name)
     rt, rl, margins, amax = SR.sample_search(P, enc, temperature, top_k, seed, cell=g["_cell"])
-    dec, cfg, inp, hid = _decoder(g, P, "f32")
+    dec, cfg, inp, hid = decoder_for(g, P, "f32")
     toks, lps = R.sample_search(cfg, dec, inp, hid, enc.cuda(), temperature=temperature, top_k=top_k, seed=seed)
     toks, lps = np.array(toks, dtype=np.int64), np.array(lps, dtype=np.float64)
     assert toks.shape == rt.shape and lps.shape == rt.shape, (toks.shape, rt.shape)
@@ -121,7 +91,7 @@ def test_sample_search_matches_the_restated_loop(name, seed, temperature, top_k)
     worst = 0.0
     for t in range(rt.shape[0]):
         err = np.abs(lps[t] - rl[t])[keep[t]]
-        bar = _lp_bar(amax[t], temperature)
+        bar = lp_bar(amax[t], temperature)
         if err.size:
             worst = max(worst, float(err.max() / bar))
             assert err.max() <= bar, (t, float(err.max()), bar)
@@ -132,7 +102,7 @@ def test_sample_search_matches_the_restated_loop(name, seed, temperature, top_k)
 def test_top_k_one_is_greedy_search(name, prec):
     """Both searches run the same step at the same precision with the same tie rule: exact, for every seed."""
     g, P, enc = load_search_case(name)
-    dec, cfg, inp, hid = _decoder(g, P, prec)
+    dec, cfg, inp, hid = decoder_for(g, P, prec)
     encd = enc.cuda()
     greedy = R.greedy_search(cfg, dec, inp, hid, encd)
     if prec == "f32":
@@ -145,13 +115,11 @@ def test_top_k_one_is_greedy_search(name, prec):
 
 def test_determinism_and_seeds():
     g, P, enc = load_search_case("search_small")
-    dec, cfg, inp, hid = _decoder(g, P, "f32")
+    dec, cfg, inp, hid = decoder_for(g, P, "f32")
     encd = enc.cuda()
     greedy = R.greedy_search(cfg, dec, inp, hid, encd)
     B, F = enc.shape[0], enc.shape[1]
-    eng = Engine(dec.dims(B, F), None, "f32", dec.hyper(), device=encd.device)
-    eng.bind_decoder({k: v.data for k, v in dec.named_tensors().items()})
-    eng.pack_weights()
+    eng = bound_engine(dec, B, F, "f32")
     a = eng.sample_search(encd, 1.0, 0, 1)
     b = eng.sample_search(encd, 1.0, 0, 1)
     c = eng.sample_search(encd, 1.0, 0, 2)
@@ -194,12 +162,10 @@ def test_evaluate_accepts_the_sample_method():
 
 def test_library_refuses_bad_arguments_and_recovers():
     g, P, enc = load_search_case("search_small")
-    dec, cfg, inp, hid = _decoder(g, P, "f32")
+    dec, cfg, inp, hid = decoder_for(g, P, "f32")
     encd = enc.cuda()
     B, F, V = enc.shape[0], enc.shape[1], int(g["meta_dims"][3])
-    eng = Engine(dec.dims(B, F), None, "f32", dec.hyper(), device=encd.device)
-    eng.bind_decoder({k: v.data for k, v in dec.named_tensors().items()})
-    eng.pack_weights()
+    eng = bound_engine(dec, B, F, "f32")
     x = torch.from_numpy(SR.row_logits(V, 3, False)).cuda()
     with pytest.raises(_lib.RecNetError, match="top_k"):
         eng.sample_search(encd, 1.0, V + 1, 1)

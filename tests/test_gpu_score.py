@@ -16,38 +16,16 @@ import recnet_amd as R
 from recnet_amd.engine import Engine, _lib      # the engine's own _lib: the module whose RecNetError it raises
 from tests import golden_util as GU
 from tests import score_ref as SC
+from tests.golden_util import CASES, load_search_case
 from tests.gpu_util import load_case, make_models
-from tests.test_search_oracle import CASES, load_search_case
+from tests.search_kit import bound_engine, decoder_for, rows_engine
 
 pytestmark = pytest.mark.gpu
 
 
-class _Cfg:
-    caption_max_len = 30
-    decoder_model = "LSTM"
-
-
-def _decoder(P, dims7, cell, prec):
-    """(Decoder module, config, <SOS> input, zero hidden state) for the Python searches."""
-    B, F, D, V, E, H, A = dims7
-    dec = R.Decoder(cell, 1, D, E, 1, H, A, V, 0.5, 0.5, 0.5, precision=prec)
-    dec.load_state_dict(P)
-    dec = dec.cuda().eval()
-    cfg = _Cfg()
-    cfg.batch_size, cfg.decoder_model = B, cell
-    inp = torch.full((1, B), 1, dtype=torch.long, device="cuda")
-    hid = (torch.zeros(1, B, H, device="cuda"), torch.zeros(1, B, H, device="cuda"))
-    if cell == "GRU":
-        hid = hid[0]
-    return dec, cfg, inp, hid
-
-
-def _engine(dec, B, F, prec):
-    """An engine of the test's own with the decoder's parameters bound."""
-    eng = Engine(dec.dims(B, F), None, prec, dec.hyper(), device="cuda")
-    eng.bind_decoder({k: v.data for k, v in dec.named_tensors().items()})
-    eng.pack_weights()
-    return eng
+def _dims_decoder(P, dims7, cell, prec):
+    """search_kit.decoder_for on bare dims and a cell instead of a search golden."""
+    return decoder_for({"meta_dims": dims7, "_cell": cell}, P, prec)
 
 
 def _first_eos_lengths(tokens):
@@ -57,18 +35,12 @@ def _first_eos_lengths(tokens):
 
 
 # ------------------------------------------------------------------------------------------------ 1. the kernel alone
-@functools.lru_cache(maxsize=None)
-def _rows_engine():
-    """A handle for recnet_logprob_rows: it supplies the device only, no decoder is bound."""
-    return Engine(dict(B=2, F=2, D=8, E=4, H=8, A=4, V=8), None, "f32")
-
-
 @pytest.mark.parametrize("V", SC.ROW_VS)
 def test_logprob_rows(V):
     """Gaussian, Gaussian x 60 and quantised logits, rows 1 and 7, three temperatures; tokens 0, V - 1, the arg-max, -1 and V:
     in-range results finite and within the fp32 row bar of the float64 restatement, out-of-range ones -inf, V = 1 exactly 0, the
     logits bit-identical afterwards."""
-    eng = _rows_engine()
+    eng = rows_engine()
     worst = 0.0
     seen_out = 0
     for rows, kind, temperature, shift in SC.row_cases(V):
@@ -105,8 +77,8 @@ def test_eval_goldens_f32(name):
     cell = g["_cells"][0]
     T = g["step_logits"].shape[0]
     caps = targets[:T].contiguous()
-    dec, _, _, _ = _decoder(decP, dims[:7], cell, "f32")
-    eng = _engine(dec, dims[0], dims[1], "f32")
+    dec, _, _, _ = _dims_decoder(decP, dims[:7], cell, "f32")
+    eng = bound_engine(dec, dims[0], dims[1], "f32")
     lps, cap, ln = (x.cpu().numpy() for x in eng.score_captions(enc.cuda(), caps.cuda(), 1.0))
     ref = SC.golden_logprobs(g["step_logits"], caps.numpy())
     rlp, amax = SC.score_captions(decP, enc, caps.numpy(), 1.0, cell=cell)
@@ -136,7 +108,7 @@ def test_scorer_and_sampler_agree_f32(name, temperature):
     scorer also meets the single row bar against the restatement.  The *_stop goldens give T = 1."""
     g, P, enc = load_search_case(name)
     dims7 = [int(x) for x in g["meta_dims"]]
-    dec, cfg, inp, hid = _decoder(P, dims7, g["_cell"], "f32")
+    dec, cfg, inp, hid = _dims_decoder(P, dims7, g["_cell"], "f32")
     encd = enc.cuda()
     toks, lps = R.sample_search(cfg, dec, inp, hid, encd, temperature=temperature, top_k=0, seed=3)
     n = len(toks)
@@ -185,8 +157,8 @@ def test_bf16_chain_and_per_step(name, per_step, monkeypatch):
     if per_step:
         monkeypatch.setenv("RN_PER_STEP", "dec")
     dims7, cell, decP, enc, caps, rlp, amax, rsum, rlen = _chain_case(name)
-    dec, _, _, _ = _decoder(decP, dims7, cell, "bf16")
-    eng = _engine(dec, dims7[0], dims7[1], "bf16")
+    dec, _, _, _ = _dims_decoder(decP, dims7, cell, "bf16")
+    eng = bound_engine(dec, dims7[0], dims7[1], "bf16")
     encd, capd = enc.cuda(), caps.cuda()
     out = []
     n_chain = eng.profile_site(9, lambda: out.append(eng.score_captions(encd, capd, 1.0)), 1)[0]      # RECNET_SITE_DEC_CHAIN_FWD
@@ -212,7 +184,7 @@ def test_bf16_sampler_rollouts_rescored_through_the_chain(temperature):
     """lr_global_chain's decoder, bf16: the sampler runs the per-step kernels, the scorer the persistent chain; on the sampler's
     own tokens the two agree within twice the bf16 row bar."""
     dims7, cell, decP, enc, _, _, _, _, _ = _chain_case("lr_global_chain")
-    dec, cfg, inp, hid = _decoder(decP, dims7, cell, "bf16")
+    dec, cfg, inp, hid = _dims_decoder(decP, dims7, cell, "bf16")
     encd = enc.cuda()
     toks, lps = R.sample_search(cfg, dec, inp, hid, encd, temperature=temperature, top_k=0, seed=5)
     slp, scap, slen = R.score_captions(cfg, dec, encd, toks, temperature)
@@ -240,13 +212,13 @@ def test_shared_invariants_and_determinism(which):
         dims7, cell, P, enc = _chain_case("lr_global_chain")[:4]
         prec = "bf16"
     B, F, V = dims7[0], dims7[1], dims7[3]
-    dec, cfg, inp, hid = _decoder(P, dims7, cell, prec)
+    dec, cfg, inp, hid = _dims_decoder(P, dims7, cell, prec)
     encd = enc.cuda()
     greedy = R.greedy_search(cfg, dec, inp, hid, encd)
     rs = np.random.RandomState(3)
     A = torch.from_numpy(rs.randint(0, V, size=(9, B))).cuda()
     Bt = torch.from_numpy(rs.randint(0, V, size=(31, B))).cuda()
-    eng = _engine(dec, B, F, prec)
+    eng = bound_engine(dec, B, F, prec)
     eng.score_captions(encd, A)
     reuse = eng.score_captions(None, Bt)
     full = eng.score_captions(encd, Bt)

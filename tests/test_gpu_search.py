@@ -6,35 +6,16 @@ import pytest
 import torch
 
 import recnet_amd as R
-from tests.test_search_oracle import CASES, load_search_case
+from tests.golden_util import CASES, load_search_case
+from tests.search_kit import Cfg, decoder_for, rows_engine
 
 pytestmark = pytest.mark.gpu
-
-
-class _Cfg:
-    caption_max_len = 30
-    decoder_model = "LSTM"
-
-
-def _decoder(g, P, prec):
-    B, F, D, V, E, H, A = [int(x) for x in g["meta_dims"]]
-    cell = g["_cell"]
-    dec = R.Decoder(cell, 1, D, E, 1, H, A, V, 0.5, 0.5, 0.5, precision=prec)
-    dec.load_state_dict(P)
-    dec = dec.cuda().eval()
-    cfg = _Cfg()
-    cfg.batch_size, cfg.decoder_model = B, cell
-    inp = torch.full((1, B), 1, dtype=torch.long, device="cuda")
-    hid = (torch.zeros(1, B, H, device="cuda"), torch.zeros(1, B, H, device="cuda"))
-    if cell == "GRU":
-        hid = hid[0]                                     # a single tensor (eval.py:136-141)
-    return dec, cfg, inp, hid
 
 
 @pytest.mark.parametrize("name", CASES)
 def test_greedy_search_fp32_exact(name):
     g, P, enc = load_search_case(name)
-    dec, cfg, inp, hid = _decoder(g, P, "f32")
+    dec, cfg, inp, hid = decoder_for(g, P, "f32")
     out = R.greedy_search(cfg, dec, inp, hid, enc.cuda())
     assert np.array_equal(np.array(out, dtype=np.int64), g["greedy"])
 
@@ -43,7 +24,7 @@ def test_greedy_search_fp32_exact(name):
 @pytest.mark.parametrize("name", CASES)
 def test_beam_search_fp32_exact(name, bw):
     g, P, enc = load_search_case(name)
-    dec, cfg, inp, hid = _decoder(g, P, "f32")
+    dec, cfg, inp, hid = decoder_for(g, P, "f32")
     out = R.beam_search(cfg, bw, None, dec, inp, hid, enc.cuda())
     assert np.array_equal(np.array(out, dtype=np.int64), g["beam%d" % bw])
 
@@ -53,7 +34,7 @@ def test_step_api_loop_equals_device_loop(name):
     """eval.py's own greedy loop driven through Decoder.forward (the per-step API, invariants cached) gives the
     same tokens as the fused device-side loop."""
     g, P, enc = load_search_case(name)
-    dec, cfg, inp, hid = _decoder(g, P, "f32")
+    dec, cfg, inp, hid = decoder_for(g, P, "f32")
     encd = enc.cuda()
     toks, tok, h = [], inp, hid
     with torch.no_grad():
@@ -71,7 +52,7 @@ def test_bf16_search_mostly_agrees():
     """bf16 MFMA operands flip near-tie argmax decisions (and everything downstream of a flip), so only the
     first two steps are compared and a minority of captions may differ."""
     g, P, enc = load_search_case("search_small")
-    dec, cfg, inp, hid = _decoder(g, P, "bf16")
+    dec, cfg, inp, hid = decoder_for(g, P, "bf16")
     out = np.array(R.greedy_search(cfg, dec, inp, hid, enc.cuda()), dtype=np.int64)
     assert out.shape == g["greedy"].shape
     agree = (out[:2] == g["greedy"][:2]).mean()
@@ -128,7 +109,7 @@ def test_equal_maxima_go_to_the_lowest_index(cell, prec, pair):
         dec.out.bias[lo] += 50.0
         dec.out.bias[hi] += 50.0
     dec = dec.cuda().eval()
-    cfg = _Cfg()
+    cfg = Cfg()
     cfg.batch_size, cfg.decoder_model, cfg.caption_max_len = B, cell, 7
     enc = torch.randn(B, F, D, device="cuda")
     inp = torch.full((1, B), 1, dtype=torch.long, device="cuda")
@@ -146,9 +127,8 @@ def test_equal_maxima_go_to_the_lowest_index(cell, prec, pair):
     assert greedy.shape == (31, B) and (greedy == lo).all(), greedy
     best = np.array(R.beam_search(cfg, 2, None, dec, inp, hid, enc), dtype=np.int64)
     assert best.shape == (B, 31) and (best == lo).all(), best
-    rows = R.engine.Engine(dict(B=2, F=2, D=8, E=4, H=8, A=4, V=8), None, "f32")      # (supplies the device only)
-    vals, idx = rows.beam_select_rows(logits0[None].contiguous(), torch.zeros(1, B, device="cuda"),
-                                      torch.zeros(1, B, dtype=torch.int32, device="cuda"), 2)
+    vals, idx = rows_engine().beam_select_rows(logits0[None].contiguous(), torch.zeros(1, B, device="cuda"),
+                                               torch.zeros(1, B, dtype=torch.int32, device="cuda"), 2)
     assert torch.equal(vals[:, 0].view(torch.int32), vals[:, 1].view(torch.int32)), vals
     assert idx.cpu().tolist() == [[lo, hi]] * B, idx
     nbest = R.beam_search_nbest(cfg, dec, inp, hid, enc, 2)

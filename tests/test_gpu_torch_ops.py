@@ -10,6 +10,7 @@ import recnet_amd as R
 from recnet_amd import _lib, _ops
 from tests import golden_util as GU
 from tests.gpu_util import TOL, load_case, make_models, rel_err
+from tests.search_kit import bound_engine, decoder_for, rows_engine, same
 
 pytestmark = pytest.mark.gpu
 
@@ -81,42 +82,30 @@ def test_ops_validate_their_tensors():
         ops.forward_decoder(h, enc, targets, T, w.cpu(), True, 1)          # CPU tensors: no kernel registered
 
 
-def _bits(outs):
-    return [o.view(torch.int32) if o.dtype == torch.float32 else o for o in outs]
-
-
-def _same(a, b):
-    return len(a) == len(b) and all(torch.equal(x, y) for x, y in zip(_bits(a), _bits(b)))
-
-
 @pytest.mark.parametrize("family", ["sample_rows", "sample_search", "beam_select_rows"])
 def test_search_family_ops_equal_their_engine_methods(family):
     """The op and the Engine method of every member share one implementation per layer: equal bits, member by member.  The
     smallest shape that wraps the 256-thread stride with two hypotheses: rows = 3, V = 300, nb = 2, width 2."""
-    from tests.test_gpu_beam import _rows_engine
     ops = _ops.load()
     gen = torch.Generator().manual_seed(11)
     x = torch.randn(2, 3, 300, generator=gen).cuda()
     if family == "sample_rows":
-        eng, x2 = _rows_engine(), x[0].contiguous()
+        eng, x2 = rows_engine(), x[0].contiguous()
         h = int(eng.handle.value)
         plain = ops.sample_rows(h, x2, 0.7, 40, 5, 3)
-        assert _same(plain, eng.sample_rows(x2, 0.7, 40, 5, 3))
-        assert _same(ops.sample_rows_nucleus(h, x2, 0.7, 40, 0.8, 5, 3), eng.sample_rows_nucleus(x2, 0.7, 40, 0.8, 5, 3))
+        assert same(plain, eng.sample_rows(x2, 0.7, 40, 5, 3))
+        assert same(ops.sample_rows_nucleus(h, x2, 0.7, 40, 0.8, 5, 3), eng.sample_rows_nucleus(x2, 0.7, 40, 0.8, 5, 3))
         tok, lp, na = ops.sample_rows_nucleus(h, x2, 0.7, 40, 1.0, 5, 3)      # (no nucleus cut: the plain draw, and the count)
-        assert _same((tok, lp), plain) and (na == 40).all()
+        assert same((tok, lp), plain) and (na == 40).all()
     elif family == "sample_search":
-        from tests.test_gpu_nucleus import _engine_for
-        from tests.test_gpu_sample import _decoder
-        from tests.test_search_oracle import load_search_case
-        g, P, enc = load_search_case("search_small")
+        g, P, enc = GU.load_search_case("search_small")
         encd = enc.cuda()
-        eng = _engine_for(_decoder(g, P, "f32")[0], encd)
+        eng = bound_engine(decoder_for(g, P, "f32")[0], *encd.shape[:2], "f32")
         h = int(eng.handle.value)
-        assert _same(ops.sample_search(h, encd, 0.5, 5, 3), eng.sample_search(encd, 0.5, 5, 3))
-        assert _same(ops.sample_search_nucleus(h, encd, 0.5, 5, 0.8, 3), eng.sample_search_nucleus(encd, 0.5, 5, 0.8, 3))
+        assert same(ops.sample_search(h, encd, 0.5, 5, 3), eng.sample_search(encd, 0.5, 5, 3))
+        assert same(ops.sample_search_nucleus(h, encd, 0.5, 5, 0.8, 3), eng.sample_search_nucleus(encd, 0.5, 5, 0.8, 3))
     else:
-        eng = _rows_engine()
+        eng = rows_engine()
         h = int(eng.handle.value)
         cum = torch.randn(2, 3, generator=gen).cuda()
         fin = torch.tensor([[0, 0, 4], [0, 0, 0]], dtype=torch.int32).cuda()
@@ -127,12 +116,12 @@ def test_search_family_ops_equal_their_engine_methods(family):
                       eng.beam_select_rows(x, cum, fin, 2, hist=hist, t=3), ops.beam_select_rows_constrained(h, x, cum, fin, hist, 3, 2, 0, 0, []),
                       eng.beam_select_rows_diverse(x, cum, fin, 2, 1, 2.5, hist=hist, t=3),
                       ops.beam_select_rows_diverse(h, x, cum, fin, hist, 3, 2, 1, 2.5, 0, 0, [])):
-            assert _same(plain, other)
+            assert same(plain, other)
         con = eng.beam_select_rows(x, cum, fin, 2, hist=hist, t=3, no_repeat_ngram=2, min_length=4, banned_tokens=(7,))
         for other in (ops.beam_select_rows_constrained(h, x, cum, fin, hist, 3, 2, 2, 4, [7]),
                       eng.beam_select_rows_diverse(x, cum, fin, 2, 1, 2.5, hist=hist, t=3, no_repeat_ngram=2, min_length=4, banned_tokens=(7,)),
                       ops.beam_select_rows_diverse(h, x, cum, fin, hist, 3, 2, 1, 2.5, 2, 4, [7])):
-            assert _same(con, other)
+            assert same(con, other)
         two = eng.beam_select_rows_diverse(x, cum, fin, 2, 2, 0.5, hist=hist, t=3, no_repeat_ngram=2)
-        assert _same(two, ops.beam_select_rows_diverse(h, x, cum, fin, hist, 3, 2, 2, 0.5, 2, 0, []))
+        assert same(two, ops.beam_select_rows_diverse(h, x, cum, fin, hist, 3, 2, 2, 0.5, 2, 0, []))
     torch.cuda.synchronize()

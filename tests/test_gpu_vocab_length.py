@@ -22,7 +22,7 @@ from oracle import recnet_oracle as O
 from tests import golden_util as GU
 from tests import recon_ref as RR
 from tests import score_ref as SC
-from tests.gpu_util import TOL, make_models, oracle_grads, rel_err
+from tests.gpu_util import LR_TOL, REG_SLACK, TOL, make_models, moved, oracle_grads, rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -319,7 +319,6 @@ def test_replayed_update_path_at_Tm45(prec):
     oracle's train step (torch.optim.Adam as the reference builds it; pinned to the reference at these learning rates by
     tests/test_oracle_golden.py: test_large_learning_rate_runs_pin_the_update_rule) — every loss, the parameters and both
     moments relative to how far they moved, the packed operand images word for word."""
-    from tests.test_gpu_parity import LR_TOL, REG_SLACK, _moved
     cml, lens, n = 44, [40, 3, 0, 33, 7, 12], 3
     dims = [len(lens), F, D, V_LEN, E, H, A, RA]
     decP, recP = _params(V_LEN, "global")
@@ -354,7 +353,7 @@ def test_replayed_update_path_at_Tm45(prec):
         fl = md["_state"].flat()
         for k in P0:
             got = md["model"].state_dict()[k].cpu().numpy()
-            e, d = _moved(got, P[k].detach().numpy(), P0[k].numpy())
+            e, d = moved(got, P[k].detach().numpy(), P0[k].numpy())
             assert d > 1e-3, (grp, k, d)
             s = opt.state[P[k]]
             em = rel_err(fl["exp_avg"].views[k].cpu().numpy(), s["exp_avg"].numpy())

@@ -2,7 +2,6 @@
 against exact rational arithmetic on rows of equal values, the prefix property, a chi^2 test of the restated draw, the
 conditions under which tests/test_gpu_nucleus.py compares the device with it, and the argument checks of the boundary."""
 import ctypes as C
-import functools
 import math
 from fractions import Fraction
 
@@ -13,8 +12,8 @@ import torch
 from recnet_amd import search                   # (not `from recnet_amd.search import`: that would load a second copy of the module)
 from tests import nucleus_ref as NR
 from tests import sample_ref as SR
-from tests.test_sample_ref import _chi2_quantile_1m1e6, _step0_logits
-from tests.test_search_oracle import load_search_case
+from tests.golden_util import load_search_case
+from tests.search_kit import chi2_quantile_1m1e6, no_library, nucleus_row_sizes, step0_logits
 
 _check_top_p = search._check_top_p              # (these tests belong to the feature: without it the module does not import)
 TOP_PS = (1e-6, 0.05, 0.5, 0.9, 0.999, 1.0)
@@ -117,7 +116,7 @@ def test_top_p_one_is_the_draw_without_the_cut():
 def test_restated_draw_samples_the_renormalised_nucleus():
     """Pearson chi^2 of 20 000 draws of one row (row 0 of search_small_b's step-0 logits, tiled so that every copy has its own
     counters, (seed, t) varied) against the renormalised nucleus at top_p = 0.9; nothing outside it is ever drawn."""
-    row = _step0_logits()[0]
+    row = step0_logits()[0]
     copies, n_calls = 200, 100
     lg = np.tile(row, (copies, 1))
     V = row.shape[0]
@@ -133,28 +132,18 @@ def test_restated_draw_samples_the_renormalised_nucleus():
     p /= p.sum()
     e = copies * n_calls * p[ok]
     chi2 = float(((counts[ok] - e) ** 2 / e).sum())
-    bar = _chi2_quantile_1m1e6(n - 1)
+    bar = chi2_quantile_1m1e6(n - 1)
     print("nucleus", n, "of", V, "chi2", chi2, "bar", bar, "least expected count", e.min())
     assert chi2 < bar
 
 
 # ------------------------------------------------------------------------- the conditions of the GPU tests, held on the CPU
-@functools.lru_cache(maxsize=None)
-def _row_sizes(V):
-    out = {}
-    for rows, quantised, top_k, temperature, top_p, t, seed in NR.row_cases(V):
-        key = (rows, quantised, top_k, temperature, top_p)
-        if key not in out:
-            out[key] = NR.nucleus_sizes(SR.row_logits(V, rows, quantised), temperature, top_k, top_p)
-    return out
-
-
 @pytest.mark.parametrize("V", SR.ROW_VS)
 def test_row_cases_keep_the_rounding_bound_and_mostly_single_valued_bands(V):
     """b <= EPS / 2 on every row case, and at least 3/4 of the rows have n_lo == n_hi, so that the size check is exact there."""
     total = single = 0
     worst = 0.0
-    for key, (n, n_lo, n_hi, b) in _row_sizes(V).items():
+    for key, (n, n_lo, n_hi, b) in nucleus_row_sizes(V).items():
         assert (b <= NR.EPS / 2).all(), (V, key, b.max())
         assert ((1 <= n_lo) & (n_lo <= n) & (n <= n_hi)).all()
         worst = max(worst, float(b.max()))
@@ -169,7 +158,7 @@ def test_near_tie_exclusion_stays_inside_its_cap_for_the_row_cases(V):
     """At most 2 % of the rows drop out of the token comparison (sample_ref's cap), at the restatement's own sizes."""
     n = near = 0
     for rows, quantised, top_k, temperature, top_p, t, seed in NR.row_cases(V):
-        size = _row_sizes(V)[(rows, quantised, top_k, temperature, top_p)][0]
+        size = nucleus_row_sizes(V)[(rows, quantised, top_k, temperature, top_p)][0]
         margins = NR.draw(SR.row_logits(V, rows, quantised), size, temperature, seed, t)[2]
         n += rows
         near += int((margins < SR.NEAR_TIE).sum())
@@ -223,14 +212,7 @@ def test_python_accepts_every_top_p_in_range():
 @pytest.mark.parametrize("top_p", [0.0, -0.1, 1.5, float("nan"), float("inf"), "0.9", None])
 def test_python_checks_top_p_before_the_library(top_p, monkeypatch):
     import recnet_amd as R
-    import sys
-
-    def no_library(*a, **k):
-        raise AssertionError("the library was loaded")
-    loaders = [m for n, m in list(sys.modules.items()) if n.endswith(("_amd._lib", "_amd._ops")) and m is not None]
-    assert loaders
-    for m in loaders:
-        monkeypatch.setattr(m, "load", no_library)
+    no_library(monkeypatch)
     dec = R.Decoder("LSTM", 1, 32, 12, 1, 24, 8, 41, 0.5, 0.5, 0.5, precision="f32")
     inp = torch.full((1, 4), 1, dtype=torch.long)
     hid = (torch.zeros(1, 4, 24), torch.zeros(1, 4, 24))

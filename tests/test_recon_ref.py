@@ -2,7 +2,6 @@
 MSE term on the eval goldens — mean_b err[b] == rec_mse — and four plausible wrong definitions are shown to miss that pin; the host
 side of the feature (search.canonical_captions, pick_best_of_n's combined score, the argument checks of
 search.reconstruction_errors) is held where no engine exists."""
-import sys
 
 import numpy as np
 import pytest
@@ -10,6 +9,7 @@ import torch
 
 from tests import recon_ref as RR
 from tests.gpu_util import TOL, load_case
+from tests.search_kit import Cfg, no_library
 
 PIN = TOL["f32"]["loss"]          # relative bar of mean(err) against the golden rec_mse (the gap is the reference's own float32)
 
@@ -156,21 +156,6 @@ def test_pick_best_of_n_with_errors_is_the_brute_force_argmax():
 
 
 # ------------------------------------------------------------------------------------------------ argument checks before any launch
-class _Cfg:
-    caption_max_len = 30
-    decoder_model = "LSTM"
-    batch_size = 4
-
-
-def _no_library(monkeypatch):
-    def no_library(*a, **k):
-        raise AssertionError("the library was loaded")
-    loaders = [m for n, m in list(sys.modules.items()) if n.endswith(("_amd._lib", "_amd._ops")) and m is not None]
-    assert loaders
-    for m in loaders:
-        monkeypatch.setattr(m, "load", no_library)
-
-
 _V = 41
 _GOOD = [[3, 4, 5, 6], [7, 2, 2, 8]]
 BAD_CALLS = [
@@ -196,7 +181,7 @@ BAD_CALLS = [
 @pytest.mark.parametrize("what,kw,match", BAD_CALLS, ids=[c[0] for c in BAD_CALLS])
 def test_reconstruction_errors_checks_its_arguments_before_the_library(what, kw, match, kind, monkeypatch):
     import recnet_amd as R
-    _no_library(monkeypatch)
+    no_library(monkeypatch)
     dec = R.Decoder("LSTM", 1, 32, 12, 1, 24, 8, _V, 0.5, 0.5, 0.5, precision="f32")
     rec = (R.GlobalReconstructor("LSTM", 1, 24, 32, 0.5, 0.5, 30, precision="f32") if kind == "global"
            else R.LocalReconstructor("LSTM", 1, 24, 32, 0.5, 0.5, 8, precision="f32"))
@@ -204,24 +189,24 @@ def test_reconstruction_errors_checks_its_arguments_before_the_library(what, kw,
     enc = kw.pop("encoder_outputs", torch.zeros(4, 5, 32))
     rec = kw.pop("reconstructor", rec)
     with pytest.raises(ValueError, match=match):
-        R.reconstruction_errors(_Cfg(), dec, rec, enc, **kw)
+        R.reconstruction_errors(Cfg(), dec, rec, enc, **kw)
 
 
 def test_mismatched_models_are_refused_before_the_library(monkeypatch):
     import recnet_amd as R
-    _no_library(monkeypatch)
+    no_library(monkeypatch)
     dec = R.Decoder("LSTM", 1, 32, 12, 1, 24, 8, _V, 0.5, 0.5, 0.5, precision="f32")
     enc = torch.zeros(4, 5, 32)
     with pytest.raises(ValueError, match="decoder states"):
-        R.reconstruction_errors(_Cfg(), dec, R.LocalReconstructor("LSTM", 1, 16, 32, 0.5, 0.5, 8, precision="f32"), enc, _GOOD)
+        R.reconstruction_errors(Cfg(), dec, R.LocalReconstructor("LSTM", 1, 16, 32, 0.5, 0.5, 8, precision="f32"), enc, _GOOD)
     with pytest.raises(ValueError, match="caption_max_len"):
-        R.reconstruction_errors(_Cfg(), dec, R.GlobalReconstructor("LSTM", 1, 24, 32, 0.5, 0.5, 20, precision="f32"), enc, _GOOD)
+        R.reconstruction_errors(Cfg(), dec, R.GlobalReconstructor("LSTM", 1, 24, 32, 0.5, 0.5, 20, precision="f32"), enc, _GOOD)
     with pytest.raises(ValueError, match="precision"):
-        R.reconstruction_errors(_Cfg(), dec, R.LocalReconstructor("LSTM", 1, 24, 32, 0.5, 0.5, 8, precision="bf16"), enc, _GOOD)
+        R.reconstruction_errors(Cfg(), dec, R.LocalReconstructor("LSTM", 1, 24, 32, 0.5, 0.5, 8, precision="bf16"), enc, _GOOD)
     inp = torch.full((1, 4), 1, dtype=torch.long)
     hid = (torch.zeros(1, 4, 24), torch.zeros(1, 4, 24))
     with pytest.raises(ValueError, match="needs a reconstructor"):
-        R.best_of_n(_Cfg(), dec, inp, hid, enc, 2, recon_weight=0.5)
+        R.best_of_n(Cfg(), dec, inp, hid, enc, 2, recon_weight=0.5)
     with pytest.raises(ValueError, match="finite"):
-        R.best_of_n(_Cfg(), dec, inp, hid, enc, 2, reconstructor=R.LocalReconstructor("LSTM", 1, 24, 32, 0.5, 0.5, 8, precision="f32"),
+        R.best_of_n(Cfg(), dec, inp, hid, enc, 2, reconstructor=R.LocalReconstructor("LSTM", 1, 24, 32, 0.5, 0.5, 8, precision="f32"),
                     recon_weight=float("nan"))

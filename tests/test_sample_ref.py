@@ -2,7 +2,6 @@
 top_k = 1 form is the reference's greedy search, the near-tie exclusion stays inside its caps for every case the GPU tests
 compare, sequence_logprob, and the boundary's argument checks."""
 import ctypes as C
-import math
 
 import numpy as np
 import pytest
@@ -10,33 +9,15 @@ import torch
 
 from oracle import search_oracle as S
 from tests import sample_ref as SR
-from tests.test_search_oracle import CASES, load_search_case
-
-
-def _chi2_quantile_1m1e6(dof):
-    """1 - 1e-6 quantile of chi^2(dof): scipy when present, else Wilson-Hilferty with z = 4.753424 (Phi(z) = 1 - 1e-6)."""
-    try:
-        from scipy.stats import chi2
-        return float(chi2.ppf(1.0 - 1e-6, dof))
-    except ImportError:
-        z = 4.753424
-        return dof * (1.0 - 2.0 / (9.0 * dof) + z * math.sqrt(2.0 / (9.0 * dof))) ** 3
-
-
-def _step0_logits():
-    g, P, enc = load_search_case("search_small_b")
-    B, H = enc.shape[0], P["rnn.weight_hh_l0"].shape[1]
-    with torch.no_grad():
-        logits, _ = SR.O.decoder_step(P, torch.full((1, B), 1, dtype=torch.long), SR.O.zero_hidden(B, H, g["_cell"]), enc,
-                                      cell=g["_cell"], t=0)
-    return logits.numpy()
+from tests.golden_util import CASES, load_search_case
+from tests.search_kit import chi2_quantile_1m1e6, no_library, step0_logits
 
 
 @pytest.mark.parametrize("top_k", [0, 5])
 def test_restated_sampler_samples_the_softmax(top_k):
     """Pearson chi^2 of >= 20 000 draws (all rows of search_small_b's step-0 logits, (seed, t) varied) against softmax(logits),
     resp. against the renormalised five largest with no token outside them."""
-    lg = _step0_logits()
+    lg = step0_logits()
     B, V = lg.shape
     assert V == 61
     n_calls = -(-20000 // B)
@@ -50,7 +31,7 @@ def test_restated_sampler_samples_the_softmax(top_k):
     p /= p.sum(axis=1, keepdims=True)
     assert (counts[~ok] == 0).all()                              # nothing outside the allowed set is ever drawn
     dof = (top_k or V) - 1
-    bar = _chi2_quantile_1m1e6(dof)
+    bar = chi2_quantile_1m1e6(dof)
     for b in range(B):
         e = n_calls * p[b][ok[b]]
         chi2 = float(((counts[b][ok[b]] - e) ** 2 / e).sum())
@@ -135,15 +116,7 @@ def test_sampling_entry_points_need_a_bound_workspace(lib):
                                 dict(temperature=float("inf")), dict(top_k=-1), dict(top_k=42), dict(top_k=2.5)])
 def test_python_sample_search_checks_its_arguments_before_the_library(kw, monkeypatch):
     import recnet_amd as R
-    import sys
-
-    def no_library(*a, **k):
-        raise AssertionError("the library was loaded")
-    # the package is importable under two names; patch every loaded copy of the two loader modules
-    loaders = [m for n, m in list(sys.modules.items()) if n.endswith(("_amd._lib", "_amd._ops")) and m is not None]
-    assert loaders
-    for m in loaders:
-        monkeypatch.setattr(m, "load", no_library)
+    no_library(monkeypatch)
     dec = R.Decoder("LSTM", 1, 32, 12, 1, 24, 8, 41, 0.5, 0.5, 0.5, precision="f32")
     inp = torch.full((1, 4), 1, dtype=torch.long)
     hid = (torch.zeros(1, 4, 24), torch.zeros(1, 4, 24))

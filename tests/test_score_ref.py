@@ -2,7 +2,6 @@
 and to the sampling restatement's rollouts, its per-caption rule is search.sequence_logprob's, and the host side of the feature
 — search.score_captions' argument checks, best_of_n's selection rule — is held where no engine exists."""
 import math
-import sys
 
 import numpy as np
 import pytest
@@ -11,8 +10,9 @@ import torch
 from tests import golden_util as GU
 from tests import sample_ref as SR
 from tests import score_ref as SC
+from tests.golden_util import load_search_case
 from tests.gpu_util import load_case
-from tests.test_search_oracle import load_search_case
+from tests.search_kit import Cfg, no_library
 
 
 @pytest.mark.parametrize("name", SC.EVAL_GOLDENS)
@@ -96,22 +96,6 @@ def test_row_cases_cover_every_kind_of_token():
 
 
 # ------------------------------------------------------------------------------------------------ host side of the feature
-class _Cfg:
-    caption_max_len = 30
-    decoder_model = "LSTM"
-    batch_size = 4
-
-
-def _no_library(monkeypatch):
-    def no_library(*a, **k):
-        raise AssertionError("the library was loaded")
-    # the package is importable under two names; patch every loaded copy of the two loader modules
-    loaders = [m for n, m in list(sys.modules.items()) if n.endswith(("_amd._lib", "_amd._ops")) and m is not None]
-    assert loaders
-    for m in loaders:
-        monkeypatch.setattr(m, "load", no_library)
-
-
 _V = 41
 _GOOD = [[3, 4, 5, 6], [7, 2, 2, 8]]
 BAD_CALLS = [
@@ -137,10 +121,10 @@ BAD_CALLS = [
 @pytest.mark.parametrize("what,kw,match", BAD_CALLS, ids=[c[0] for c in BAD_CALLS])
 def test_score_captions_checks_its_arguments_before_the_library(what, kw, match, monkeypatch):
     import recnet_amd as R
-    _no_library(monkeypatch)
+    no_library(monkeypatch)
     dec = R.Decoder("LSTM", 1, 32, 12, 1, 24, 8, _V, 0.5, 0.5, 0.5, precision="f32")
     with pytest.raises(ValueError, match=match):
-        R.score_captions(_Cfg(), dec, torch.zeros(4, 5, 32), **kw)
+        R.score_captions(Cfg(), dec, torch.zeros(4, 5, 32), **kw)
 
 
 def test_good_arguments_pass_the_checks_and_reach_the_engine():
@@ -153,7 +137,7 @@ def test_good_arguments_pass_the_checks_and_reach_the_engine():
     dec = R.Decoder("LSTM", 1, 32, 12, 1, 24, 8, _V, 0.5, 0.5, 0.5, precision="f32")
     for caps in (_GOOD, torch.tensor(_GOOD), [[3, 4, 5, 6]] * 31):
         with pytest.raises(RuntimeError, match="needs a GPU"):
-            R.score_captions(_Cfg(), dec, torch.zeros(4, 5, 32), caps)
+            R.score_captions(Cfg(), dec, torch.zeros(4, 5, 32), caps)
 
 
 def test_best_of_n_selection_rule():
@@ -179,10 +163,10 @@ def test_best_of_n_selection_rule():
 
 def test_best_of_n_checks_n_before_the_library(monkeypatch):
     import recnet_amd as R
-    _no_library(monkeypatch)
+    no_library(monkeypatch)
     dec = R.Decoder("LSTM", 1, 32, 12, 1, 24, 8, _V, 0.5, 0.5, 0.5, precision="f32")
     inp = torch.full((1, 4), 1, dtype=torch.long)
     hid = (torch.zeros(1, 4, 24), torch.zeros(1, 4, 24))
     for n in (0, -1, 2.5):
         with pytest.raises(ValueError, match="n must be"):
-            R.best_of_n(_Cfg(), dec, inp, hid, torch.zeros(4, 5, 32), n)
+            R.best_of_n(Cfg(), dec, inp, hid, torch.zeros(4, 5, 32), n)

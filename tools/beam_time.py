@@ -12,38 +12,22 @@ the plain selection at the same nb = width: read them against the plain rows of 
 
     python tools/beam_time.py [--B 100 --F 28 --D 1536 --V 4188 --widths 1,5,8 --reps 10 --warmup 3 --rounds 5 --groups 8:2,8:4]
 """
-import argparse
 import json
-import os
-import statistics
-import sys
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import _timing
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    for k, v in (("B", 100), ("F", 28), ("D", 1536), ("E", 468), ("H", 512), ("A", 128), ("V", 4188), ("reps", 10), ("warmup", 3),
-                 ("rounds", 5), ("constrained", 1)):
-        ap.add_argument("--" + k, type=int, default=v)
+    ap = _timing.parser(reps=10, warmup=3, constrained=1)
     ap.add_argument("--widths", default="1,5,8")
     ap.add_argument("--groups", default="")
     ap.add_argument("--penalty", type=float, default=0.5)
     ap.add_argument("--length_alpha", type=float, default=0.7)
-    ap.add_argument("--precision", default="bf16")
     a = ap.parse_args()
     widths = [int(w) for w in a.widths.split(",")]
-    import recnet_amd as R
-    from recnet_amd.engine import Engine
-    if not torch.cuda.is_available():
-        raise SystemExit("beam_time.py needs a GPU: a CPU run says nothing about these times")
-    torch.manual_seed(0)
-    dec = R.Decoder("LSTM", 1, a.D, a.E, 1, a.H, a.A, a.V, 0.5, 0.5, 0.5, precision=a.precision).cuda().eval()
-    eng = Engine(dec.dims(a.B, a.F), None, a.precision, dec.hyper(), device="cuda")
-    eng.bind_decoder({k: v.data for k, v in dec.named_tensors().items()})
-    eng.pack_weights()
+    eng = _timing.bound_engine(a, _timing.decoder(a, "beam_time.py"))
     enc = torch.randn(a.B, a.F, a.D, device="cuda")
     nb = 8
     logits = torch.randn(nb, a.B, a.V, device="cuda") * 2.0
@@ -66,28 +50,12 @@ def main():
         calls["beam_search_nbest_diverse_w%d_g%d" % (w, G)] = lambda w=w, G=G: eng.beam_search_nbest_diverse(enc, w, a.length_alpha, G, a.penalty)
         calls["beam_select_rows_diverse_nb%d_w%d_g%d" % (w, w, G)] = lambda w=w, G=G: eng.beam_select_rows_diverse(logits[:w], cum[:w], fin[:w], w, G, a.penalty)
         calls["beam_select_rows_nb%d_w%d" % (w, w)] = lambda w=w: eng.beam_select_rows(logits[:w], cum[:w], fin[:w], w)
-    for fn in calls.values():
-        for _ in range(a.warmup):
-            fn()
-    torch.cuda.synchronize()
-    ms = {k: [] for k in calls}
-    for _ in range(a.rounds):
-        for k, fn in calls.items():
-            reps = a.reps * (20 if k.startswith("beam_select") else 1)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(reps):
-                fn()
-            e1.record()
-            e1.synchronize()
-            ms[k].append(e0.elapsed_time(e1) / reps)
+    ms = _timing.time_calls(a, calls, lambda k: 20 if k.startswith("beam_select") else 1)
     assert eng.chain_status() == 0
-    out = {"shape": {k: getattr(a, k) for k in ("B", "F", "D", "E", "H", "A", "V")}, "T": Tm, "constraints": {k: list(v) if isinstance(v, tuple) else v for k, v in con.items()},
+    out = {"shape": _timing.shape(a), "T": Tm, "constraints": {k: list(v) if isinstance(v, tuple) else v for k, v in con.items()},
            "precision": a.precision, "length_alpha": a.length_alpha, "reps": a.reps, "rounds": a.rounds, "groups": a.groups, "penalty": a.penalty,
            "select_bytes_unique": nb * a.B * a.V * 4, "select_bytes_read": 3 * nb * a.B * a.V * 4}
-    for k, v in ms.items():
-        out[k + "_ms"] = {"median": statistics.median(v), "min": min(v), "max": max(v)}
-    print(json.dumps(out))
+    print(json.dumps(dict(out, **ms)))
 
 
 if __name__ == "__main__":

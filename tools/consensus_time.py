@@ -8,16 +8,12 @@ printed as one JSON line.  Read the rerank against the search of the same run.
 
     python tools/consensus_time.py [--B 100 --F 28 --D 1536 --V 4188 --width 8 --shapes 8:31,16:31,32:64 --reps 10 --warmup 3 --rounds 5]
 """
-import argparse
 import json
-import os
-import statistics
-import sys
 import time
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import _timing
 
 
 def random_captions(N, T, B, gen):
@@ -29,23 +25,16 @@ def random_captions(N, T, B, gen):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    for k, v in (("B", 100), ("F", 28), ("D", 1536), ("E", 468), ("H", 512), ("A", 128), ("V", 4188), ("width", 8), ("reps", 10),
-                 ("warmup", 3), ("rounds", 5), ("host_runs", 3)):
-        ap.add_argument("--" + k, type=int, default=v)
+    ap = _timing.parser(reps=10, warmup=3, width=8, host_runs=3)
     ap.add_argument("--shapes", default="8:31,16:31,32:64")
     ap.add_argument("--length_alpha", type=float, default=0.7)
     ap.add_argument("--consensus_weight", type=float, default=0.5)
-    ap.add_argument("--precision", default="bf16")
     a = ap.parse_args()
     import recnet_amd as R
     from recnet_amd import search
     from tests import consensus_ref as CR
-    if not torch.cuda.is_available():
-        raise SystemExit("consensus_time.py needs a GPU: a CPU run says nothing about these times")
-    torch.manual_seed(0)
+    dec = _timing.decoder(a, "consensus_time.py")
     gen = torch.Generator().manual_seed(0)
-    dec = R.Decoder("LSTM", 1, a.D, a.E, 1, a.H, a.A, a.V, 0.5, 0.5, 0.5, precision=a.precision).cuda().eval()
 
     class Cfg:
         caption_max_len, decoder_model, batch_size = 30, "LSTM", a.B
@@ -61,21 +50,7 @@ def main():
         calls["consensus_rows_N%d_T%d" % (N, T)] = lambda caps=caps: eng.consensus_rows(caps)
     calls["beam_search_nbest_w%d" % a.width] = nbest
     calls["beam_search_nbest_w%d_then_consensus_rows" % a.width] = lambda: eng.consensus_rows(nbest())
-    for fn in calls.values():
-        for _ in range(a.warmup):
-            fn()
-    torch.cuda.synchronize()
-    ms = {k: [] for k in calls}
-    for _ in range(a.rounds):
-        for k, fn in calls.items():
-            reps = a.reps * (20 if k.startswith("consensus_rows") else 1)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(reps):
-                fn()
-            e1.record()
-            e1.synchronize()
-            ms[k].append(e0.elapsed_time(e1) / reps)
+    ms = _timing.time_calls(a, calls, lambda k: 20 if k.startswith("consensus_rows") else 1)
     # the public call, host wall time (it ends in read-backs and builds Python lists)
     wall = {"best_of_beam_w%d" % a.width: 0.0, "best_of_beam_w%d_consensus" % a.width: a.consensus_weight}
     for k, cw in list(wall.items()):
@@ -95,11 +70,12 @@ def main():
         ref = CR.consensus(toks.cpu().numpy())["util"]
         host.append((time.perf_counter() - t0) * 1e3)
     dev_util = eng.consensus_rows(toks).cpu().numpy()
-    out = {"shape": {k: getattr(a, k) for k in ("B", "F", "D", "E", "H", "A", "V")}, "precision": a.precision, "width": a.width,
+    out = {"shape": _timing.shape(a), "precision": a.precision, "width": a.width,
            "length_alpha": a.length_alpha, "reps": a.reps, "rounds": a.rounds, "search_steps": int(toks.shape[1]),
            "device_minus_host_max_abs": float(abs(dev_util - ref).max())}
-    for k, v in list(ms.items()) + [(k + "_wall", v) for k, v in wall.items()] + [("host_restatement_with_readback_wall", host)]:
-        out[k + "_ms"] = {"median": statistics.median(v), "min": min(v), "max": max(v)}
+    out.update(ms)
+    for k, v in [(k + "_wall", v) for k, v in wall.items()] + [("host_restatement_with_readback_wall", host)]:
+        out[k + "_ms"] = _timing.summary(v)
     print(json.dumps(out))
 
 

@@ -7,7 +7,7 @@ import sys, time, torch, ctypes as Cc
 sys.path.insert(0, __import__('os').path.dirname(__import__('os').path.dirname(__import__('os').path.abspath(__file__))))
 from recnet_amd.engine import Engine
 from recnet_amd import _lib
-eng = Engine(dict(B=2, F=2, D=8, E=4, H=8, A=4, V=8), None, "bf16")
+eng = Engine.device_only()
 thrash = torch.empty(160 << 20, device="cuda")      # 640 MB of fp32
 def graph_time(fns, n=10):
     for f in fns: f()

@@ -7,7 +7,7 @@ from recnet_amd import _lib
 M, N, K, ac, bc, sk = (int(x) for x in sys.argv[1:7])
 impl = sys.argv[7] if len(sys.argv) > 7 else "ours"
 n = int(sys.argv[8]) if len(sys.argv) > 8 else 20
-eng = Engine(dict(B=2, F=2, D=8, E=4, H=8, A=4, V=8), None, "bf16")
+eng = Engine.device_only()
 ld = lambda x: (x + 7) // 8 * 8
 A16 = torch.randn((K, ld(M)) if ac else (M, ld(K)), device="cuda").bfloat16(); B16 = torch.randn((K, ld(N)) if bc else (N, ld(K)), device="cuda").bfloat16()
 C = torch.zeros(M, N, device="cuda"); ws = torch.empty(max(sk, 1) * M * N, device="cuda")

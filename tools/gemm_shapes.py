@@ -2,7 +2,7 @@ import sys, time, torch, ctypes as Cc
 sys.path.insert(0, __import__('os').path.dirname(__import__('os').path.dirname(__import__('os').path.abspath(__file__))))
 from recnet_amd.engine import Engine
 from recnet_amd import _lib
-eng = Engine(dict(B=2, F=2, D=8, E=4, H=8, A=4, V=8), None, "bf16")
+eng = Engine.device_only()
 def bench(fn, n=20):
     for _ in range(2): fn()
     torch.cuda.synchronize()

@@ -8,16 +8,12 @@ and spreads are printed as one JSON line per kind.
 
     python tools/recon_time.py [--B 100 --F 28 --D 1536 --V 4188 --T 31 --reps 20 --warmup 5 --rounds 5 --kinds global,local]
 """
-import argparse
 import ctypes as C
 import json
-import os
-import statistics
-import sys
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import _timing
 
 
 def kernel_bytes(kind, B, F, D, want_recon):
@@ -27,29 +23,16 @@ def kernel_bytes(kind, B, F, D, want_recon):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    for k, v in (("B", 100), ("F", 28), ("D", 1536), ("E", 468), ("H", 512), ("A", 128), ("RA", 128), ("V", 4188), ("T", 31), ("reps", 20),
-                 ("warmup", 5), ("rounds", 5)):
-        ap.add_argument("--" + k, type=int, default=v)
-    ap.add_argument("--precision", default="bf16")
+    ap = _timing.parser(reps=20, warmup=5, RA=128, T=31)
     ap.add_argument("--kinds", default="global,local")
     a = ap.parse_args()
     import recnet_amd as R
     from recnet_amd import _lib
-    from recnet_amd.engine import Engine
-    if not torch.cuda.is_available():
-        raise SystemExit("recon_time.py needs a GPU: a CPU run says nothing about these times")
     for kind in a.kinds.split(","):
-        torch.manual_seed(0)
-        dec = R.Decoder("LSTM", 1, a.D, a.E, 1, a.H, a.A, a.V, 0.5, 0.5, 0.5, precision=a.precision).cuda().eval()
+        dec = _timing.decoder(a, "recon_time.py")
         rec = (R.GlobalReconstructor("LSTM", 1, a.H, a.D, 0.5, 0.5, 30, precision=a.precision) if kind == "global"
                else R.LocalReconstructor("LSTM", 1, a.H, a.D, 0.5, 0.5, a.RA, precision=a.precision)).cuda().eval()
-        dims = dec.dims(a.B, a.F)
-        dims.update(R=a.D, RA=a.RA if kind == "local" else 0, rec_cell="LSTM")
-        eng = Engine(dims, kind, a.precision, dec.hyper(), device="cuda")
-        eng.bind_decoder({k: v.data for k, v in dec.named_tensors().items()})
-        eng.bind_reconstructor({k: v.data for k, v in rec.named_tensors().items()})
-        eng.pack_weights()
+        eng = _timing.bound_engine(a, dec, rec, R=a.D, RA=a.RA if kind == "local" else 0, rec_cell="LSTM")
         enc = torch.randn(a.B, a.F, a.D, device="cuda")
         toks = torch.randint(3, a.V, (a.T, a.B), device="cuda")
         hid = torch.tanh(torch.randn(a.T, 1, a.B, a.H, device="cuda"))
@@ -58,20 +41,7 @@ def main():
                  "hiddens_with_recon": lambda: eng.reconstruction_error(enc, hiddens=hid, want_recon=True)}
         n_dec = eng.profile_site(9, calls["tokens"], 1)[0]
         n_rec = eng.profile_site(7, calls["hiddens"], 1)[0]
-        for fn in calls.values():
-            for _ in range(a.warmup):
-                fn()
-        torch.cuda.synchronize()
-        ms = {k: [] for k in calls}
-        for _ in range(a.rounds):
-            for k, fn in calls.items():
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(a.reps):
-                    fn()
-                e1.record()
-                e1.synchronize()
-                ms[k].append(e0.elapsed_time(e1) / a.reps)
+        ms = _timing.time_calls(a, calls)
         # the row kernel alone: its bracket minus E, what the two event records add to every bracket — from empty brackets of one and
         # of two empty kernels, bracket(count) = E + count * f (include/recnet_hip.h: recnet_profile_null_launch)
         def empty_bracket(count):
@@ -92,10 +62,7 @@ def main():
         assert eng.chain_status() == 0
         out = {"kind": kind, "shape": {k: getattr(a, k) for k in ("B", "F", "D", "E", "H", "A", "RA", "V", "T")}, "precision": a.precision,
                "decoder_chain_launches_per_call": n_dec, "reconstructor_chain_launches_per_call": n_rec, "reps": a.reps, "rounds": a.rounds}
-        for k, v in ms.items():
-            out[k + "_ms"] = {"median": statistics.median(v), "min": min(v), "max": max(v)}
-        out["error_kernel"] = kern
-        print(json.dumps(out))
+        print(json.dumps(dict(out, **ms, error_kernel=kern)))
 
 
 if __name__ == "__main__":
