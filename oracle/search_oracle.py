@@ -24,8 +24,12 @@ def greedy_search(P, enc, caption_max_len=30, cell="LSTM"):
     return np.stack(out)
 
 
-def beam_search(P, enc, beam_width, caption_max_len=30, cell="LSTM"):
-    """eval.py:36-120.  Returns the top-1 hypothesis per caption, [B][n_steps] int64."""
+def beam_search(P, enc, beam_width, caption_max_len=30, cell="LSTM", margins=False, beams=False):
+    """eval.py:36-120.  Returns the top-1 hypothesis per caption, [B][n_steps] int64.  margins=True: returns (that, margins float64
+    [n_steps][B]) — per decision the smallest non-zero gap between neighbours among the top beam_width + 1 scores, as
+    tests/beam_ref.py reports it (inf when there is none): a decision below a near-tie threshold may go the other way in another
+    fp32 evaluation order.  beams=True (with margins): a third output, per step t the pair (histories [beam_width][B][t + 1] of the
+    beams after that step's selection, the top beam_width + 1 scores [B][<= beam_width + 1] float64 it was made from)."""
     B = enc.shape[0]
     H = P["rnn.weight_hh_l0"].shape[1]
     V = P["out.weight"].shape[0]
@@ -33,6 +37,7 @@ def beam_search(P, enc, beam_width, caption_max_len=30, cell="LSTM"):
     hids = [O.zero_hidden(B, H, cell)]
     cums = [torch.zeros(B)]                                          # :39-40 log(1)
     hist = np.zeros((1, B, 0), dtype=np.int64)                       # [beam][B][t]
+    gaps, steps = [], []
     for t in range(caption_max_len + 1):
         scores, nxt = [], []
         for i in range(len(toks)):
@@ -48,6 +53,11 @@ def beam_search(P, enc, beam_width, caption_max_len=30, cell="LSTM"):
             scores.append(torch.log(torch.sigmoid(logits)) + cp.unsqueeze(1))   # :61-62
         allsc = torch.cat(scores, dim=1)                             # :63
         vals, flat = allsc.topk(beam_width)                          # :64
+        if margins:
+            top = allsc.topk(min(beam_width + 1, allsc.shape[1]))[0].double().numpy()
+            with np.errstate(invalid="ignore"):
+                d = top[:, :-1] - top[:, 1:]
+            gaps.append(np.where(np.isnan(d) | (d == 0), np.inf, d).min(axis=1))
         src, tok = (flat // V).numpy(), (flat % V).numpy()           # :68-69
         new_hist = np.zeros((beam_width, B, t + 1), dtype=np.int64)
         toks2, hids2, cums2 = [], [], []
@@ -64,6 +74,10 @@ def beam_search(P, enc, beam_width, caption_max_len=30, cell="LSTM"):
                 new_hist[k, b, :t] = hist[src[b, k], b]
                 new_hist[k, b, t] = tok[b, k]                        # :104-108
         toks, hids, cums, hist = toks2, hids2, cums2, new_hist
+        if margins and beams:
+            steps.append((new_hist, top))
         if t == caption_max_len or all(bool((x == 0).all()) for x in toks):   # :116
             break
-    return hist[0]                                                   # :119
+    if margins and beams:
+        return hist[0], np.stack(gaps), steps
+    return (hist[0], np.stack(gaps)) if margins else hist[0]         # :119

@@ -305,7 +305,9 @@ static int pack_weights(recnet_handle* h, hipStream_t st) {
 static void launch_dec_cell(recnet_handle* h, const DecCellArgs& args, int rows, hipStream_t st) {
   DecCellArgs a = args;
   a.B = rows;
-  if (h->lp && (h->H & 7) == 0 && h->F <= 32 && h->A <= 128 && (h->ld4H & 7) == 0) {
+  // (A % 4: the kernel's LDS rows behind swh[A] are written with 16-byte stores, so A floats must keep them 16-byte aligned; the
+  // persistent chain of host_decoder.inc asks for (4H + A) % 16 == 0 with H % 8 == 0, which implies A % 16 == 0)
+  if (h->lp && (h->H & 7) == 0 && h->F <= 32 && h->A <= 128 && (h->A & 3) == 0 && (h->ld4H & 7) == 0) {
     const size_t smv = (size_t)(h->A + ((h->F + 3) & ~3) + 4 * 512 + 16) * 4;
     hipLaunchKernelGGL(dec_cell_vec_kernel<bf16_t>, dim3(rows, cdiv(h->H, 512)), dim3(256), smv, st, a);
     return;

@@ -148,7 +148,7 @@ __global__ __launch_bounds__(1024) void dec_cell_kernel(const DecCellArgs p) {
     for (int j = H + tid; j < p.ld_hlp; j += NT) reinterpret_cast<AT*>(p.h_lp)[(size_t)b * p.ld_hlp + j] = (AT)0.f;
 }
 
-// Vector form of dec_cell_kernel for the bf16 path (H % 8 == 0, F <= 32, A <= 128): wave = gate, each lane owns 8
+// Vector form of dec_cell_kernel for the bf16 path (H % 8 == 0, F <= 32, A <= 128, A % 4 == 0): wave = gate, each lane owns 8
 // consecutive hidden units, so every P / Xe / slab access is a 16-byte load and a wave-instruction covers 1 KiB of
 // one row (the generic kernel reads P with 2-byte loads, 128 B per instruction).  One workgroup covers 512 units
 // x 4 gates of one caption; all loads are issued before the scores are computed.
@@ -157,7 +157,7 @@ __global__ __launch_bounds__(256) void dec_cell_vec_kernel(const DecCellArgs p) 
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* swh = smem;            // [A]
   float* sa = swh + p.A;        // [F] (+ pad to 16 B)
-  float* spre = sa + ((p.F + 3) & ~3);   // [4][512]
+  float* spre = sa + ((p.F + 3) & ~3);   // [4][512], stored to as f32x4: 16-byte aligned because A % 4 == 0 (launch_dec_cell)
   const int b = blockIdx.x, u0 = blockIdx.y * 512, tid = threadIdx.x, lane = tid & 63, g = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int bc = p.nc ? b % p.nc : b;         // the caption whose Uv / P this row reads
   const int H = p.H, A = p.A, F = p.F, W4 = 4 * H, WS = 4 * H + A;

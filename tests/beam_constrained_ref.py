@@ -186,6 +186,9 @@ RUNS = [
     dict(name="search_gru_b", bw=5, cml=30, n=3, m=0, banned=(), cap=0.75, steps=(31, 31), unc=(20, 0, 0), total=30, share=0.962, full=(5, 6)),
     dict(name="search_gru", bw=3, cml=30, n=2, m=0, banned=(), cap=0.75, steps=(31, 31), unc=(6, 0, 0), total=18, share=0.855, full=(5, 6)),
     dict(name="search_gru", bw=3, cml=30, n=1, m=0, banned=(), cap=0.75, steps=(31, 26), unc=(6, 0, 0), total=18, share=1.000, full=(6, 6)),
+    # shape_rows160: the shape case rows160 of tests/search_shapes.py (B = 20, H = 320): 160 rows, the ring GEMM past one row tile;
+    # one banned id, the most frequent one of the unconstrained result
+    dict(name="rows160", bw=8, cml=7, n=2, m=3, banned=(72,), cap=0.75, steps=(8, 8), unc=(75, 75, 118), total=160, share=0.838, full=(14, 20)),
 ]
 
 

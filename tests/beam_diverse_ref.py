@@ -169,6 +169,8 @@ RUNS = [
     _run("search_gru", 6, 3, 1.0, 7, 8, 1.000, (6, 6), n=2, m=3, banned=(55, 78)),
     _run("search_gru_stop", 6, 3, 0.5, 7, 8, 0.781, (2, 4), n=2),
     _run("search_small_b", 6, 2, 0.5, 7, 8, 0.750, (2, 4), n=2),
+    # shape_rows160: the shape case rows160 of tests/search_shapes.py (B = 20, H = 320): 160 rows, the ring GEMM past one row tile
+    _run("rows160", 8, 2, 0.5, 7, 8, 0.994, (18, 20)),
 ]
 
 

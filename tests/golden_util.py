@@ -76,18 +76,36 @@ def load(name):
 CASES = ["search_small", "search_small_b", "search_eos", "search_stop", "search_gru", "search_gru_b", "search_gru_stop"]
 
 
-def load_search_case(name):
-    """(golden, decoder parameters, features) of one of the search goldens (CASES)."""
-    g = load(name)
-    B, F, D, V, E, H, A = [int(x) for x in g["meta_dims"]]
-    g["_cell"] = cells_of(g)[0]
-    P = formula_params(decoder_shapes(V, E, H, A, D, g["_cell"]), int(g["meta_seed"]))
-    sc = float(g["meta_scale"])
+def search_params(dims, seed, scale, eos_bias, pad_bias, cell):
+    """The decoder parameters of a search case: formula_params at `seed`, out.* times `scale` (peaked distributions: few near-ties),
+    then the <EOS> / <PAD> biases.  dims = (B, F, D, V, E, H, A)."""
+    B, F, D, V, E, H, A = [int(x) for x in dims]
+    P = formula_params(decoder_shapes(V, E, H, A, D, cell), int(seed))
+    sc = float(scale)
     P["out.weight"] = P["out.weight"] * sc
     P["out.bias"] = P["out.bias"] * sc
-    P["out.bias"][2] += float(g["meta_eos_bias"])
-    P["out.bias"][0] += float(g["meta_pad_bias"])
-    return g, P, torch.from_numpy(g["enc"])
+    P["out.bias"][2] += float(eos_bias)
+    P["out.bias"][0] += float(pad_bias)
+    return P
+
+
+def load_search_case(name):
+    """(golden, decoder parameters, features) of one of the search goldens (CASES), or of a shape case of tests/search_shapes.py
+    (SHAPES, REF_SHAPES): those have no .npz behind them — g holds the meta_* entries and _cell only, the features are randn(B, F, D) from
+    Generator(seed + 50)."""
+    from tests.search_shapes import REF_SHAPES, SHAPES
+    if name in SHAPES or name in REF_SHAPES:
+        c = SHAPES[name] if name in SHAPES else REF_SHAPES[name]
+        g = {"meta_dims": np.array(c["dims"], dtype=np.int64), "meta_seed": np.int64(c["seed"]), "meta_scale": np.float64(c["scale"]),
+             "meta_eos_bias": np.float64(c["eos_bias"]), "meta_pad_bias": np.float64(c["pad_bias"]), "_cell": c["cell"]}
+        B, F, D = c["dims"][:3]
+        enc = torch.randn(B, F, D, generator=torch.Generator().manual_seed(int(c["seed"]) + 50))
+    else:
+        g = load(name)
+        g["_cell"] = cells_of(g)[0]
+        enc = torch.from_numpy(g["enc"])
+    P = search_params(g["meta_dims"], g["meta_seed"], g["meta_scale"], g["meta_eos_bias"], g["meta_pad_bias"], g["_cell"])
+    return g, P, enc
 
 
 RECSTEP_CASES = ["recstep_global_eval", "recstep_global_train", "recstep_local_eval", "recstep_local_train",

@@ -129,7 +129,9 @@ def comparable(run):
 SEARCH_RUNS = [("search_small", 2, 1.0, 0, 0.9), ("search_small_b", 1, 1.0, 0, 0.9), ("search_eos", 1, 1.0, 0, 0.9),
                ("search_stop", 1, 1.0, 0, 0.9), ("search_gru", 7, 1.0, 0, 0.9), ("search_gru_b", 1, 1.0, 0, 0.9),
                ("search_gru_stop", 1, 1.0, 0, 0.9), ("search_small", 1, 0.5, 5, 0.8), ("search_gru", 1, 0.5, 5, 0.8),
-               ("search_small_b", 1, 1.0, 0, 0.5), ("search_gru_b", 1, 1.0, 0, 0.5)]
+               ("search_small_b", 1, 1.0, 0, 0.5), ("search_gru_b", 1, 1.0, 0, 0.5),
+               # shape_rows160: the shape case rows160 of tests/search_shapes.py (B = 20, H = 320: three slabs)
+               ("rows160", 2, 1.0, 20, 0.9)]
 
 ROW_TOP_P = (0.05, 0.5, 0.9, 0.999)
 

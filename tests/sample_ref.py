@@ -100,7 +100,9 @@ def comparable(margins):
 # (tests/test_sample_ref.py holds the cap of one caption per run without a GPU).
 SEARCH_RUNS = [("search_small", 4, 1.0, 0), ("search_small_b", 3, 1.0, 0), ("search_eos", 4, 1.0, 0), ("search_stop", 2, 1.0, 0),
                ("search_gru", 7, 1.0, 0), ("search_gru_b", 2, 1.0, 0), ("search_gru_stop", 2, 1.0, 0),
-               ("search_small", 5, 0.5, 5), ("search_gru", 6, 0.5, 5)]
+               ("search_small", 5, 0.5, 5), ("search_gru", 6, 0.5, 5),
+               # shape_rows160: the shape case rows160 of tests/search_shapes.py (B = 20, H = 320: three slabs), top_k = 20
+               ("rows160", 2, 1.0, 20)]
 
 # Kernel-alone cases: one element, the goldens' vocabulary (61), the block size and its neighbours, the benchmark vocabulary,
 # and a row longer than the 12288 floats the kernel keeps in LDS.

@@ -1,15 +1,19 @@
 """What the search tests share (a plain module: no fixtures): the config and the decoder of a search golden with its start state,
-engines of a test's own, the guard that shows a check comes before the library, bit-equality of op outputs, and the statistics the
-sampling tests hold their draws to."""
+engines of a test's own, the guard that shows a check comes before the library, bit-equality of op outputs, the statistics the
+sampling tests hold their draws to, and the two test bodies tests/test_gpu_beam.py shares with tests/test_gpu_search_shapes.py."""
 import functools
 import math
 import sys
 
+import numpy as np
 import torch
 
 import recnet_amd as R
+from recnet_amd import search
+from tests import beam_ref as BR
 from tests import nucleus_ref as NR
 from tests import sample_ref as SR
+from tests import score_ref as SC
 from tests.golden_util import load_search_case
 from tests.gpu_util import TOL
 
@@ -103,3 +107,89 @@ def nucleus_row_sizes(V):
         if key not in out:
             out[key] = NR.nucleus_sizes(SR.row_logits(V, rows, quantised), temperature, top_k, top_p)
     return out
+
+
+def check_nbest_against_restatement(name, bw, cml, r=None):
+    """The body of tests/test_gpu_beam.py::test_search_matches_the_restatement (its docstring says what is held), shared with
+    tests/test_gpu_search_shapes.py.  r: beam_ref.beam_search_nbest(P, enc, bw, BR.LENGTH_ALPHA, cml, cell) of the case when the
+    caller has it already."""
+    g, P, enc = load_search_case(name)
+    if r is None:
+        r = BR.beam_search_nbest(P, enc, bw, BR.LENGTH_ALPHA, cml, g["_cell"])
+    dec, cfg, inp, hid = decoder_for(g, P, "f32", cml)
+    toks, cum, ln, score = search._beam_nbest(cfg, dec, inp, hid, enc.cuda(), bw, BR.LENGTH_ALPHA)
+    toks, cum, ln, score = toks.cpu().numpy(), cum.cpu().numpy().astype(np.float64), ln.cpu().numpy(), score.cpu().numpy().astype(np.float64)
+    keep = BR.comparable_captions(r)
+    n = toks.shape[1]
+    assert toks.shape == (bw, n, enc.shape[0]) and 1 <= n <= cml + 1
+    if keep.all():
+        assert n == r["n_steps"]
+    m = min(n, r["n_steps"])
+    assert np.array_equal(ln[:, keep], r["len"][:, keep])
+    assert np.array_equal(toks[:, :m][:, :, keep], r["tokens"][:, :m][:, :, keep])
+    assert (toks[:, m:][:, :, keep] == 0).all() and (r["tokens"][:, m:][:, :, keep] == 0).all()
+    bar = r["len"] * SC.row_bar("f32", r["amax"].max(), 1.0)
+    err = np.abs(cum - r["cum"])[:, keep]
+    errs = np.abs(score - r["score"])[:, keep]
+    worst = float((err / bar[:, keep]).max()) if err.size else 0.0
+    print(name, "width", bw, "cml", cml, "steps", n, "captions compared", int(keep.sum()), "of", keep.size, "worst cum error / bar:", worst)
+    assert (err <= bar[:, keep]).all() and (errs <= bar[:, keep]).all()
+    # an excluded caption is compared up to its first near-tie decision t0: the beams after step t0 - 1 are the restatement's, and
+    # every returned hypothesis descends from one of them, so its first t0 tokens are one of their histories
+    t0 = BR.comparable_steps(r["margins"]).sum(axis=0)
+    prefixes = 0
+    for b in np.nonzero(~keep)[0]:
+        k = int(t0[b])
+        if k == 0:
+            continue
+        allowed = {tuple(h) for h in r["trace"][k - 1][3][:, b, :k].tolist()}
+        for rank in range(bw):
+            got = toks[rank, :k, b].tolist()
+            got += [0] * (k - len(got))          # (a search that stopped earlier carries <PAD>)
+            assert tuple(got) in allowed, (b, rank, k, got, allowed)
+        prefixes += k
+    print(name, "width", bw, "decisions compared through excluded captions' prefixes:", prefixes)
+    assert keep.any() or prefixes > 0            # every run checks tokens on the device
+    # the public list form of the same call
+    hyps = R.beam_search_nbest(cfg, dec, inp, hid, enc.cuda(), bw, BR.LENGTH_ALPHA)
+    assert len(hyps) == enc.shape[0] and all(len(h) == bw for h in hyps)
+    for b, h in enumerate(hyps):
+        for k, (t, c, l, s) in enumerate(h):
+            assert l == ln[k, b] and t == toks[k, :l, b].tolist() and c == float(cum[k, b]) and s == float(score[k, b])
+
+
+def check_self_consistency(name, prec, amax=None):
+    """The body of tests/test_gpu_beam.py::test_self_consistency, shared with tests/test_gpu_search_shapes.py.  amax: max |logit| of
+    the case for the row bar, when the caller has a restatement of it already (default: the width-3 restatement over 31 steps).
+    Returns the worst error / bar."""
+    g, P, enc = load_search_case(name)
+    dec, cfg, inp, hid = decoder_for(g, P, prec)
+    encd = enc.cuda()
+    greedy = np.array(R.greedy_search(cfg, dec, inp, hid, encd), dtype=np.int64)      # [n][B]
+    t1, _, l1, _ = search._beam_nbest(cfg, dec, inp, hid, encd, 1, 0.0)
+    t1, l1 = t1.cpu().numpy()[0], l1.cpu().numpy()[0]
+    for b in range(enc.shape[0]):
+        n = min(greedy.shape[0], t1.shape[0])
+        eos = np.nonzero(greedy[:n, b] == BR.EOS)[0]
+        upto = int(eos[0]) + 1 if eos.size else n
+        assert np.array_equal(t1[:upto, b], greedy[:upto, b]), (b, t1[:, b], greedy[:, b])
+        assert l1[b] == (upto if eos.size else t1.shape[0])
+    if amax is None:
+        amax = BR.beam_search_nbest(P, enc, 3, 0.7, 30, g["_cell"])["amax"].max()
+    worst = 0.0
+    for bw in (3, 8):
+        a = search._beam_nbest(cfg, dec, inp, hid, encd, bw, 0.7)
+        b2 = search._beam_nbest(cfg, dec, inp, hid, encd, bw, 0.7)
+        assert all(torch.equal(x, y) for x, y in zip(a, b2))
+        toks, cum, ln, score = a
+        assert (score[:-1] >= score[1:]).all()
+        for k in range(bw):
+            assert torch.equal(R.canonical_captions(toks[k]), toks[k])
+            _, cap, sl = search._score(dec, encd, toks[k].contiguous(), 1.0, False)
+            assert torch.equal(sl.cpu(), ln[k].cpu()), (k, sl, ln[k])
+            bar = ln[k].cpu().numpy() * SC.row_bar(prec, amax, 1.0)
+            err = np.abs(cap.cpu().numpy().astype(np.float64) - cum[k].cpu().numpy())
+            worst = max(worst, float((err / bar).max()))
+            assert (err <= bar).all(), (k, err, bar)
+    print(name, prec, "worst |score_captions - cum| / (len x row bar):", worst)
+    return worst

@@ -45,7 +45,7 @@ def test_runs_hold_their_table(run):
     u = _unconstrained(name, bw, cml)
     r = _constrained(name, bw, cml, n, m, banned)
     if banned:                                   # the hard-coded ids are what the rule gives on the unconstrained result
-        assert CR.frequent_ids(u["tokens"], u["len"]) == banned
+        assert CR.frequent_ids(u["tokens"], u["len"], len(banned)) == banned
     assert bw + len(banned) + cml + 1 <= int(g["meta_dims"][3])
     # the constraints bind on the unconstrained result, in every constraint the run switches on, and hold on the constrained one
     uv = CR.violations(u["tokens"], u["len"], n, m, banned)

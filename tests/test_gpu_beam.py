@@ -21,7 +21,7 @@ from tests import score_ref as SC
 from tests.golden_util import load_search_case
 from tests.gpu_util import make_models
 from tests.sample_ref import NEAR_TIE
-from tests.search_kit import decoder_for, rows_engine
+from tests.search_kit import check_nbest_against_restatement, check_self_consistency, decoder_for, rows_engine
 
 pytestmark = pytest.mark.gpu
 
@@ -93,48 +93,7 @@ def test_search_matches_the_restatement(name, bw, cml, cap):
     """fp32 path: n_steps (when no caption is excluded), tokens, len and the rank order equal the restatement on the captions without
     any near-tie decision; cum within len x the row bar, score within the same bar (len^alpha >= 1).  A caption with a near-tie is
     compared up to that decision: the first t0 tokens of each of its returned hypotheses against the restatement's beams."""
-    g, P, enc = load_search_case(name)
-    r = BR.beam_search_nbest(P, enc, bw, BR.LENGTH_ALPHA, cml, g["_cell"])
-    dec, cfg, inp, hid = decoder_for(g, P, "f32", cml)
-    toks, cum, ln, score = search._beam_nbest(cfg, dec, inp, hid, enc.cuda(), bw, BR.LENGTH_ALPHA)
-    toks, cum, ln, score = toks.cpu().numpy(), cum.cpu().numpy().astype(np.float64), ln.cpu().numpy(), score.cpu().numpy().astype(np.float64)
-    keep = BR.comparable_captions(r)
-    n = toks.shape[1]
-    assert toks.shape == (bw, n, enc.shape[0]) and 1 <= n <= cml + 1
-    if keep.all():
-        assert n == r["n_steps"]
-    m = min(n, r["n_steps"])
-    assert np.array_equal(ln[:, keep], r["len"][:, keep])
-    assert np.array_equal(toks[:, :m][:, :, keep], r["tokens"][:, :m][:, :, keep])
-    assert (toks[:, m:][:, :, keep] == 0).all() and (r["tokens"][:, m:][:, :, keep] == 0).all()
-    bar = r["len"] * SC.row_bar("f32", r["amax"].max(), 1.0)
-    err = np.abs(cum - r["cum"])[:, keep]
-    errs = np.abs(score - r["score"])[:, keep]
-    worst = float((err / bar[:, keep]).max()) if err.size else 0.0
-    print(name, "width", bw, "cml", cml, "steps", n, "captions compared", int(keep.sum()), "of", keep.size, "worst cum error / bar:", worst)
-    assert (err <= bar[:, keep]).all() and (errs <= bar[:, keep]).all()
-    # an excluded caption is compared up to its first near-tie decision t0: the beams after step t0 - 1 are the restatement's, and
-    # every returned hypothesis descends from one of them, so its first t0 tokens are one of their histories
-    t0 = BR.comparable_steps(r["margins"]).sum(axis=0)
-    prefixes = 0
-    for b in np.nonzero(~keep)[0]:
-        k = int(t0[b])
-        if k == 0:
-            continue
-        allowed = {tuple(h) for h in r["trace"][k - 1][3][:, b, :k].tolist()}
-        for rank in range(bw):
-            got = toks[rank, :k, b].tolist()
-            got += [0] * (k - len(got))          # (a search that stopped earlier carries <PAD>)
-            assert tuple(got) in allowed, (b, rank, k, got, allowed)
-        prefixes += k
-    print(name, "width", bw, "decisions compared through excluded captions' prefixes:", prefixes)
-    assert keep.any() or prefixes > 0            # every run checks tokens on the device
-    # the public list form of the same call
-    hyps = R.beam_search_nbest(cfg, dec, inp, hid, enc.cuda(), bw, BR.LENGTH_ALPHA)
-    assert len(hyps) == enc.shape[0] and all(len(h) == bw for h in hyps)
-    for b, h in enumerate(hyps):
-        for k, (t, c, l, s) in enumerate(h):
-            assert l == ln[k, b] and t == toks[k, :l, b].tolist() and c == float(cum[k, b]) and s == float(score[k, b])
+    check_nbest_against_restatement(name, bw, cml)
 
 
 @pytest.mark.parametrize("name", ["search_small", "search_gru"])
@@ -143,35 +102,7 @@ def test_self_consistency(name, prec):
     """Width 1 is greedy_search up to each caption's first <EOS>, exactly (the same step at the same precision, the same tie rule);
     score_captions on each returned rank reproduces len exactly and cum within len x the row bar of the precision; a second call
     gives the same bits; every rank is canonical."""
-    g, P, enc = load_search_case(name)
-    dec, cfg, inp, hid = decoder_for(g, P, prec)
-    encd = enc.cuda()
-    greedy = np.array(R.greedy_search(cfg, dec, inp, hid, encd), dtype=np.int64)      # [n][B]
-    t1, _, l1, _ = search._beam_nbest(cfg, dec, inp, hid, encd, 1, 0.0)
-    t1, l1 = t1.cpu().numpy()[0], l1.cpu().numpy()[0]
-    for b in range(enc.shape[0]):
-        n = min(greedy.shape[0], t1.shape[0])
-        eos = np.nonzero(greedy[:n, b] == BR.EOS)[0]
-        upto = int(eos[0]) + 1 if eos.size else n
-        assert np.array_equal(t1[:upto, b], greedy[:upto, b]), (b, t1[:, b], greedy[:, b])
-        assert l1[b] == (upto if eos.size else t1.shape[0])
-    amax = BR.beam_search_nbest(P, enc, 3, 0.7, 30, g["_cell"])["amax"].max()
-    worst = 0.0
-    for bw in (3, 8):
-        a = search._beam_nbest(cfg, dec, inp, hid, encd, bw, 0.7)
-        b2 = search._beam_nbest(cfg, dec, inp, hid, encd, bw, 0.7)
-        assert all(torch.equal(x, y) for x, y in zip(a, b2))
-        toks, cum, ln, score = a
-        assert (score[:-1] >= score[1:]).all()
-        for k in range(bw):
-            assert torch.equal(R.canonical_captions(toks[k]), toks[k])
-            _, cap, sl = search._score(dec, encd, toks[k].contiguous(), 1.0, False)
-            assert torch.equal(sl.cpu(), ln[k].cpu()), (k, sl, ln[k])
-            bar = ln[k].cpu().numpy() * SC.row_bar(prec, amax, 1.0)
-            err = np.abs(cap.cpu().numpy().astype(np.float64) - cum[k].cpu().numpy())
-            worst = max(worst, float((err / bar).max()))
-            assert (err <= bar).all(), (k, err, bar)
-    print(name, prec, "worst |score_captions - cum| / (len x row bar):", worst)
+    check_self_consistency(name, prec)
 
 
 # ------------------------------------------------------------------------------------------------ 3. reranking, evaluate
