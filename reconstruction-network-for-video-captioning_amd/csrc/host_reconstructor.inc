@@ -551,7 +551,10 @@ static int bwd_rec_local_deferred(recnet_handle* h, hipStream_t st, int part = 0
     if (hh) hipMemsetAsync(h->rG.rnn_weight_hh_l0, 0, (size_t)GR * R * 4, st);
   }
   gg_add(h, g, h->dGr, ld4R, h->Xcat_r, ldHR, h->rG.rnn_weight_ih_l0, H, nullptr, GR, H, FB, 1.f, 0, st);
-  colsum_at(h, h->dWhrs, FB, RA, h->ldRA, h->rG.attn_b, st);
+  // d attn_b = sum_{s,b,t} dz = the column sums of dUd (fp32, [T][B][RA], written whole by every backward form).  The same sum over dWhrs
+  // would add bf16-rounded terms of a sum that nearly cancels (the softmax gradient sums to zero over t): the chain and the per-step
+  // form round dWhr_s at different points and differed by 2.6e-3 of this gradient (tests/test_gpu_cells.py: test_gru_local_chain_variants)
+  colsum_t<float>(h->dUd, TB, RA, RA, h->rG.attn_b, st);
   colsum_t<float>(h->dwacc_r, RN_TCH * B, RA, RA, h->rG.attn_w_weight, st);
   gate_bias_grad(h, h->dGr, FB, R, ld4R, h->rG.rnn_bias_ih_l0, h->rG.rnn_bias_hh_l0, h->rgru, st);
   gg_run(h, g, st, stamp_site(2));      // (behind the column sums: see bwd_rec_global_deferred)

@@ -43,6 +43,8 @@ def _same(a, b, name, exact):
     return torch.allclose(a, b, rtol=2e-4, atol=2e-8)
 
 
+LL, GG, LG = ("LSTM", "LSTM"), ("GRU", "GRU"), ("LSTM", "GRU")      # (decoder cell, reconstructor cell)
+
 # the optimiser settings the reference's defaults never reach: AMSGrad on the reconstructor (the ad_vmax branch of the GEMM
 # epilogue, the split update), a weight decay that matters, other betas
 HYPER = dict(reconstructor_use_amsgrad=True, decoder_weight_decay=1e-2, reconstructor_weight_decay=1e-2, adam_beta1=0.8, adam_beta2=0.95)
@@ -58,13 +60,13 @@ def _preload_vmax(md, seed):
             v.copy_((10.0 ** (-12.0 * torch.rand(v.shape, generator=g))).to(v.device))
 
 
-def _run(kind, prec, dims, deferred, lens_sets, order, lr=None, hyper=None, epilogue=False):
+def _run(kind, prec, dims, deferred, lens_sets, order, lr=None, hyper=None, epilogue=False, cells=LL):
     B, F, D, V, E, H, A, RA = dims
-    decP = GU.formula_params(GU.decoder_shapes(V, E, H, A, D), 3)
-    recP = GU.formula_params(GU.rec_shapes(kind, H, D, RA), 4)
+    decP = GU.formula_params(GU.decoder_shapes(V, E, H, A, D, cells[0]), 3)
+    recP = GU.formula_params(GU.rec_shapes(kind, H, D, RA, cells[1]), 4)
     cfg = {} if lr is None else dict(decoder_learning_rate=lr, reconstructor_learning_rate=lr)
     cfg.update(hyper or {})
-    _, dec, rec = make_models(list(dims), kind, prec, decP, recP, **cfg)
+    _, dec, rec = make_models(list(dims), kind, prec, decP, recP, cells=cells, **cfg)
     step = R.DataParallelTrainStep(dec, rec, B, 0, 1, n_frames=F)
     if hyper and hyper.get("reconstructor_use_amsgrad"):
         _preload_vmax(rec, 21)
@@ -99,6 +101,20 @@ def test_deferred_update_equals_the_immediate_one_once_flushed(lr, mode, lengths
 
 
 @pytest.mark.parametrize("prec", ["bf16", "f32"])
+@pytest.mark.parametrize("kind", ["global", "local"])
+@pytest.mark.parametrize("shape", list(SHAPES))
+@pytest.mark.parametrize("lengths", ["full", "alternating"])
+@pytest.mark.parametrize("mode", [True, "recurrent"])
+@pytest.mark.parametrize("lr", [None, 1e-2])
+@pytest.mark.parametrize("cells", [GG, LG], ids=["GG", "LG"])
+def test_deferred_update_equals_the_immediate_one_once_flushed_with_gru_cells(cells, lr, mode, lengths, shape, kind, prec):
+    """The cells axis of the test above (which is its LSTM / LSTM value and keeps its ids): a GRU reconstructor behind either decoder
+    cell.  The pending d W_hh is two members of the grouped launch under GRU and its fused Adam epilogue has two windows
+    (csrc/host_reconstructor.inc); same matrix, same assertions."""
+    _deferred_equals_immediate(lr, mode, lengths, shape, kind, prec, cells=cells)
+
+
+@pytest.mark.parametrize("prec", ["bf16", "f32"])
 @pytest.mark.parametrize("mode,kind", [(True, "global"), ("recurrent", "global"), ("recurrent", "local")])
 def test_deferred_update_equals_the_immediate_one_at_other_hyper_parameters(mode, kind, prec):
     """The hyper-parameter axis of the test above, restricted to shape "chains", full lengths and lr 1e-2 (HYPER: AMSGrad on the
@@ -109,7 +125,7 @@ def test_deferred_update_equals_the_immediate_one_at_other_hyper_parameters(mode
     _deferred_equals_immediate(1e-2, mode, "full", "chains", kind, prec, HYPER)
 
 
-def _deferred_equals_immediate(lr, mode, lengths, shape, kind, prec, hyper=None):
+def _deferred_equals_immediate(lr, mode, lengths, shape, kind, prec, hyper=None, cells=LL):
     """lr None: the reference's learning rates (1e-5 / 1e-6) — the updates are too small to feed rounding differences of the
     atomically summed gradients back into the next step, so GEMM-produced tensors can be held BIT for bit.  lr 1e-2 (at
     the defaults four steps move a weight by less than the tolerances, so a missing update would pass): every step moves every
@@ -134,15 +150,15 @@ def _deferred_equals_immediate(lr, mode, lengths, shape, kind, prec, hyper=None)
     # (mode "recurrent": the in-step half is a different grouped launch than the immediate update's — other split factors,
     # equal to fp32 rounding)
     exact = lengths == "full" and mode is True
-    d0, r0, l0 = _run(kind, prec, dims, False, sets, order, lr, hyper)
+    d0, r0, l0 = _run(kind, prec, dims, False, sets, order, lr, hyper, cells=cells)
     d1, r1, l1 = _run(kind, prec, dims, mode, sets, order, lr, hyper,
-                      epilogue=hyper is not None and prec == "bf16" and mode == "recurrent" and shape == "chains")
+                      epilogue=hyper is not None and prec == "bf16" and mode == "recurrent" and shape == "chains", cells=cells)
     if hyper and hyper.get("reconstructor_use_amsgrad"):
         # the stored maximum is the larger operand for some elements of W_hh and the smaller for others, after the last step too
         v, vmax = r1["exp_avg_sq.rnn.weight_hh_l0"], r1["max_exp_avg_sq.rnn.weight_hh_l0"]
         kept, fresh = int((vmax > v).sum()), int((vmax == v).sum())
         assert kept + fresh == v.numel() and kept > v.numel() // 20 and fresh > v.numel() // 20, (kept, fresh, v.numel())
-    recP = GU.formula_params(GU.rec_shapes(kind, dims[5], dims[2], dims[7]), 4)
+    recP = GU.formula_params(GU.rec_shapes(kind, dims[5], dims[2], dims[7], cells[1]), 4)
     if lr is None:
         assert np.allclose(l0[:, :7], l1[:, :7], rtol=1e-6 if mode is True else 3e-6, atol=0), (l0[:, 6], l1[:, 6])
         for k in d0:
@@ -157,7 +173,7 @@ def _deferred_equals_immediate(lr, mode, lengths, shape, kind, prec, hyper=None)
     # large updates: rounding differences of the atomically summed gradients (biases, embedding rows) are fed back through the
     # parameters, so nothing stays bit-identical over four steps; the schedules agree to a small fraction of how far each tensor moved
     assert np.allclose(l0[:, :7], l1[:, :7], rtol=2e-5, atol=0), (l0[:, 6], l1[:, 6])
-    decP = GU.formula_params(GU.decoder_shapes(dims[3], dims[4], dims[5], dims[6], dims[2]), 3)
+    decP = GU.formula_params(GU.decoder_shapes(dims[3], dims[4], dims[5], dims[6], dims[2], cells[0]), 3)
     for st0, st1, P in ((d0, d1, decP), (r0, r1, recP)):
         for k, v in P.items():
             a, b = st0["p." + k].cpu().double(), st1["p." + k].cpu().double()

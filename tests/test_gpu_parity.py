@@ -146,7 +146,9 @@ def test_fused_train_steps_match_reference_optimizer(name, prec):
         assert rel_err(fl["exp_avg_sq"].views[k].cpu().numpy(), g["dec_opt/exp_avg_sq/" + k]) <= max(tol["grad"], 1e-4) * 4
 
 
-LR_CASES = ["lr_global_chain", "lr_local_chain", "lr_gru_global_chain"]
+LR_CASES = ["lr_global_chain", "lr_local_chain", "lr_gru_global_chain",
+            # GRU local chains, the reference's default pair (GRU decoder, LSTM local reconstructor), LSTM decoder + GRU global chains
+            "lr_gru_local_chain", "lr_refcells_local_chain", "lr_lstm_gru_global_chain"]
 @pytest.mark.parametrize("prec", ["f32", "bf16"])
 @pytest.mark.parametrize("mode", ["eager", "graph", "graph_split_update"])
 @pytest.mark.parametrize("name", LR_CASES)
@@ -427,6 +429,7 @@ EDGE = {
     "B57_second_half_one_row": ([57, 3, 32, 29, 8, 24, 16, 16], [(5 * i) % 7 for i in range(57)]),
     "B112_R40_all_rows": ([112, 2, 40, 29, 8, 24, 16, 16], [(3 * i) % 6 for i in range(112)]),
     # shapes the persistent decoder chains take (csrc/dec_chain.hpp: H % 16 == 0, (4H + A) % 16 == 0, H <= 512, A <= 128)
+    # (the two A = 40 shapes do NOT: 4H + A = 232 — they hold the per-step kernels; tests/test_gpu_cells.py has A = 48 twins on the chains)
     "H32_A16_persistent_decoder": ([100, 5, 48, 29, 8, 32, 16, 16], [(7 * i) % 9 for i in range(100)]),
     "H48_A40_F3_partial_ksteps": ([37, 3, 32, 29, 8, 48, 40, 16], [(5 * i) % 8 for i in range(37)]),
     "H512_A128_one_chunk": ([9, 4, 32, 29, 8, 512, 128, 16], [3, 1, 4, 1, 5, 2, 6, 5, 3]),

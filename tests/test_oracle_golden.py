@@ -168,7 +168,9 @@ def test_teacher_forcing_ratio_below_one_in_training(name):
         np.testing.assert_allclose(st.rec[k].detach().numpy(), v.numpy(), atol=1e-6, rtol=0)
 
 
-LR_CASES = ["lr_global_chain", "lr_local_chain", "lr_gru_global_chain"]
+LR_CASES = ["lr_global_chain", "lr_local_chain", "lr_gru_global_chain",
+            # GRU local chains, the reference's default pair (GRU decoder, LSTM local reconstructor), LSTM decoder + GRU global chains
+            "lr_gru_local_chain", "lr_refcells_local_chain", "lr_lstm_gru_global_chain"]
 
 
 @pytest.mark.parametrize("name", LR_CASES)
