@@ -21,7 +21,7 @@ extern "C" {
 #endif
 
 /* 12 still: recnet_beam_select_rows_constrained / recnet_beam_search_nbest_constrained, and after them
- * recnet_beam_select_rows_diverse / recnet_beam_search_nbest_diverse, and recnet_consensus_rows, were added without changing any existing entry.  A library built before them is still caught: a binding that resolves every declared symbol fails on the first one missing. */
+ * recnet_beam_select_rows_diverse / recnet_beam_search_nbest_diverse, and recnet_consensus_rows, and the three ensemble entries (recnet_ensemble_mix_rows, recnet_beam_search_nbest_ensemble, recnet_score_captions_ensemble), were added without changing any existing entry.  A library built before them is still caught: a binding that resolves every declared symbol fails on the first one missing. */
 #define RECNET_ABI_VERSION 12
 #define RECNET_ATTN_NONE 0
 #define RECNET_ATTN_SOFTMAX 1
@@ -325,6 +325,47 @@ int recnet_beam_search_nbest_diverse(recnet_handle* h, const float* enc, int32_t
                                      float diversity_penalty, int32_t no_repeat_ngram, int32_t min_length, const int32_t* banned,
                                      int32_t n_banned, int64_t* tokens_out, float* cum_out, int32_t* len_out, float* score_out,
                                      int32_t* group_out, int32_t* n_steps_out, void* stream);
+
+/* ---- Ensemble decoding: beam search and scoring over M decoders (no counterpart in the reference; added at
+ * version 12 without changing any existing entry).  An ensemble is M handles (1 <= M <= 8, all different) with a bound workspace
+ * and a bound decoder, on one device, that agree on B, F, D, V and caption_max_len; E, H, A, the cell, the attention normalisation
+ * and the precision may differ.  weights: a HOST array of M positive finite floats (NULL: uniform), normalised by the library in
+ * float64 to w_m, sum 1.  For one row, with x_m [V] the logits of member m and l_m = log_softmax(x_m) (the formulas of
+ * recnet_logprob_rows at temperature 1):
+ *   RECNET_ENS_ARITHMETIC  y[v] = a + log sum_m exp(log w_m + l_m[v] - a),  a = max_m (log w_m + l_m[v])    (log of the mean probability)
+ *   RECNET_ENS_GEOMETRIC   y[v] = sum_m w_m l_m[v]                                                          (mean log-probability)
+ * summed over m ASCENDING by the one thread that owns v: no atomics, two calls give the same bits, equal rows get equal bits.  y
+ * are the ensemble's LOGITS: the selection and the scorer form cum + (y[v] - logsumexp(y)) from them as from one model's (the usual
+ * renormalisation in the geometric mode; logsumexp(y) = 0 up to rounding in the arithmetic one), so constraints, groups, the ranking
+ * and "recnet_score_captions reproduces cum" hold for the ensemble entries as they do for the single-model ones. */
+#define RECNET_ENS_ARITHMETIC 0
+#define RECNET_ENS_GEOMETRIC 1
+/* recnet_ensemble_mix_rows: the mix alone on caller-supplied rows.  logits: a HOST array of M device pointers, each [rows][V] float,
+ * read only; y_out [rows][V] may be logits[0] itself (in place) and must overlap no other input.  It runs for M = 1 too
+ * (y = log_softmax(x_0)).  The handle supplies the device only.  RECNET_EINVAL before any launch: a NULL pointer, M outside [1, 8],
+ * a weight that is not positive and finite, an unknown mode, rows or V below 1, an overlap other than the one allowed. */
+int recnet_ensemble_mix_rows(recnet_handle* h, const float* const* logits, int32_t M, const float* weights, int32_t mode, int32_t rows,
+                             int32_t V, float* y_out, void* stream);
+/* recnet_beam_search_nbest_ensemble: recnet_beam_search_nbest_diverse on the ensemble's logits; the arguments from beam_width on are
+ * that entry's.  hs: a HOST array of M handles.  Every step runs the decode step of every member on the tokens member 0 holds,
+ * mixes the nb * B rows, selects as before, and applies the regather (src = idx / V) to every member's own recurrent state;
+ * history, cum, lengths and tokens exist once.  M = 1 launches what recnet_beam_search_nbest_diverse launches and returns its bits.
+ * RECNET_EINVAL / RECNET_ESTATE before any launch: hs NULL, M outside [1, 8], a NULL or repeated member, a member without workspace
+ * or bound decoder, members on different devices or with unequal B, F, D, V or caption_max_len, a bad weight or mode, and
+ * everything recnet_beam_search_nbest_diverse refuses. */
+int recnet_beam_search_nbest_ensemble(recnet_handle* const* hs, int32_t M, const float* weights, int32_t mode, const float* enc,
+                                      int32_t beam_width, float length_alpha, int32_t n_groups, float diversity_penalty,
+                                      int32_t no_repeat_ngram, int32_t min_length, const int32_t* banned, int32_t n_banned,
+                                      int64_t* tokens_out, float* cum_out, int32_t* len_out, float* score_out, int32_t* group_out,
+                                      int32_t* n_steps_out, void* stream);
+/* recnet_score_captions_ensemble: recnet_score_captions at temperature 1 on the ensemble's logits: the teacher-forced forward and
+ * the vocabulary product of every member, one mix over the T * B rows, then the row kernel and the per-caption sums.  It reproduces
+ * the cum of recnet_beam_search_nbest_ensemble as recnet_score_captions does for one model.  enc NULL: every member reuses its own
+ * invariants.  M = 1 launches what recnet_score_captions launches.  Refusals: those of the ensemble search on hs / M / weights /
+ * mode, and those of recnet_score_captions. */
+int recnet_score_captions_ensemble(recnet_handle* const* hs, int32_t M, const float* weights, int32_t mode, const float* enc,
+                                   const int64_t* tokens, int32_t T, float* logprobs_out, float* caption_logprob_out, int32_t* length_out,
+                                   void* stream);
 
 /* ---- Consensus (minimum-Bayes-risk) scoring of hypotheses against a reference set by n-gram overlap (no counterpart in the
  * reference; added at version 12 without changing any existing entry).

@@ -165,6 +165,14 @@ EXPORTS["recnet_beam_search_nbest_constrained"] = (_i, [C.c_void_p, C.c_void_p, 
 EXPORTS["recnet_beam_select_rows_diverse"] = (_i, [C.c_void_p] * 5 + [_i] * 7 + [_f, _i, _i, C.POINTER(_i), _i, C.c_void_p, C.c_void_p, C.c_void_p])
 EXPORTS["recnet_beam_search_nbest_diverse"] = (_i, [C.c_void_p, C.c_void_p, _i, _f, _i, _f, _i, _i, C.POINTER(_i), _i] + [C.c_void_p] * 7)
 EXPORTS["recnet_consensus_rows"] = (_i, [C.c_void_p, C.c_void_p, _i, _i, C.c_void_p, _i, _i, _i, C.c_void_p, _d] + [C.c_void_p] * 8)
+# ensemble decoding: the member handles / row pointers travel as host arrays
+ENS_ARITHMETIC, ENS_GEOMETRIC = 0, 1
+ENS_MODES = {"arithmetic": ENS_ARITHMETIC, "geometric": ENS_GEOMETRIC}
+ENS_MAX_M = 8
+EXPORTS["recnet_ensemble_mix_rows"] = (_i, [C.c_void_p, C.POINTER(C.c_void_p), _i, C.POINTER(_f), _i, _i, _i, C.c_void_p, C.c_void_p])
+EXPORTS["recnet_beam_search_nbest_ensemble"] = (_i, [C.POINTER(C.c_void_p), _i, C.POINTER(_f), _i, C.c_void_p, _i, _f, _i, _f, _i, _i,
+                                                      C.POINTER(_i), _i] + [C.c_void_p] * 7)
+EXPORTS["recnet_score_captions_ensemble"] = (_i, [C.POINTER(C.c_void_p), _i, C.POINTER(_f), _i, C.c_void_p, C.c_void_p, _i] + [C.c_void_p] * 4)
 EXPORTS["recnet_logprob_rows"] =(_i, [C.c_void_p, C.c_void_p, C.c_void_p, _i, _i, _f, C.c_void_p, C.c_void_p])
 EXPORTS["recnet_score_captions"] = (_i, [C.c_void_p, C.c_void_p, C.c_void_p, _i, _f, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
 EXPORTS["recnet_reconstruction_error"] = (_i, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _i, C.c_void_p, C.c_void_p, C.c_void_p])

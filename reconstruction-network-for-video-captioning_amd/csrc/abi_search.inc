@@ -266,9 +266,18 @@ int recnet_logprob_rows(recnet_handle* h, const float* logits, const int64_t* to
   return RECNET_OK;
 }
 
-// The teacher-forced forward in eval mode (the persistent chain where the handle runs it, the per-step kernels otherwise), the
-// batched vocabulary product into h->logits, the row kernel, the per-caption sums.  Hs / acts / logits no longer hold a training
-// forward afterwards: a backward call is refused until the next forward.
+// The teacher-forced forward in eval mode (the persistent chain where the handle runs it, the per-step kernels otherwise) and the
+// batched vocabulary product into h->logits [T * B][V].  Hs / acts / logits no longer hold a training forward afterwards: a backward
+// call is refused until the next forward.
+static int score_logits(recnet_handle* h, const float* enc, const int64_t* tokens, int T, hipStream_t st) {
+  // step 0 is fed <SOS>, step t > 0 tokens[t - 1] (embed_fwd_kernel's teacher-forcing rule); enc == NULL: the invariants of the
+  // previous call / of recnet_decoder_prepare
+  int r = dec_fwd_chain(h, enc, tokens, T, 0, st, nullptr, nullptr, DFC_NO_REG_NORM | (enc ? 0 : DFC_REUSE_INVARIANTS)); if (r) return r;
+  h->fwd_dec_done = h->fwd_rec_done = 0; h->ss.mp_done = 0; h->ss.xcat_done = 0;
+  gemm(h, h->Hs_lp, 0, h->ldH, h->Wo_w, 0, h->ldH, h->logits, h->V, h->dP.out_bias, T * h->B, h->V, h->H, 1.f, 0, st);
+  return RECNET_OK;
+}
+// score_logits, the row kernel, the per-caption sums.
 int recnet_score_captions(recnet_handle* h, const float* enc, const int64_t* tokens, int32_t T, float temperature,
                           float* logprobs_out, float* caption_logprob_out, int32_t* length_out, void* stream) {
   REQUIRE_WS(h);
@@ -278,14 +287,9 @@ int recnet_score_captions(recnet_handle* h, const float* enc, const int64_t* tok
   if (!tokens || !logprobs_out || !caption_logprob_out || !length_out) return fail(RECNET_EINVAL, "null argument");
   int r = check_sample(temperature, 0, h->V); if (r) return r;
   hipStream_t st = (hipStream_t)stream;
-  const int B = h->B, H = h->H, V = h->V;
-  // step 0 is fed <SOS>, step t > 0 tokens[t - 1] (embed_fwd_kernel's teacher-forcing rule); enc == NULL: the invariants of the
-  // previous call / of recnet_decoder_prepare
-  r = dec_fwd_chain(h, enc, tokens, T, 0, st, nullptr, nullptr, DFC_NO_REG_NORM | (enc ? 0 : DFC_REUSE_INVARIANTS)); if (r) return r;
-  h->fwd_dec_done = h->fwd_rec_done = 0; h->ss.mp_done = 0; h->ss.xcat_done = 0;
-  gemm(h, h->Hs_lp, 0, h->ldH, h->Wo_w, 0, h->ldH, h->logits, V, h->dP.out_bias, T * B, V, H, 1.f, 0, st);
-  launch_logprob_rows(h->logits, tokens, T * B, V, temperature, logprobs_out, st);
-  hipLaunchKernelGGL(caption_logprob_kernel, dim3(cdiv(B, 256)), dim3(256), 0, st, logprobs_out, tokens, T, B, caption_logprob_out, length_out);
+  r = score_logits(h, enc, tokens, T, st); if (r) return r;
+  launch_logprob_rows(h->logits, tokens, T * h->B, h->V, temperature, logprobs_out, st);
+  hipLaunchKernelGGL(caption_logprob_kernel, dim3(cdiv(h->B, 256)), dim3(256), 0, st, logprobs_out, tokens, T, h->B, caption_logprob_out, length_out);
   LAUNCH_OK();
   return RECNET_OK;
 }
@@ -518,19 +522,117 @@ int recnet_beam_select_rows_diverse(recnet_handle* h, const float* logits, const
                               no_repeat_ngram, min_length, banned, n_banned, vals_out, idx_out, stream);
 }
 
-// The loop of the N-best searches on checked arguments.  group_out (may be null): the group of each returned rank.
-static void beam_search_nbest_run(recnet_handle* h, const float* enc, int bw, float length_alpha, const BeamBans& bans, int n_groups,
-                                  float diversity_penalty, int64_t* tokens_out, float* cum_out, int32_t* len_out, float* score_out,
-                                  int32_t* group_out, int32_t* n_steps_out, hipStream_t st) {
-  const int B = h->B, V = h->V, Tm = h->Tm;
-  search_begin(h, enc, n_steps_out, 0, st);
-  const DecStepRows rows = dec_rows_beams(h);
+// ---- ensemble decoding (the reference has no counterpart; DESIGN.md section 19): M decoders, their rows mixed into one row of logits
+// the checked weights of an ensemble: normalised to sum 1 in float64, and their logs
+struct EnsMix { int M = 1, geo = 0; float w[ENS_MAX_M] = {}, lw[ENS_MAX_M] = {}; };
+static int check_ens_mix(int M, const float* weights, int mode, EnsMix* e) {
+  if (M < 1 || M > ENS_MAX_M) return fail(RECNET_EINVAL, "an ensemble has between 1 and 8 members");
+  if (mode != RECNET_ENS_ARITHMETIC && mode != RECNET_ENS_GEOMETRIC) return fail(RECNET_EINVAL, "unknown ensemble mode");
+  double sum = 0.0;
+  for (int m = 0; m < M; ++m) {
+    const float w = weights ? weights[m] : 1.f;
+    if (!(w > 0.f) || !std::isfinite(w)) return fail(RECNET_EINVAL, "ensemble weights must be positive and finite");
+    sum += (double)w;
+  }
+  e->M = M; e->geo = mode == RECNET_ENS_GEOMETRIC;
+  for (int m = 0; m < M; ++m) {
+    const double w = (double)(weights ? weights[m] : 1.f) / sum;
+    e->w[m] = (float)w; e->lw[m] = (float)std::log(w);
+  }
+  return RECNET_OK;
+}
+// the members: distinct handles with a workspace and a bound decoder, on one device, that agree on B, F, D, V and Tm
+static int check_ens_members(recnet_handle* const* hs, int M) {
+  if (!hs) return fail(RECNET_EINVAL, "null argument");
+  if (M < 1 || M > ENS_MAX_M) return fail(RECNET_EINVAL, "an ensemble has between 1 and 8 members");
+  int dev0 = -1;
+  for (int m = 0; m < M; ++m) {
+    recnet_handle* h = hs[m];
+    if (!h) return fail(RECNET_EINVAL, "null ensemble member");
+    REQUIRE_WS(h);
+    if (!h->dec_bound) return fail(RECNET_ESTATE, "decoder not bound");
+    for (int j = 0; j < m; ++j)
+      if (hs[j] == h) return fail(RECNET_EINVAL, "ensemble members must be distinct handles (each keeps its own state)");
+    if (h->B != hs[0]->B || h->F != hs[0]->F || h->D != hs[0]->D || h->V != hs[0]->V || h->Tm != hs[0]->Tm)
+      return fail(RECNET_EINVAL, "ensemble members must agree on B, F, D, V and caption_max_len");
+    if (M > 1) {
+      hipPointerAttribute_t at;
+      if (hipPointerGetAttributes(&at, h->ws) != hipSuccess) { (void)hipGetLastError(); return fail(RECNET_EINVAL, "ensemble member: workspace is not device memory"); }
+      if (m == 0) dev0 = at.device;
+      else if (at.device != dev0) return fail(RECNET_EINVAL, "ensemble members must live on one device");
+    }
+  }
+  return RECNET_OK;
+}
+// y [rows][V] from the members' rows x[m] [rows][V]; y may be x[0]
+static void launch_ensemble_mix(const EnsMix& e, const float* const* x, int rows, int V, float* y, hipStream_t st) {
+  EnsMixArgs a;
+  a.M = e.M; a.V = V; a.geo = e.geo; a.y = y;
+  bool vec = (V & 3) == 0 && (((uintptr_t)y) & 15) == 0;
+  for (int m = 0; m < ENS_MAX_M; ++m) {
+    a.x[m] = m < e.M ? x[m] : nullptr; a.w[m] = m < e.M ? e.w[m] : 0.f; a.lw[m] = m < e.M ? e.lw[m] : 0.f;
+    vec = vec && (((uintptr_t)a.x[m]) & 15) == 0;
+  }
+  const size_t floats = (size_t)e.M * ens_row_stride(V);
+  const bool res = floats <= ENS_LDS_FLOATS;
+  const size_t sm = res ? floats * 4 : 0;
+#define RN_ENS(RES, VEC) do {                                                                                             \
+    static bool attr_done = false;                                                                                        \
+    if (RES && !attr_done) {                                                                                              \
+      hipFuncSetAttribute(reinterpret_cast<const void*>(ensemble_mix_rows_kernel<RES, VEC>), hipFuncAttributeMaxDynamicSharedMemorySize, ENS_LDS_FLOATS * 4); \
+      attr_done = true;                                                                                                   \
+    }                                                                                                                     \
+    hipLaunchKernelGGL((ensemble_mix_rows_kernel<RES, VEC>), dim3(rows), dim3(256), sm, st, a);                           \
+  } while (0)
+  if (res) { if (vec) RN_ENS(true, 4); else RN_ENS(true, 1); }
+  else { if (vec) RN_ENS(false, 4); else RN_ENS(false, 1); }
+#undef RN_ENS
+}
+
+int recnet_ensemble_mix_rows(recnet_handle* h, const float* const* logits, int32_t M, const float* weights, int32_t mode, int32_t rows,
+                             int32_t V, float* y_out, void* stream) {
+  REQUIRE_WS(h);
+  if (!logits || !y_out) return fail(RECNET_EINVAL, "null argument");
+  EnsMix e;
+  int r = check_ens_mix(M, weights, mode, &e); if (r) return r;
+  if (rows < 1 || V < 1) return fail(RECNET_EINVAL, "rows and V must be positive");
+  const size_t n = (size_t)rows * V;
+  for (int m = 0; m < M; ++m) {
+    if (!logits[m]) return fail(RECNET_EINVAL, "null argument");
+    const bool apart = logits[m] + n <= y_out || y_out + n <= logits[m];
+    if (!apart && !(m == 0 && logits[0] == y_out)) return fail(RECNET_EINVAL, "y_out may be the rows of member 0 or overlap none");
+  }
+  launch_ensemble_mix(e, logits, rows, V, y_out, (hipStream_t)stream);
+  LAUNCH_OK();
+  return RECNET_OK;
+}
+
+// The loop of the N-best searches on checked arguments.  group_out (may be null): the group of each returned rank.  hs[0 .. mix.M):
+// the members (one: the single-model search, which launches what it always did).  Every member runs the step on the tokens of
+// member 0 and keeps its own state; their rows are mixed into member 0's, the selection and member 0's regather are unchanged, the
+// other members regather their states by member 0's decisions.
+static void beam_search_nbest_run(recnet_handle* const* hs, const EnsMix& mix, const float* enc, int bw, float length_alpha,
+                                  const BeamBans& bans, int n_groups, float diversity_penalty, int64_t* tokens_out, float* cum_out,
+                                  int32_t* len_out, float* score_out, int32_t* group_out, int32_t* n_steps_out, hipStream_t st) {
+  recnet_handle* h = hs[0];
+  const int B = h->B, V = h->V, Tm = h->Tm, M = mix.M;
+  const float* x[ENS_MAX_M];
+  for (int m = 0; m < M; ++m) { search_begin(hs[m], enc, n_steps_out, m == 0 ? 0 : -1, st); x[m] = hs[m]->sr_scores; }
   int cur = 0, nb = 1;
   for (int t = 0; t < Tm; ++t) {   // all nb * B hypotheses in one decode step, the captions' Uv / P shared by their beams
-    dec_step(h, nb * B, B, rows, h->sr_tok[cur], h->sr_h[cur], h->sr_c[cur], h->sr_scores, h->sr_hn, h->sr_cn, 0, t, st);
+    for (int m = 0; m < M; ++m) {
+      recnet_handle* g = hs[m];
+      dec_step(g, nb * B, B, dec_rows_beams(g), h->sr_tok[cur], g->sr_h[cur], g->sr_c[cur], g->sr_scores, g->sr_hn, g->sr_cn, 0, t, st);
+    }
+    if (M > 1) launch_ensemble_mix(mix, x, nb * B, V, h->sr_scores, st);
     launch_beam_select(h->sr_scores, h->sr_cum[cur], h->sr_eos[cur], nb, B, V, bw, h->sr_vals, h->sr_idx, st, &bans, h->sr_hist[cur], Tm, t,
                        n_groups, diversity_penalty);
     hipLaunchKernelGGL(beam_update_kernel<true>, dim3(bw, B), dim3(128), 0, st, beam_update_args(h, bw, t, cur, nullptr));
+    for (int m = 1; m < M; ++m) {
+      recnet_handle* g = hs[m];
+      hipLaunchKernelGGL(beam_regather_state_kernel, dim3(bw, B), dim3(128), 0, st, (const int32_t*)h->sr_idx, B, g->H, V, bw,
+                         (const float*)g->sr_hn, (const float*)(g->dgru ? nullptr : g->sr_cn), g->sr_h[cur ^ 1], g->sr_c[cur ^ 1]);
+    }
     hipLaunchKernelGGL(search_stop_kernel, dim3(1), dim3(256), 0, st, (const int64_t*)nullptr, h->sr_eos[cur ^ 1], bw * B, t, n_steps_out);
     cur ^= 1; nb = bw;
   }
@@ -543,16 +645,42 @@ static void beam_search_nbest_run(recnet_handle* h, const float* enc, int bw, fl
     hipLaunchKernelGGL(beam_group_kernel, dim3(cdiv(bw * B, 256)), dim3(256), 0, st, (const int32_t*)h->bs_order, bw / n_groups, bw * B, group_out);
 }
 
+// the checks every N-best search makes on its arguments behind those on its handle(s)
+static int check_nbest_args(const recnet_handle* h, const float* enc, int beam_width, float length_alpha, int n_groups, float diversity_penalty,
+                            int no_repeat_ngram, int min_length, const int32_t* banned, int n_banned, const void* tokens_out,
+                            const void* cum_out, const void* len_out, const void* score_out, const void* n_steps_out, BeamBans* bans) {
+  if (!(enc && tokens_out && cum_out && len_out && score_out && n_steps_out)) return fail(RECNET_EINVAL, "null argument");
+  int r = check_beam(beam_width, h->V, length_alpha); if (r) return r;
+  r = check_beam_groups(beam_width, n_groups, diversity_penalty); if (r) return r;
+  return check_beam_bans(no_repeat_ngram, min_length, banned, n_banned, beam_width, h->V, h->Tm, h->Tm - 1, bans);
+}
+
+int recnet_beam_search_nbest_ensemble(recnet_handle* const* hs, int32_t M, const float* weights, int32_t mode, const float* enc,
+                                      int32_t beam_width, float length_alpha, int32_t n_groups, float diversity_penalty,
+                                      int32_t no_repeat_ngram, int32_t min_length, const int32_t* banned, int32_t n_banned,
+                                      int64_t* tokens_out, float* cum_out, int32_t* len_out, float* score_out, int32_t* group_out,
+                                      int32_t* n_steps_out, void* stream) {
+  int r = check_ens_members(hs, M); if (r) return r;
+  EnsMix mix;
+  r = check_ens_mix(M, weights, mode, &mix); if (r) return r;
+  BeamBans bans;
+  r = check_nbest_args(hs[0], enc, beam_width, length_alpha, n_groups, diversity_penalty, no_repeat_ngram, min_length, banned, n_banned,
+                       tokens_out, cum_out, len_out, score_out, n_steps_out, &bans); if (r) return r;
+  beam_search_nbest_run(hs, mix, enc, beam_width, length_alpha, bans, n_groups, diversity_penalty, tokens_out, cum_out, len_out, score_out,
+                        group_out, n_steps_out, (hipStream_t)stream);
+  LAUNCH_OK();
+  return RECNET_OK;
+}
+
 int recnet_beam_search_nbest_diverse(recnet_handle* h, const float* enc, int32_t beam_width, float length_alpha, int32_t n_groups,
                                      float diversity_penalty, int32_t no_repeat_ngram, int32_t min_length, const int32_t* banned,
                                      int32_t n_banned, int64_t* tokens_out, float* cum_out, int32_t* len_out, float* score_out,
                                      int32_t* group_out, int32_t* n_steps_out, void* stream) {
   int r = search_check(h, enc && tokens_out && cum_out && len_out && score_out && n_steps_out); if (r) return r;
-  r = check_beam(beam_width, h->V, length_alpha); if (r) return r;
-  r = check_beam_groups(beam_width, n_groups, diversity_penalty); if (r) return r;
   BeamBans bans;
-  r = check_beam_bans(no_repeat_ngram, min_length, banned, n_banned, beam_width, h->V, h->Tm, h->Tm - 1, &bans); if (r) return r;
-  beam_search_nbest_run(h, enc, beam_width, length_alpha, bans, n_groups, diversity_penalty, tokens_out, cum_out, len_out, score_out,
+  r = check_nbest_args(h, enc, beam_width, length_alpha, n_groups, diversity_penalty, no_repeat_ngram, min_length, banned, n_banned,
+                       tokens_out, cum_out, len_out, score_out, n_steps_out, &bans); if (r) return r;
+  beam_search_nbest_run(&h, EnsMix(), enc, beam_width, length_alpha, bans, n_groups, diversity_penalty, tokens_out, cum_out, len_out, score_out,
                         group_out, n_steps_out, (hipStream_t)stream);
   LAUNCH_OK();
   return RECNET_OK;
@@ -571,6 +699,31 @@ int recnet_beam_search_nbest(recnet_handle* h, const float* enc, int32_t beam_wi
                              float* cum_out, int32_t* len_out, float* score_out, int32_t* n_steps_out, void* stream) {
   return recnet_beam_search_nbest_constrained(h, enc, beam_width, length_alpha, 0, 0, nullptr, 0, tokens_out, cum_out, len_out, score_out,
                                               n_steps_out, stream);
+}
+
+// recnet_score_captions over the members: score_logits of each, one mix over the T * B rows into member 0's, then the row kernel at
+// temperature 1 and the per-caption sums, unchanged.  One member: the kernels of recnet_score_captions at temperature 1.
+int recnet_score_captions_ensemble(recnet_handle* const* hs, int32_t M, const float* weights, int32_t mode, const float* enc,
+                                   const int64_t* tokens, int32_t T, float* logprobs_out, float* caption_logprob_out, int32_t* length_out,
+                                   void* stream) {
+  int r = check_ens_members(hs, M); if (r) return r;
+  EnsMix mix;
+  r = check_ens_mix(M, weights, mode, &mix); if (r) return r;
+  if (check_T(hs[0], T)) return fail(RECNET_EINVAL, "T out of range");
+  if (!tokens || !logprobs_out || !caption_logprob_out || !length_out) return fail(RECNET_EINVAL, "null argument");
+  for (int m = 0; m < M; ++m) FLUSH_PENDING(hs[m], stream);
+  hipStream_t st = (hipStream_t)stream;
+  recnet_handle* h = hs[0];
+  const float* x[ENS_MAX_M];
+  for (int m = 0; m < M; ++m) {
+    r = score_logits(hs[m], enc, tokens, T, st); if (r) return r;
+    x[m] = hs[m]->logits;
+  }
+  if (M > 1) launch_ensemble_mix(mix, x, T * h->B, h->V, h->logits, st);
+  launch_logprob_rows(h->logits, tokens, T * h->B, h->V, 1.f, logprobs_out, st);
+  hipLaunchKernelGGL(caption_logprob_kernel, dim3(cdiv(h->B, 256)), dim3(256), 0, st, logprobs_out, tokens, T, h->B, caption_logprob_out, length_out);
+  LAUNCH_OK();
+  return RECNET_OK;
 }
 
 // ---- consensus (minimum-Bayes-risk) scoring by n-gram overlap (the reference has no counterpart; DESIGN.md section 16)

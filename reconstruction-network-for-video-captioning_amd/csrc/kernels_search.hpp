@@ -669,6 +669,103 @@ __global__ __launch_bounds__(256) void beam_nbest_rank_kernel(const float* __res
   }
 }
 
+// ---- ensemble decoding: the rows of M decoders mixed into one row of logits (the reference has no counterpart; DESIGN.md section 19
+// states the definition, tests/ensemble_ref.py restates it).  With l_m = log_softmax(x_m) by logprob_rows_kernel's formulas at
+// temperature 1 and weights w_m > 0 that sum to 1 (lw_m = log w_m, both formed by the host in float64):
+//   arithmetic  y[v] = a + log sum_m exp(lw_m + l_m[v] - a),  a = max_m (lw_m + l_m[v])     log of the weighted mean of the probabilities
+//   geometric   y[v] = sum_m w_m l_m[v]                                                     weighted mean of the log-probabilities
+// Both sums over m run upward from m = 0 in the one thread that owns v: no atomics, two calls give the same bits, equal rows too.
+#define ENS_MAX_M 8
+#define ENS_LDS_FLOATS 24576           // floats of the M rows that are kept in LDS (96 KB of the CU's 160); above: the streaming form
+struct EnsMixArgs {
+  const float* x[ENS_MAX_M];           // logits [rows][V] of each member, read only (slots >= M unused); y may be x[0], nothing else
+  float w[ENS_MAX_M], lw[ENS_MAX_M];
+  int M, V, geo;                       // geo != 0: the geometric mode
+  float* y;                            // [rows][V]
+};
+// rows of LDS start 16 bytes apart at least
+__host__ __device__ __forceinline__ int ens_row_stride(int V) { return (V + 3) & ~3; }
+template <int VEC> __device__ __forceinline__ void ens_load(const float* p, float (&v)[VEC]) {
+  if constexpr (VEC == 4) { const float4 q = *reinterpret_cast<const float4*>(p); v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w; }
+  else v[0] = *p;
+}
+// One workgroup per row.  RES: (0) the M rows go to LDS, every logit read from global memory once; else every phase reads global
+// memory (the second and third pass mostly from the caches).  (1) per member the maximum and log sum exp(x - max), in the strided
+// order and by the formulas of logprob_rows_kernel whichever way the row was loaded, so RES and VEC change no bit.  (2) every thread
+// forms the y of its own v (VEC = 4: of four neighbours, V % 4 == 0 and 16-byte aligned rows).  In place over member 0: with RES all
+// reads of global memory end at the barrier behind (0); without, (1) ends at a barrier and in (2) the thread that writes y[v] is the
+// only one that still reads x_m[v], before it writes.
+template <bool RES, int VEC> __global__ __launch_bounds__(256) void ensemble_mix_rows_kernel(const EnsMixArgs p) {
+  extern __shared__ __attribute__((aligned(16))) float ens_rows[];
+  __shared__ float sf[4]; __shared__ float s_mx[ENS_MAX_M], s_ls[ENS_MAX_M];
+  const int tid = threadIdx.x, V = p.V, M = p.M, S = ens_row_stride(V);
+  const size_t ro = (size_t)blockIdx.x * V;
+  if (RES) {                                                           // (0)
+    for (int m = 0; m < M; ++m) {
+      const float* x = p.x[m] + ro;
+      float* r = ens_rows + m * S;
+      for (int q = tid; q < V / VEC; q += 256) {
+        float t[VEC];
+        ens_load<VEC>(x + q * VEC, t);
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) r[q * VEC + j] = t[j];
+      }
+    }
+    __syncthreads();
+  }
+  for (int m = 0; m < M; ++m) {                                        // (1)
+    const float* x = RES ? ens_rows + m * S : p.x[m] + ro;
+    float mx = -INFINITY, sum = 0.f;
+    for (int v = tid; v < V; v += 256) mx = fmaxf(mx, x[v]);
+    mx = block_max256(mx, sf);
+    for (int v = tid; v < V; v += 256) sum += rn_exp(x[v] - mx);
+    sum = block_sum256(sum, sf);
+    if (tid == 0) { s_mx[m] = mx; s_ls[m] = logf(sum); }
+  }
+  __syncthreads();
+  for (int q = tid; q < V / VEC; q += 256) {                           // (2)
+    float a[VEC], s[VEC], xv[VEC];
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) { a[j] = -INFINITY; s[j] = 0.f; }
+    if (p.geo) {
+      for (int m = 0; m < M; ++m) {
+        ens_load<VEC>((RES ? ens_rows + m * S : p.x[m] + ro) + q * VEC, xv);
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) s[j] += p.w[m] * ((xv[j] - s_mx[m]) - s_ls[m]);
+      }
+    } else {
+      for (int m = 0; m < M; ++m) {
+        ens_load<VEC>((RES ? ens_rows + m * S : p.x[m] + ro) + q * VEC, xv);
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) a[j] = fmaxf(a[j], p.lw[m] + ((xv[j] - s_mx[m]) - s_ls[m]));
+      }
+      for (int m = 0; m < M; ++m) {
+        ens_load<VEC>((RES ? ens_rows + m * S : p.x[m] + ro) + q * VEC, xv);
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) s[j] += rn_exp((p.lw[m] + ((xv[j] - s_mx[m]) - s_ls[m])) - a[j]);
+      }
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) s[j] = a[j] == -INFINITY ? -INFINITY : a[j] + logf(s[j]);    // (-inf in every member stays -inf)
+    }
+    float* y = p.y + ro + q * VEC;
+    if constexpr (VEC == 4) *reinterpret_cast<float4*>(y) = make_float4(s[0], s[1], s[2], s[3]);
+    else y[0] = s[0];
+  }
+}
+// The regather of a further member's recurrent state by the decisions member 0's selection left in idx [B][bw] (src = idx / V):
+// beam_update_kernel's state copy alone; history, cum, lengths and tokens exist once, on member 0.  c_next null: a GRU has no c.
+__global__ __launch_bounds__(128) void beam_regather_state_kernel(const int32_t* __restrict__ idx, int B, int H, int V, int bw,
+                                                                  const float* __restrict__ h_next, const float* __restrict__ c_next,
+                                                                  float* __restrict__ h_new, float* __restrict__ c_new) {
+  const int k = blockIdx.x, b = blockIdx.y;
+  const int src = idx[b * bw + k] / V;
+  const size_t so = ((size_t)src * B + b) * H, dn = ((size_t)k * B + b) * H;
+  for (int j = threadIdx.x; j < H; j += 128) {
+    h_new[dn + j] = h_next[so + j];
+    if (c_next) c_new[dn + j] = c_next[so + j];
+  }
+}
+
 // ---- consensus (minimum-Bayes-risk) reranking: n-gram overlap of hypotheses with a reference set
 // The words of a caption column are its tokens before the first <EOS> (2), at most T.  With c_n(g) the occurrences of n-gram g,
 //   Q_n(c) = sum_g c_n(g)^2 = sum over the positions p of c of c_n(g(p)),

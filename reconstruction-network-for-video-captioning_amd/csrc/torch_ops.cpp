@@ -19,6 +19,7 @@
 //   score_captions                                      teacher-forced log-probabilities of given captions (train.py:25,45, eval mode)
 //   reconstruction_error                                per-caption reconstruction error and the reconstruction (train.py:96-102 / :125-128, eval mode)
 //   consensus_rows                                      n-gram consensus (minimum-Bayes-risk) utilities of hypotheses against a reference set (no counterpart; section 16)
+//   ensemble_mix_rows, beam_search_nbest_ensemble, score_captions_ensemble   N-best beam search and scoring over several decoders (no counterpart; section 19)
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
 #include <torch/library.h>
@@ -429,6 +430,77 @@ std::tuple<at::Tensor, at::Tensor> reconstruction_error(int64_t h, const at::Ten
                                  want_recon ? recon.data_ptr<float>() : nullptr, stream()), "reconstruction_error");
   return {err, recon};
 }
+// ---- ensemble decoding.  handle: the engine handle of member 0, like every op's leading argument;
+// more_handles: those of members 1 .. M - 1 (M <= 8; empty: an ensemble of one); weights: one positive finite number per member,
+// member 0 first (the library normalises them); mode: RECNET_ENS_ARITHMETIC / RECNET_ENS_GEOMETRIC.  Shapes come from member 0;
+// that the members agree is the library's check.
+static std::vector<recnet_handle*> ens_handles(int64_t handle, at::IntArrayRef more_handles) {
+  TORCH_CHECK(more_handles.size() <= 7, "recnet: an ensemble has between 1 and 8 members, got ", more_handles.size() + 1);
+  std::vector<recnet_handle*> hs{H(handle)};
+  for (const int64_t h : more_handles) hs.push_back(H(h));
+  return hs;
+}
+static std::vector<float> ens_weights(at::ArrayRef<double> weights, size_t M) {
+  TORCH_CHECK(weights.size() == M, "recnet: ", weights.size(), " weights for ", M, " ensemble members");
+  return std::vector<float>(weights.begin(), weights.end());
+}
+// logits: M tensors [rows, V] float -> y [rows, V]; in_place: y is logits[0] itself (it is returned)
+at::Tensor ensemble_mix_rows(int64_t h, at::TensorList logits, at::ArrayRef<double> weights, int64_t mode, bool in_place) {
+  TORCH_CHECK(logits.size() >= 1 && logits.size() <= 8, "recnet: an ensemble has between 1 and 8 members, got ", logits.size());
+  const auto w = ens_weights(weights, logits.size());
+  std::vector<const float*> xs;
+  for (const at::Tensor& x : logits) {
+    chk(x, at::kFloat, "logits");
+    TORCH_CHECK(x.dim() == 2 && x.sizes() == logits[0].sizes() && x.size(0) >= 1 && x.size(1) >= 1 && x.size(0) <= INT32_MAX && x.size(1) <= INT32_MAX,
+                "recnet: logits must be M tensors [rows, V] of one shape, got ", x.sizes());
+    xs.push_back(x.data_ptr<float>());
+  }
+  at::Tensor y = in_place ? logits[0] : at::empty_like(logits[0]);
+  ok(recnet_ensemble_mix_rows(H(h), xs.data(), (int32_t)xs.size(), w.data(), (int32_t)mode, (int32_t)logits[0].size(0), (int32_t)logits[0].size(1),
+                              y.data_ptr<float>(), stream()), "ensemble_mix_rows");
+  return y;
+}
+NbestGroupOut beam_search_nbest_ensemble(int64_t h, at::IntArrayRef more_handles, at::ArrayRef<double> weights, int64_t mode, const at::Tensor& enc,
+                                         int64_t beam_width, double length_alpha, int64_t n_groups, double diversity_penalty,
+                                         int64_t no_repeat_ngram, int64_t min_length, at::IntArrayRef banned) {
+  const auto hs = ens_handles(h, more_handles);
+  const auto w = ens_weights(weights, hs.size());
+  chk_enc(h, enc);
+  TORCH_CHECK(beam_width >= 1 && beam_width <= 8 && beam_width <= dim(h, RECNET_DIM_V), "recnet: beam_width must be in [1, min(8, V)], got ", beam_width);
+  const Bans b{no_repeat_ngram, min_length, banned};
+  const Groups g{n_groups, diversity_penalty};
+  chk_groups(beam_width, &g);
+  const auto ids = ban_ids(&b);
+  const int64_t B = enc.size(0);
+  auto toks = at::zeros({beam_width, dim(h, RECNET_DIM_TM), B}, enc.options().dtype(at::kLong));
+  auto cum = at::zeros({beam_width, B}, enc.options()), score = at::zeros({beam_width, B}, enc.options());
+  auto len = at::zeros({beam_width, B}, enc.options().dtype(at::kInt)), group = at::zeros({beam_width, B}, enc.options().dtype(at::kInt));
+  auto n = at::zeros({1}, enc.options().dtype(at::kInt));
+  ok(recnet_beam_search_nbest_ensemble(hs.data(), (int32_t)hs.size(), w.data(), (int32_t)mode, enc.data_ptr<float>(), (int32_t)beam_width,
+                                       (float)length_alpha, (int32_t)n_groups, (float)diversity_penalty, (int32_t)no_repeat_ngram,
+                                       (int32_t)min_length, ids.data(), (int32_t)ids.size(), toks.data_ptr<int64_t>(), cum.data_ptr<float>(),
+                                       len.data_ptr<int32_t>(), score.data_ptr<float>(), group.data_ptr<int32_t>(), n.data_ptr<int32_t>(), stream()),
+     "beam_search_nbest_ensemble");
+  return {toks, cum, len, score, group, n};
+}
+std::tuple<at::Tensor, at::Tensor, at::Tensor> score_captions_ensemble(int64_t h, at::IntArrayRef more_handles, at::ArrayRef<double> weights, int64_t mode,
+                                                                       const c10::optional<at::Tensor>& enc, const at::Tensor& tokens) {
+  const auto hs = ens_handles(h, more_handles);
+  const auto w = ens_weights(weights, hs.size());
+  if (enc.has_value() && enc->defined()) chk_enc(h, *enc);
+  chk(tokens, at::kLong, "tokens");
+  TORCH_CHECK(tokens.dim() == 2 && tokens.size(1) == dim(h, RECNET_DIM_B), "recnet: tokens has sizes ", tokens.sizes(), ", the engine expects [T, ",
+              dim(h, RECNET_DIM_B), "]");
+  const int64_t T = tokens.size(0), B = tokens.size(1);
+  TORCH_CHECK(T <= INT32_MAX, "recnet: T out of range");
+  auto lps = at::zeros({T, B}, tokens.options().dtype(at::kFloat));
+  auto cap = at::zeros({B}, tokens.options().dtype(at::kFloat));
+  auto len = at::zeros({B}, tokens.options().dtype(at::kInt));
+  ok(recnet_score_captions_ensemble(hs.data(), (int32_t)hs.size(), w.data(), (int32_t)mode, fptr(enc, "encoder_outputs"),
+                                    tokens.data_ptr<int64_t>(), (int32_t)T, lps.data_ptr<float>(), cap.data_ptr<float>(), len.data_ptr<int32_t>(),
+                                    stream()), "score_captions_ensemble");
+  return {lps, cap, len};
+}
 // ---- consensus scoring by n-gram overlap.  hyp [N_h, T_h, B] int64, ref [N_r, T_r, B] int64 or undefined
 // (the hypotheses are their own references), weights [N_r, B] float or undefined.  Returns util [N_h, B] double, sim [N_h, N_r, B]
 // double (want_sim) and counts [N_h, N_r, B, 4], q_hyp [N_h, B, 4], q_ref [N_r, B, 4], len_hyp [N_h, B], len_ref [N_r, B] int32
@@ -495,6 +567,9 @@ TORCH_LIBRARY(recnet, m) {
   m.def("beam_search_nbest_diverse(int handle, Tensor encoder_outputs, int beam_width, float length_alpha, int n_groups, float diversity_penalty, int no_repeat_ngram, int min_length, int[] banned) -> (Tensor tokens, Tensor cum, Tensor lengths, Tensor score, Tensor group, Tensor n_steps)");
   m.def("score_captions(int handle, Tensor? encoder_outputs, Tensor tokens, float temperature) -> (Tensor logprobs, Tensor caption_logprob, Tensor lengths)");
   m.def("reconstruction_error(int handle, Tensor encoder_outputs, Tensor? tokens, Tensor? decoder_hiddens, bool want_recon) -> (Tensor err, Tensor recon)");
+  m.def("ensemble_mix_rows(int handle, Tensor[] logits, float[] weights, int mode, bool in_place) -> Tensor y");
+  m.def("beam_search_nbest_ensemble(int handle, int[] more_handles, float[] weights, int mode, Tensor encoder_outputs, int beam_width, float length_alpha, int n_groups, float diversity_penalty, int no_repeat_ngram, int min_length, int[] banned) -> (Tensor tokens, Tensor cum, Tensor lengths, Tensor score, Tensor group, Tensor n_steps)");
+  m.def("score_captions_ensemble(int handle, int[] more_handles, float[] weights, int mode, Tensor? encoder_outputs, Tensor tokens) -> (Tensor logprobs, Tensor caption_logprob, Tensor lengths)");
   m.def("consensus_rows(int handle, Tensor hyp, Tensor? ref, Tensor? weights, float sigma, bool want_sim, bool want_counts) -> (Tensor util, Tensor sim, Tensor counts, Tensor q_hyp, Tensor q_ref, Tensor len_hyp, Tensor len_ref)");
 }
 
@@ -527,6 +602,9 @@ TORCH_LIBRARY_IMPL(recnet, CUDA, m) {
   m.impl("score_captions", score_captions);
   m.impl("reconstruction_error", reconstruction_error);
   m.impl("consensus_rows", consensus_rows);
+  m.impl("ensemble_mix_rows", ensemble_mix_rows);
+  m.impl("beam_search_nbest_ensemble", beam_search_nbest_ensemble);
+  m.impl("score_captions_ensemble", score_captions_ensemble);
 }
 TORCH_LIBRARY_IMPL(recnet, CompositeExplicitAutograd, m) {
   m.impl("add_reg_grad", add_reg_grad);

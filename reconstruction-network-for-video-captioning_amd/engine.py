@@ -477,6 +477,74 @@ class Engine:
         out = (util,) + ((sim,) if want_sim else ()) + ((ints,) if want_counts else ())
         return out[0] if len(out) == 1 else out
 
+    # ------------------------------------------------------------------ ensemble decoding
+    @staticmethod
+    def _ens_args(n, weights, mode):
+        """(weights as the host float array the ensemble entries read during the call, the mode's number); weights None: uniform.
+        The library checks the values."""
+        w = [1.0] * n if weights is None else [float(x) for x in weights]
+        if len(w) != n:
+            raise RuntimeError("%d weights for %d ensemble members" % (len(w), n))
+        return (C.c_float * n)(*w), (_lib.ENS_MODES[mode] if isinstance(mode, str) else int(mode))
+
+    def ensemble_mix_rows(self, logits, weights=None, mode="arithmetic", in_place=False):
+        """The ensemble's logits of caller-supplied device rows (recnet_ensemble_mix_rows; no decoder needed): logits a list of M
+        tensors [rows, V] float32, one per member.  Returns y [rows, V] float32: the log of the weighted mean of the members'
+        probabilities (arithmetic) or the weighted mean of their log-probabilities (geometric); in_place: written over logits[0],
+        which is returned.  The library checks M, the weights and the mode."""
+        logits = list(logits)
+        if not logits or logits[0].dim() != 2:
+            raise RuntimeError("logits: expected a list of [rows, V] tensors")
+        rows, V = logits[0].shape
+        for x in logits:
+            _chk_tensor(x, (rows, V), torch.float32, "logits")
+        w, md = self._ens_args(len(logits), weights, mode)
+        y = logits[0] if in_place else torch.empty_like(logits[0])
+        ptrs = (C.c_void_p * len(logits))(*[x.data_ptr() for x in logits])
+        _lib.check(self.lib.recnet_ensemble_mix_rows(self.handle, ptrs, len(logits), w, md, int(rows), int(V), _ptr(y), _stream()),
+                   "recnet_ensemble_mix_rows")
+        return y
+
+    @staticmethod
+    def beam_search_nbest_ensemble(engines, enc, beam_width, length_alpha=0.0, weights=None, mode="arithmetic", n_groups=1,
+                                   diversity_penalty=0.0, no_repeat_ngram=0, min_length=0, banned_tokens=()):
+        """beam_search_nbest_diverse over the engines of an ensemble (recnet_beam_search_nbest_ensemble; member 0 first): every
+        step mixes the members' rows into the ensemble's logits, every member keeps its own state.  Returns that call's tensors
+        (tokens, cum, len, score, group, n_steps).  The library checks the members, the weights, the mode and the search's own
+        arguments before any launch of its own."""
+        engines = list(engines)
+        e0 = engines[0]
+        toks, cum, ln, score, group, n = e0._nbest_outputs(enc, beam_width, with_group=True)
+        w, md = Engine._ens_args(len(engines), weights, mode)
+        hs = (C.c_void_p * len(engines))(*[e.handle.value for e in engines])
+        ban, n_ban = Engine._ban_array(banned_tokens)
+        _lib.check(e0.lib.recnet_beam_search_nbest_ensemble(hs, len(engines), w, md, _ptr(enc), int(beam_width), float(length_alpha),
+                                                            int(n_groups), float(diversity_penalty), int(no_repeat_ngram), int(min_length),
+                                                            ban, n_ban, _ptr(toks), _ptr(cum), _ptr(ln), _ptr(score), _ptr(group), _ptr(n),
+                                                            _stream()), "recnet_beam_search_nbest_ensemble")
+        return toks, cum, ln, score, group, n
+
+    @staticmethod
+    def score_captions_ensemble(engines, enc, tokens, weights=None, mode="arithmetic"):
+        """score_captions at temperature 1 under the ensemble (recnet_score_captions_ensemble): the teacher-forced forward of every
+        member, one mix of the T * B rows.  Returns (logprobs [T, B], caption_logprob [B], lengths [B]) like score_captions."""
+        engines = list(engines)
+        e0, d = engines[0], engines[0].dims
+        if enc is not None:
+            _chk_tensor(enc, (d["B"], d["F"], d["D"]), torch.float32, "encoder_outputs")
+        if tokens.dim() != 2:
+            raise RuntimeError("tokens: expected [T, B], got %s" % (tuple(tokens.shape),))
+        T = tokens.shape[0]
+        _chk_tensor(tokens, (T, d["B"]), torch.int64, "tokens")
+        lps = torch.zeros(T, d["B"], dtype=torch.float32, device=e0.device)
+        cap = torch.zeros(d["B"], dtype=torch.float32, device=e0.device)
+        ln = torch.zeros(d["B"], dtype=torch.int32, device=e0.device)
+        w, md = Engine._ens_args(len(engines), weights, mode)
+        hs = (C.c_void_p * len(engines))(*[e.handle.value for e in engines])
+        _lib.check(e0.lib.recnet_score_captions_ensemble(hs, len(engines), w, md, _ptr(enc), _ptr(tokens), int(T), _ptr(lps), _ptr(cap),
+                                                         _ptr(ln), _stream()), "recnet_score_captions_ensemble")
+        return lps, cap, ln
+
     def score_captions(self, enc, tokens, temperature=1.0):
         """Teacher-forced log-probabilities of given captions, eval mode (recnet_score_captions).  tokens [T, B] int64 with every
         entry in [0, V) (the caller's duty: search.score_captions checks); enc None reuses the invariants of the previous call.

@@ -19,8 +19,67 @@ import numbers
 
 import torch
 
-from . import _ops
+from . import _lib, _ops
 from .engine import Engine
+
+
+class Ensemble:
+    """Several decoders that are decoded together, passed where the calls of this module take `decoder`:
+    beam_search_nbest, best_of_beam (with consensus_weight), score_captions, loop.evaluate's "beam_nbest" / "beam_consensus" and
+    loop.perplexity.  decoders: 1 to 8 different Decoder objects that share the vocabulary and the feature size; embedding, hidden
+    and attention sizes, the cell and the precision may differ.  weights: one positive finite number per member (None: uniform),
+    normalised to sum 1.  mode "arithmetic": the ensemble's distribution is the weighted mean of the members' probabilities;
+    "geometric": the renormalised weighted mean of their log-probabilities.  At every step every member is fed the ensemble's
+    token and keeps its own state.  Arguments are checked here; no library is loaded.  An ensemble of one is that decoder, bit for
+    bit."""
+
+    def __init__(self, decoders, weights=None, mode="arithmetic"):
+        members = list(decoders)
+        if not 1 <= len(members) <= _lib.ENS_MAX_M:
+            raise ValueError("an ensemble has between 1 and %d members (got %d)" % (_lib.ENS_MAX_M, len(members)))
+        if len({id(d) for d in members}) != len(members):
+            raise ValueError("the members of an ensemble must be different objects: each keeps its own state (build a second decoder with "
+                             "the same parameters to use one twice)")
+        w = [1.0] * len(members) if weights is None else list(weights)
+        if len(w) != len(members):
+            raise ValueError("%d weights for %d members" % (len(w), len(members)))
+        for x in w:
+            if not (isinstance(x, numbers.Real) and math.isfinite(x) and x > 0):
+                raise ValueError("ensemble weights must be positive finite numbers (got %r)" % (x,))
+        if mode not in _lib.ENS_MODES:
+            raise ValueError('mode must be "arithmetic" or "geometric" (got %r)' % (mode,))
+        for k, d in enumerate(members):
+            if d.output_size != members[0].output_size or d.encoder_size != members[0].encoder_size:
+                raise ValueError("member %d has vocabulary %d and feature size %d, member 0 has %d and %d"
+                                 % (k, d.output_size, d.encoder_size, members[0].output_size, members[0].encoder_size))
+        total = math.fsum(float(x) for x in w)
+        self.members, self.mode = members, mode
+        self.weights = [float(x) / total for x in w]
+
+    # what loop.evaluate / loop.perplexity and the checks of this module ask a decoder for: member 0's
+    hidden_size = property(lambda self: self.members[0].hidden_size)
+    output_size = property(lambda self: self.members[0].output_size)
+    encoder_size = property(lambda self: self.members[0].encoder_size)
+
+    def eval(self):
+        for d in self.members:
+            d.eval()
+        return self
+
+    def parameters(self):
+        for d in self.members:
+            yield from d.parameters()
+
+    def _call_args(self, engines):
+        """The leading arguments of the ensemble ops: member 0's handle, the other members' handles, weights, mode."""
+        hs = [int(e.handle.value) for e in engines]
+        return hs[0], hs[1:], self.weights, _lib.ENS_MODES[self.mode]
+
+
+def _no_ensemble(decoder, call):
+    if isinstance(decoder, Ensemble):
+        raise NotImplementedError("%s does not take an Ensemble: ensembles are decoded by beam_search_nbest / best_of_beam (with "
+                                  "consensus_weight) and scored by score_captions" % call)
 
 
 def _cached_engine(decoder, encoder_outputs, reconstructor=None, caption_max_len=None):
@@ -80,6 +139,7 @@ def _check_start(config, input, hidden):
 def greedy_search(config, decoder, input, hidden, encoder_outputs):
     """eval.py:19-33.  Returns output_indices: list over steps of lists over the batch (python ints), like the
     reference's list of lists of 0-d tensors."""
+    _no_ensemble(decoder, "greedy_search")
     _check_start(config, input, hidden)
     eng = _cached_engine(decoder, encoder_outputs)
     toks, n = _ops.load().greedy_search(int(eng.handle.value), encoder_outputs.contiguous())
@@ -89,6 +149,7 @@ def greedy_search(config, decoder, input, hidden, encoder_outputs):
 
 def beam_search(config, beam_width, vocab, decoder, input, hidden, encoder_outputs):
     """eval.py:36-120.  Returns top1_output_list: one token list per caption."""
+    _no_ensemble(decoder, "beam_search")
     _check_start(config, input, hidden)
     eng = _cached_engine(decoder, encoder_outputs)
     best, n = _ops.load().beam_search(int(eng.handle.value), encoder_outputs.contiguous(), int(beam_width))
@@ -105,6 +166,7 @@ def sample_search(config, decoder, input, hidden, encoder_outputs, temperature=1
     sequence_logprob).  top_p < 1 adds a nucleus cut behind the top_k cut (recnet_sample_search_nucleus):
     of the entries top_k leaves, only the most probable ones whose mass reaches top_p are drawn from, and logprobs are under
     that set; top_p = 1.0 is the call without it."""
+    _no_ensemble(decoder, "sample_search")
     _check_temperature(temperature)
     if int(top_k) != top_k or not 0 <= top_k <= decoder.output_size:
         raise ValueError("top_k must be an integer in [0, %d] (got %r)" % (decoder.output_size, top_k))
@@ -183,13 +245,19 @@ _SHARED_CML = 30          # Engine's default caption_max_len: the shared engine 
 def _score(decoder, encoder_outputs, tokens, temperature, reuse_features, caption_max_len=None):
     """Device tensors (logprobs [T, B], caption_logprob [B], lengths [B]) of checked tokens [T, B].  caption_max_len: the config's —
     another one than the shared engine's runs on the engine keyed by it (_nbest_engine's), whose Tm admits the caption_max_len + 1
-    rows _caption_tensor lets through (the shared engine refused captions of more than 31 rows: T out of range)."""
-    if caption_max_len is None or int(caption_max_len) == _SHARED_CML:
-        eng = _cached_engine(decoder, encoder_outputs)
-    else:
-        eng = _cached_engine(decoder, encoder_outputs, caption_max_len=caption_max_len)
+    rows _caption_tensor lets through (the shared engine refused captions of more than 31 rows: T out of range).  decoder an
+    Ensemble: the same engine of every member, recnet_score_captions_ensemble; temperature 1 only."""
+    def engine_of(dec):
+        if caption_max_len is None or int(caption_max_len) == _SHARED_CML:
+            return _cached_engine(dec, encoder_outputs)
+        return _cached_engine(dec, encoder_outputs, caption_max_len=caption_max_len)
     enc = None if reuse_features else encoder_outputs.contiguous()
-    return _ops.load().score_captions(int(eng.handle.value), enc, tokens.to(encoder_outputs.device).contiguous(), float(temperature))
+    tokens = tokens.to(encoder_outputs.device).contiguous()
+    if isinstance(decoder, Ensemble):
+        if temperature != 1.0:
+            raise NotImplementedError("score_captions with an Ensemble scores at temperature 1 (got %r)" % (temperature,))
+        return _ops.load().score_captions_ensemble(*decoder._call_args([engine_of(d) for d in decoder.members]), enc, tokens)
+    return _ops.load().score_captions(int(engine_of(decoder).handle.value), enc, tokens, float(temperature))
 
 
 def score_captions(config, decoder, encoder_outputs, captions, temperature=1.0, reuse_features=False):
@@ -200,7 +268,8 @@ def score_captions(config, decoder, encoder_outputs, captions, temperature=1.0, 
     captions[t][b] under softmax(logits_t / temperature), every row; lengths[b] = the position of the caption's first <EOS>
     + 1 (T when it has none); caption_logprob[b] = the sum of the first lengths[b] rows (the rule of sequence_logprob).
     reuse_features=True: the caller asserts that the previous call on this decoder used the same encoder_outputs and
-    parameters — the loop invariants (Uv, P) are not recomputed.  Arguments are checked before anything is launched."""
+    parameters — the loop invariants (Uv, P) are not recomputed.  Arguments are checked before anything is launched.
+    decoder may be an Ensemble (temperature 1): the log-probabilities are the ensemble's, the ones its beam search sums."""
     _check_temperature(temperature)
     if encoder_outputs.dim() != 3:
         raise ValueError("encoder_outputs must be [B, F, D] (got %s)" % (tuple(encoder_outputs.shape),))
@@ -274,6 +343,7 @@ def reconstruction_errors(config, decoder, reconstructor, encoder_outputs, capti
     <PAD> rows up to T).  The global error depends on T: compare errors of one video only at a common T.  Returns err [B] as a
     list, or (err, reconstruction) with want_recon: a device tensor, global [B, R] = mean_t out_t, local [B, F, D].
     Arguments are checked before anything is launched."""
+    _no_ensemble(decoder, "reconstruction_errors")
     _check_reconstructor(config, decoder, reconstructor, encoder_outputs)
     tokens = _caption_tensor(config, decoder, encoder_outputs.shape[0], captions)
     if T is not None and (int(T) != T or not tokens.shape[0] <= T <= config.caption_max_len + 1):
@@ -460,6 +530,7 @@ def best_of_n(config, decoder, input, hidden, encoder_outputs, n, temperature=1.
     candidate sets are stacked on the device at the common length of the longest rollout, one more launch, and the n x B utilities
     are one more read-back; it needs n <= 32 and caption_max_len + 1 <= 64.  consensus_weight = 0 launches nothing new.  Returns
     (captions: [B] token lists cut after their <EOS>, chosen k [B], score [B])."""
+    _no_ensemble(decoder, "best_of_n")
     if int(n) != n or n < 1:
         raise ValueError("n must be a positive integer (got %r)" % (n,))
     _check_top_p(top_p)
@@ -529,6 +600,14 @@ def _beam_nbest(config, decoder, input, hidden, encoder_outputs, beam_width, len
     ids = _check_constraints(config, decoder, beam_width, no_repeat_ngram, min_length, banned_tokens)
     _check_groups(beam_width, n_groups, diversity_penalty)
     _check_start(config, input, hidden)
+    if isinstance(decoder, Ensemble):    # (one member: the library launches the single-model search)
+        engines = [_nbest_engine(config, d, encoder_outputs) for d in decoder.members]
+        toks, cum, ln, score, group, n = _ops.load().beam_search_nbest_ensemble(*decoder._call_args(engines), encoder_outputs.contiguous(),
+                                                                                int(beam_width), float(length_alpha), int(n_groups),
+                                                                                float(diversity_penalty), int(no_repeat_ngram),
+                                                                                int(min_length), ids)
+        out = (toks[:, :int(n.item())], cum, ln, score)
+        return out + (group,) if want_groups else out
     eng = _nbest_engine(config, decoder, encoder_outputs)
     if int(n_groups) == 1:
         # (constraints all off: the library launches the unconstrained selection, recnet_beam_search_nbest's own path)
@@ -565,7 +644,10 @@ def beam_search_nbest(config, decoder, input, hidden, encoder_outputs, beam_widt
     other, and a candidate pays diversity_penalty for every hypothesis of an earlier group that chose its token at this step.  The
     penalty steers the selection only: cum, length and score are as above, and the final order runs over all groups.  Different
     groups may still return the same caption (nbest_diversity counts).  return_groups: the tuples get the group of the hypothesis
-    as a fifth field.  n_groups = 1 is the search above for any penalty."""
+    as a fifth field.  n_groups = 1 is the search above for any penalty.
+    decoder may be an Ensemble (recnet_beam_search_nbest_ensemble): the search runs on the ensemble's
+    distribution, every member on the ensemble's tokens with its own state; everything above holds, with score_captions on the
+    Ensemble in place of the model's."""
     out = _beam_nbest(config, decoder, input, hidden, encoder_outputs, beam_width, length_alpha, no_repeat_ngram, min_length,
                       banned_tokens, n_groups, diversity_penalty, bool(return_groups))
     toks, cum, ln, score = (x.cpu().tolist() for x in out[:4])
@@ -603,7 +685,10 @@ def best_of_beam(config, decoder, input, hidden, encoder_outputs, beam_width, le
     hypotheses that differ.  consensus_weight != 0 adds consensus_weight * U_k, the consensus utilities of the ranks among
     themselves (consensus_scores) on the search's own device tensor: one more launch and one more read-back,
     of the beam_width x B utilities; it needs caption_max_len + 1 <= 64, and 0 launches nothing new.  Returns what best_of_n
-    returns: (captions: [B] token lists cut after their <EOS>, chosen k [B], score [B])."""
+    returns: (captions: [B] token lists cut after their <EOS>, chosen k [B], score [B]).  decoder may be an Ensemble, without a
+    reconstructor: reranking an ensemble's beams by one member's reconstructor is not defined."""
+    if isinstance(decoder, Ensemble) and reconstructor is not None:
+        raise NotImplementedError("best_of_beam(reconstructor=) does not take an Ensemble: the reconstructor reads one decoder's states")
     use_rec, recon_weight = _check_recon_weight(config, decoder, reconstructor, encoder_outputs, recon_weight)
     consensus_weight = _check_consensus_weight(config, consensus_weight, 1)
     toks, cum, ln, _ = _beam_nbest(config, decoder, input, hidden, encoder_outputs, beam_width, length_alpha, no_repeat_ngram,
@@ -613,3 +698,22 @@ def best_of_beam(config, decoder, input, hidden, encoder_outputs, beam_width, le
                          [toks[r] for r in range(int(beam_width))] if use_rec else None, consensus_weight,
                          toks.contiguous() if consensus_weight != 0 else None)
     return _cut_winners(toks.cpu().tolist(), ks, lens), ks, scores
+
+
+def ensemble_logits(ens, rows_of_logits, device=None):
+    """The ensemble's logits of given rows (recnet_ensemble_mix_rows): rows_of_logits holds one [rows, V] array of logits per member
+    of `ens` (tensors or anything torch.as_tensor takes).  Returns y [rows, V] float32 on the device: log of the weighted mean of
+    the members' softmax (arithmetic) or the weighted mean of their log_softmax (geometric, not renormalised: log_softmax(y) is the
+    ensemble's distribution in both modes).  device: for inputs that do not live on one (default: the current HIP device)."""
+    if not isinstance(ens, Ensemble):
+        raise ValueError("ens must be an Ensemble (got %r)" % (type(ens).__name__,))
+    xs = [torch.as_tensor(x, dtype=torch.float32) for x in rows_of_logits]
+    if len(xs) != len(ens.members):
+        raise ValueError("%d rows of logits for %d members" % (len(xs), len(ens.members)))
+    for x in xs:
+        if x.dim() != 2 or x.shape != xs[0].shape or x.shape[0] < 1 or x.shape[1] != ens.output_size:
+            raise ValueError("every member's logits must be [rows, V = %d] of one shape (got %s)" % (ens.output_size, tuple(x.shape)))
+    dev = torch.device(device) if device is not None else next((x.device for x in xs if x.is_cuda), torch.device("cuda"))
+    eng = _consensus_engine(dev)
+    return _ops.load().ensemble_mix_rows(int(eng.handle.value), [x.to(eng.device).contiguous() for x in xs], ens.weights,
+                                         _lib.ENS_MODES[ens.mode], False)
