@@ -36,7 +36,7 @@
 
 // ---------------------------------------------------------------- launch epoch and phase stamps
 // Grid barrier, split in two so that the stores nobody waits for are issued between the halves.
-//   arrive: the caller has already waited for its write-through stores of h_t (s_waitcnt vmcnt(0) + __syncthreads);
+//   arrive: the caller has already waited for its write-through stores of h_t (s_waitcnt vmcnt(0) + __syncthreads: cs_publish_arrive);
 //           one agent-scope store of the step number into this workgroup's own flag — no read-modify-write, so the
 //           arrivals of the R / 8 workgroups do not serialise on one address;
 //   wait:   wave 0 polls all flags (one agent-scope load per 64 workgroups) until every one has reached the step, then
@@ -115,6 +115,16 @@ __device__ __forceinline__ void cs_poll_wave(const unsigned* mine, unsigned targ
 __device__ __forceinline__ int cs_wg() { return (int)(blockIdx.y * gridDim.x + blockIdx.x); }
 __device__ __forceinline__ void cs_arrive(unsigned* flag, unsigned v) {
   if (threadIdx.x == 0) __hip_atomic_store(flag, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// The hand-over tail of a producer: its write-through stores are acknowledged (cs_publish_sync: by every thread of the workgroup), then
+// it arrives.  Stores nobody waits for are issued BEHIND this, so that they do not sit in the vmcnt that is being waited for.
+__device__ __forceinline__ void cs_publish_sync() {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+}
+__device__ __forceinline__ void cs_publish_arrive(unsigned* flag, unsigned v) {
+  cs_publish_sync();
+  cs_arrive(flag, v);
 }
 // every workgroup of the grid polls every flag
 __device__ __forceinline__ void cs_wait_grid(unsigned* bar, unsigned target) {

@@ -450,9 +450,8 @@ __global__ __launch_bounds__(256) void dec_chain_kernel(const DecChainArgs p) {
       if (tid < (H >> 3)) {
         rc_store16(p.Pan + (size_t)t * pan_t + ((size_t)tid * RC_PAN_ROWS + b) * 8, hl + tid * 8);
       }
-      if (t + 1 < p.T) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       // (the stores below are issued after the arrive, see the end of the loop body)
-      if (t + 1 < p.T) { __syncthreads(); DC_TS(6); ++ph; cs_arrive_part(p.rep, b / own, b % own, fb + ph); }
+      if (t + 1 < p.T) { cs_publish_sync(); DC_TS(6); ++ph; cs_arrive_part(p.rep, b / own, b % own, fb + ph); }
       bf16_t* Lt = p.Hlp + ((size_t)t * Bs + b) * p.ld_hlp;
       if (tid < (H >> 3)) *reinterpret_cast<bf16x8*>(Lt + tid * 8) = *reinterpret_cast<const bf16x8*>(hl + tid * 8);
       if (p.Xcat && tid < (H >> 3)) *reinterpret_cast<bf16x8*>(p.Xcat + ((size_t)t * Bs + b) * p.ld_xcat + tid * 8) = *reinterpret_cast<const bf16x8*>(hl + tid * 8);
@@ -842,7 +841,7 @@ __global__ __launch_bounds__(256) void dec_chain_bwd_kernel(const DecChainBwdArg
       for (int kg = tid; kg < (KA >> 3); kg += 256) {
         rc_store16(p.Pan + (size_t)s * pan_t + ((size_t)kg * RC_PAN_ROWS + b) * 8, srow + kg * 8);
       }
-      if (more) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads(); ++ph; cs_arrive_part(p.rep, b / own, b % own, fb + ph); }
+      if (more) { cs_publish_sync(); ++ph; cs_arrive_part(p.rep, b / own, b % own, fb + ph); }
       DCB_TS(5);
       // ---- off the critical path: the row-major copy [dgates | dWh | 0 ..] for the deferred GEMMs
       bf16_t* Gt = p.dGx + ((size_t)t * Bs + b) * p.ld_dgx;

@@ -87,17 +87,13 @@ __global__ __launch_bounds__(256) void lcbig_bwd_kernel(const LocBigBwdArgs p) {
   // among the other 4 (NCB - NXB) workgroups finish under the caption phase; barriers 1 and 3 of a step are full and relayed.
   const int cb = wg % p.NCB, kqi = wg / p.NCB, NXB = H >> 6;
   unsigned* myflag = p.bar + (cb < NXB ? kqi * NXB + cb : 4 * NXB + kqi * (p.NCB - NXB) + (cb - NXB));
-  auto bar_arrive = [&](unsigned phase) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    cs_arrive(myflag, fb + phase);
-  };
+  auto bar_arrive = [&](unsigned phase) { cs_publish_arrive(myflag, fb + phase); };
   auto bar_wait = [&](unsigned phase) { lc_wait_or_relay(relay, p.bar, CS_REL_A, p.bar, p.NWG, fb + phase); };
 
   // ---------------------------------------------------------------- P: residents
   const int kw0 = kqi * R + wave * (STEPS * 32);            // this wave's K range inside the quarter (K quarter = R gate rows)
   const int rot = wg % NP;
-  auto k_of = [&](int pr, int hh) { int prr = pr + rot; prr = prr >= NP ? prr - NP : prr; return kw0 + (prr * 2 + hh) * 32; };
+  auto k_of = [&](int pr, int hh) { return ct_k_of<NP>(kw0, rot, pr, hh); };
   bf16x8 wb[SR][CG];
 #pragma unroll
   for (int g = 0; g < CG; ++g) {
@@ -116,7 +112,7 @@ __global__ __launch_bounds__(256) void lcbig_bwd_kernel(const LocBigBwdArgs p) {
       for (int g = 0; g < CG; ++g)
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(wst + (size_t)(((2 * NPG + j) * CG + g) * 512)),
                                          (__attribute__((address_space(3))) void*)(wl + (size_t)((wave * NL + j) * CG + g) * 1024), 16, 0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (the DMAs have landed: no hand-over, so no cs_publish_arrive)
   }
 
   // ---------------------------------------------------------------- L: residents (workgroups j < R / 16)
@@ -445,8 +441,7 @@ __global__ __launch_bounds__(256) void lcbig_pack_stream_kernel(const bf16_t* __
   const size_t r = f >> 8;
   const int js = (int)(r % NS), wave = (int)((r / NS) & 3), wg = (int)(r / NS / 4);
   const int cb = wg % NCB, kqi = wg / NCB;
-  int prr = NPR + js / 2 + wg % NP; prr = prr >= NP ? prr - NP : prr;
-  const int k = kqi * R + wave * (STEPS * 32) + (prr * 2 + (js & 1)) * 32 + (lane >> 4) * 8;
+  const int k = ct_k_of(NP, kqi * R + wave * (STEPS * 32), wg % NP, NPR + js / 2, js & 1) + (lane >> 4) * 8;      // the consumer's kw0, rot and pair_of(i) = NPR + i
   *reinterpret_cast<bf16x8*>(dst + f * 8) = *reinterpret_cast<const bf16x8*>(WT + (size_t)(cb * 64 + g * 16 + (lane & 15)) * ldwt + k);
 }
 

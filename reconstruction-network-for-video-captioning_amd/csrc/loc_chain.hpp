@@ -222,9 +222,7 @@ __global__ __launch_bounds__(256) void loc_chain_kernel(const LocChainArgs p) {
       const int pc = tid >> 6, kg = tid & 63, pb = ci * LC_CPW + pc;
       const bool pon = tid < LC_CPW * 64 && pb < B && kg < (H >> 3);
       if (pon) rc_store16(p.PanX + (size_t)s * pan_x + ((size_t)kg * RC_PAN_ROWS + pb) * 8, xl + pc * 512 + kg * 8);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      cs_arrive(p.bar + p.NU + ci, fb + (unsigned)(s + 1));
+      cs_publish_arrive(p.bar + p.NU + ci, fb + (unsigned)(s + 1));
       if (ci == 0) LC_TS(1, s, 3);
       if (pon) *reinterpret_cast<bf16x8*>(p.Xcat + ((size_t)s * Bs + pb) * p.ld_xcat + kg * 8) = *reinterpret_cast<const bf16x8*>(xl + pc * 512 + kg * 8);
       if (fold && tid < 64) {      // "every caption workgroup has published x_s": release the unit owners
@@ -260,7 +258,7 @@ __global__ __launch_bounds__(256) void loc_chain_kernel(const LocChainArgs p) {
   const int kw0 = wave * (STEPS * 32);
   const int kq = (lane >> 4) * 8;
   const int rot = ug % NP;
-  auto k_of = [&](int pr, int hh) { int prr = pr + rot; prr = prr >= NP ? prr - NP : prr; return kw0 + (prr * 2 + hh) * 32; };
+  auto k_of = [&](int pr, int hh) { return ct_k_of<NP>(kw0, rot, pr, hh); };
 
   // ---- residents: W_hh (registers), W_ih (LDS, each lane keeps its own fragments), W_r columns of the own units
   bf16x8 wb[SR][CG];
@@ -415,9 +413,7 @@ __global__ __launch_bounds__(256) void loc_chain_kernel(const LocChainArgs p) {
         }
       }
       if (wg == 0) LC_TS(0, s, 3);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      cs_arrive(p.bar + wg, fb + (unsigned)(s + 1));
+      cs_publish_arrive(p.bar + wg, fb + (unsigned)(s + 1));
       if (wg == 0) LC_TS(0, s, 4);
     }
     // ---- off the critical path: what the backward and the output layer read
@@ -519,8 +515,7 @@ __global__ __launch_bounds__(256) void lc_pack_stream_kernel(const bf16_t* __res
   const size_t r = f >> 8;
   const int js = (int)(r % NS), wave = (int)((r / NS) & 3), ug = (int)(r / NS / 4);
   const int col = g * 16 + (lane & 15), gate = col / 16, ul = col % 16, kq = (lane >> 4) * 8;
-  int prr = NPR + js / 2 + ug % NP; prr = prr >= NP ? prr - NP : prr;
-  const int k = wave * (STEPS * 32) + (prr * 2 + (js & 1)) * 32;
+  const int k = ct_k_of(NP, wave * (STEPS * 32), ug % NP, NPR + js / 2, js & 1);      // the consumer's kw0, rot and pair_of(i) = NPR + i
   const bf16_t* src = W + (size_t)(gate * R + ug * 16 + ul) * ldw + H + k + kq;
   bf16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
   if (k + kq < R) v = *reinterpret_cast<const bf16x8*>(src);
@@ -568,7 +563,7 @@ struct LocChainBwdArgs {
 template <int STEPS, int PF, int RB>
 __device__ __forceinline__ void lcb_product(f32x4 (&acc)[RB], const bf16x8 (&wb)[STEPS], const bf16_t* A, int K, int kw0, int rot) {
   constexpr int NP = STEPS / 2;
-  auto k_of = [&](int pr, int hh) { int prr = pr + rot; prr = prr >= NP ? prr - NP : prr; return kw0 + (prr * 2 + hh) * 32; };
+  auto k_of = [&](int pr, int hh) { return ct_k_of<NP>(kw0, rot, pr, hh); };
   bf16x8 fa[PF][2][RB];
   auto issue_pair = [&](int slot, int pr) {
 #pragma unroll
@@ -604,8 +599,7 @@ __device__ __forceinline__ void lcb_load_weights(bf16x8 (&wb)[STEPS], const bf16
   for (int pr = 0; pr < NP; ++pr)
 #pragma unroll
     for (int hh = 0; hh < 2; ++hh) {
-      int prr = pr + rot; prr = prr >= NP ? prr - NP : prr;
-      const int k = kw0 + (prr * 2 + hh) * 32;
+      const int k = ct_k_of<NP>(kw0, rot, pr, hh);
       wb[pr * 2 + hh] = (k + kq < K) ? *reinterpret_cast<const bf16x8*>(wrow + k + kq) : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
     }
 }
@@ -631,7 +625,7 @@ __device__ __forceinline__ void lcb_xsplit_role(const LocChainBwdArgs& p, float*
   const int r0 = own_lo < RC_PAN_ROWS - ROWS ? own_lo : RC_PAN_ROWS - ROWS;
   const int kq = (lane >> 4) * 8, kw0 = kp * (XS * 128) + wave * (XS * 32);
   const int rot = xg % NP;
-  auto k_of = [&](int pr, int hh) { int prr = pr + rot; prr = prr >= NP ? prr - NP : prr; return kw0 + (prr * 2 + hh) * 32; };
+  auto k_of = [&](int pr, int hh) { return ct_k_of<NP>(kw0, rot, pr, hh); };
   bf16x8 wb[XS][CG];
 #pragma unroll
   for (int g = 0; g < CG; ++g) {
@@ -719,9 +713,7 @@ __device__ __forceinline__ void lcb_xsplit_role(const LocChainBwdArgs& p, float*
         rc_store16f(dst, v);
       }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    cs_arrive(p.bar + wg, fb + (unsigned)(q + 1));
+    cs_publish_arrive(p.bar + wg, fb + (unsigned)(q + 1));
     if (xi == 0) LC_TS(5, q, 2);
   }
   __syncthreads();
@@ -847,9 +839,7 @@ __global__ __launch_bounds__(256) void loc_chain_bwd_kernel(const LocChainBwdArg
       const bool pon = tid < LC_CPW * 64 && pb < B;
       // (k-groups up to the next multiple of 32 columns: the consumer's k-step reads them; swl holds zeros beyond A)
       if (pon && kg < (((A + 31) >> 5) << 2)) rc_store16(p.PanW + (size_t)q * pan_w + ((size_t)kg * RC_PAN_ROWS + pb) * 8, swl + pc * 128 + kg * 8);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      cs_arrive(p.bar + NU + NX + ci, fb + (unsigned)(q + 1));
+      cs_publish_arrive(p.bar + NU + NX + ci, fb + (unsigned)(q + 1));
       if (ci == 0) LC_TS(6, q, 2);
       if (pon && kg < (p.ld_dwhr >> 3) && kg < 16)
         *reinterpret_cast<bf16x8*>(p.dWhrs + ((size_t)s * Bs + pb) * p.ld_dwhr + kg * 8) = *reinterpret_cast<const bf16x8*>(swl + pc * 128 + kg * 8);
@@ -923,9 +913,7 @@ __global__ __launch_bounds__(256) void loc_chain_bwd_kernel(const LocChainBwdArg
           __hip_atomic_store(reinterpret_cast<uint64_t*>(p.Dx + ((size_t)q * B + rg) * H + j0 + pc), pk.u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
       }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      cs_arrive(p.bar + wg, fb + (unsigned)(q + 1));
+      cs_publish_arrive(p.bar + wg, fb + (unsigned)(q + 1));
       if (xi == 0) LC_TS(5, q, 2);
     }
     __syncthreads();
@@ -1041,9 +1029,7 @@ __global__ __launch_bounds__(256) void loc_chain_bwd_kernel(const LocChainBwdArg
 #pragma unroll
     for (int jj = 0; jj < IPT; ++jj)
       if (it_on[jj]) rc_store16(p.PanG + (size_t)q * pan_g + ((size_t)(it_col[jj] >> 3) * RC_PAN_ROWS + it_rg[jj]) * 8, it_src[jj]);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    cs_arrive(p.bar + wg, fb + (unsigned)(q + 1));
+    cs_publish_arrive(p.bar + wg, fb + (unsigned)(q + 1));
     if (wg == 0) LC_TS(4, q, 4);
     // ---- off the critical path: the row-major copy for the deferred weight-gradient GEMMs
     bf16_t* Gt = p.dG + (size_t)s * Bs * p.ld_dg;

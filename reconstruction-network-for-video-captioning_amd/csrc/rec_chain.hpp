@@ -16,6 +16,7 @@
 #pragma once
 #include "common.hpp"
 #include "chain_sync.hpp"
+#include "chain_tile.hpp"
 
 struct RecChainArgs {
   int T, B, R, gru;
@@ -134,7 +135,7 @@ __global__ __launch_bounds__(256) void rec_chain_kernel(const RecChainArgs p) {
   if (role.master) { rc_master_loop(p.bar, nwx * (int)gridDim.y, fb, p.T - 1 + p.epi); return; }
   if (role.idle) return;
   const int rot = vx % NP;                               // workgroups start at different k: spreads the L2 channels
-  auto k_of = [&](int pr, int hh) { int prr = pr + rot; prr = prr >= NP ? prr - NP : prr; return kw0 + (prr * 2 + hh) * 32; };
+  auto k_of = [&](int pr, int hh) { return ct_k_of<NP>(kw0, rot, pr, hh); };
 
   // ---- resident weights: tile column g*16 + c  <->  gate (g*16+c) / UW, unit u0 + (g*16+c) % UW
   bf16x8 wb[STEPS][CG];
@@ -271,11 +272,7 @@ __global__ __launch_bounds__(256) void rec_chain_kernel(const RecChainArgs p) {
       rc_store16(p.Pan + (size_t)t * pan_t + ((size_t)(vx * KG + it_j) * RC_PAN_ROWS + it_rg) * 8, it_src);
     }
     const bool more = t + 1 < p.T;
-    if (more) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      cs_arrive(p.bar + widx, fb + (unsigned)(t + 1));
-    }
+    if (more) cs_publish_arrive(p.bar + widx, fb + (unsigned)(t + 1));
     // ---- everything below is off the critical path of the chain
     float* Ht = p.H + (size_t)t * Bs * R;
     float* Ct = p.C + (size_t)t * Bs * R;
@@ -338,6 +335,8 @@ __global__ __launch_bounds__(256) void rec_chain_kernel(const RecChainArgs p) {
       if (tid < KG * own && it_rg < B)
         rc_store16(p.PanM + ((size_t)(vx * KG + it_j) * RC_PAN_ROWS + it_rg) * 8, hl + (it_rg - r0) * UW + it_j * 8);
     }
+    // (this tail and the one of the second phase below are written out on purpose: as cs_publish_arrive calls seven instantiations
+    // of this kernel come out reordered and <8, 3, 7, 2> with other opcode counts, which the rule of DESIGN.md section 4 does not admit)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     cs_arrive(p.bar + widx, fb + (unsigned)p.T);
@@ -537,7 +536,7 @@ __global__ __launch_bounds__(256) void rec_chain_bwd_kernel(const RecChainBwdArg
   if (role.master) { rc_master_loop(p.bar, nwx * (int)gridDim.y, fb, p.T - 1); return; }
   if (role.idle) return;
   const int rot = vx % NP;
-  auto k_of = [&](int pr, int hh) { int prr = pr + rot; prr = prr >= NP ? prr - NP : prr; return kw0 + (prr * 2 + hh) * 32; };
+  auto k_of = [&](int pr, int hh) { return ct_k_of<NP>(kw0, rot, pr, hh); };
 
   bf16x8 wb[KREG > 0 ? KREG : 1][CG];
 #pragma unroll
@@ -671,11 +670,7 @@ __global__ __launch_bounds__(256) void rec_chain_bwd_kernel(const RecChainBwdArg
         rc_store16(p.Pan + (size_t)s * pan_t + ((size_t)(it_col[j] >> 3) * RC_PAN_ROWS + it_rg[j]) * 8, it_src[j]);
       }
     const bool more = s + 1 < p.T;
-    if (more) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      cs_arrive(p.bar + widx, fb + (unsigned)(s + 1));
-    }
+    if (more) cs_publish_arrive(p.bar + widx, fb + (unsigned)(s + 1));
     // ---- off the critical path: the row-major copy for the deferred weight-gradient GEMMs
     bf16_t* Gt = p.dG + (size_t)t * Bs * p.ld_dg;
 #pragma unroll
