@@ -21,7 +21,7 @@ extern "C" {
 #endif
 
 /* 12 still: recnet_beam_select_rows_constrained / recnet_beam_search_nbest_constrained, and after them
- * recnet_beam_select_rows_diverse / recnet_beam_search_nbest_diverse, and recnet_consensus_rows, and the three ensemble entries (recnet_ensemble_mix_rows, recnet_beam_search_nbest_ensemble, recnet_score_captions_ensemble), were added without changing any existing entry.  A library built before them is still caught: a binding that resolves every declared symbol fails on the first one missing. */
+ * recnet_beam_select_rows_diverse / recnet_beam_search_nbest_diverse, and recnet_consensus_rows, and the three ensemble entries (recnet_ensemble_mix_rows, recnet_beam_search_nbest_ensemble, recnet_score_captions_ensemble), and the three stochastic beam search entries (recnet_sbs_select_rows, recnet_stochastic_beam_search, recnet_stochastic_beam_search_ensemble), were added without changing any existing entry.  A library built before them is still caught: a binding that resolves every declared symbol fails on the first one missing. */
 #define RECNET_ABI_VERSION 12
 #define RECNET_ATTN_NONE 0
 #define RECNET_ATTN_SOFTMAX 1
@@ -366,6 +366,42 @@ int recnet_beam_search_nbest_ensemble(recnet_handle* const* hs, int32_t M, const
 int recnet_score_captions_ensemble(recnet_handle* const* hs, int32_t M, const float* weights, int32_t mode, const float* enc,
                                    const int64_t* tokens, int32_t T, float* logprobs_out, float* caption_logprob_out, int32_t* length_out,
                                    void* stream);
+
+/* ---- Stochastic beam search (Kool, van Hoof, Welling 2019; no counterpart in the reference; added at
+ * version 12 without changing any existing entry): beam_width captions per video drawn WITHOUT replacement from the model's
+ * sequence distribution at the given temperature, in one search of that width.  A hypothesis carries phi, its log-probability (the
+ * cum of recnet_beam_search_nbest), and G, its perturbed score; the start hypothesis has phi = G = 0.
+ * recnet_sbs_select_rows: one selection step on caller-supplied device arrays.  logits [nb][rows][V] contiguous, read only; cum,
+ * gum [nb][rows] float (phi and G); finished [nb][rows] int32.  A live hypothesis i of row r offers every v with
+ *   phi_v = cum[i][r] + log_softmax(logits[i][r] / temperature)[v]     (the formulas of recnet_logprob_rows, bit for bit)
+ *   Gt_v  = phi_v + g_v, g_v the Gumbel of recnet_sample_rows on the counter ((t * beam_width * rows + i * rows + r) * V + v) mod 2^32
+ *   Ghat_v = -log(exp(-gum[i][r]) - exp(-max_v Gt_v) + exp(-Gt_v))     (in double from the fp32 inputs, rounded to fp32)
+ * so that the largest Ghat of a parent is the parent's G exactly; a finished one (finished != 0) offers v = <PAD> (0) at
+ * (cum[i][r], gum[i][r]) without noise and -inf at every other v.  vals_out / gum_out / idx_out [rows][beam_width]: phi, Ghat and
+ * idx = i * V + v of the beam_width largest Ghat in descending order, the lowest idx first among equal values.  1 <= nb <= 8,
+ * 1 <= beam_width <= min(8, V), temperature positive and finite, t >= 0.  One launch, no score array, no atomics: two calls give
+ * the same bits.  The handle supplies the device only, as for recnet_beam_select_rows.
+ * recnet_stochastic_beam_search: the loop of recnet_beam_search_nbest (one batched decode step for all hypotheses, only <EOS>
+ * finishes, the same n_steps_out and fixed trip count) with the selection above at every step t, beam_width the search's width in
+ * the counter at step 0 too.  Rank = slot: G descending, the lowest slot among equals.  Rank 0 is an exact sample from the model,
+ * ranks 0 .. beam_width - 1 a sample without replacement; with beam_width = 1 the counters are those of
+ * recnet_sample_search(temperature, top_k = 0, seed).  tokens_out [beam_width][caption_max_len+1][B] int64, rank-major and canonical
+ * like recnet_beam_search_nbest's; cum_out (phi) / gum_out (G) [beam_width][B] float; len_out [beam_width][B] int32.  A hypothesis
+ * that reaches caption_max_len + 1 tokens without <EOS> is a PREFIX: its cum is the probability of the prefix, not of a caption.
+ * recnet_score_captions at the same temperature reproduces cum and len.  No top-k / top-p cut, constraints or groups: they change
+ * the distribution the conditioning assumes.
+ * recnet_stochastic_beam_search_ensemble: the same search on the ensemble's logits (hs, M, weights, mode as for
+ * recnet_beam_search_nbest_ensemble; M = 1 launches what the single-model entry launches and returns its bits).
+ * RECNET_EINVAL before any launch: a NULL pointer, beam_width outside [1, min(8, V)], temperature not positive and finite, the
+ * refusals of the ensemble entries; RECNET_ESTATE: decoder not bound. */
+int recnet_sbs_select_rows(recnet_handle* h, const float* logits, const float* cum, const float* gum, const int32_t* finished, int32_t nb,
+                           int32_t rows, int32_t V, int32_t beam_width, float temperature, uint32_t seed, int32_t t, float* vals_out,
+                           float* gum_out, int32_t* idx_out, void* stream);
+int recnet_stochastic_beam_search(recnet_handle* h, const float* enc, int32_t beam_width, float temperature, uint32_t seed,
+                                  int64_t* tokens_out, float* cum_out, int32_t* len_out, float* gum_out, int32_t* n_steps_out, void* stream);
+int recnet_stochastic_beam_search_ensemble(recnet_handle* const* hs, int32_t M, const float* weights, int32_t mode, const float* enc,
+                                           int32_t beam_width, float temperature, uint32_t seed, int64_t* tokens_out, float* cum_out,
+                                           int32_t* len_out, float* gum_out, int32_t* n_steps_out, void* stream);
 
 /* ---- Consensus (minimum-Bayes-risk) scoring of hypotheses against a reference set by n-gram overlap (no counterpart in the
  * reference; added at version 12 without changing any existing entry).

@@ -15,6 +15,7 @@ Host-side mirror of the reference interface for the hot path:
   (no counterpart) diverse (group) beams     -> the same two with n_groups / diversity_penalty, search.nbest_diversity
   (no counterpart) consensus (MBR) reranking -> search.consensus_scores, best_of_n / best_of_beam with consensus_weight
   (no counterpart) ensemble decoding         -> search.Ensemble in place of the decoder, search.ensemble_logits
+  (no counterpart) stochastic beam search    -> search.stochastic_beam_search, search.sbs_weights, best_of_n(distinct=True)
 All compute goes through csrc/librecnet_hip.so (C ABI: include/recnet_hip.h).
 """
 from .config import TrainConfig, make_config  # noqa: F401
@@ -25,6 +26,6 @@ from .api import (build_decoder, build_reconstructor, forward_decoder, forward_g
 from .dp import DataParallelTrainStep, shard_bounds  # noqa: F401
 from .search import (greedy_search, beam_search, sample_search, sequence_logprob, score_captions, best_of_n,  # noqa: F401
                      pick_best_of_n, canonical_captions, reconstruction_errors, beam_search_nbest, best_of_beam, nbest_diversity,
-                     consensus_scores, Ensemble, ensemble_logits)
+                     consensus_scores, Ensemble, ensemble_logits, stochastic_beam_search, sbs_weights)
 from .loop import Trainer, evaluate, perplexity  # noqa: F401
 from .checkpoint import save_checkpoint, load_checkpoint, read_checkpoint  # noqa: F401

@@ -173,6 +173,11 @@ EXPORTS["recnet_ensemble_mix_rows"] = (_i, [C.c_void_p, C.POINTER(C.c_void_p), _
 EXPORTS["recnet_beam_search_nbest_ensemble"] = (_i, [C.POINTER(C.c_void_p), _i, C.POINTER(_f), _i, C.c_void_p, _i, _f, _i, _f, _i, _i,
                                                       C.POINTER(_i), _i] + [C.c_void_p] * 7)
 EXPORTS["recnet_score_captions_ensemble"] = (_i, [C.POINTER(C.c_void_p), _i, C.POINTER(_f), _i, C.c_void_p, C.c_void_p, _i] + [C.c_void_p] * 4)
+# stochastic beam search
+EXPORTS["recnet_sbs_select_rows"] = (_i, [C.c_void_p] * 5 + [_i, _i, _i, _i, _f, C.c_uint32, _i] + [C.c_void_p] * 4)
+EXPORTS["recnet_stochastic_beam_search"] = (_i, [C.c_void_p, C.c_void_p, _i, _f, C.c_uint32] + [C.c_void_p] * 6)
+EXPORTS["recnet_stochastic_beam_search_ensemble"] = (_i, [C.POINTER(C.c_void_p), _i, C.POINTER(_f), _i, C.c_void_p, _i, _f, C.c_uint32]
+                                                     + [C.c_void_p] * 6)
 EXPORTS["recnet_logprob_rows"] =(_i, [C.c_void_p, C.c_void_p, C.c_void_p, _i, _i, _f, C.c_void_p, C.c_void_p])
 EXPORTS["recnet_score_captions"] = (_i, [C.c_void_p, C.c_void_p, C.c_void_p, _i, _f, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
 EXPORTS["recnet_reconstruction_error"] = (_i, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _i, C.c_void_p, C.c_void_p, C.c_void_p])

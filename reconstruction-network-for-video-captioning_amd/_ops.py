@@ -14,7 +14,7 @@ OP_NAMES = ("forward_decoder", "forward_decoder_free", "backward_decoder", "forw
             "reconstruction_error", "beam_search_nbest", "beam_select_rows", "beam_search_nbest_constrained",
             "beam_select_rows_constrained", "sample_search_nucleus", "sample_rows_nucleus", "beam_search_nbest_diverse",
             "beam_select_rows_diverse", "consensus_rows", "ensemble_mix_rows", "beam_search_nbest_ensemble",
-            "score_captions_ensemble")
+            "score_captions_ensemble", "sbs_select_rows", "stochastic_beam_search", "stochastic_beam_search_ensemble")
 _loaded = False
 
 

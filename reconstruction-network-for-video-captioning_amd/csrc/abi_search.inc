@@ -701,6 +701,95 @@ int recnet_beam_search_nbest(recnet_handle* h, const float* enc, int32_t beam_wi
                                               n_steps_out, stream);
 }
 
+// ---- stochastic beam search (the reference has no counterpart; DESIGN.md section 21): bw captions per video drawn without
+// replacement from the model's sequence distribution, in one search of width bw
+static int check_sbs(int beam_width, int V, float temperature) {
+  if (beam_width < 1 || beam_width > 8 || beam_width > V) return fail(RECNET_EINVAL, "beam_width must be in [1, min(8, V)]");
+  if (!(temperature > 0.f) || !std::isfinite(temperature)) return fail(RECNET_EINVAL, "temperature must be positive and finite");
+  return RECNET_OK;
+}
+// one selection step: (phi, G, finished) [nb][rows] and logits [nb][rows][V] into vals = phi, gum_out = G, idx [rows][bw]
+static void launch_sbs_select(const float* logits, const float* cum, const float* gum, const int32_t* fin, int nb, int rows, int V, int bw,
+                              float temperature, uint32_t seed, int t, float* vals, float* gum_out, int32_t* idx, hipStream_t st) {
+  SbsSelArgs a;
+  a.x = logits; a.cum = cum; a.gum = gum; a.fin = fin; a.nb = nb; a.rows = rows; a.V = V; a.t = t;
+  a.temp = temperature; a.key = rn_site_key(seed, RN_SITE_SAMPLE); a.vals = vals; a.gum_out = gum_out; a.idx = idx;
+#define RN_SBS(W) case W: hipLaunchKernelGGL((sbs_select_kernel<W>), dim3(rows), dim3(256), 0, st, a); break;
+  switch (bw) { RN_SBS(1) RN_SBS(2) RN_SBS(3) RN_SBS(4) RN_SBS(5) RN_SBS(6) RN_SBS(7) RN_SBS(8) }
+#undef RN_SBS
+}
+
+int recnet_sbs_select_rows(recnet_handle* h, const float* logits, const float* cum, const float* gum, const int32_t* finished, int32_t nb,
+                           int32_t rows, int32_t V, int32_t beam_width, float temperature, uint32_t seed, int32_t t, float* vals_out,
+                           float* gum_out, int32_t* idx_out, void* stream) {
+  REQUIRE_WS(h);
+  if (!logits || !cum || !gum || !finished || !vals_out || !gum_out || !idx_out) return fail(RECNET_EINVAL, "null argument");
+  if (rows < 1 || V < 1 || nb < 1 || nb > 8 || t < 0) return fail(RECNET_EINVAL, "rows and V must be positive, nb in [1, 8], t non-negative");
+  if ((long)nb * V > 0x7fffffffL) return fail(RECNET_EINVAL, "nb * V must fit an int32 index");
+  int r = check_sbs(beam_width, V, temperature); if (r) return r;
+  launch_sbs_select(logits, cum, gum, finished, nb, rows, V, beam_width, temperature, seed, t, vals_out, gum_out, idx_out, (hipStream_t)stream);
+  LAUNCH_OK();
+  return RECNET_OK;
+}
+
+// beam_search_nbest_run's loop with the stochastic selection: the same batched step, regather (which carries G beside phi), member
+// regathers and stop rule; no constraints, no groups.  The slots leave every step in rank order, so the outputs are the slots.
+static void sbs_run(recnet_handle* const* hs, const EnsMix& mix, const float* enc, int bw, float temperature, uint32_t seed,
+                    int64_t* tokens_out, float* cum_out, int32_t* len_out, float* gum_out, int32_t* n_steps_out, hipStream_t st) {
+  recnet_handle* h = hs[0];
+  const int B = h->B, V = h->V, Tm = h->Tm, M = mix.M;
+  const float* x[ENS_MAX_M];
+  for (int m = 0; m < M; ++m) { search_begin(hs[m], enc, n_steps_out, m == 0 ? 0 : -1, st); x[m] = hs[m]->sr_scores; }
+  hipMemsetAsync(h->sr_gum[0], 0, (size_t)B * 4, st);
+  int cur = 0, nb = 1;
+  for (int t = 0; t < Tm; ++t) {
+    for (int m = 0; m < M; ++m) {
+      recnet_handle* g = hs[m];
+      dec_step(g, nb * B, B, dec_rows_beams(g), h->sr_tok[cur], g->sr_h[cur], g->sr_c[cur], g->sr_scores, g->sr_hn, g->sr_cn, 0, t, st);
+    }
+    if (M > 1) launch_ensemble_mix(mix, x, nb * B, V, h->sr_scores, st);
+    launch_sbs_select(h->sr_scores, h->sr_cum[cur], h->sr_gum[cur], h->sr_eos[cur], nb, B, V, bw, temperature, seed, t, h->sr_vals,
+                      h->sr_gvals, h->sr_idx, st);
+    BeamUpdArgs u = beam_update_args(h, bw, t, cur, nullptr);
+    u.gum_vals = h->sr_gvals; u.gum_new = h->sr_gum[cur ^ 1];
+    hipLaunchKernelGGL(beam_update_kernel<true>, dim3(bw, B), dim3(128), 0, st, u);
+    for (int m = 1; m < M; ++m) {
+      recnet_handle* g = hs[m];
+      hipLaunchKernelGGL(beam_regather_state_kernel, dim3(bw, B), dim3(128), 0, st, (const int32_t*)h->sr_idx, B, g->H, V, bw,
+                         (const float*)g->sr_hn, (const float*)(g->dgru ? nullptr : g->sr_cn), g->sr_h[cur ^ 1], g->sr_c[cur ^ 1]);
+    }
+    hipLaunchKernelGGL(search_stop_kernel, dim3(1), dim3(256), 0, st, (const int64_t*)nullptr, h->sr_eos[cur ^ 1], bw * B, t, n_steps_out);
+    cur ^= 1; nb = bw;
+  }
+  search_end(h, n_steps_out, st);
+  hipLaunchKernelGGL(sbs_finish_kernel, dim3(cdiv(bw * B, 256)), dim3(256), 0, st, (const float*)h->sr_cum[cur], (const float*)h->sr_gum[cur],
+                     (const int32_t*)h->sr_eos[cur], (const int32_t*)n_steps_out, B, bw, cum_out, len_out, gum_out, h->bs_order);
+  hipLaunchKernelGGL(beam_gather_kernel, dim3(cdiv(bw * Tm * B, 256)), dim3(256), 0, st, h->sr_hist[cur], h->bs_order, tokens_out,
+                     B, Tm, bw);
+}
+
+int recnet_stochastic_beam_search(recnet_handle* h, const float* enc, int32_t beam_width, float temperature, uint32_t seed,
+                                  int64_t* tokens_out, float* cum_out, int32_t* len_out, float* gum_out, int32_t* n_steps_out, void* stream) {
+  int r = search_check(h, enc && tokens_out && cum_out && len_out && gum_out && n_steps_out); if (r) return r;
+  r = check_sbs(beam_width, h->V, temperature); if (r) return r;
+  sbs_run(&h, EnsMix(), enc, beam_width, temperature, seed, tokens_out, cum_out, len_out, gum_out, n_steps_out, (hipStream_t)stream);
+  LAUNCH_OK();
+  return RECNET_OK;
+}
+
+int recnet_stochastic_beam_search_ensemble(recnet_handle* const* hs, int32_t M, const float* weights, int32_t mode, const float* enc,
+                                           int32_t beam_width, float temperature, uint32_t seed, int64_t* tokens_out, float* cum_out,
+                                           int32_t* len_out, float* gum_out, int32_t* n_steps_out, void* stream) {
+  int r = check_ens_members(hs, M); if (r) return r;
+  EnsMix mix;
+  r = check_ens_mix(M, weights, mode, &mix); if (r) return r;
+  if (!(enc && tokens_out && cum_out && len_out && gum_out && n_steps_out)) return fail(RECNET_EINVAL, "null argument");
+  r = check_sbs(beam_width, hs[0]->V, temperature); if (r) return r;
+  sbs_run(hs, mix, enc, beam_width, temperature, seed, tokens_out, cum_out, len_out, gum_out, n_steps_out, (hipStream_t)stream);
+  LAUNCH_OK();
+  return RECNET_OK;
+}
+
 // recnet_score_captions over the members: score_logits of each, one mix over the T * B rows into member 0's, then the row kernel at
 // temperature 1 and the per-caption sums, unchanged.  One member: the kernels of recnet_score_captions at temperature 1.
 int recnet_score_captions_ensemble(recnet_handle* const* hs, int32_t M, const float* weights, int32_t mode, const float* enc,

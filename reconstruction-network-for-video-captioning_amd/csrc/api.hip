@@ -126,6 +126,7 @@ struct recnet_handle {
   float *sr_logits, *sr_scores, *sr_h[2], *sr_c[2], *sr_hn, *sr_cn, *sr_cum[2], *sr_vals;
   int64_t *sr_tok[2], *sr_hist[2]; int32_t *sr_eos[2], *sr_idx;
   void *bs_emb = nullptr, *bs_hlp = nullptr; float* bs_Xe = nullptr; int32_t* bs_order = nullptr;   // recnet_beam_search_nbest
+  float *sr_gum[2] = {nullptr, nullptr}, *sr_gvals = nullptr;   // recnet_stochastic_beam_search: the perturbed scores [8][B] beside sr_cum, [B][8] beside sr_vals
   int64_t* in_tok = nullptr;   // [Tm][B] tokens fed by the last free-running forward (its backward scatters the embedding gradient by them)
   int free_fwd = 0;
   size_t gws_floats, slab_floats;
@@ -365,6 +366,9 @@ static size_t carve(recnet_handle* h, char* base) {
     o.d_pnorm = take(16);
     o.d_gnorm = take(16);
   }
+  // the stochastic beam search's perturbed scores (behind everything else: no older buffer moves)
+  for (int i = 0; i < 2; ++i) h->sr_gum[i] = take(8 * B);
+  h->sr_gvals = take(8 * B);
   return off;
 }
 

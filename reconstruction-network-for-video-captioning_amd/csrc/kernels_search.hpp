@@ -339,6 +339,8 @@ struct BeamUpdArgs {
   const int32_t* eos_old; const int64_t* hist_old;       // [nb_old][B], [nb_old][B][Tm]
   float* h_new; float* c_new; float* cum_new; int32_t* eos_new; int64_t* hist_new; int64_t* tok_new;
   const int32_t* n_steps;                                // reference search only; != 0: the search already stopped (eval.py:116)
+  const float* gum_vals = nullptr; float* gum_new = nullptr;   // stochastic beam search only (section 21): the perturbed scores [B][bw] of
+                                                         // the selection, regathered beside cum into [bw][B]; null everywhere else
 };
 template <bool NBEST> __global__ __launch_bounds__(128) void beam_update_kernel(const BeamUpdArgs p) {
   const int k = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
@@ -356,6 +358,7 @@ template <bool NBEST> __global__ __launch_bounds__(128) void beam_update_kernel(
   if (tid == 0) {
     const int e = p.eos_old[so];
     p.cum_new[dn] = p.vals[b * p.bw + k];
+    if (NBEST && p.gum_new) p.gum_new[dn] = p.gum_vals[b * p.bw + k];
     p.eos_new[dn] = NBEST ? (e ? e : (tok == 2 ? p.t + 1 : 0)) : (tok == 2 ? p.t : e);
     p.tok_new[dn] = tok;
   }
@@ -667,6 +670,138 @@ __global__ __launch_bounds__(256) void beam_nbest_rank_kernel(const float* __res
     const int f = fin[bi * B + b];
     cum_out[r * B + b] = cum[bi * B + b]; len_out[r * B + b] = f ? f : ns; score_out[r * B + b] = best; order[r * B + b] = bi;
   }
+}
+
+// ---- stochastic beam search (Kool, van Hoof, Welling 2019, "Stochastic Beams and Where to Find Them"; the reference has no
+// counterpart; DESIGN.md section 21 states the definition, tests/sbs_ref.py restates it): Gumbel-top-k over whole sequences, done
+// lazily inside a beam search.  A hypothesis carries phi (its log-probability, the cum of section 11) and G (its perturbed score).  A
+// live hypothesis i offers every v at phi_v = phi_i + log_softmax(x_i / temp)[v]; Gt_v = phi_v + g_v with the Gumbel of section 8 on
+// the counter ((t * bw * rows + i * rows + r) * V + v) mod 2^32; the maximum Z_i of the Gt_v is conditioned to be G_i:
+//   Ghat_v = -log(exp(-G_i) - exp(-Z_i) + exp(-Gt_v))
+// and the bw largest Ghat of the caption become the new hypotheses.  A finished hypothesis offers <PAD> at (phi_i, G_i), no noise.
+struct SbsSelArgs {
+  const float* x;                      // logits [nb][rows][V], read only
+  const float* cum; const float* gum;  // [nb][rows]: phi and G of the hypotheses
+  const int32_t* fin;                  // [nb][rows], != 0: the hypothesis is finished
+  int nb, rows, V, t;
+  float temp; uint32_t key;            // key = rn_site_key(seed, RN_SITE_SAMPLE)
+  float* vals; float* gum_out; int32_t* idx;   // [rows][BW], Ghat descending; vals = phi, idx = i * V + v
+};
+// The transform (G_i, Gt_v, Z_i) -> Ghat_v in double, in the form that neither cancels nor overflows: with a = Gt - Z <= 0,
+// l = log(1 - exp(a)) by the branch that is accurate on either side of -ln 2, w = G - Gt + l, Ghat = G - softplus(w).  a = 0 (the
+// parent's best child): l = w = -inf and Ghat = G exactly.
+__device__ __forceinline__ double sbs_condition(double G, double Gt, double Z) {
+  const double a = Gt - Z;
+  const double l = a > -0.6931471805599453 ? log(-expm1(a)) : log1p(-exp(a));
+  const double w = G - Gt + l;
+  if (w == -INFINITY) return G;
+  return G - fmax(0.0, w) - log1p(exp(-fabs(w)));
+}
+// beam_select_kernel's launch shape: one workgroup of 256 per caption.  Within one parent Ghat is increasing in Gt, so the overall
+// top BW lie among each parent's top BW by Gt: one pass of noise per candidate is enough.  (1) Row statistics of x / temp per live
+// hypothesis, logprob_rows_kernel's formulas and summation order (a division by 1.0f is exact: temperature 1 keeps beam_select_kernel's
+// bits).  (2) Per live parent: the per-thread best-BW walk of beam_select_kernel on bs_pack(Gt_v, i * V + v), the Gumbel hashed and
+// formed here, once per candidate; then BW arg-max rounds put the parent's BW best (Gt, flat index) into an LDS table, in order: the
+// first is Z_i.  A finished parent writes its single entry (and, so that -inf fills a caption that has fewer than BW candidates, its
+// next BW - 1 tokens at -inf) without a walk.  (3) Wave 0: lane l owns table entry l (nb * BW <= 64), forms its Ghat in double from
+// the fp32 inputs — the one pass through the double-precision code of the launch — rounds it to fp32, and BW butterfly rounds
+// pick the largest by (value, lowest flat index); the owner recomputes phi from its row with beam_select_kernel's expression and
+// writes the three outputs.  No score array, no atomics: two calls give the same bits.
+template <int BW> __global__ __launch_bounds__(256) void sbs_select_kernel(const SbsSelArgs p) {
+  __shared__ float sf[4]; __shared__ float s_mx[8], s_ls[8], s_z[8]; __shared__ unsigned long long wc[2][4];
+  __shared__ float t_gt[64]; __shared__ int t_idx[64];
+  const int r = blockIdx.x, tid = threadIdx.x, V = p.V, nb = p.nb;
+  const int lane = tid & 63, wave = tid >> 6;
+  for (int i = 0; i < nb; ++i) {                                         // (1)
+    if (p.fin[i * p.rows + r]) continue;                                 // (uniform over the workgroup)
+    const float* x = p.x + ((size_t)i * p.rows + r) * V;
+    float mx = -INFINITY, sum = 0.f;
+    for (int v = tid; v < V; v += 256) mx = fmaxf(mx, x[v] / p.temp);
+    mx = block_max256(mx, sf);
+    for (int v = tid; v < V; v += 256) sum += rn_exp(x[v] / p.temp - mx);
+    sum = block_sum256(sum, sf);
+    if (tid == 0) { s_mx[i] = mx; s_ls[i] = logf(sum); }
+  }
+  if (tid < 64) { t_gt[tid] = -INFINITY; t_idx[tid] = -1; }              // -1: no entry
+  __syncthreads();
+  int rd = 0;                                                            // arg-max rounds so far: wc's two buffers alternate across parents
+  for (int i = 0; i < nb; ++i) {                                         // (2)
+    const float c = p.cum[i * p.rows + r];
+    if (p.fin[i * p.rows + r] != 0) {                                    // (uniform over the workgroup)
+      if (tid < BW && tid < V) { t_gt[i * BW + tid] = tid == 0 ? p.gum[i * p.rows + r] : -INFINITY; t_idx[i * BW + tid] = i * V + tid; }
+      continue;
+    }
+    const float* x = p.x + ((size_t)i * p.rows + r) * V;
+    const float mx = s_mx[i], ls = s_ls[i];
+    const uint32_t base = (((uint32_t)p.t * (uint32_t)BW + (uint32_t)i) * (uint32_t)p.rows + (uint32_t)r) * (uint32_t)V;
+    unsigned long long lc[BW];
+#pragma unroll
+    for (int k = 0; k < BW; ++k) lc[k] = 0ull;
+    for (int v = tid; v < V; v += 256) {
+      const float phi = c + ((x[v] / p.temp - mx) - ls);
+      const uint32_t h = rn_fmix32((base + (uint32_t)v) * 0x9E3779B1u + p.key);
+      const float u = ((float)(h >> 9) + 0.5f) * 0x1p-23f;               // exact in fp32, inside (0, 1)
+      const float gt = phi - logf(-logf(u));
+      unsigned long long e = bs_pack(gt, i * V + v);
+      if (e > lc[BW - 1]) {
+#pragma unroll
+        for (int k = 0; k < BW; ++k)
+          if (e > lc[k]) { const unsigned long long d = lc[k]; lc[k] = e; e = d; }
+      }
+    }
+    for (int k = 0; k < BW; ++k, ++rd) {
+      BS_ARGMAX_ROUND(rd)
+      if (e != 0ull && lc[0] == e) {           // (candidates are distinct: their indices are)
+#pragma unroll
+        for (int q = 0; q + 1 < BW; ++q) lc[q] = lc[q + 1];
+        lc[BW - 1] = 0ull;
+      }
+      if (tid == 0 && e != 0ull) {             // (e == 0: fewer than BW candidates compared, NaN-free inputs never get here)
+        t_gt[i * BW + k] = bs_value(e); t_idx[i * BW + k] = bs_index(e);
+        if (k == 0) s_z[i] = bs_value(e);
+      }
+    }
+  }
+  __syncthreads();
+  if (wave != 0) return;                                                 // (3)  (no barrier follows)
+  unsigned long long ent = 0ull; float gh = -INFINITY; int flat = -1, pi = 0;
+  if (lane < nb * BW) {
+    flat = t_idx[lane]; pi = lane / BW;
+    if (flat >= 0) {
+      const float gt = t_gt[lane];
+      gh = p.fin[pi * p.rows + r] != 0 ? gt : (float)sbs_condition((double)p.gum[pi * p.rows + r], (double)gt, (double)s_z[pi]);
+      ent = bs_pack(gh, flat);
+    }
+  }
+  for (int k = 0; k < BW; ++k) {
+    unsigned long long e = ent;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const unsigned long long d = __shfl_xor(e, o);
+      e = d > e ? d : e;
+    }
+    const size_t o = (size_t)r * BW + k;
+    if (e != 0ull && ent == e) {               // (entries are distinct: their flat indices are) the one lane that owns the winner
+      const int v = flat - pi * V;
+      const float c = p.cum[pi * p.rows + r];
+      const bool fin = p.fin[pi * p.rows + r] != 0;
+      p.vals[o] = fin ? (v == 0 ? c : -INFINITY) : c + ((p.x[((size_t)pi * p.rows + r) * V + v] / p.temp - s_mx[pi]) - s_ls[pi]);
+      p.gum_out[o] = gh; p.idx[o] = flat;
+      ent = 0ull;
+    }
+    if (e == 0ull && lane == 0) { p.vals[o] = -INFINITY; p.gum_out[o] = -INFINITY; p.idx[o] = 0; }
+  }
+}
+// the outputs of the stochastic beam search, one thread per (rank, caption): the slots after the last step are in rank order (G
+// descending, the lowest slot among equals), so rank r is slot r; len = fin, or n_steps without an <EOS>; order = the identity
+__global__ __launch_bounds__(256) void sbs_finish_kernel(const float* __restrict__ cum, const float* __restrict__ gum,
+                                                         const int32_t* __restrict__ fin, const int32_t* __restrict__ n_steps, int B, int bw,
+                                                         float* __restrict__ cum_out, int32_t* __restrict__ len_out,
+                                                         float* __restrict__ gum_out, int32_t* __restrict__ order) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= bw * B) return;
+  const int f = fin[i];
+  cum_out[i] = cum[i]; gum_out[i] = gum[i]; len_out[i] = f ? f : *n_steps; order[i] = i / B;
 }
 
 // ---- ensemble decoding: the rows of M decoders mixed into one row of logits (the reference has no counterpart; DESIGN.md section 19

@@ -20,6 +20,7 @@
 //   reconstruction_error                                per-caption reconstruction error and the reconstruction (train.py:96-102 / :125-128, eval mode)
 //   consensus_rows                                      n-gram consensus (minimum-Bayes-risk) utilities of hypotheses against a reference set (no counterpart; section 16)
 //   ensemble_mix_rows, beam_search_nbest_ensemble, score_captions_ensemble   N-best beam search and scoring over several decoders (no counterpart; section 19)
+//   sbs_select_rows, stochastic_beam_search, stochastic_beam_search_ensemble   stochastic beam search: sampled captions without replacement (no counterpart; section 21)
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
 #include <torch/library.h>
@@ -501,6 +502,57 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> score_captions_ensemble(int64_t h
                                     stream()), "score_captions_ensemble");
   return {lps, cap, len};
 }
+// ---- stochastic beam search.  logits [nb, rows, V], cum / gum [nb, rows] float, finished [nb, rows] int32 ->
+// vals (phi), gum_out (G) [rows, beam_width] float, idx [rows, beam_width] int32
+std::tuple<at::Tensor, at::Tensor, at::Tensor> sbs_select_rows(int64_t h, const at::Tensor& logits, const at::Tensor& cum, const at::Tensor& gum,
+                                                               const at::Tensor& finished, int64_t beam_width, double temperature, int64_t seed,
+                                                               int64_t t) {
+  chk(logits, at::kFloat, "logits"); chk(cum, at::kFloat, "cum"); chk(gum, at::kFloat, "gum"); chk(finished, at::kInt, "finished");
+  TORCH_CHECK(logits.dim() == 3 && logits.size(0) >= 1 && logits.size(1) >= 1 && logits.size(2) >= 1 && logits.size(1) <= INT32_MAX &&
+              logits.size(2) <= INT32_MAX && logits.size(0) <= 8, "recnet: logits must be [nb <= 8, rows, V], got ", logits.sizes());
+  shape(cum, {logits.size(0), logits.size(1)}, "cum"); shape(gum, {logits.size(0), logits.size(1)}, "gum");
+  shape(finished, {logits.size(0), logits.size(1)}, "finished");
+  TORCH_CHECK(beam_width >= 1 && beam_width <= 8 && beam_width <= logits.size(2), "recnet: beam_width must be in [1, min(8, V)], got ", beam_width);
+  TORCH_CHECK(t >= 0 && t <= INT32_MAX, "recnet: t out of range");
+  auto vals = at::empty({logits.size(1), beam_width}, logits.options()), gout = at::empty({logits.size(1), beam_width}, logits.options());
+  auto idx = at::empty({logits.size(1), beam_width}, logits.options().dtype(at::kInt));
+  ok(recnet_sbs_select_rows(H(h), logits.data_ptr<float>(), cum.data_ptr<float>(), gum.data_ptr<float>(), finished.data_ptr<int32_t>(),
+                            (int32_t)logits.size(0), (int32_t)logits.size(1), (int32_t)logits.size(2), (int32_t)beam_width, (float)temperature,
+                            (uint32_t)seed, (int32_t)t, vals.data_ptr<float>(), gout.data_ptr<float>(), idx.data_ptr<int32_t>(), stream()),
+     "sbs_select_rows");
+  return {vals, gout, idx};
+}
+// tokens [beam_width, Tm, B] rank-major, cum / gum [beam_width, B] float, len [beam_width, B] int32, n_steps [1] int32; hs empty:
+// the single-model entry (the width is checked here before the outputs are allocated and zeroed; the temperature by the library)
+using SbsOut = std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor>;
+static SbsOut sbs_impl(int64_t h, const std::vector<recnet_handle*>& hs, const std::vector<float>& w, int64_t mode, const at::Tensor& enc,
+                       int64_t beam_width, double temperature, int64_t seed) {
+  chk_enc(h, enc);
+  TORCH_CHECK(beam_width >= 1 && beam_width <= 8 && beam_width <= dim(h, RECNET_DIM_V), "recnet: beam_width must be in [1, min(8, V)], got ", beam_width);
+  const int64_t B = enc.size(0);
+  auto toks = at::zeros({beam_width, dim(h, RECNET_DIM_TM), B}, enc.options().dtype(at::kLong));
+  auto cum = at::zeros({beam_width, B}, enc.options()), gum = at::zeros({beam_width, B}, enc.options());
+  auto len = at::zeros({beam_width, B}, enc.options().dtype(at::kInt));
+  auto n = at::zeros({1}, enc.options().dtype(at::kInt));
+  if (hs.empty())
+    ok(recnet_stochastic_beam_search(H(h), enc.data_ptr<float>(), (int32_t)beam_width, (float)temperature, (uint32_t)seed, toks.data_ptr<int64_t>(),
+                                     cum.data_ptr<float>(), len.data_ptr<int32_t>(), gum.data_ptr<float>(), n.data_ptr<int32_t>(), stream()),
+       "stochastic_beam_search");
+  else
+    ok(recnet_stochastic_beam_search_ensemble(hs.data(), (int32_t)hs.size(), w.data(), (int32_t)mode, enc.data_ptr<float>(), (int32_t)beam_width,
+                                              (float)temperature, (uint32_t)seed, toks.data_ptr<int64_t>(), cum.data_ptr<float>(),
+                                              len.data_ptr<int32_t>(), gum.data_ptr<float>(), n.data_ptr<int32_t>(), stream()),
+       "stochastic_beam_search_ensemble");
+  return {toks, cum, len, gum, n};
+}
+SbsOut stochastic_beam_search(int64_t h, const at::Tensor& enc, int64_t beam_width, double temperature, int64_t seed) {
+  return sbs_impl(h, {}, {}, 0, enc, beam_width, temperature, seed);
+}
+SbsOut stochastic_beam_search_ensemble(int64_t h, at::IntArrayRef more_handles, at::ArrayRef<double> weights, int64_t mode, const at::Tensor& enc,
+                                       int64_t beam_width, double temperature, int64_t seed) {
+  const auto hs = ens_handles(h, more_handles);
+  return sbs_impl(h, hs, ens_weights(weights, hs.size()), mode, enc, beam_width, temperature, seed);
+}
 // ---- consensus scoring by n-gram overlap.  hyp [N_h, T_h, B] int64, ref [N_r, T_r, B] int64 or undefined
 // (the hypotheses are their own references), weights [N_r, B] float or undefined.  Returns util [N_h, B] double, sim [N_h, N_r, B]
 // double (want_sim) and counts [N_h, N_r, B, 4], q_hyp [N_h, B, 4], q_ref [N_r, B, 4], len_hyp [N_h, B], len_ref [N_r, B] int32
@@ -570,6 +622,9 @@ TORCH_LIBRARY(recnet, m) {
   m.def("ensemble_mix_rows(int handle, Tensor[] logits, float[] weights, int mode, bool in_place) -> Tensor y");
   m.def("beam_search_nbest_ensemble(int handle, int[] more_handles, float[] weights, int mode, Tensor encoder_outputs, int beam_width, float length_alpha, int n_groups, float diversity_penalty, int no_repeat_ngram, int min_length, int[] banned) -> (Tensor tokens, Tensor cum, Tensor lengths, Tensor score, Tensor group, Tensor n_steps)");
   m.def("score_captions_ensemble(int handle, int[] more_handles, float[] weights, int mode, Tensor? encoder_outputs, Tensor tokens) -> (Tensor logprobs, Tensor caption_logprob, Tensor lengths)");
+  m.def("sbs_select_rows(int handle, Tensor logits, Tensor cum, Tensor gum, Tensor finished, int beam_width, float temperature, int seed, int t) -> (Tensor vals, Tensor gum_out, Tensor idx)");
+  m.def("stochastic_beam_search(int handle, Tensor encoder_outputs, int beam_width, float temperature, int seed) -> (Tensor tokens, Tensor cum, Tensor lengths, Tensor gum, Tensor n_steps)");
+  m.def("stochastic_beam_search_ensemble(int handle, int[] more_handles, float[] weights, int mode, Tensor encoder_outputs, int beam_width, float temperature, int seed) -> (Tensor tokens, Tensor cum, Tensor lengths, Tensor gum, Tensor n_steps)");
   m.def("consensus_rows(int handle, Tensor hyp, Tensor? ref, Tensor? weights, float sigma, bool want_sim, bool want_counts) -> (Tensor util, Tensor sim, Tensor counts, Tensor q_hyp, Tensor q_ref, Tensor len_hyp, Tensor len_ref)");
 }
 
@@ -605,6 +660,9 @@ TORCH_LIBRARY_IMPL(recnet, CUDA, m) {
   m.impl("ensemble_mix_rows", ensemble_mix_rows);
   m.impl("beam_search_nbest_ensemble", beam_search_nbest_ensemble);
   m.impl("score_captions_ensemble", score_captions_ensemble);
+  m.impl("sbs_select_rows", sbs_select_rows);
+  m.impl("stochastic_beam_search", stochastic_beam_search);
+  m.impl("stochastic_beam_search_ensemble", stochastic_beam_search_ensemble);
 }
 TORCH_LIBRARY_IMPL(recnet, CompositeExplicitAutograd, m) {
   m.impl("add_reg_grad", add_reg_grad);

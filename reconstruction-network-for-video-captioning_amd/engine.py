@@ -545,6 +545,47 @@ class Engine:
                                                          _ptr(ln), _stream()), "recnet_score_captions_ensemble")
         return lps, cap, ln
 
+    # ------------------------------------------------------------------ stochastic beam search
+    def sbs_select_rows(self, logits, cum, gum, finished, beam_width, temperature=1.0, seed=0, t=0):
+        """One selection step of the stochastic beam search on caller-supplied device arrays (recnet_sbs_select_rows; no decoder
+        needed): logits [nb, rows, V] float32 (only read), cum / gum [nb, rows] float32 (the log-probability phi and the perturbed
+        score G of each hypothesis), finished [nb, rows] int32.  Returns (vals [rows, bw] float32 = phi, gum [rows, bw] float32 = G,
+        idx [rows, bw] int32 = i * V + v) of the bw largest conditioned perturbed scores, descending, the lowest idx first among
+        equals.  The library checks the width, the temperature and t."""
+        nb, rows, V, _, vals, idx = self._select_rows_args(logits, cum, finished, beam_width, None)
+        _chk_tensor(gum, (nb, rows), torch.float32, "gum")
+        gout = torch.empty_like(vals)
+        _lib.check(self.lib.recnet_sbs_select_rows(self.handle, _ptr(logits), _ptr(cum), _ptr(gum), _ptr(finished), nb, rows, V,
+                                                   int(beam_width), float(temperature), seed & 0xFFFFFFFF, int(t), _ptr(vals), _ptr(gout),
+                                                   _ptr(idx), _stream()), "recnet_sbs_select_rows")
+        return vals, gout, idx
+
+    def stochastic_beam_search(self, enc, beam_width, temperature=1.0, seed=0):
+        """Stochastic beam search (recnet_stochastic_beam_search): beam_width captions per video drawn without replacement from the
+        model's sequence distribution at `temperature`.  Returns device tensors (tokens [bw, Tm, B] int64 rank-major and canonical,
+        cum [bw, B] float32: the log-probability, len [bw, B] int32, gum [bw, B] float32: the perturbed score the ranks descend in,
+        n_steps int32[1]).  The library checks the width and the temperature before any launch of its own."""
+        return Engine.stochastic_beam_search_ensemble([self], enc, beam_width, temperature, seed)
+
+    @staticmethod
+    def stochastic_beam_search_ensemble(engines, enc, beam_width, temperature=1.0, seed=0, weights=None, mode="arithmetic"):
+        """stochastic_beam_search over the engines of an ensemble (recnet_stochastic_beam_search_ensemble; member 0 first); a list of
+        one engine without weights calls the single-model entry.  Returns that call's tensors."""
+        engines = list(engines)
+        e0 = engines[0]
+        toks, cum, ln, gum, _, n = e0._nbest_outputs(enc, beam_width)
+        if len(engines) == 1 and weights is None:
+            _lib.check(e0.lib.recnet_stochastic_beam_search(e0.handle, _ptr(enc), int(beam_width), float(temperature), seed & 0xFFFFFFFF,
+                                                            _ptr(toks), _ptr(cum), _ptr(ln), _ptr(gum), _ptr(n), _stream()),
+                       "recnet_stochastic_beam_search")
+            return toks, cum, ln, gum, n
+        w, md = Engine._ens_args(len(engines), weights, mode)
+        hs = (C.c_void_p * len(engines))(*[e.handle.value for e in engines])
+        _lib.check(e0.lib.recnet_stochastic_beam_search_ensemble(hs, len(engines), w, md, _ptr(enc), int(beam_width), float(temperature),
+                                                                 seed & 0xFFFFFFFF, _ptr(toks), _ptr(cum), _ptr(ln), _ptr(gum), _ptr(n),
+                                                                 _stream()), "recnet_stochastic_beam_search_ensemble")
+        return toks, cum, ln, gum, n
+
     def score_captions(self, enc, tokens, temperature=1.0):
         """Teacher-forced log-probabilities of given captions, eval mode (recnet_score_captions).  tokens [T, B] int64 with every
         entry in [0, V) (the caller's duty: search.score_captions checks); enc None reuses the invariants of the previous call.

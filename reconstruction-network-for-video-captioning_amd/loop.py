@@ -21,7 +21,7 @@ from .checkpoint import load_checkpoint, save_checkpoint
 from .dp import DataParallelTrainStep
 from .feed import DeviceFeeder
 from .search import (_caption_tensor, _score, beam_search, beam_search_nbest, best_of_beam, best_of_n, greedy_search,
-                     sample_search)
+                     sample_search, stochastic_beam_search)
 
 
 class Trainer:
@@ -239,6 +239,13 @@ def _split_top_p(search_method, n):
     return search_method[:n], search_method[n]
 
 
+def _arity(name, fields, n):
+    """The fields of a method without a tail, which nothing else counts."""
+    if len(fields) != n:
+        raise ValueError("the %r method takes %d fields (got %r)" % (name, n, tuple(fields)))
+    return fields
+
+
 def _by_caption(steps):
     """[n_steps][B] token lists (greedy_search, sample_search) as one token list per caption."""
     return list(map(list, zip(*steps)))
@@ -273,6 +280,17 @@ _METHODS = {
     # ... or with their consensus utility (groups are the natural partner)
     "beam_consensus": (("width", "length_alpha", "consensus_weight"), "constraints", False,
                        lambda a, f, con, rec: best_of_beam(*a, *f[:2], consensus_weight=f[2], **con)[0]),
+    # search.stochastic_beam_search: rank 0 of `width` captions sampled without replacement, an exact sample from the model
+    "sbs": (("width", "temperature", "seed"), None, False,
+            lambda a, f, _, rec: [hyps[0][0] for hyps in stochastic_beam_search(*a, *_arity("sbs", f, 3))]),
+    # search.best_of_n(distinct=True): the best of n DIFFERENT sampled candidates (one stochastic beam search of width n) by the
+    # model's length-normalised log-probability, ...
+    "best_of_distinct": (("n", "temperature", "seed"), None, False,
+                         lambda a, f, _, rec: best_of_n(*a, *_arity("best_of_distinct", f, 3)[:2], seed=f[2], distinct=True)[0]),
+    # ... with consensus_weight times their importance-weighted consensus utility added to it
+    "best_of_distinct_consensus": (("n", "temperature", "seed", "consensus_weight"), None, False,
+                                   lambda a, f, _, rec: best_of_n(*a, *_arity("best_of_distinct_consensus", f, 4)[:2], seed=f[2],
+                                                                  consensus_weight=f[3], distinct=True)[0]),
 }
 
 

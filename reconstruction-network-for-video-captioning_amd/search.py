@@ -9,7 +9,9 @@ a caption (recnet_reconstruction_error) — and best_of_n can rank by that as we
 standard in its scoring (sums of log-softmax, recnet_beam_search_nbest): it returns all beam_width hypotheses with scores that
 compare with score_captions / sequence_logprob, and best_of_beam reranks them by the reconstructor.  consensus_scores ranks candidates
 by their n-gram overlap with one another (minimum-Bayes-risk selection, recnet_consensus_rows): best_of_n and best_of_beam add it to
-their score on request, on the candidates where the searches leave them.
+their score on request, on the candidates where the searches leave them.  stochastic_beam_search draws beam_width DIFFERENT captions
+per video, a sample without replacement from the model's distribution, in one search (recnet_stochastic_beam_search); sbs_weights
+gives their importance weights, and best_of_n(distinct=True) reranks them in place of n rollouts.
 
 Differences from the reference that a caller can observe: `input` / `hidden` must be the start state the
 reference's own `evaluate()` builds (<SOS> tokens, zero hidden state, eval.py:131-141) — that is the only
@@ -17,6 +19,7 @@ state the reference ever passes; beam_width <= 8."""
 import math
 import numbers
 
+import numpy as np
 import torch
 
 from . import _lib, _ops
@@ -376,10 +379,13 @@ def _pad_eos(tokens, T, eos=2):
     return tokens if T == T0 else torch.cat([tokens, tokens.new_full((T - T0, B), eos)], dim=0)
 
 
-def _consensus_utilities(hyp):
-    """Host table [N][B] of the self-consensus utilities of checked device captions hyp [N, T, B]: one launch, one read-back."""
+def _consensus_utilities(hyp, weights=None):
+    """Host table [N][B] of the self-consensus utilities of checked device captions hyp [N, T, B]: one launch, one read-back.
+    weights: None (the uniform mean), or a host table [N][B] of finite numbers >= 0, one per candidate as a reference: they reach
+    the kernel as consensus_scores(weights=) passes them, in float32."""
     eng = _consensus_engine(hyp.device)
-    return _ops.load().consensus_rows(int(eng.handle.value), hyp, None, None, 6.0, False, False)[0].cpu().tolist()
+    w = None if weights is None else torch.tensor(weights, dtype=torch.float64).to(hyp.device, torch.float32).contiguous()
+    return _ops.load().consensus_rows(int(eng.handle.value), hyp, None, w, 6.0, False, False)[0].cpu().tolist()
 
 
 def _check_consensus_weight(config, consensus_weight, n):
@@ -499,12 +505,14 @@ def pick_best_of_n(caption_logprobs, lengths, rec_errors=None, recon_weight=0.0,
     return ks, scores
 
 
-def _rerank(caption_logprobs, lengths, recon_weight, rec_args, rec_tokens, consensus_weight, hyp):
+def _rerank(caption_logprobs, lengths, recon_weight, rec_args, rec_tokens, consensus_weight, hyp, consensus_ref_weights=None):
     """The tail of best_of_n / best_of_beam on host tables [n][B] of sums and lengths.  rec_tokens: the n candidate sets as
     _rec_errors takes them behind its leading arguments rec_args (checked, canonical, one common T), or None: no reconstruction
-    error; the n x B errors are read back once.  hyp: the candidates stacked [n, T, B] on the device, or None: no consensus."""
+    error; the n x B errors are read back once.  hyp: the candidates stacked [n, T, B] on the device, or None: no consensus.
+    consensus_ref_weights: _consensus_utilities' weights (None: the uniform mean, what every caller but best_of_n(distinct=True)
+    passes)."""
     errs = None if rec_tokens is None else torch.stack([_rec_errors(*rec_args, tokens)[0] for tokens in rec_tokens]).cpu().tolist()
-    util = None if hyp is None else _consensus_utilities(hyp)
+    util = None if hyp is None else _consensus_utilities(hyp, consensus_ref_weights)
     return pick_best_of_n(caption_logprobs, lengths, errs, recon_weight, util, consensus_weight)
 
 
@@ -514,7 +522,7 @@ def _cut_winners(tokens, ks, lengths):
 
 
 def best_of_n(config, decoder, input, hidden, encoder_outputs, n, temperature=1.0, top_k=0, seed=0, reconstructor=None,
-              recon_weight=0.0, top_p=1.0, consensus_weight=0.0):
+              recon_weight=0.0, top_p=1.0, consensus_weight=0.0, distinct=False):
     """n sampled candidates per video, ranked by the model's own length-normalised log-probability.  Candidate k is
     sample_search's rollout with seed (seed + k) & 0xFFFFFFFF; every candidate set is scored by score_captions at temperature
     1 (the sampler's own log-probabilities are under the tempered / cut distribution), the invariants of the features computed
@@ -529,14 +537,38 @@ def best_of_n(config, decoder, input, hidden, encoder_outputs, n, temperature=1.
     the score, U the consensus utilities of the n candidates among themselves (consensus_scores): the
     candidate sets are stacked on the device at the common length of the longest rollout, one more launch, and the n x B utilities
     are one more read-back; it needs n <= 32 and caption_max_len + 1 <= 64.  consensus_weight = 0 launches nothing new.  Returns
-    (captions: [B] token lists cut after their <EOS>, chosen k [B], score [B])."""
+    (captions: [B] token lists cut after their <EOS>, chosen k [B], score [B]).
+    distinct=True (needs n <= 8, top_k = 0, top_p = 1): the n candidates are the ranks of ONE
+    stochastic_beam_search of width n at (temperature, seed) — n different captions per video, sampled without replacement — instead
+    of n rollouts that repeat one another.  caption_logprob / length come from the search; they are re-scored by score_captions at
+    temperature 1 only when temperature != 1 (the rule above: scores are those of the full distribution at temperature 1).  The
+    tail is the same, except that the consensus utilities weigh reference k by sbs_weights (its normalised importance weight: the
+    candidates are no longer an i.i.d. sample whose plain mean estimates the expectation).  distinct=False is the call as it was."""
     _no_ensemble(decoder, "best_of_n")
     if int(n) != n or n < 1:
         raise ValueError("n must be a positive integer (got %r)" % (n,))
     _check_top_p(top_p)
+    if distinct:
+        if n > 8:
+            raise ValueError("distinct=True takes at most 8 candidates, the widest stochastic beam search (got n = %r)" % (n,))
+        if top_k != 0 or top_p != 1.0:
+            raise ValueError("distinct=True samples from the full distribution: top_k must be 0 and top_p 1 (got %r, %r); the cuts "
+                             "change the distribution the stochastic beam search conditions on" % (top_k, top_p))
+        _check_sbs(decoder, n, temperature)
     use_rec, recon_weight = _check_recon_weight(config, decoder, reconstructor, encoder_outputs, recon_weight)
     consensus_weight = _check_consensus_weight(config, consensus_weight, n)
-    cands = [sample_search(config, decoder, input, hidden, encoder_outputs, temperature, top_k, (seed + k) & 0xFFFFFFFF, top_p)[0]
+    if distinct:
+        toks, cum, ln, gum = _sbs(config, decoder, input, hidden, encoder_outputs, int(n), temperature, seed)
+        weights = sbs_weights(cum.cpu().tolist(), gum.cpu().tolist()) if consensus_weight != 0 else None
+        if temperature != 1.0:
+            cum = torch.stack([_score(decoder, encoder_outputs, toks[k].contiguous(), 1.0, k > 0, config.caption_max_len)[1]
+                               for k in range(int(n))])
+        lens = ln.cpu().tolist()
+        ks, scores = _rerank(cum.cpu().tolist(), lens, recon_weight, (config, decoder, reconstructor, encoder_outputs),
+                             [toks[k] for k in range(int(n))] if use_rec else None, consensus_weight,
+                             toks.contiguous() if consensus_weight != 0 else None, weights)
+        return _cut_winners(toks.cpu().tolist(), ks, lens), ks, scores
+    cands =[sample_search(config, decoder, input, hidden, encoder_outputs, temperature, top_k, (seed + k) & 0xFFFFFFFF, top_p)[0]
              for k in range(int(n))]
     caps, lens, checked = [], [], []
     for k, toks in enumerate(cands):
@@ -698,6 +730,104 @@ def best_of_beam(config, decoder, input, hidden, encoder_outputs, beam_width, le
                          [toks[r] for r in range(int(beam_width))] if use_rec else None, consensus_weight,
                          toks.contiguous() if consensus_weight != 0 else None)
     return _cut_winners(toks.cpu().tolist(), ks, lens), ks, scores
+
+
+# ---- stochastic beam search (recnet_stochastic_beam_search)
+def _check_sbs(decoder, beam_width, temperature):
+    if not isinstance(beam_width, numbers.Real) or int(beam_width) != beam_width or not 1 <= beam_width <= min(8, decoder.output_size):
+        raise ValueError("beam_width must be an integer in [1, %d] (got %r)" % (min(8, decoder.output_size), beam_width))
+    _check_temperature(temperature)
+    if isinstance(decoder, Ensemble) and temperature != 1.0:
+        raise NotImplementedError("stochastic_beam_search with an Ensemble samples at temperature 1 (got %r): score_captions on an "
+                                  "Ensemble has no temperature to hold the result to" % (temperature,))
+
+
+def _sbs(config, decoder, input, hidden, encoder_outputs, beam_width, temperature, seed):
+    """Device tensors (tokens [bw, n_steps, B], cum [bw, B], len [bw, B], gum [bw, B]) of the checked search."""
+    _check_sbs(decoder, beam_width, temperature)
+    _check_start(config, input, hidden)
+    if isinstance(decoder, Ensemble):    # (one member: the library launches the single-model search)
+        engines = [_nbest_engine(config, d, encoder_outputs) for d in decoder.members]
+        toks, cum, ln, gum, n = _ops.load().stochastic_beam_search_ensemble(*decoder._call_args(engines), encoder_outputs.contiguous(),
+                                                                            int(beam_width), float(temperature), int(seed) & 0xFFFFFFFF)
+    else:
+        eng = _nbest_engine(config, decoder, encoder_outputs)
+        toks, cum, ln, gum, n = _ops.load().stochastic_beam_search(int(eng.handle.value), encoder_outputs.contiguous(), int(beam_width),
+                                                                   float(temperature), int(seed) & 0xFFFFFFFF)
+    return toks[:, :int(n.item())], cum, ln, gum
+
+
+def stochastic_beam_search(config, decoder, input, hidden, encoder_outputs, beam_width, temperature=1.0, seed=0):
+    """beam_width DIFFERENT captions per video, sampled without replacement from the model's sequence distribution at `temperature`
+    (Kool, van Hoof, Welling 2019; recnet_stochastic_beam_search): Gumbel-top-k over whole captions, done lazily
+    inside one beam search of that width on the batched decode step of beam_search_nbest.  Every hypothesis carries its
+    log-probability cum and a perturbed score G = cum + Gumbel noise, conditioned at every step so that the best child of a
+    hypothesis inherits its G; the beam keeps the beam_width largest G.  Rank 0 is an exact sample from the model (with beam_width
+    = 1 the search draws sample_search(temperature, seed=seed)'s tokens, up to near-ties), ranks 0 .. beam_width - 1 are a sample
+    without replacement, in descending G.  The draw is a pure function of (seed, step, slot, caption, vocabulary index).  Returns,
+    per caption, a list of beam_width tuples (tokens cut after <EOS>, cum, length, G) in rank order; cum and length are what
+    score_captions(temperature=temperature) returns for the tokens.  A hypothesis that reaches caption_max_len + 1 tokens without
+    <EOS> is a prefix: its cum is the probability of all captions that begin with it.  sbs_weights turns (cum, G) into importance
+    weights.  There are no top-k / top-p cuts, constraints or groups here: they change the distribution the conditioning assumes.
+    decoder may be an Ensemble (recnet_stochastic_beam_search_ensemble), at temperature 1.  Arguments are checked before anything
+    is launched."""
+    toks, cum, ln, gum = (x.cpu().tolist() for x in _sbs(config, decoder, input, hidden, encoder_outputs, beam_width, temperature, seed))
+    return [[([toks[r][t][b] for t in range(ln[r][b])], cum[r][b], ln[r][b], gum[r][b]) for r in range(int(beam_width))]
+            for b in range(encoder_outputs.shape[0])]
+
+
+def _exp_e1(c):
+    """exp(c) E1(c) for float64 c > 0 (E1 the exponential integral): the power series up to 1, the continued fraction above."""
+    c = np.asarray(c, dtype=np.float64)
+    lo = np.minimum(c, 1.0)
+    term, series = np.ones_like(lo), np.zeros_like(lo)
+    for k in range(1, 40):
+        term = term * -lo / k
+        series = series - term / k
+    small = np.exp(lo) * (-0.5772156649015329 - np.log(lo) + series)
+    hi = np.maximum(c, 1.0)
+    f = np.zeros_like(hi)
+    for k in range(80, 0, -1):                        # 1 / (c + 1 - 1 / (c + 3 - 4 / (c + 5 - ...)))
+        f = k * k / (hi + 2 * k + 1 - f)
+    return np.where(c <= 1.0, small, 1.0 / (hi + 1 - f))
+
+
+_LAGUERRE = np.polynomial.laguerre.laggauss(48)
+
+
+def sbs_weights(cum, gum, normalize=True):
+    """Importance weights of the ranks of a stochastic beam search (Kool et al. 2019, section 4.2), host only, float64.  cum, gum:
+    tables [bw][B] (lists or tensors) of log-probabilities and perturbed scores in rank order.  With kappa the smallest perturbed
+    score kept, rank k < bw - 1 gets w = p / q, p = exp(cum) and q = P(G > kappa) = 1 - exp(-exp(cum - kappa)) = -expm1(-exp(cum -
+    kappa)), its probability of being among the first bw - 1; rank bw - 1, which sets the threshold, gets 0; width 1 gets [1].
+    sum_k w_k f(y_k) then estimates E f without bias — for a kappa of Gumbels whose maximum is free.  The search pins the maximum: its
+    start hypothesis has G = 0 where a free one has a Gumbel(0) draw g0, and with it exp(-kappa_free) = exp(-gum[bw - 1]) - 1 +
+    exp(-g0), exp(-g0) an Exp(1) variable independent of everything the search returns (the conditioning of section 21 is a shift of
+    exp(-G)).  Plugging gum[bw - 1] in for kappa is biased low; the weight returned is the mean of p / q over that variable,
+        w = int_0^inf p / (1 - exp(-p (c + e))) exp(-e) de,   c = exp(-gum[bw - 1]) - 1 >= 0,
+    which is unbiased (tests/test_sbs_ref.py holds it to that) and has no more variance than a weight from one draw of g0.  Evaluated
+    as exp(c) E1(c), the integral of 1 / (c + e), plus a 48-point Gauss-Laguerre sum of the smooth remainder.  normalize=True divides
+    by the sum over the ranks (the lower-variance, slightly biased estimator, and what a reference set's weights should be).  Returns
+    [bw][B] Python floats."""
+    c = torch.as_tensor(cum, dtype=torch.float64).cpu().numpy()
+    g = torch.as_tensor(gum, dtype=torch.float64).cpu().numpy()
+    if c.ndim != 2 or c.shape != g.shape or c.shape[0] < 1:
+        raise ValueError("cum and gum must be tables [bw][B] of one shape (got %s, %s)" % (tuple(c.shape), tuple(g.shape)))
+    bw = c.shape[0]
+    if bw == 1:
+        return np.ones_like(c).tolist()
+    p = np.exp(c)
+    with np.errstate(over="ignore"):
+        shift = np.maximum(np.expm1(-g[bw - 1:bw]), 1e-300)              # c of the docstring (kappa <= 0; 0 only at an exact tie)
+    nodes, wts = _LAGUERRE
+    x = p[..., None] * (shift[..., None] + nodes)                        # [bw, B, nodes]
+    with np.errstate(over="ignore", divide="ignore", invalid="ignore"):
+        smooth = np.where(x < 1e-3, 0.5 + x / 12.0, 1.0 / -np.expm1(-x) - 1.0 / x)     # 1 / (1 - exp(-x)) - 1 / x, in [1/2, 1)
+    w = np.broadcast_to(_exp_e1(shift), c.shape) + p * (smooth * wts).sum(axis=-1)
+    w[bw - 1] = 0.0
+    if normalize:
+        w = w / w.sum(axis=0, keepdims=True)
+    return w.tolist()
 
 
 def ensemble_logits(ens, rows_of_logits, device=None):
