@@ -21,7 +21,7 @@ extern "C" {
 #endif
 
 /* 12 still: recnet_beam_select_rows_constrained / recnet_beam_search_nbest_constrained, and after them
- * recnet_beam_select_rows_diverse / recnet_beam_search_nbest_diverse, and recnet_consensus_rows, and the three ensemble entries (recnet_ensemble_mix_rows, recnet_beam_search_nbest_ensemble, recnet_score_captions_ensemble), and the three stochastic beam search entries (recnet_sbs_select_rows, recnet_stochastic_beam_search, recnet_stochastic_beam_search_ensemble), were added without changing any existing entry.  A library built before them is still caught: a binding that resolves every declared symbol fails on the first one missing. */
+ * recnet_beam_select_rows_diverse / recnet_beam_search_nbest_diverse, and recnet_consensus_rows, and the three ensemble entries (recnet_ensemble_mix_rows, recnet_beam_search_nbest_ensemble, recnet_score_captions_ensemble), and the three stochastic beam search entries (recnet_sbs_select_rows, recnet_stochastic_beam_search, recnet_stochastic_beam_search_ensemble), and the four learning-rate schedule entries (recnet_set_lr_schedule, recnet_get_lr_schedule, recnet_lr_at, recnet_read_lr, with the struct recnet_lr_schedule), were added without changing any existing entry.  A library built before them is still caught: a binding that resolves every declared symbol fails on the first one missing. */
 #define RECNET_ABI_VERSION 12
 #define RECNET_ATTN_NONE 0
 #define RECNET_ATTN_SOFTMAX 1
@@ -134,6 +134,42 @@ int recnet_set_shard(recnet_handle* h, int32_t global_batch_size, int32_t batch_
  * (lr, weight decay, eps >= 0; 0 <= beta < 1), else RECNET_EINVAL. */
 int recnet_set_optimizer_hyper(recnet_handle* h, int32_t which, double lr, double weight_decay, double beta1, double beta2,
                                double eps);
+
+/* Learning-rate schedules that a captured step follows.  The lr above is the BASE lr; every Adam launch
+ * multiplies it, on the device and in double, by scale * warm(n) * decay(n) for the 1-based optimiser step n it belongs to (the
+ * device's step counter, so a graph captured at any time follows a schedule installed later).  With W = warmup_steps,
+ * m = max(0, n - W), M = total_steps - W:
+ *   warm(n)  = n / W for n < W, else 1
+ *   decay(n) = CONSTANT 1 | LINEAR 1 - (1 - min_factor) min(m, M) / M | COSINE min_factor + (1 - min_factor) (1 + cos(pi min(m, M) / M)) / 2
+ *            | INVSQRT max(min_factor, sqrt(W' / max(n, W'))), W' = max(W, 1) | STEP max(min_factor, gamma ^ floor(m / period))
+ * NONE, every handle's state at creation, is the factor 1 exactly; scale (host-driven, e.g. reduce-on-plateau) applies under every
+ * kind.  Weight decay, betas and eps stay captured values. */
+#define RECNET_LR_NONE 0
+#define RECNET_LR_CONSTANT 1
+#define RECNET_LR_LINEAR 2
+#define RECNET_LR_COSINE 3
+#define RECNET_LR_INVSQRT 4
+#define RECNET_LR_STEP 5
+typedef struct recnet_lr_schedule {
+  int32_t kind, warmup_steps, total_steps, period;      /* RECNET_LR_*; total_steps: LINEAR / COSINE; period: STEP */
+  double min_factor, gamma, scale;                      /* in [0, 1]; in (0, 1]; > 0 */
+} recnet_lr_schedule;
+/* Installs the schedule of one optimiser (which: 0 decoder, 1 reconstructor).  Checked on the host, RECNET_EINVAL for: which outside
+ * {0, 1}; an unknown kind; negative warmup_steps / total_steps; total_steps <= warmup_steps (LINEAR, COSINE); period <= 0 (STEP);
+ * min_factor outside [0, 1]; gamma outside (0, 1]; scale <= 0 or infinite; any NaN.  A pending deferred reconstructor update is
+ * completed first, as by recnet_flush (it belongs to a step of the old schedule); then the descriptor is written stream-ordered by
+ * a one-thread kernel: no copy from pageable memory, no host synchronisation.  Legal while captured graphs of the handle are alive —
+ * their next replay steps with the new schedule; RECNET_ESTATE when `stream` itself is being captured.  Before a workspace is bound
+ * only the host copy is set (recnet_bind_workspace uploads it). */
+int recnet_set_lr_schedule(recnet_handle* h, int32_t which, const recnet_lr_schedule* sched, void* stream);
+/* The host copy of what the last recnet_set_lr_schedule installed (kind NONE, scale 1 after recnet_create). */
+int recnet_get_lr_schedule(const recnet_handle* h, int32_t which, recnet_lr_schedule* out);
+/* lr(step) = base_lr * scale * warm * decay on the host: no handle, no GPU; the same inline function the kernels call.  The
+ * descriptor is checked like recnet_set_lr_schedule's; step >= 1. */
+int recnet_lr_at(const recnet_lr_schedule* sched, double base_lr, int64_t step, double* out);
+/* out[0] / out[1]: the lr the decoder's / reconstructor's most recent Adam launch used, as that launch wrote it (0 before the
+ * first).  Synchronises `stream`, like recnet_read_step_ring. */
+int recnet_read_lr(recnet_handle* h, double* out2, void* stream);
 
 /* Bytes of device scratch the caller must provide (activations saved for backward, split-K slabs,
  * packed weights).  Must stay alive and untouched between a forward and its backward. */

@@ -193,3 +193,34 @@ EXPORTS["recnet_set_deferred_reconstructor_update"] = (_i, [C.c_void_p, _i, C.c_
 EXPORTS["recnet_flush"] = (_i, [C.c_void_p, C.c_void_p])
 EXPORTS["recnet_mark_pending"] = (_i, [C.c_void_p])
 EXPORTS["recnet_debug_offset"] = (C.c_int64, [C.c_void_p, _i])
+
+
+# learning-rate schedules (added at ABI version 12 without a bump, like the entries above)
+LR_NONE, LR_CONSTANT, LR_LINEAR, LR_COSINE, LR_INVSQRT, LR_STEP = range(6)
+LR_KINDS = {"constant": LR_CONSTANT, "linear": LR_LINEAR, "cosine": LR_COSINE, "invsqrt": LR_INVSQRT, "step": LR_STEP}
+
+
+class LRScheduleDesc(C.Structure):
+    """struct recnet_lr_schedule"""
+    _fields_ = [(n, _i) for n in ("kind", "warmup_steps", "total_steps", "period")] + [(n, _d) for n in ("min_factor", "gamma", "scale")]
+
+
+EXPORTS["recnet_set_lr_schedule"] = (_i, [C.c_void_p, _i, C.POINTER(LRScheduleDesc), C.c_void_p])
+EXPORTS["recnet_get_lr_schedule"] = (_i, [C.c_void_p, _i, C.POINTER(LRScheduleDesc)])
+EXPORTS["recnet_lr_at"] = (_i, [C.POINTER(LRScheduleDesc), _d, C.c_int64, C.POINTER(_d)])
+EXPORTS["recnet_read_lr"] = (_i, [C.c_void_p, C.POINTER(_d), C.c_void_p])
+
+
+def lr_desc(fields=None, scale=1.0):
+    """The descriptor of a schedule given as LRSchedule.to_dict()'s dict (None: no schedule, the factor 1) with `scale`."""
+    f = fields or {}
+    kind = LR_KINDS[f["kind"]] if fields else LR_NONE
+    return LRScheduleDesc(kind, int(f.get("warmup_steps", 0)), int(f.get("total_steps", 0)), int(f.get("period", 0)),
+                          float(f.get("min_factor", 0.0)), float(f.get("gamma", 1.0)), float(scale))
+
+
+def lr_at(fields, scale, base_lr, step):
+    """lr(step) of recnet_lr_at: host-only, the function the kernels call."""
+    out = _d(0.0)
+    check(load().recnet_lr_at(C.byref(lr_desc(fields, scale)), float(base_lr), int(step), C.byref(out)), "recnet_lr_at")
+    return out.value

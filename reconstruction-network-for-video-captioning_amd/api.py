@@ -118,16 +118,108 @@ def _dims(dec_model, B, F, rec_model=None):
 
 
 # ----------------------------------------------------------------------------- optimiser
+class LRSchedule:
+    """A learning-rate schedule as a plain value: lr(n) = base_lr * scale * warm(n) * decay(n) for the
+    1-based optimiser step n, evaluated on the device inside the Adam launches, so it runs under graph replay.  warm(n) = n /
+    warmup_steps below warmup_steps, else 1; with m = max(0, n - warmup_steps), M = total_steps - warmup_steps, decay(n) is
+      "constant" 1 | "linear" 1 - (1 - min_factor) min(m, M) / M | "cosine" min_factor + (1 - min_factor) (1 + cos(pi min(m, M) / M)) / 2
+      | "invsqrt" max(min_factor, sqrt(W / max(n, W))), W = max(warmup_steps, 1) | "step" max(min_factor, gamma ^ floor(m / period)).
+    The library checks the ranges where the schedule is installed (FusedAdam.set_lr_schedule)."""
+    KINDS = ("constant", "linear", "cosine", "invsqrt", "step")
+    FIELDS = ("kind", "warmup_steps", "total_steps", "period", "min_factor", "gamma")
+
+    def __init__(self, kind, warmup_steps=0, total_steps=0, period=0, min_factor=0.0, gamma=1.0):
+        if kind not in self.KINDS:
+            raise ValueError("unknown lr schedule kind %r: one of %s" % (kind, ", ".join(self.KINDS)))
+        self.kind = kind
+        self.warmup_steps, self.total_steps, self.period = int(warmup_steps), int(total_steps), int(period)
+        self.min_factor, self.gamma = float(min_factor), float(gamma)
+
+    def to_dict(self):
+        return {k: getattr(self, k) for k in self.FIELDS}
+
+    @classmethod
+    def from_dict(cls, d):
+        """d: to_dict()'s dict (missing fields take their defaults), an LRSchedule, or None (no schedule: None)."""
+        if d is None or isinstance(d, cls):
+            return d
+        unknown = sorted(set(d) - set(cls.FIELDS))
+        if unknown:
+            raise ValueError("unknown lr schedule field(s) %s: the fields are %s" % (unknown, ", ".join(cls.FIELDS)))
+        return cls(**d)
+
+    def __eq__(self, other):
+        return isinstance(other, LRSchedule) and self.to_dict() == other.to_dict()
+
+    def __repr__(self):
+        return "LRSchedule(%s)" % ", ".join("%s=%r" % kv for kv in self.to_dict().items())
+
+
 class FusedAdam(torch.optim.Optimizer):
     """torch.optim.Adam semantics (coupled weight decay, optional AMSGrad — train.py:149,186) executed by
     the multi-tensor HIP kernel.  `state_dict()` has torch.optim.Adam's layout (step / exp_avg /
-    exp_avg_sq / max_exp_avg_sq per parameter) so checkpoints interchange (train.py:398-420)."""
+    exp_avg_sq / max_exp_avg_sq per parameter) so checkpoints interchange (train.py:398-420).
+
+    param_groups[0]['lr'] is the BASE lr.  A schedule (set_lr_schedule) and a host-driven multiplier (scale_lr / lr_scale:
+    reduce-on-plateau) live in param_groups[0]['lr_schedule'] (LRSchedule.to_dict()'s dict or None) and ['lr_scale'], so
+    state_dict() carries them; the device multiplies the base lr by them per step, also in replayed graphs."""
 
     def __init__(self, mstate, which, lr, weight_decay=0.0, amsgrad=False, betas=(0.9, 0.999), eps=1e-8,
                  hyper=None):
         self._ms, self._which, self._hyper = mstate, which, dict(hyper or {})
         params = [p for _, p in mstate.model.named_parameters()]
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad))
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad,
+                                      lr_schedule=None, lr_scale=1.0))
+
+    # ---- learning-rate schedule (device-resident: legal under a live GraphedStep, unlike an edit of the base lr)
+    @property
+    def lr_schedule(self):
+        return LRSchedule.from_dict(self.param_groups[0]["lr_schedule"])
+
+    @property
+    def lr_scale(self):
+        return float(self.param_groups[0]["lr_scale"])
+
+    @lr_scale.setter
+    def lr_scale(self, value):
+        self._set_lr(self.param_groups[0]["lr_schedule"], value)
+
+    def set_lr_schedule(self, schedule):
+        """schedule: an LRSchedule, its dict, or None (back to the constant base lr; lr_scale stays).  Reaches every engine the
+        model is bound to now, and those bound later at their next step."""
+        s = LRSchedule.from_dict(schedule)
+        self._set_lr(s.to_dict() if s is not None else None, self.lr_scale)
+
+    def scale_lr(self, factor):
+        """lr_scale *= factor (reduce-on-plateau).  Returns the new scale."""
+        self.lr_scale = self.lr_scale * float(factor)
+        return self.lr_scale
+
+    def _set_lr(self, fields, scale):
+        _lib.lr_at(fields, scale, 1.0, 1)               # the library's range checks, host-only: nothing is stored when it refuses
+        g = self.param_groups[0]
+        g["lr_schedule"], g["lr_scale"] = (dict(fields) if fields else None), float(scale)
+        self.push_lr_schedule()
+
+    def push_lr_schedule(self):
+        """Hands the schedule and the scale to every engine this model is bound to whose copy differs (the compare-then-push of
+        push_hyper).  No refusal under a live GraphedStep: the captured Adam launches read the descriptor from device memory."""
+        g = self.param_groups[0]
+        want = (g.get("lr_schedule"), float(g.get("lr_scale", 1.0)))
+        for eng in self._ms.engines.values():
+            if getattr(eng, "lr_sched", {}).get(self._which, (None, 1.0)) != want:
+                eng.set_lr_schedule(self._which, *want)
+
+    def get_last_lr(self):
+        """The lr of the model's current optimiser step (the last one taken; step 1 before the first), computed on the host by
+        recnet_lr_at — the function the kernels call.  Never synchronises."""
+        g = self.param_groups[0]
+        return _lib.lr_at(g.get("lr_schedule"), g.get("lr_scale", 1.0), g["lr"], max(int(self._ms.step), 1))
+
+    def read_lr(self):
+        """The lr the device stepped this model with last, as its Adam launch wrote it (Engine.read_lr of the engine step() uses).
+        Synchronises."""
+        return self._engine().read_lr()[self._which]
 
     def _ensure_state(self):
         fl = self._ms.flat()
@@ -158,7 +250,7 @@ class FusedAdam(torch.optim.Optimizer):
 
     def push_hyper(self):
         """Hands the param group's lr, weight decay, betas and eps to every engine this model is bound to
-        (recnet_set_optimizer_hyper): they may have been edited through param_groups (lr schedules) or replaced by
+        (recnet_set_optimizer_hyper): they may have been edited through param_groups or replaced by
         load_state_dict.  Host-side and only when a value changed.  Raises when `amsgrad` no longer is what the state was
         bound with, and when a value changed while an engine has a live GraphedStep: a captured graph keeps the
         hyper-parameters it was captured with, so it has to be dropped and captured again after the edit."""
@@ -175,6 +267,7 @@ class FusedAdam(torch.optim.Optimizer):
                                    "the captured graph holds the old values; drop it and capture again"
                                    % (eng.opt_hyper[self._which], hp))
             eng.set_optimizer_hyper(self._which, *hp)
+        self.push_lr_schedule()                    # (an engine bound since the schedule was set, or a loaded state dict)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -228,6 +321,11 @@ class FusedAdam(torch.optim.Optimizer):
         for k in ("lr", "betas", "eps", "weight_decay", "amsgrad"):
             if k in sg:
                 g[k] = sg[k]
+        # the lr schedule and scale, where the dict has them (the reference's checkpoints and ours from before do not: what is
+        # installed stays); they reach the engines with the next step's push_hyper
+        if "lr_schedule" in sg or "lr_scale" in sg:
+            sched = LRSchedule.from_dict(sg.get("lr_schedule", g["lr_schedule"]))
+            self._set_lr(sched.to_dict() if sched is not None else None, sg.get("lr_scale", g["lr_scale"]))
         for st in self.state.values():
             st["step"] = torch.tensor(float(self._ms.step))
 
@@ -260,6 +358,8 @@ def build_decoder(n_vocabs, C=TrainConfig):
     hy = _hyper_from(C)
     opt = FusedAdam(ms, 0, lr=C.decoder_learning_rate, weight_decay=C.decoder_weight_decay,
                     amsgrad=C.decoder_use_amsgrad, betas=(hy["adam_beta1"], hy["adam_beta2"]), eps=hy["adam_eps"], hyper=hy)
+    if getattr(C, "decoder_lr_schedule", None) is not None:
+        opt.set_lr_schedule(C.decoder_lr_schedule)
     return {"model": model, "loss": "masked-cross-entropy (fused, train.py:54-68)", "optimizer": opt,
             "lambda_reg": hy["decoder_lambda_reg"], "_state": ms, "_hyper": hy, "_C": C}
 
@@ -286,6 +386,8 @@ def build_reconstructor(C=TrainConfig):
     hy = _hyper_from(C)
     opt = FusedAdam(ms, 1, lr=C.reconstructor_learning_rate, weight_decay=C.reconstructor_weight_decay,
                     amsgrad=C.reconstructor_use_amsgrad, betas=(hy["adam_beta1"], hy["adam_beta2"]), eps=hy["adam_eps"], hyper=hy)
+    if getattr(C, "reconstructor_lr_schedule", None) is not None:
+        opt.set_lr_schedule(C.reconstructor_lr_schedule)
     return {"model": model, "loss": "mse (fused, train.py:101,128)", "optimizer": opt,
             "lambda_reg": hy["reconstructor_lambda_reg"], "_state": ms, "_hyper": hy, "_C": C}
 
@@ -563,7 +665,9 @@ class GraphedStep:
     A captured graph holds the optimiser's hyper-parameters (lr, weight decay, betas, eps) as kernel arguments: the values of
     the two optimisers' param_groups at construction.  Editing them afterwards cannot reach the replays, so it is refused
     while a GraphedStep of the engine is alive: the next replay, FusedAdam.step or TrainStep call raises RuntimeError
-    (FusedAdam.push_hyper, a host-side comparison) — drop the GraphedStep, edit, capture again.
+    (FusedAdam.push_hyper, a host-side comparison) — drop the GraphedStep, edit, capture again.  The lr in the param group is
+    the BASE lr: a learning-rate schedule and the reduce-on-plateau scale (FusedAdam.set_lr_schedule / scale_lr) live in device
+    memory, the captured Adam launches evaluate them at the device's step counter, and both may change while a GraphedStep is alive.
 
     One rank: a single graph (fwd + bwd + optimiser).  Data parallel: three graphs with the two gradient
     all-reduces in between,

@@ -35,6 +35,9 @@ _DEFAULTS = dict(
     precision="bf16",            # "bf16" (bf16 MFMA operands, fp32 accumulate) | "f32" (exact fp32 MFMA)
     decoder_attn_normalize="none",   # "none": the reference (decoder.py:30's softmax is never called) | "softmax": opt-in
     dropout_seed=42,
+    # learning-rate schedules (api.LRSchedule.from_dict's dicts, or None: the constant lr of the reference); device-resident, so
+    # they run under graph replay
+    decoder_lr_schedule=None, reconstructor_lr_schedule=None,
 )
 
 

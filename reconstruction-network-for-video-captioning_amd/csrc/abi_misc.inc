@@ -149,6 +149,59 @@ int recnet_read_step_ring(recnet_handle* h, uint64_t* out16, void* stream) {
   HIPCHK(hipMemcpy(&out16[8], h->scal + RN_SCAL_RING, 8 * 8, hipMemcpyDeviceToHost));
   return RECNET_OK;
 }
+// ---- learning-rate schedules (include/recnet_hip.h; the formula: common.hpp, rn_lr_at)
+static_assert(sizeof(recnet_lr_schedule) == sizeof(RnLrSched) && offsetof(recnet_lr_schedule, scale) == offsetof(RnLrSched, scale), "recnet_lr_schedule is RnLrSched's layout");
+// nullptr, or what is wrong with the descriptor (every comparison is written so that a NaN fails it)
+static const char* lr_sched_problem(const recnet_lr_schedule* s) {
+  if (s->kind < RECNET_LR_NONE || s->kind > RECNET_LR_STEP) return "unknown kind";
+  if (s->warmup_steps < 0 || s->total_steps < 0) return "negative warmup_steps / total_steps";
+  if ((s->kind == RECNET_LR_LINEAR || s->kind == RECNET_LR_COSINE) && s->total_steps <= s->warmup_steps) return "total_steps must exceed warmup_steps (linear, cosine)";
+  if (s->kind == RECNET_LR_STEP && s->period <= 0) return "period must be positive (step)";
+  if (!(s->min_factor >= 0.0 && s->min_factor <= 1.0)) return "min_factor outside [0, 1]";
+  if (!(s->gamma > 0.0 && s->gamma <= 1.0)) return "gamma outside (0, 1]";
+  if (!(s->scale > 0.0 && s->scale <= 1.7976931348623157e308)) return "scale must be positive and finite";
+  return nullptr;
+}
+int recnet_set_lr_schedule(recnet_handle* h, int32_t which, const recnet_lr_schedule* sched, void* stream) {
+  if (!h || !sched) return fail(RECNET_EINVAL, "null argument");
+  if (which < 0 || which > 1) return fail(RECNET_EINVAL, "bad model index");
+  if (const char* bad = lr_sched_problem(sched)) return fail(RECNET_EINVAL, std::string("lr schedule: ") + bad);
+  RnLrSched d;
+  memcpy(&d, sched, sizeof(d));
+  if (h->ws) {
+    hipStream_t st = (hipStream_t)stream;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone)
+      return fail(RECNET_ESTATE, "recnet_set_lr_schedule on a capturing stream: a captured graph reads the descriptor, it does not set it");
+    FLUSH_PENDING(h, st);      // (a pending reconstructor update belongs to a step of the old schedule)
+    hipLaunchKernelGGL(set_lr_sched_kernel, dim3(1), dim3(1), 0, st, h->lrs + which, d);
+    LAUNCH_OK();
+  }
+  h->lr_sched[which] = d;
+  return RECNET_OK;
+}
+int recnet_get_lr_schedule(const recnet_handle* h, int32_t which, recnet_lr_schedule* out) {
+  if (!h || !out) return fail(RECNET_EINVAL, "null argument");
+  if (which < 0 || which > 1) return fail(RECNET_EINVAL, "bad model index");
+  memcpy(out, &h->lr_sched[which], sizeof(*out));
+  return RECNET_OK;
+}
+int recnet_lr_at(const recnet_lr_schedule* sched, double base_lr, int64_t step, double* out) {
+  if (!sched || !out) return fail(RECNET_EINVAL, "null argument");
+  if (const char* bad = lr_sched_problem(sched)) return fail(RECNET_EINVAL, std::string("lr schedule: ") + bad);
+  if (step < 1) return fail(RECNET_EINVAL, "step must be >= 1");
+  RnLrSched d;
+  memcpy(&d, sched, sizeof(d));
+  *out = rn_lr_at(d, base_lr, (long long)step);
+  return RECNET_OK;
+}
+int recnet_read_lr(recnet_handle* h, double* out2, void* stream) {
+  REQUIRE_WS(h);
+  if (!out2) return fail(RECNET_EINVAL, "null argument");
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+  for (int g = 0; g < 2; ++g) HIPCHK(hipMemcpy(&out2[g], &h->lrs[g].last_lr, 8, hipMemcpyDeviceToHost));
+  return RECNET_OK;
+}
 int recnet_chain_reset(recnet_handle* h, int32_t disable_persistent, void* stream) {
   REQUIRE_WS(h);
   hipStream_t st = (hipStream_t)stream;

@@ -64,6 +64,9 @@ struct recnet_handle {
   recnet_config c;
   // optimiser hyper-parameters per model (0 decoder, 1 reconstructor): from the config at creation, then recnet_set_optimizer_hyper
   struct OptHyper { double lr, wd, beta1, beta2, eps; } oh[2];
+  // learning-rate schedule per optimiser (recnet_set_lr_schedule): the host copies, and the device words the Adam launches read
+  // through a pointer (descriptor + the lr the last launch used; carved from the workspace, uploaded by recnet_bind_workspace)
+  RnLrSched lr_sched[2]; RnLrSlot* lrs = nullptr;
   int B, F, D, E, H, A, V, R, RA, Tm, kind, prec, cml;
   int dgru = 0, rgru = 0; // recurrent cell of the decoder / reconstructor: 0 LSTM, 1 GRU (4-block gate layout, kernels.hpp)
   int lp;                // 1: operand copies / packed weights are bf16 (DMA-staged GEMM); 0: fp32 (exact path)
@@ -369,6 +372,7 @@ static size_t carve(recnet_handle* h, char* base) {
   // the stochastic beam search's perturbed scores (behind everything else: no older buffer moves)
   for (int i = 0; i < 2; ++i) h->sr_gum[i] = take(8 * B);
   h->sr_gvals = take(8 * B);
+  h->lrs = (RnLrSlot*)take(2 * sizeof(RnLrSlot) / 4);      // the two optimisers' schedule descriptors and last-lr words
   return off;
 }
 
@@ -438,6 +442,7 @@ int recnet_create(const recnet_config* cfg, recnet_handle** out) {
   h->c = c;
   h->oh[0] = {c.decoder_learning_rate, c.decoder_weight_decay, c.adam_beta1, c.adam_beta2, c.adam_eps};
   h->oh[1] = {c.reconstructor_learning_rate, c.reconstructor_weight_decay, c.adam_beta1, c.adam_beta2, c.adam_eps};
+  for (RnLrSched& s : h->lr_sched) s = RnLrSched{RN_LR_NONE, 0, 0, 0, 0.0, 1.0, 1.0};
   if (h->c.global_batch_size <= 0) h->c.global_batch_size = c.batch_size;
   h->B = c.batch_size; h->F = c.encoder_output_len; h->D = c.encoder_output_size; h->E = c.embedding_size;
   h->H = c.decoder_hidden_size; h->A = c.decoder_attn_size; h->V = c.n_vocabs;
@@ -628,6 +633,10 @@ int recnet_bind_workspace(recnet_handle* h, void* workspace, size_t bytes) {
   // stamped exchange buffers and the launch-epoch words start from zero (a stamp is never zero)
   HIPCHK(hipMemset(h->gbar, 0, CS_WS_WORDS * 4)); HIPCHK(hipMemset(h->scal, 0, RN_SCAL_WORDS * 4)); HIPCHK(hipMemset(h->dc_G1, 0, (size_t)2 * h->Tm * h->B * (4 * h->H + h->A) * 4));
   HIPCHK(hipMemset(h->dc_G2, 0, (size_t)2 * h->Tm * h->B * h->H * DCB_KS * 4));
+  {      // the schedules installed so far (NONE with scale 1 unless recnet_set_lr_schedule ran before the workspace was bound)
+    const RnLrSlot up[2] = {{h->lr_sched[0], 0.0}, {h->lr_sched[1], 0.0}};
+    HIPCHK(hipMemcpy(h->lrs, up, sizeof(up), hipMemcpyHostToDevice));
+  }
   sched_reset(h);
   if (!h->s2) {
     h->overlap = 1;

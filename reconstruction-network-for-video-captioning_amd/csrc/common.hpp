@@ -109,6 +109,30 @@ __device__ __forceinline__ float rn_tanh(float x) {
   return copysignf(r, x);
 }
 
+// ---------------------------------------------------------------- learning-rate schedule
+// lr(n) = base_lr * scale * warm(n) * decay(n) for the 1-based optimiser step n, in double: the one definition, called by both Adam
+// sites on the device (their first thread, beside the bias corrections) and by recnet_lr_at on the host.  With W = warmup_steps,
+// m = max(0, n - W), M = total_steps - W:  warm = n / W below W, else 1;  decay = 1 (CONSTANT) | 1 - (1 - fmin) min(m, M) / M (LINEAR) |
+// fmin + (1 - fmin) (1 + cos(pi min(m, M) / M)) / 2 (COSINE) | max(fmin, sqrt(W' / max(n, W'))), W' = max(W, 1) (INVSQRT) |
+// max(fmin, gamma ^ floor(m / period)) (STEP).  NONE (a handle's state at creation) is the factor 1.0 exactly: base_lr * 1.0 * 1.0
+// has base_lr's bits.  The ranges are checked where a descriptor is installed (recnet_set_lr_schedule).
+enum { RN_LR_NONE = 0, RN_LR_CONSTANT = 1, RN_LR_LINEAR = 2, RN_LR_COSINE = 3, RN_LR_INVSQRT = 4, RN_LR_STEP = 5 };
+struct RnLrSched { int32_t kind, warmup_steps, total_steps, period; double min_factor, gamma, scale; };      // (recnet_lr_schedule's layout)
+// one optimiser's words in device memory: the descriptor the Adam launches read, and the lr the last of them used
+struct RnLrSlot { RnLrSched s; double last_lr; };
+__host__ __device__ inline double rn_lr_factor(const RnLrSched& s, long long n) {
+  if (s.kind == RN_LR_NONE) return 1.0;
+  const long long W = s.warmup_steps, m = n > W ? n - W : 0, M = (long long)s.total_steps - W;
+  const double warm = n < W ? (double)n / (double)W : 1.0, fmin = s.min_factor;
+  double decay = 1.0;
+  if (s.kind == RN_LR_LINEAR) decay = 1.0 - (1.0 - fmin) * (double)(m < M ? m : M) / (double)M;
+  else if (s.kind == RN_LR_COSINE) decay = fmin + (1.0 - fmin) * 0.5 * (1.0 + cos(3.14159265358979323846 * (double)(m < M ? m : M) / (double)M));
+  else if (s.kind == RN_LR_INVSQRT) { const long long W1 = W > 1 ? W : 1; decay = sqrt((double)W1 / (double)(n > W1 ? n : W1)); decay = decay > fmin ? decay : fmin; }
+  else if (s.kind == RN_LR_STEP) { decay = pow(s.gamma, (double)(m / s.period)); decay = decay > fmin ? decay : fmin; }
+  return warm * decay;
+}
+__host__ __device__ inline double rn_lr_at(const RnLrSched& s, double base_lr, long long n) { return base_lr * s.scale * rn_lr_factor(s, n); }
+
 // ---------------------------------------------------------------- Adam (shared by adam_chunk_kernel and the GEMM epilogue)
 // torch.optim.Adam (single-tensor form of torch 2.10): g' = clip * (g + reg) + wd * p ; m <- lerp(m, g', 1-b1) ;
 // v <- b2 v + (1-b2) g'^2 ; [vmax <- max(vmax, v)] ; p <- p - (lr / bc1) * m / (sqrt(v̂) / sqrt(bc2) + eps).
@@ -116,7 +140,8 @@ __device__ __forceinline__ float rn_tanh(float x) {
 // the update in its epilogue (gemm_lds.hpp) round identically.
 struct AdamHyper { double lr, beta1, beta2; float eps, wd, one_m_b1, beta2f, one_m_b2; int amsgrad; float reg_coef; };
 // what the products of one grouped launch share when they apply Adam in their epilogue (gemm_lds.hpp)
-struct AdamShared { AdamHyper hp; const int32_t* step_ptr; const float* poison; const uint32_t* pending; int step_off; int pad; };
+// (lrs: the optimiser's schedule descriptor and last-lr word; hp.lr is the base lr)
+struct AdamShared { AdamHyper hp; const int32_t* step_ptr; const float* poison; const uint32_t* pending; int step_off; int pad; RnLrSlot* lrs; };
 __device__ __forceinline__ float rn_adam_update(float p, float gr, float& m, float& v, float& vmx, float k, float cl, const AdamHyper& hp,
                                                 float step_size, float bc2s) {
 #pragma clang fp contract(on)

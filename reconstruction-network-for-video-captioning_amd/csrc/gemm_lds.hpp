@@ -384,11 +384,17 @@ __device__ __forceinline__ void gemm_lds_tile(const ArgsT& p, const int bx, cons
       // 64 contiguous bytes.  What a separate Adam kernel (28 B per parameter through ~120 CUs) and two transpose kernels did.
       float* hy = reinterpret_cast<float*>(gl_smem + 4 * 32 * 68 * 4 + 16);
       if (tid == 0) {
-        const double st = (double)(*sh->step_ptr + sh->step_off);
+        // (the schedule descriptor's load goes out with the step counter's; the factor at the step the update belongs to: common.hpp)
+        const int32_t sv = *sh->step_ptr;
+        const RnLrSched sd = sh->lrs->s;
+        const long long n = (long long)sv + sh->step_off;
+        const double st = (double)n;
         const double bc1 = 1.0 - pow(sh->hp.beta1, st), bc2 = 1.0 - pow(sh->hp.beta2, st);
-        hy[0] = (float)(sh->hp.lr / bc1); hy[1] = (float)sqrt(bc2);
+        const double lr = rn_lr_at(sd, sh->hp.lr, n);
+        hy[0] = (float)(lr / bc1); hy[1] = (float)sqrt(bc2);
         // a chain kernel of this step gave up (poison), or no step left an update pending: gradient only
         hy[2] = ((sh->poison && *sh->poison != 0.f) || (sh->pending && *sh->pending == 0u)) ? 0.f : 1.f;
+        if (blockIdx.x == 0 && hy[2] != 0.f) sh->lrs->last_lr = lr;      // the lr this update used (recnet_read_lr)
       }
       __syncthreads();
       const float step_size = hy[0], bc2s = hy[1];

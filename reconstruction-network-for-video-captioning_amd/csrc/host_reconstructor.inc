@@ -661,7 +661,7 @@ static bool rec_pending_hh_fused(recnet_handle* h, hipStream_t s, int step_off, 
   const TensorDesc& td = o.tab[ti];      // rnn.weight_hh_l0
   AdamShared sh;
   sh.hp = adam_hyper(h, 1, flags); sh.step_ptr = (const int32_t*)(h->ctrl + RN_CTRL_STEP); sh.poison = h->scal + RN_SCAL_POISON;
-  sh.pending = (const uint32_t*)(h->ctrl + RN_CTRL_PENDING); sh.step_off = step_off; sh.pad = 0;
+  sh.pending = (const uint32_t*)(h->ctrl + RN_CTRL_PENDING); sh.step_off = step_off; sh.pad = 0; sh.lrs = h->lrs + 1;
 #ifdef RN_FAULT_INJECT
   sh.pad = getenv("RN_FAULT") ? atoi(getenv("RN_FAULT")) : 0;      // (fault-injection build only: gemm_lds.hpp)
 #endif
@@ -713,7 +713,7 @@ static int optimizer_step(recnet_handle* h, int flags, hipStream_t st, int only_
     }
     // the kernel also writes the packed operand images of the tensors it updates (no separate re-pack pass)
     hipLaunchKernelGGL(adam_chunk_kernel, dim3(o.nchunks), dim3(256), 0, st, o.d_tab, o.d_chunks, hp, o.d_pnorm, clip,
-                       (const int32_t*)(h->ctrl + RN_CTRL_STEP), (const PackDesc*)o.d_pack, h->lp, (const float*)(h->scal + RN_SCAL_POISON),
+                       (const int32_t*)(h->ctrl + RN_CTRL_STEP), (const PackDesc*)o.d_pack, h->lp, (const float*)(h->scal + RN_SCAL_POISON), h->lrs + g,
                        deferred ? (const uint32_t*)(h->ctrl + RN_CTRL_PENDING) : (const uint32_t*)nullptr, step_off, g == 1 ? skip_mask : 0u);
     if (g == 0) refresh_images(h, 0, st);
     if (g == 1) rec_images_after_update(h, st, (skip_mask >> RN_REC_T_WHH(h)) & 1u);

@@ -190,6 +190,9 @@ __global__ __launch_bounds__(256) void scale_grads_kernel(const TensorDesc* __re
   for (int i = ch.y + threadIdx.x; i < end; i += 256) td.g[i] *= c;
 }
 
+// recnet_set_lr_schedule: the descriptor travels as a kernel argument and is written in stream order (one thread; the last-lr word stays)
+__global__ void set_lr_sched_kernel(RnLrSlot* __restrict__ slot, RnLrSched s) { slot->s = s; }
+
 // (AdamHyper, rn_adam_update: common.hpp)
 // torch.optim.Adam (single-tensor form of torch 2.10): g' = clip * (g + reg) + wd * p ;
 // m <- lerp(m, g', 1-b1) ; v <- b2 v + (1-b2) g'^2 ; [vmax <- max(vmax, v)] ;
@@ -198,7 +201,7 @@ __global__ __launch_bounds__(256) void adam_chunk_kernel(const TensorDesc* __res
                                                          AdamHyper hp, const float* __restrict__ pnorm,
                                                          const float* __restrict__ clip, const int32_t* __restrict__ step_ptr,
                                                          const PackDesc* __restrict__ pack, int lp,
-                                                         const float* __restrict__ poison,
+                                                         const float* __restrict__ poison, RnLrSlot* __restrict__ lrs,
                                                          const uint32_t* __restrict__ pending = nullptr, int step_off = 0,
                                                          uint32_t skip_mask = 0u) {
   // A persistent chain kernel of this step gave up waiting (chain_sync.hpp: rc_give_up) and marked the step: its gradients
@@ -209,15 +212,26 @@ __global__ __launch_bounds__(256) void adam_chunk_kernel(const TensorDesc* __res
   // step_off = -1 when the step counter has already been advanced for the step this launch runs beside
   if (pending && *pending == 0u) return;
   // tensors another launch updates (the split reconstructor update: recurrent weights in the next step, the rest in this one)
-  if ((skip_mask >> chunks[blockIdx.x].x) & 1u) return;
+  // (block 0 goes on to its first thread's work even then: it reports the lr of this launch)
+  const bool skipped = (skip_mask >> chunks[blockIdx.x].x) & 1u;
+  if (skipped && blockIdx.x != 0) return;
   __shared__ float sc[2];
   if (threadIdx.x == 0) {
-    const double st = (double)(*step_ptr + step_off);
+    // hp.lr is the base lr: the schedule's factor (rn_lr_at, common.hpp) is taken at the step this update belongs to, like the bias
+    // corrections — the deferred reconstructor update (step_off = -1) steps with the lr of the step that left it pending.  The
+    // descriptor's load is issued with the step counter's, not behind it.
+    const int32_t sv = *step_ptr;
+    const RnLrSched sd = lrs->s;
+    const long long n = (long long)sv + step_off;
+    const double st = (double)n;
     const double bc1 = 1.0 - pow(hp.beta1, st);
     const double bc2 = 1.0 - pow(hp.beta2, st);
-    sc[0] = (float)(hp.lr / bc1);
+    const double lr = rn_lr_at(sd, hp.lr, n);
+    sc[0] = (float)(lr / bc1);
     sc[1] = (float)sqrt(bc2);
+    if (blockIdx.x == 0) lrs->last_lr = lr;      // for logging and the tests (recnet_read_lr)
   }
+  if (skipped) return;
   __syncthreads();
   const float step_size = sc[0], bc2s = sc[1];
   const int2 ch = chunks[blockIdx.x];

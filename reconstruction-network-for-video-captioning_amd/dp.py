@@ -6,6 +6,11 @@ loop length T and the MSE element count — are GLOBAL-batch quantities.  Every 
 the full [31, B_global] target matrix (it is tiny), weights its local CE terms by 1/(n_t N) and its
 squared error by 1/count, and the gradients are then summed, not averaged.  The norm regulariser,
 weight decay, clipping and Adam run identically on every rank after the reduction.
+
+Learning-rate schedules: every rank installs the same schedule and scale on its own optimisers
+(FusedAdam.set_lr_schedule / scale_lr) and every rank's step counter counts the same steps, so the replicas step with the
+same lr.  The three-graph form and the one-graph form run the same Adam kernels, which read the schedule from device
+memory: nothing in this module knows about it.
 """
 import torch
 

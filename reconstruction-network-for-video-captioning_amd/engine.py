@@ -128,6 +128,9 @@ class Engine:
         self.opt_hyper = {w: (float(hy[n + "_learning_rate"]), float(hy[n + "_weight_decay"]), float(hy["adam_beta1"]),
                               float(hy["adam_beta2"]), float(hy["adam_eps"])) for w, n in ((0, "decoder"), (1, "reconstructor"))}
         self.captured_steps = weakref.WeakSet()      # live api.GraphedStep objects: their graphs hold opt_hyper as kernel arguments
+        # the lr schedule the handle holds for each model: (LRSchedule.to_dict()'s dict or None, scale); set_lr_schedule keeps it
+        # current.  Device-resident, so unlike opt_hyper it may change under a live GraphedStep.
+        self.lr_sched = {0: (None, 1.0), 1: (None, 1.0)}
 
     @classmethod
     def device_only(cls, device=None, precision="f32"):
@@ -207,6 +210,28 @@ class Engine:
         hp = (float(lr), float(weight_decay), float(beta1), float(beta2), float(eps))
         _lib.check(self.lib.recnet_set_optimizer_hyper(self.handle, int(which), *hp), "recnet_set_optimizer_hyper")
         self.opt_hyper[int(which)] = hp
+
+    def set_lr_schedule(self, which, fields, scale=1.0):
+        """The learning-rate schedule of one model's optimiser (recnet_set_lr_schedule): `fields` is LRSchedule.to_dict()'s dict or
+        None (no schedule), `scale` the host-driven multiplier.  Written to the device in stream order; a live GraphedStep
+        follows it from its next replay on.  A pending deferred reconstructor update is completed first, with the old schedule."""
+        d = _lib.lr_desc(fields, scale)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.recnet_set_lr_schedule(self.handle, int(which), C.byref(d), _stream()), "recnet_set_lr_schedule")
+        self.lr_sched[int(which)] = (dict(fields) if fields else None, float(scale))
+
+    def get_lr_schedule(self, which):
+        """The handle's host copy of the descriptor (recnet_get_lr_schedule) as a _lib.LRScheduleDesc."""
+        d = _lib.LRScheduleDesc()
+        _lib.check(self.lib.recnet_get_lr_schedule(self.handle, int(which), C.byref(d)), "recnet_get_lr_schedule")
+        return d
+
+    def read_lr(self):
+        """(decoder lr, reconstructor lr): what the most recent Adam launch of each model stepped with, as the launch wrote it
+        (recnet_read_lr; 0.0 before the first).  Synchronises the stream."""
+        out = (C.c_double * 2)()
+        _lib.check(self.lib.recnet_read_lr(self.handle, out, _stream()), "recnet_read_lr")
+        return float(out[0]), float(out[1])
 
     # ------------------------------------------------------------------ hot path
     def pack_weights(self):

@@ -28,8 +28,14 @@ class Trainer:
     """decoder / reconstructor dicts as train.py:222-225 builds them, plus the step machinery."""
 
     def __init__(self, C, n_vocabs, rank=0, world_size=1, group=None, use_graphs=True, eager_steps=2,
-                 defer_reconstructor_update=False):
+                 defer_reconstructor_update=False, plateau=None):
+        """plateau: None, or dict(factor=, patience=, min_scale=, which=(0, 1)) — reduce-on-plateau on fit's validation loss: after
+        `patience` validations in a row without a new best, the lr scale of the named optimisers (0 decoder, 1 reconstructor) is
+        multiplied by `factor`, never below `min_scale` (FusedAdam.scale_lr: device-resident, the captured graphs follow it).
+        Every rank has to see the same validation losses for the ranks to stay in step: fit validates on rank 0 only, so under
+        data parallelism call plateau_step on every rank with the broadcast loss instead."""
         self.C, self.rank, self.world = C, rank, world_size
+        self._plateau_init(plateau)
         self.decoder = build_decoder(n_vocabs, C)
         self.reconstructor = build_reconstructor(C) if C.use_recon else None
         self.global_batch = C.batch_size
@@ -43,6 +49,51 @@ class Trainer:
         self._graphs, self._static = {}, None
         self.iteration = 0
         self._eager_until = eager_steps       # optimiser step count up to which steps are launched eagerly
+
+    # ------------------------------------------------------------------ reduce-on-plateau (host logic only)
+    def _plateau_init(self, plateau):
+        self.plateau = None
+        if plateau is not None:
+            p = dict(factor=0.5, patience=2, min_scale=0.0, which=(0, 1))
+            unknown = sorted(set(plateau) - set(p))
+            if unknown:
+                raise ValueError("unknown plateau field(s) %s: the fields are factor, patience, min_scale, which" % unknown)
+            p.update(plateau)
+            p["which"] = tuple(int(w) for w in p["which"])
+            if not (0.0 < float(p["factor"]) < 1.0) or int(p["patience"]) < 1 or not (0.0 <= float(p["min_scale"]) <= 1.0) \
+                    or any(w not in (0, 1) for w in p["which"]):
+                raise ValueError("plateau: 0 < factor < 1, patience >= 1, 0 <= min_scale <= 1, which a subset of (0, 1); got %r" % (plateau,))
+            self.plateau = p
+        self._plateau_best, self._plateau_bad = None, 0
+
+    def _plateau_optimizers(self):
+        models = (self.decoder, self.reconstructor)
+        return [models[w]["optimizer"] for w in self.plateau["which"] if models[w] is not None]
+
+    def plateau_step(self, val_loss):
+        """One validation result: a new best resets the count; the `patience`-th result in a row without one multiplies the lr
+        scale of the named optimisers by `factor`, floored at `min_scale`, and starts the count again.  Returns True when it scaled."""
+        if self.plateau is None:
+            return False
+        val_loss = float(val_loss)
+        if self._plateau_best is None or val_loss < self._plateau_best:
+            self._plateau_best, self._plateau_bad = val_loss, 0
+            return False
+        self._plateau_bad += 1
+        if self._plateau_bad < int(self.plateau["patience"]):
+            return False
+        self._plateau_bad = 0
+        factor, floor = float(self.plateau["factor"]), float(self.plateau["min_scale"])
+        scaled = False
+        for opt in self._plateau_optimizers():
+            cur = opt.lr_scale
+            if cur * factor >= floor:
+                opt.scale_lr(factor)
+                scaled = True
+            elif cur > floor:                 # the floor itself, once; at the floor nothing is sent
+                opt.lr_scale = floor
+                scaled = True
+        return scaled
 
     def flush(self):
         """Completes a pending deferred reconstructor update (stream-ordered; a no-op when there is none)."""
@@ -195,6 +246,8 @@ class Trainer:
                 hist.append({"iteration": it, "val_loss": v["loss"], "val_dec": v["dec"], "val_rec": v["rec"]})
                 log("[Validation] Iter {} / {}: loss {:.5f} (dec {:.5f} + rec {:.5f})".format(it, n_iterations, v["loss"],
                                                                                             v["dec"], v["rec"]))
+                if self.plateau_step(v["loss"]):
+                    log("[Plateau] Iter {}: lr scale {}".format(it, [o.lr_scale for o in self._plateau_optimizers()]))
             if save_every and save_dpath and it % save_every == 0:
                 if not checked:
                     self.check_health(sc); checked = True   # never write weights of a step that went wrong
